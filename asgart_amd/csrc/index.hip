@@ -24,9 +24,9 @@ static thread_local char g_err[512] = "";
 thread_local bool tl_owns_pass_mu = false;
 
 // Runtime note.  The extension tiers of one call run on six HIP streams (twelve with
-// two calls in flight); ROCm maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and kernels of
-// streams that share a queue run one after the other.  The HOST exports GPU_MAX_HW_QUEUES=8 before its first HIP
-// call (the Python binding and bench.py do); the library never touches the process environment.
+// two calls in flight); ROCm maps streams onto the hardware queues the process may open (GPU_MAX_HW_QUEUES) and
+// kernels of streams that share a queue run one after the other.  How many queues a process gets is the host's
+// environment's to decide; the library never touches the process environment.
 void set_error(const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -985,8 +985,8 @@ const char *asgart_last_error(void) { return asgart::g_err; }
 const char *asgart_version(void) { return "asgart-hip 0.2.0 gfx950"; }
 
 // ---- native stacks of every thread (asgart_hip.h: asgart_debug_dump_stacks) ------------------------------------------
-// A last resort beside a debugger from a child process (tests/conftest.py tries gdb / rocgdb first): every thread is
-// sent a signal and writes its own stack from the handler.  The signal is a realtime signal of the library's own, its
+// What tests/conftest.py prints before a stalled GPU test is ended (no debugger is attached to a process with the GPU
+// open): every thread is sent a signal and writes its own stack from the handler.  The signal is a realtime signal of the library's own, its
 // handler is installed ONCE and stays installed: a thread that has the signal blocked, or sits in an uninterruptible
 // driver wait -- the stall this exists for -- takes it whenever it comes back, finds nobody asking for its stack any more
 // and returns; the process is never left with a default disposition and a pending signal.  The handler formats with

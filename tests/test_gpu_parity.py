@@ -816,6 +816,27 @@ def test_bench_reads_real_fasta(hiplib, tmp_path):
     assert line["work_per_step"]["proto_sds"] > 0
 
 
+def test_bench_dump_outputs_are_what_the_path_computes(hiplib, tmp_path):
+    """bench.py --dump-outputs: the last timed step's families of every pass, written as float64 .npy, equal the
+    oracle's on the same (seeded) workload."""
+    import json
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2",
+                          "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["dumped_outputs"]["dir"] == str(tmp_path)
+    pr = prep.prepare_records(synth.config_genome(2, 0.05))
+    oidx = oracle.Index.build(pr.data)
+    for tag, (r, c) in (("direct", (False, False)), ("revcomp", (True, True))):
+        eoffs, esds = oidx.run_raw(pr.chunks, oracle.make_settings(k=20, gap=100, reverse=r, complement=c))
+        offs = np.load(tmp_path / f"{tag}_family_offsets.npy")
+        sds = np.load(tmp_path / f"{tag}_proto_sds.npy")
+        assert offs.dtype == np.float64 and sds.dtype == np.float64
+        assert np.array_equal(offs.astype(np.uint64), eoffs) and np.array_equal(sds.astype(np.uint64), esds), tag
+
+
 @pytest.mark.parametrize("rc", [False, True])
 def test_fasta_to_run_result_end_to_end(hiplib, tmp_path, rc):
     """FASTA files -> prepare -> HIP search step -> FilterNs/ReOrder/ReduceOverlap/Sort -> RunResult,
