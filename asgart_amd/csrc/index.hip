@@ -56,7 +56,6 @@ const OptDesc kOptions[] = {
     {"ptab_depth", &Options::ptab_depth, 0, 15},
     {"force_wide", &Options::force_wide, 0, 1},
     {"test_wide_batch", &Options::test_wide_batch, 0, 1ll << 40},
-    {"kfilter_bits", &Options::kfilter_bits, 0, 34},
     {"lazy_aux", &Options::lazy_aux, 0, 1},
     {"fuse_passes", &Options::fuse_passes, 0, 2},
     {"fuse_pole_pct", &Options::fuse_pole_pct, 1, 1000},
@@ -80,7 +79,7 @@ const OptDesc kOptions[] = {
     {"test_fail_alloc", &Options::test_fail_alloc, -1, 1000000000},
     {"cap6w_pct", &Options::cap6w_pct, 100, 400},
     {"solo", &Options::solo, 0, 48},
-    {"posbits", &Options::posbits, 0, 2},
+    {"posbits", &Options::posbits, 0, 1},
 };
 }  // namespace
 
@@ -363,101 +362,6 @@ __global__ __launch_bounds__(256) void add_offset_kernel(SlotT *__restrict__ sa,
         sa[r] = (SlotT)((uint64_t)sa[r] + add);
 }
 
-// presence filter of one orientation (search_dev.hpp): one thread per suffix-array slot, the first
-// slot of every run of equal keys decides for its k-mer
-template <class SlotT>
-__global__ __launch_bounds__(256) void build_filter_kernel(IndexView<SlotT> ix, bool reverse, bool complement,
-                                                           unsigned long long *__restrict__ flt, int bits) {
-    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < ix.n; r += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t u = ix.keys[r];
-    if (r > 0 && ix.keys[r - 1] == u) continue;
-    bool full = true;  // all k bases inside the text (no '$' / end padding): only those can equal a probe
-    for (int j = 0; j < ix.k; ++j) full &= ((u >> (3 * j)) & 7u) != 0u;
-    if (!full) continue;
-    bool keep;
-    if (!reverse && !complement) {
-        keep = r + 1 < ix.n && ix.keys[r + 1] == u;  // occurs at least twice
-    } else {
-        const uint64_t t = transform_key(u, ix.k, reverse, complement);
-        uint64_t lo0 = 0, hi0 = ix.n;
-        uint32_t p;
-        if (prefix_index(t, ix.k, ix.d, p)) {
-            lo0 = ix.ptab[p];
-            hi0 = ix.ptab[p + 1];
-        }
-        const uint64_t l = lower_bound_keys(ix.keys, lo0, hi0, t);
-        keep = l < hi0 && ix.keys[l] == t;
-    }
-    if (keep) {
-        uint64_t w, m;
-        filter_slot(u, bits, w, m);
-        atomicOr(&flt[w], (unsigned long long)m);
-    }
-    }
-}
-
-// The filter's answers by text position: bit p = "the probe that covers text[p .. p + k) in this orientation
-// passes the filter" (or is one of the text-tail corner probes, which never take the filter).  One thread per
-// 64 positions: both rolling keys (forward, and reversed for -R), one filter word per position.
-// refine (option posbits = 2): a position that passes the k-mer filter is looked up once, here, and keeps its bit only
-// if a hit of its probe can be KEPT.  The hit filter of src/automaton.rs:105-114 in text coordinates: a probe that covers
-// text[p .. p + k) keeps the occurrences x > p of its k-mer (needle not reversed: x > i + needle_offset, and i +
-// needle_offset = p) or x >= p + k (reversed needle: x >= needle_offset + L - i = p + k; the extra `m.start != i`
-// only removes hits) -- a property of the text and the position alone, whatever chunk list a call brings.  In the
-// direct pass the LEFT one of every pair of occurrences keeps a hit and the right one does not: half the lookups
-// the k-mer filter lets through end with nothing kept.  Decided exactly for intervals of up to kSmallInterval
-// occurrences (scanned) and, when the index has the position-sorted lists, for those of more than kRankMin (the
-// list's last entry is the interval's largest position); the others keep the k-mer filter's answer.
-template <class SlotT>
-__global__ __launch_bounds__(256) void build_posbits_kernel(IndexView<SlotT> ix, bool reverse, bool complement,
-                                                            const uint64_t *__restrict__ flt, int bits, bool refine,
-                                                            unsigned long long *__restrict__ out, uint64_t n_words) {
-    const int k = ix.k;
-    const uint64_t mask = k >= 21 ? ~0ull >> 1 : (1ull << (3 * k)) - 1ull;
-    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t p0 = w * 64ull;
-        auto code_at = [&](uint64_t p) -> uint64_t {
-            uint32_t c = p < ix.n ? base_code(ix.text[p]) : 0u;
-            if (complement && c) c = comp_code(c);
-            return (uint64_t)c;
-        };
-        uint64_t fk = 0, rk = 0;  // keys of the window that ENDS just before the next base
-        for (int j = 0; j < k - 1; ++j) {
-            const uint64_t c = code_at(p0 + (uint64_t)j);
-            fk = (fk << 3) | c;
-            rk = (rk >> 3) | (c << (3 * (k - 1)));
-        }
-        unsigned long long word = 0;
-        for (int b = 0; b < 64; ++b) {
-            const uint64_t p = p0 + (uint64_t)b;
-            const uint64_t c = code_at(p + (uint64_t)(k - 1));
-            fk = ((fk << 3) | c) & mask;
-            rk = (rk >> 3) | (c << (3 * (k - 1)));
-            const uint64_t q = reverse ? rk : fk;
-            bool pass = true;
-            if (p + (uint64_t)k <= ix.n && !is_tail_corner(ix, q)) {
-                pass = filter_test(flt, bits, q);
-                if (pass && refine) {
-                    uint64_t lo, hi;
-                    ProbeRef pr;  // (read only by probes of more than 42 bases: the filter is for one-word probes)
-                    if (kmer_range(ix, q, 0ull, pr, lo, hi)) {  // (every occurrence of the k-mer)
-                        const uint64_t thr = reverse ? p + (uint64_t)k : p + 1u;  // a hit x is kept iff x >= thr
-                        if (hi - lo <= (uint64_t)kSmallInterval) {
-                            bool any = false;
-                            for (uint64_t r = lo; r < hi; ++r) any |= (uint64_t)ix.sa[r] >= thr;
-                            pass = any;
-                        } else if (ix.sap && hi - lo > (uint64_t)kRankMin) {
-                            pass = (uint64_t)ix.sap[hi - 1u] >= thr;
-                        }
-                    }
-                }
-            }
-            word |= (unsigned long long)(pass ? 1u : 0u) << b;
-        }
-        out[w] = word;
-    }
-}
-
 template <class SlotT>
 __global__ __launch_bounds__(256) void cache_get_kernel(IndexView<SlotT> ix,
                                                         const uint8_t *__restrict__ pats,
@@ -558,24 +462,6 @@ static inline unsigned grid_capped(uint64_t n, unsigned block = 256) {
     return (unsigned)(g < (1ull << 22) ? g : (1ull << 22));
 }
 
-// the presence filters of every orientation, their position bitmaps and the "no memory for it" marks: ONE place
-// (option kfilter_bits used to drop the hashed tables only: the bitmaps leaked on the rebuild and went on filtering
-// after the filter had been switched off)
-static void free_filters(asgart_index *idx) {
-    for (auto &f : idx->d_filter) {
-        if (f) dev_free(f);
-        f = nullptr;
-    }
-    for (auto &f : idx->d_pbits) {
-        if (f) dev_free(f);
-        f = nullptr;
-    }
-    for (auto &f : idx->filter_off) f = false;
-    for (auto &f : idx->pbits_learn) f = false;
-    for (auto &u : idx->pbits_uses) u = 0;
-    idx->filter_bits = 0;
-}
-
 // (the prefix table stays: its size depends on the text length alone unless k is tiny, and it was allocated when the
 // index was created -- see prealloc_ptab; asgart_index_destroy frees it)
 static void free_k_specific(asgart_index *idx) {
@@ -584,14 +470,17 @@ static void free_k_specific(asgart_index *idx) {
     if (idx->d_c8hi) dev_free(idx->d_c8hi);
     if (idx->d_sap) dev_free(idx->d_sap);
     idx->d_sap = nullptr;
-    free_filters(idx);
+    for (auto &f : idx->d_pbits) {
+        if (f) dev_free(f);
+        f = nullptr;
+    }
+    for (auto &f : idx->filter_off) f = false;
+    for (auto &u : idx->pbits_uses) u = 0;
     idx->d_keys = nullptr;
     idx->d_c8lo = idx->d_c8hi = nullptr;
-    idx->filter_bits = 0;
     idx->k = 0;
     idx->sap_tried = false;
     idx->calls_total = 0;
-    for (auto &c : idx->mode_calls) c = 0;
     idx->split_blocked.clear();
 }
 
@@ -847,11 +736,13 @@ int32_t index_prepare(asgart_index *idx, uint64_t k) {
     return 0;
 }
 
-// Option lazy_aux: no filter is built for orientation `mode`; a blank position bitmap (all ones) is set up instead, which
-// the orientation's searches fill in (RunParams::learn).  Without memory for it the orientation is searched without.
+// The position bits of orientation `mode`: a blank bitmap (all ones, n bits padded so that a workgroup's 16-byte loads never
+// leave it) that the orientation's searches fill in (RunParams::pbits).  Without memory for it the orientation is searched
+// without.  (A --trim index has none: its array does not hold the probes' own positions; nor have probes longer than one
+// key word.)
 int32_t index_prepare_learned_bits(asgart_index *idx, uint64_t k, int mode) {
     RC_TRY(index_prepare(idx, k));
-    if (idx->opt.kfilter_bits == 0 || idx->opt.posbits == 0 || idx->trimmed || mode < 0 || mode > 3 || k > (uint64_t)kMaxKey) return 0;
+    if (idx->opt.posbits == 0 || idx->trimmed || mode < 0 || mode > 3 || k > (uint64_t)kMaxKey) return 0;
     REFUSE_POISONED(idx);
     idx->acquire_all();
     struct Unlock {
@@ -878,99 +769,7 @@ int32_t index_prepare_learned_bits(asgart_index *idx, uint64_t k, int mode) {
         return rc;
     }
     idx->d_pbits[mode] = pb;
-    idx->pbits_learn[mode] = true;
     idx->pbits_uses[mode] = 0;
-    return 0;
-}
-
-// Builds the presence filter of orientation `mode` for probe size k (keys prepared first).
-int32_t index_prepare_filter(asgart_index *idx, uint64_t k, int mode) {
-    RC_TRY(index_prepare(idx, k));
-    // (a --trim index has no filter: its array does not hold the probes' own positions)
-    // (nor have probes longer than one key word: the filter is keyed by the key word)
-    if (idx->opt.kfilter_bits == 0 || idx->trimmed || mode < 0 || mode > 3 || k > (uint64_t)kMaxKey) return 0;
-    {
-        std::lock_guard<std::mutex> lk(idx->mu);
-        if (idx->k == k && (idx->d_filter[mode] || idx->filter_off[mode])) return 0;
-    }
-    REFUSE_POISONED(idx);
-    idx->acquire_all();
-    struct Unlock {
-        asgart_index *i;
-        ~Unlock() { i->release_all(); }
-    } unlock{idx};
-    if (idx->k != k || idx->d_filter[mode] || idx->filter_off[mode]) return 0;
-    HIP_TRY(hipSetDevice(idx->device));
-    if (!idx->filter_bits) {
-        // about 8 bits per text position, at most the configured size (the default, 2^30 bits =
-        // 128 MiB, fits the Infinity Cache next to the streams of a search call)
-        int bits = 16;
-        while (bits < 40 && (1ll << bits) < idx->n) ++bits;
-        bits += 3;
-        if (bits > (int)idx->opt.kfilter_bits) bits = (int)idx->opt.kfilter_bits;
-        if (bits < 16) bits = 16;
-        idx->filter_bits = bits;
-    }
-    const int bits = idx->filter_bits;
-    const size_t bytes = (size_t)1 << (bits - 3);
-    uint64_t *flt = nullptr;
-    if (dev_malloc((void **)&flt, bytes) != hipSuccess) {
-        // the filter is an optimisation: without memory for it this orientation is searched without (every probe
-        // takes the lookup); the call that needed it goes on
-        (void)hipGetLastError();
-        idx->filter_off[mode] = true;
-        return 0;
-    }
-    hipStream_t s = idx->ctx[0].stream;
-    const bool rev = (mode & 2) != 0, comp = (mode & 1) != 0;
-    int32_t rc = [&]() -> int32_t {
-        HIP_TRY(hipMemsetAsync(flt, 0, bytes, s));
-        const unsigned g = grid_capped((uint64_t)idx->n);
-        if (idx->wide)
-            build_filter_kernel<uint64_t><<<g, 256, 0, s>>>(idx->view<uint64_t>(), rev, comp,
-                                                            (unsigned long long *)flt, bits);
-        else
-            build_filter_kernel<uint32_t><<<g, 256, 0, s>>>(idx->view<uint32_t>(), rev, comp,
-                                                            (unsigned long long *)flt, bits);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(stream_sync(s));
-        return 0;
-    }();
-    if (rc != 0) {
-        dev_free(flt);
-        return rc;
-    }
-    if (idx->opt.posbits) {
-        // the same answers by text position (n bits, padded so that a workgroup's 16-byte loads never leave it)
-        const uint64_t n_words = ((uint64_t)idx->n + 63u) / 64u;
-        uint64_t *pb = nullptr;
-        if (dev_malloc((void **)&pb, (size_t)n_words * 8 + 512) == hipSuccess) {
-            rc = [&]() -> int32_t {
-                HIP_TRY(hipMemsetAsync(pb, 0xFF, (size_t)n_words * 8 + 512, s));
-                const unsigned g = grid_capped(n_words);
-                const bool refine = idx->opt.posbits >= 2 && !idx->trimmed;
-                if (idx->wide)
-                    build_posbits_kernel<uint64_t><<<g, 256, 0, s>>>(idx->view<uint64_t>(), rev, comp, flt, bits, refine,
-                                                                     (unsigned long long *)pb, n_words);
-                else
-                    build_posbits_kernel<uint32_t><<<g, 256, 0, s>>>(idx->view<uint32_t>(), rev, comp, flt, bits, refine,
-                                                                     (unsigned long long *)pb, n_words);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(stream_sync(s));
-                return 0;
-            }();
-            if (rc != 0) {
-                dev_free(pb);
-                dev_free(flt);
-                return rc;
-            }
-            if (idx->d_pbits[mode]) dev_free(idx->d_pbits[mode]);
-            idx->d_pbits[mode] = pb;
-        } else {
-            (void)hipGetLastError();  // no memory: the hashed filter serves
-        }
-    }
-    idx->d_filter[mode] = flt;
     return 0;
 }
 
@@ -1510,14 +1309,9 @@ int32_t asgart_index_set_option(asgart_index *idx, const char *name, int64_t val
         set_error("option %s is fixed when the index is created (set ASGART_<NAME> in the environment before)", name);
         return ASGART_E_ARG;
     }
-    if (name && !strcmp(name, "kfilter_bits")) REFUSE_POISONED(idx);  // (it frees device buffers)
     idx->acquire_all();  // never changes under a running call
     const int32_t rc = option_set(idx->opt, name, value);
     if (rc == 0 && !strcmp(name, "test_fail_alloc")) asgart::fail_alloc_countdown().store(value);  // (process-wide)
-    if (rc == 0 && !strcmp(name, "kfilter_bits")) {  // rebuilt at the new size by the next call (0: searched without)
-        (void)hipSetDevice(idx->device);
-        free_filters(idx);
-    }
     idx->release_all();
     return rc;
 }

@@ -40,7 +40,7 @@ struct IndexView {
     uint32_t tail8[kMaxK];
     int n_tail8;
     uint64_t tail_bloom;
-    // (the presence filters and their position bitmaps are per orientation: RunParams::flt / pbits)
+    // (the position bits are per orientation: RunParams::pbits)
     // occurrences of every k-mer interval sorted by position (sa_build.hip: build_rank_lists); null: none
     const SlotT *sap;
     // number of suffix-array slots: n, or end - start + 1 for a --trim index (reference
@@ -86,15 +86,12 @@ struct RunParams {
     // extension tier over the merged, cost-sorted segment list.
     uint32_t n_passes, pass_chunks;
     uint32_t modes;       // 8 bits per pass: bit 1 = reversed needle, bit 0 = complemented
-    const uint64_t *flt[4];    // per pass: presence filter of its orientation (search_dev.hpp); null: none
-    const uint64_t *pbits[4];  // ... its answers laid out by TEXT POSITION (bit p: the probe that covers text[p .. p + k) in
-                               // this orientation passes the filter); null: the kernels test the hashed filter
-    int flt_bits;
-    uint32_t blank;            // bit p: ... and this call finds them blank (the accounting pass prices its probes unfiltered)
-    uint32_t learn;            // bit p: pass p's position bits are LEARNED by the search (option lazy_aux: no filter is ever built for
-                               // the orientation; its bitmap starts all ones and probe_count_kernel clears the bit of every probe it
-                               // finds without an occurrence that could be kept -- the same index-derived fact the refined build
-                               // computes, one call late and only where calls probe)
+    const uint64_t *pbits[4];  // per pass: position bits of its orientation (bit p: the probe that covers text[p .. p + k) in this
+                               // orientation may keep a hit); null: every probe is looked up.  LEARNED by the searches: the bitmap
+                               // starts all ones and probe_count_kernel clears the bit of every probe it finds without an occurrence
+                               // that could be kept (a fact about the text and the position, whatever chunk list a call brings; the
+                               // accounting instantiation reads them and never clears a bit)
+    uint32_t blank;            // bit p: this call finds pass p's bits blank (the accounting pass prices its probes unfiltered)
     __host__ __device__ inline uint32_t pass_of(int c) const {
         if (n_passes <= 1u) return 0u;
         const uint32_t uc = (uint32_t)c;
@@ -289,7 +286,6 @@ struct Options {
     int64_t ptab_depth = 0;         // 0: chosen from the text length
     int64_t force_wide = 0;         // tests: 64-bit slots and positions for a small text
     int64_t test_wide_batch = 0;    // tests: batch size of the 64-bit suffix sorter's doubling rounds (0: 2^29)
-    int64_t kfilter_bits = 30;      // log2(bits) of the k-mer presence filter (search_dev.hpp); 0: no filter
     int64_t rank_lists = 1;         // 1: position-sorted occurrence lists for the cardinality test (k <= 21, no --trim)
     int64_t cap6_pct = 140;         // tier 6 accepts segments whose arm bound is up to this percentage of its capacity
     int64_t test_fail_alloc = -1;   // tests: the (n+1)-th device allocation from now on fails once (common.hpp); -1 = off
@@ -297,10 +293,9 @@ struct Options {
     int64_t cap6w_pct = 160;        // ... with 64-bit positions (the bound is three to four times what a segment really holds there)
     int64_t cap45_pct = 100;        // tiers 4 and 5 accept segments whose arm bound is up to this percentage of their capacity (what overflows is re-run)
     int64_t cap3_pct = 160;         // tier 3 accepts segments whose arm bound is up to this percentage of its capacity
-    int64_t posbits = 2;            // the presence filter's answers laid out by text position (built with the filter; the search reads those):
-                                    // 1 = the k-mer filter's answer, 2 = refined -- a position keeps its bit only if a hit of its probe can be
-                                    // KEPT (an occurrence behind the probe: half the lookups the k-mer filter lets through keep nothing;
-                                    // build_posbits_kernel, index.hip), 0 = none: the kernels test the hashed filter
+    int64_t posbits = 1;            // 1: position bits per orientation (RunParams::pbits), learned by its searches: its first search looks
+                                    // every probe up, the later ones skip the probes that cannot keep a hit; 0: none, every probe is looked
+                                    // up (bits already learned are kept, not freed, and serve again when the option returns to 1)
     int64_t barren = 2;             // segments that provably emit nothing are not run at all: 1 = those with too few hit-probes for any arm to
                                     // reach min_duplication_length (pipeline_dev.hpp: segment_is_barren); 2 = also those whose hits leave
                                     // no run of consecutive occupied position buckets long enough (cluster_barren_kernel: the bursts of
@@ -315,13 +310,9 @@ struct Options {
                                     // 2 178 ms) the next calls are TIMED both ways, two each, and the faster way is kept (a GRCh38-shaped
                                     // step sits at 85-87 per cent: a guess at the threshold would cost it 40 ms)
     int64_t fuse_pole_pct = 88;
-    int64_t lazy_aux = 1;           // 1: no presence filter is BUILT: the position bits of an orientation start all ones and its first search
-                                    // clears, as a by-product of its lookups, the bit of every probe without an occurrence that could be
-                                    // kept (from its second search on the orientation is filtered); the position-sorted lists are built
-                                    // when a search call has had a predecessor (0.2 s at GRCh38 size for 0.006 s per pass) -- a host that
-                                    // runs every orientation once per index (the reference's own use, src/bin/asgart.rs:677-693) pays for
-                                    // neither; 0: filter + refined position bits built on first use (0.3 s per orientation), lists with
-                                    // the keys
+    int64_t lazy_aux = 1;           // 1: the position-sorted lists are built when a search call has had a predecessor (0.2 s at GRCh38 size
+                                    // for 0.006 s per pass) -- a host that runs every orientation once per index (the reference's own use,
+                                    // src/bin/asgart.rs:677-693) does not pay for them; 0: they are built with the keys
     int64_t dense3 = 16;            // long segments go to tier 3 (K8) only with at least this many hits per processed probe on average
                                     // (0: all of them); the sparse long ones run on tier 6's kernel (K6, solo probes)
     int64_t dense6 = 32;            // segments of ANY length whose arm bound sends them to tier 6 go to tier 3 instead with at least this
@@ -351,7 +342,7 @@ struct Options {
                                     // back to the device): giving ~100 GB back costs the next allocation of the process 20-30 ms per
                                     // GiB on most boxes of the pool -- 1.3-2.4 s of a cold GRCh38-sized run when it happened at the end of
                                     // asgart_index_prepare (0: there, as in round 4); the second call builds the position-sorted lists
-                                    // and the presence filters out of those blocks
+                                    // out of those blocks
     int64_t prewarm = 1;            // 1: asgart_index_prepare also reserves the per-probe workspace of both call contexts (sized for an
                                     // unsharded call over the whole text) and starts the worker thread of the passes call, so that the first
                                     // search calls allocate nothing chip-sized; 0: everything on first use (hosts that only issue sharded calls)
@@ -435,19 +426,16 @@ struct asgart_index {
     void *d_c8lo = nullptr;
     void *d_c8hi = nullptr;
     void *d_sap = nullptr;   // position-sorted occurrence lists (IndexView::sap), or null
-    uint64_t *d_filter[4] = {nullptr, nullptr, nullptr, nullptr};  // per orientation: reverse * 2 + complement
-    uint64_t *d_pbits[4] = {nullptr, nullptr, nullptr, nullptr};   // ... its answers by text position (n bits + padding)
-    bool filter_off[4] = {false, false, false, false};             // no memory for it: this orientation is searched without
-    bool pbits_learn[4] = {false, false, false, false};            // its position bits are learned by the searches (RunParams::learn)
-    uint64_t pbits_uses[4] = {0, 0, 0, 0};                         // ... search calls that have used them so far
-    int filter_bits = 0;                                           // log2 of their size in bits
+    uint64_t *d_pbits[4] = {nullptr, nullptr, nullptr, nullptr};  // per orientation (reverse * 2 + complement): position bits
+                                                                  // (RunParams::pbits; n bits + padding)
+    bool filter_off[4] = {false, false, false, false};            // no memory for them: this orientation is searched without
+    uint64_t pbits_uses[4] = {0, 0, 0, 0};                        // search calls that have used them so far
     uint32_t tail8[asgart::kMaxK];
     int n_tail8 = 0;
     uint64_t tail_bloom = 0;
     std::vector<uint8_t> h_tail;  // last kMaxK + 32 bytes of the text (host copy)
     bool sap_tried = false;        // the position-sorted lists were built or given up on for this probe size
-    uint64_t calls_total = 0;      // finished search calls with the current keys ...
-    uint64_t mode_calls[4] = {0, 0, 0, 0};  // ... and started ones per orientation (option lazy_aux)
+    uint64_t calls_total = 0;      // finished search calls with the current keys
     double ms_prepare = 0.0;
     std::atomic<bool> poisoned{false};  // a call gave up waiting for the device (watchdog): work may still be running on the
                                         // index's streams and buffers, every later call is refused
@@ -573,8 +561,7 @@ int32_t reserve_probe_workspace(asgart_index *idx, SearchCtx &cx, uint64_t W);
 // asgart_index_prepare: the per-probe workspace of ALL call contexts (context c for Wc[c] probes) carved out of ONE block that
 // the suffix sorter has just released, if the block cache holds one of the right size (false: nothing done)
 bool carve_probe_workspace(asgart_index *idx, const uint64_t *Wc);
-int32_t index_prepare_filter(asgart_index *idx, uint64_t k, int mode);  // mode = reverse * 2 + complement
-int32_t index_prepare_learned_bits(asgart_index *idx, uint64_t k, int mode);  // a blank bitmap the searches fill in (lazy_aux)
+int32_t index_prepare_learned_bits(asgart_index *idx, uint64_t k, int mode);  // mode = reverse * 2 + complement
 int32_t index_prepare_sap(asgart_index *idx, uint64_t k);
 int32_t run_search_passes(asgart_index *idx, const uint64_t *chunks, int64_t n_chunks,
                           const asgart_settings *sts, int32_t n_passes, int32_t shard, int32_t n_shards, bool want_csr,

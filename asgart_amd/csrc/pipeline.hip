@@ -490,19 +490,14 @@ struct SearchCall {
         rp.n_passes = (uint32_t)n_passes;
         rp.pass_chunks = (uint32_t)n_chunks_pass;
         rp.modes = 0;
-        rp.learn = rp.blank = 0;
-        rp.flt_bits = idx->filter_bits;
+        rp.blank = 0;
         for (int p = 0; p < 4; ++p) {
-            rp.flt[p] = rp.pbits[p] = nullptr;
+            rp.pbits[p] = nullptr;
             if (p >= n_passes) continue;
             const int mode = (sts[p].reverse ? 2 : 0) | (sts[p].complement ? 1 : 0);
             rp.modes |= (uint32_t)mode << (8 * p);
-            rp.flt[p] = idx->d_filter[mode];  // null: filter off
             rp.pbits[p] = opt.posbits ? idx->d_pbits[mode] : nullptr;
-            if (rp.pbits[p] && idx->pbits_learn[mode]) {
-                rp.learn |= 1u << p;
-                if (idx->pbits_uses[mode] == 0) rp.blank |= 1u << p;  // (this call finds them all ones)
-            }
+            if (rp.pbits[p] && idx->pbits_uses[mode] == 0) rp.blank |= 1u << p;  // (this call finds them all ones)
         }
         cx.last_rp = rp;
         cx.has_last = false;
@@ -1604,37 +1599,25 @@ int32_t run_search_passes(asgart_index *idx, const uint64_t *chunks, int64_t n_c
     for (;;) {
         SearchCtx &probe = idx->acquire_one(&which);
         (void)probe;
-        // The presence filter and the position-sorted lists are optimisations that cost more than they save in ONE pass
-        // (option lazy_aux): an orientation gets its filter at its second search, the index its lists at its second call.
-        // With lazy_aux no filter is built at all: an orientation's position bits start blank and its searches fill them in.
+        // An orientation's position bits start blank and its searches fill them in.  The position-sorted lists cost more
+        // than they save in ONE pass (option lazy_aux): the index gets them at its second call.
         bool want_sap, ready;
-        int need_filter = -1;  // an orientation of this call whose filter is due and missing
-        int need_blank = -1;   // ... or whose blank position bits are (lazy_aux)
+        int need_blank = -1;  // an orientation of this call whose blank position bits are due and missing
         {
             std::lock_guard<std::mutex> lk(idx->mu);
             ready = idx->k == st->probe_size;
-            const bool lazy = idx->opt.lazy_aux != 0;
-            const bool filterable = !(idx->opt.kfilter_bits == 0 || idx->trimmed || st->probe_size > (uint64_t)kMaxKey);
-            for (int32_t p = 0; p < n_passes && need_filter < 0 && need_blank < 0; ++p) {
+            const bool filterable = !(idx->opt.posbits == 0 || idx->trimmed || st->probe_size > (uint64_t)kMaxKey);
+            for (int32_t p = 0; p < n_passes && need_blank < 0; ++p) {
                 const int mode = (sts[p].reverse ? 2 : 0) | (sts[p].complement ? 1 : 0);
-                if (!filterable || !ready || idx->filter_off[mode]) continue;
-                if (lazy && idx->opt.posbits != 0) {
-                    if (!idx->d_pbits[mode]) need_blank = mode;
-                } else if (!(lazy && idx->mode_calls[mode] == 0) && !idx->d_filter[mode]) {
-                    need_filter = mode;  // (lazy without position bits: the hashed filter, on second use)
-                }
+                if (filterable && ready && !idx->filter_off[mode] && !idx->d_pbits[mode]) need_blank = mode;
             }
-            want_sap = !(lazy && (!ready || idx->calls_total == 0)) && !idx->sap_tried;
-            if (ready && need_filter < 0 && need_blank < 0 && !(want_sap && !idx->d_sap)) {
-                for (int32_t p = 0; p < n_passes; ++p) ++idx->mode_calls[(sts[p].reverse ? 2 : 0) | (sts[p].complement ? 1 : 0)];
-                break;
-            }
+            want_sap = !(idx->opt.lazy_aux && (!ready || idx->calls_total == 0)) && !idx->sap_tried;
+            if (ready && need_blank < 0 && !(want_sap && !idx->d_sap)) break;
         }
         idx->release_one(which);
         if (!ready) RC_TRY(index_prepare(idx, st->probe_size));
         else if (want_sap && !idx->d_sap) RC_TRY(index_prepare_sap(idx, st->probe_size));
-        else if (need_blank >= 0) RC_TRY(index_prepare_learned_bits(idx, st->probe_size, need_blank));
-        else RC_TRY(index_prepare_filter(idx, st->probe_size, need_filter));
+        else RC_TRY(index_prepare_learned_bits(idx, st->probe_size, need_blank));
     }
     SearchCtx &cx = idx->ctx[which];
     cx.progress = progress;
@@ -2096,14 +2079,11 @@ int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out) {
             hipStream_t s = cx.stream;
             HIP_TRY(hipMemsetAsync(d_ctr + CT_BISECT, 0, 8, s));
             RunParams rp = cx.last_rp;
-            for (uint32_t p = 0; p < rp.n_passes && p < 4u; ++p) {  // (the filters as they are now)
-                rp.flt[p] = idx->d_filter[rp.mode_of_pass(p)];
+            for (uint32_t p = 0; p < rp.n_passes && p < 4u; ++p) {  // (the position bits as they are now)
                 rp.pbits[p] = idx->opt.posbits ? idx->d_pbits[rp.mode_of_pass(p)] : nullptr;
                 // (a pass whose position bits were blank when the call ran looked every probe up)
-                if ((rp.blank >> p) & 1u) rp.flt[p] = rp.pbits[p] = nullptr;
+                if ((rp.blank >> p) & 1u) rp.pbits[p] = nullptr;
             }
-            rp.learn = 0;
-            rp.flt_bits = idx->filter_bits;
             const unsigned g = rp.n_tiles(256u);
             if (idx->wide)
                 yardstick_kernel<uint64_t><<<g, 256, 0, s>>>(idx->view<uint64_t>(), rp,

@@ -43,7 +43,7 @@ enum Counter {
     CT_RANK = 38,       // entries in rank_list (large intervals counted by bisection of the position-sorted lists)
     CT_BIG0 = 39,       // entries of big_list that big_count_kernel counted (later ones were appended for the fill)
     CT_ALG_BYTES = 68,  // accounting pass: bytes the probe-search kernels move by design
-    CT_FLT_REJECTED,    // accounting pass: probes answered by the presence filter alone
+    CT_FLT_REJECTED,    // accounting pass: probes answered by the position bits alone
     CT_LONGSEG,         // placement: segments the lane-per-segment walk handed to the wave-per-segment kernel
     CT_ALG_BYTES16,     // accounting pass: the part of CT_ALG_BYTES that is wide coalesced loads (16 bytes per lane)
     CT_HIST_PEAK = 72,   // diagnostic build: log2 histograms per launch (16 bins each)
@@ -121,8 +121,8 @@ __device__ inline unsigned long long lane_of(unsigned long long v, uint32_t l) {
 //      the key of probe t is half[t] ++ half[t+1] (plus one more base when k is odd).  -R walks
 //      the window downwards, -C complements the codes: needle preparation (reference
 //      src/bin/asgart.rs:206-218) without a needle.
-//   3. Presence filter (search_dev.hpp): one load from a cache-resident bitmap; a rejected probe
-//      has no hit and is done.
+//   3. Position bits (RunParams::pbits): one bit per probe, staged with the window; a probe whose
+//      bit is clear keeps no hit and is done.
 //   4. The others: prefix table -> bisection over the sorted keys -> filtered count of the
 //      suffix-array interval (intervals > 32 go to the wave kernel through big_list).
 //
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
                                                                     unsigned long long *__restrict__ ctr) {
     __shared__ __attribute__((aligned(16))) uint8_t s_text[kWinBytes];
     __shared__ uint32_t s_half[kProbeBlock + 2];
-    // the filter's answers for the workgroup's probes: 256 probes at stride k/2 = one contiguous run of bits
+    // the position bits of the workgroup's probes: 256 probes at stride k/2 = one contiguous run of bits
     constexpr int kPbLoads = (kProbeBlock * kMaxHalf + 127) / 128 + 2;  // 16-byte loads that cover it
     __shared__ __attribute__((aligned(16))) uint32_t s_pb[kPbLoads * 4];
     __shared__ uint8_t s_surv[kProbeBlock];
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
     const bool uniform = rp.ch.pbase[c0 + 1] > g_last && k <= kMaxKey;
     uint32_t n_rej = 0;
     // one probe's lookup: SA interval, filtered count of a small interval (large ones are marked for the wave kernels)
-    // lrn_: the pass's position bits when they are being learned (RunParams::learn), else null
+    // lrn_: the pass's position bits (RunParams::pbits), or null
     auto lookup = [&](uint32_t g_, uint64_t q_, uint64_t q2_, uint64_t i_, uint64_t s_, uint64_t L_, uint32_t md_,
                       const uint64_t *lrn_) {
         const bool reverse = (md_ & 2u) != 0u, complement = (md_ & 1u) != 0u;
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
             cb.rd(4);      //   ... which reads the mark back
         }
     };
-    // a probe the presence filter (or its first base) answers: what is written for it; -> true: it has to be looked up
+    // a probe the position bits (or its first base) answer: what is written for it; -> true: it has to be looked up
     auto screen = [&](uint32_t g_, uint32_t first_, bool pass_, uint32_t md_) {
         if (first_ == 4u) {  // needle[i] == 'N'  (automaton.rs:100-102)
             if (!COUNT) p_filt[g_] = kSkipN;
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
     if (uniform) {
         const uint32_t pass0 = rp.pass_of(c0), md = rp.mode_of_pass(pass0);  // (the orientation of the chunk's pass)
         const bool reverse = (md & 2u) != 0u, complement = (md & 1u) != 0u;
-        const uint64_t *const pbits = rp.pbits[pass0], *const flt = rp.flt[pass0];
+        const uint64_t *const pbits = rp.pbits[pass0];
         const uint64_t s = rp.ch.start[c0], L = rp.ch.len[c0];
         const uint64_t i0 = (uint64_t)(gb - rp.ch.pbase[c0] + 1) * (uint64_t)H;  // needle offset of probe gb
         const int n_half = kProbeBlock + 2;
@@ -293,8 +293,8 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
             if (k & 1) qt = (qt << 3) | (uint64_t)(s_half[t + 2] >> (3 * (H - 1)));
             return qt;
         };
-        // ---- presence filter (every probe), then the lookup of the survivors ---------------------------------
-        // About four probes in five are answered by the filter.  The lookup behind it -- prefix table, key bisection,
+        // ---- position bits (every probe), then the lookup of the survivors ---------------------------------
+        // About four probes in five are answered by the bits.  The lookup behind it -- prefix table, key bisection,
         // suffix-array entries -- is a chain of dependent random gathers, and a wave runs it at the speed of its
         // slowest lane however few lanes are left: the survivors of the tile are compacted (ballots) so that the
         // lookups run with the lanes full.
@@ -309,13 +309,10 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
                 bool pass = true;
                 if (first != 4u) {
                     const uint64_t i = i0 + (uint64_t)t * (uint64_t)H;
-                    if (pbits) {  // the filter's answer, by the text position the probe covers
+                    if (pbits) {  // the bit of the text position the probe covers
                         const long long p = reverse ? (long long)(s + L - i) - k : (long long)(s + i);
                         const uint32_t b = (uint32_t)(p - pb_lo);
                         pass = (s_pb[b >> 5] >> (b & 31u)) & 1u;
-                    } else if (flt && !is_tail_corner(ix, q)) {
-                        cb.rd(8);
-                        pass = filter_test(flt, rp.flt_bits, q);
                     }
                 }
                 survivor = screen(g, first, pass, md);
@@ -327,7 +324,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
         __syncthreads();
         for (uint32_t j = lane; j < n_surv; j += kProbeThreads) {
             const uint32_t t = s_surv[j];
-            lookup(gb + t, key_of(t), 0ull, i0 + (uint64_t)t * (uint64_t)H, s, L, md, ((rp.learn >> pass0) & 1u) ? pbits : nullptr);
+            lookup(gb + t, key_of(t), 0ull, i0 + (uint64_t)t * (uint64_t)H, s, L, md, pbits);
         }
     } else {
         // the tile straddles a chunk boundary (or the probes are longer than one key word): every probe on its own
@@ -338,7 +335,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
             const int c = chunk_of(rp.ch, g);
             const uint32_t pass_c = rp.pass_of(c), md = rp.mode_of_pass(pass_c);
             const bool reverse = (md & 2u) != 0u, complement = (md & 1u) != 0u;
-            const uint64_t *const pbits = rp.pbits[pass_c], *const flt = rp.flt[pass_c];
+            const uint64_t *const pbits = rp.pbits[pass_c];
             const uint64_t s = rp.ch.start[c], L = rp.ch.len[c];
             const uint64_t i = (uint64_t)(g - rp.ch.pbase[c] + 1) * (uint64_t)H;
             uint32_t first = 0;
@@ -346,17 +343,12 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
             const uint64_t q = probe_key(ix.text, s, L, i, k, reverse, complement, &first, &q2);
             cb.rd((uint32_t)k);
             bool pass = true;
-            if (first != 4u) {
-                if (pbits) {
-                    const long long p = reverse ? (long long)(s + L - i) - k : (long long)(s + i);
-                    cb.rd(8);
-                    pass = (pbits[(uint64_t)p >> 6] >> ((uint64_t)p & 63u)) & 1ull;
-                } else if (flt && !is_tail_corner(ix, q)) {
-                    cb.rd(8);
-                    pass = filter_test(flt, rp.flt_bits, q);
-                }
+            if (first != 4u && pbits) {
+                const long long p = reverse ? (long long)(s + L - i) - k : (long long)(s + i);
+                cb.rd(8);
+                pass = (pbits[(uint64_t)p >> 6] >> ((uint64_t)p & 63u)) & 1ull;
             }
-            if (screen(g, first, pass, md)) lookup(g, q, q2, i, s, L, md, ((rp.learn >> pass_c) & 1u) ? pbits : nullptr);
+            if (screen(g, first, pass, md)) lookup(g, q, q2, i, s, L, md, pbits);
         }
     }
     if constexpr (COUNT) {

@@ -271,41 +271,6 @@ __device__ inline bool kmer_range(const IndexView<SlotT> &ix, uint64_t q, uint64
     return true;
 }
 
-// ---- k-mer presence filter ---------------------------------------------------------------
-// A blocked two-bit Bloom filter over k-mer keys, small enough (2^filt_bits bits, 128 MiB by
-// default) to stay resident in the 256 MiB Infinity Cache: both bits of a key live in one 64-bit
-// word, so a test is ONE load that normally never reaches HBM.  One filter per orientation of
-// the run (index.hip builds it): it holds every k-mer q of the text whose probe could have a hit,
-//   direct pass:      q occurs at least twice in the text (one occurrence is the probe itself),
-//   -R / -C / -RC:    q occurs in the text AND T(q) occurs in the text, T = the needle
-//                     transformation (an involution) -- the probe IS T(some text k-mer).
-// No false negatives: a probe the filter rejects provably has no hit (its SA interval holds just
-// the probe itself in the direct pass, nothing otherwise), so it skips the prefix table, the
-// key bisection and the suffix-array read -- the random HBM gathers of the lookup.
-__device__ inline void filter_slot(uint64_t q, int bits, uint64_t &word, uint64_t &mask) {
-    const uint64_t h = q * 0x9E3779B97F4A7C15ull;
-    word = h >> (64 - (bits - 6));
-    const uint64_t h2 = (q ^ (q >> 29)) * 0xD6E8FEB86659FD93ull;
-    mask = (1ull << (h2 >> 58)) | (1ull << ((h2 >> 52) & 63u));
-}
-__device__ inline bool filter_test(const uint64_t *__restrict__ flt, int bits, uint64_t q) {
-    uint64_t w, m;
-    filter_slot(q, bits, w, m);
-    return (flt[w] & m) == m;
-}
-
-// the needle transformation on a packed key: complement every code, then reverse the order
-__device__ inline uint64_t transform_key(uint64_t q, int k, bool reverse, bool complement) {
-    uint64_t out = 0;
-    for (int j = 0; j < k; ++j) {
-        uint32_t c = (uint32_t)(q >> (3 * (k - 1 - j))) & 7u;  // j-th base
-        if (complement) c = comp_code(c);
-        const int dst = reverse ? k - 1 - j : j;               // its place in the result
-        out |= (uint64_t)c << (3 * (k - 1 - dst));
-    }
-    return out;
-}
-
 // key of the probe at needle-local offset i of chunk (s, L) under the run's
 // orientation: needle = chunk | complemented | reversed (reference
 // src/bin/asgart.rs:206-218), probe = needle[i..i+k].  *first = first base code.

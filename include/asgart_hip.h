@@ -82,11 +82,11 @@ typedef struct asgart_stats {
     double ms_probe_count;    /* probe_count_kernel alone (first kernel of ms_search) */
     /* filled only with ASGART_STATS_YARDSTICK, by an untimed accounting pass over the same probes: */
     uint64_t search_bytes;    /* bytes the probe-search kernels load and store BY DESIGN (window
-                                 staging, filter word, prefix-table entries, keys read by the bisection,
+                                 staging, position bits, prefix-table entries, keys read by the bisection,
                                  suffix-array entries read, outputs): the algorithmic bytes of this kernel */
-    uint64_t probes_filter_rejected; /* probes answered by the k-mer presence filter alone          */
+    uint64_t probes_filter_rejected; /* probes answered by the position bits alone                  */
     uint64_t search_bytes_wide_loads; /* ... of search_bytes, those loaded as whole-wave 16-byte-per-lane reads (text windows,
-                                         filter bitmaps): what FETCH_SIZE counts at half on gfx950 (accounting pass only) */
+                                         position bits): what FETCH_SIZE counts at half on gfx950 (accounting pass only) */
     double ms_longest_tier;   /* part of ms_extend: the extension tier that ran longest, from the launch of the tiers
                                  (they run side by side) -- in practice the longest serial automaton segment of the
                                  call, i.e. what sharding the probes over more GPUs cannot shorten              */
@@ -196,8 +196,8 @@ int32_t asgart_index_create_trim(const uint8_t *T, int64_t n, const int64_t *SA,
  * predecessor at the cut; where a cut does not hold the ranges in front of it stand, the rest of the segment runs as one
  * more run, and the next call over the same input starts that segment's ranges as far in front of their cuts as the
  * failed one asked for; split = 2: with 64-bit positions as well);
- * fuse_passes, fuse_pole_pct (passes of one call as one job or pipelined); kfilter_bits, posbits, rank_lists,
- * lazy_aux (the position filter and the position-sorted lists, and when they come into being); cache_calls, prewarm
+ * fuse_passes, fuse_pole_pct (passes of one call as one job or pipelined); posbits, rank_lists, lazy_aux (the
+ * position bits and the position-sorted lists, and when the lists come into being); cache_calls, prewarm
  * (memory); watchdog_s; debug; test_cap_limit, test_genbits, test_k8_delay, test_fail_alloc, test_stall_s,
  * test_wide_batch (parity and failure tests).  RESULTS NEVER DEPEND ON ANY OF THEM.  The full table with ranges is
  * kOptions in asgart_amd/csrc/index.hip, every field is described in struct Options

@@ -1165,10 +1165,10 @@ def test_watchdog_gives_up_on_a_stalled_device_and_names_the_phase(hiplib):
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
 
 
-def test_block_cache_is_trimmed_and_filter_can_be_switched_off(hiplib):
+def test_block_cache_is_trimmed_and_position_bits_can_be_switched_off(hiplib):
     """(advisor, round 3) The blocks the library keeps for reuse go back to the device when the last index closes and on
-    asgart_trim_cache; option kfilter_bits = 0 really searches without the presence filter (its position bitmaps used
-    to survive and go on filtering) and switching it back on rebuilds both without leaking the old bitmap."""
+    asgart_trim_cache; option posbits = 0 really searches without the position bits, and switching it off and on again
+    and again does not grow the footprint."""
     import torch
 
     pr, cli = _battery_case("dense_repeats")
@@ -1181,21 +1181,22 @@ def test_block_cache_is_trimmed_and_filter_can_be_switched_off(hiplib):
         return torch.cuda.mem_get_info()[0]
 
     with asgart_amd.Index(pr.data, oidx.sa) as idx:
-        a = idx.search_duplications_raw(pr.chunks, st)
+        a = idx.search_duplications_raw(pr.chunks, st)   # (the first call learns the bits)
+        a2 = idx.search_duplications_raw(pr.chunks, st)
         rej_on = idx.stats(1).probes_filter_rejected
-        idx.set_option("kfilter_bits", 0)
+        idx.set_option("posbits", 0)
         b = idx.search_duplications_raw(pr.chunks, st)
         rej_off = idx.stats(1).probes_filter_rejected
-        idx.set_option("kfilter_bits", 30)
+        idx.set_option("posbits", 1)
         f0 = None
-        for _ in range(4):   # (rebuilding the filter again and again must not grow the footprint)
-            idx.set_option("kfilter_bits", 0)
-            idx.set_option("kfilter_bits", 30)
+        for _ in range(4):   # (switching the bits off and on again and again must not grow the footprint)
+            idx.set_option("posbits", 0)
+            idx.set_option("posbits", 1)
             c = idx.search_duplications_raw(pr.chunks, st)
             f1 = free_bytes()
             assert f0 is None or f1 >= f0 - (1 << 20), (f0, f1)
             f0 = f1
-        for got in (a, b, c):
+        for got in (a, a2, b, c):
             assert np.array_equal(got[0], exp[0]) and np.array_equal(got[1], exp[1])
         assert rej_on > 0 and rej_off == 0
     assert asgart_amd.trim_cache(0) >= 0
@@ -1220,26 +1221,28 @@ def test_replica_from_device_buffers_matches(hiplib):
 
 
 @pytest.mark.parametrize("name", ["dense_repeats", "satellites", "masked", "k12"])
-def test_refined_position_bits_reject_more_and_change_nothing(hiplib, name, monkeypatch):
-    """Option posbits = 2 (default): a text position keeps its filter bit only if a hit of its probe can be KEPT (an
-    occurrence of the probe's k-mer behind the probe, src/automaton.rs:105-114 in text coordinates) -- decided once, when
-    the bits are built.  Against posbits = 1 (the k-mer filter's answer): more probes answered without a lookup, and
-    NOTHING else changes -- families, per-probe hit rows, and every counter incl. raw_hits (the intervals of the probes
-    the bits answered are looked up when the statistics are asked for), in every orientation, 32- and 64-bit slots."""
+def test_learned_position_bits_reject_more_and_change_nothing(hiplib, name, monkeypatch):
+    """Option posbits = 1 (default): a text position keeps its bit only if a hit of its probe can be KEPT (an occurrence
+    of the probe's k-mer behind the probe, src/automaton.rs:105-114 in text coordinates) -- learned by the searches, so
+    one warm-up call per orientation comes first.  Against posbits = 0 (every probe looked up): more probes answered
+    without a lookup, and NOTHING else changes -- families, per-probe hit rows, and every counter incl. raw_hits (the
+    intervals of the probes the bits answered are looked up when the statistics are asked for), in every orientation,
+    32- and 64-bit slots."""
     pr, cli = _battery_case(name)
     seen = {}
     for wide in ("0", "1"):
         monkeypatch.setenv("ASGART_FORCE_WIDE", wide)
-        for pb in ("1", "2"):
+        for pb in ("0", "1"):
             monkeypatch.setenv("ASGART_POSBITS", pb)
             with asgart_amd.Index(pr.data, None) as idx:
                 for reverse, complement in MODES:
                     st = asgart_amd.RunSettings.from_cli(reverse=reverse, complement=complement, **cli)
+                    idx.search_duplications_raw(pr.chunks, st)   # (warm-up: the bits are learned)
                     fam = idx.search_duplications_raw(pr.chunks, st)
                     stt = idx.stats(1).as_dict()
                     rows = idx.probe_hits(pr.chunks, st)
                     key = (wide, reverse, complement)
-                    if pb == "1":
+                    if pb == "0":
                         seen[key] = (fam, stt, rows)
                         continue
                     fam1, stt1, rows1 = seen[key]
@@ -1283,7 +1286,7 @@ def test_learned_position_bits_hold_for_any_chunk_list(hiplib, name, monkeypatch
 
 def test_lazy_filter_and_lists_same_results(hiplib, monkeypatch):
     """Default behaviour of an index (option lazy_aux = 1; the suite otherwise runs with 0 so that every first call
-    takes the filtered paths): the first search of an orientation runs without the presence filter and without the
+    takes the list-assisted paths): the first search of an orientation runs with blank position bits and without the
     position-sorted lists, the second one with both -- identical families, and identical to the oracle."""
     monkeypatch.setenv("ASGART_LAZY_AUX", "1")
     pr, cli = _battery_case("dense_repeats")

@@ -13,7 +13,7 @@ import asgart_amd  # noqa: E402
 from asgart_amd import prep, synth  # noqa: E402
 
 # option defaults (asgart_amd/csrc/index.hpp: struct Options); grid<t> = 0 means "default grid"
-DEFAULTS = {"shard_lookback": 4096, "arms_kernel": 1, "kfilter_bits": 30, "long3": 16384, "cap1": 256,
+DEFAULTS = {"shard_lookback": 4096, "arms_kernel": 1, "long3": 16384, "cap1": 256,
             "test_cap_limit": -1, "test_genbits": 22, "tier_order": 3654217}
 
 
