@@ -23,6 +23,7 @@ import numpy as np
 __all__ = [
     "AsgartError", "RunSettings", "ProtoSD", "Strand", "Index", "Searcher", "SearchDuplications",
     "load_library", "library_path", "ABI_SYMBOLS", "sa_build64", "search_duplications_multi", "merge_shards",
+    "score_owners", "score_costs", "compute_scores_multi",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -37,7 +38,8 @@ ABI_SYMBOLS = (
     "asgart_search_duplications_multi", "asgart_search_duplications_ex", "asgart_search_duplications_passes",
     "asgart_search_duplications_passes_shard", "asgart_families_keys",
     "asgart_index_export", "asgart_index_create_device", "asgart_trim_cache", "asgart_post_process",
-    "asgart_debug_dump_stacks", "asgart_prepare_data",
+    "asgart_debug_dump_stacks", "asgart_prepare_data", "asgart_score_owners", "asgart_score_costs",
+    "asgart_compute_scores_shard", "asgart_compute_scores_multi",
 )
 
 
@@ -172,6 +174,14 @@ def load_library() -> C.CDLL:
     L.asgart_sa_read.restype = C.c_int32
     L.asgart_compute_scores.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
     L.asgart_compute_scores.restype = C.c_int32
+    L.asgart_score_owners.argtypes = [vp, C.c_int64, C.c_int32, vp]
+    L.asgart_score_owners.restype = C.c_int32
+    L.asgart_score_costs.argtypes = [vp, C.c_int64, vp]
+    L.asgart_score_costs.restype = C.c_int32
+    L.asgart_compute_scores_shard.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.asgart_compute_scores_shard.restype = C.c_int64
+    L.asgart_compute_scores_multi.argtypes = [C.POINTER(vp), C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, vp]
+    L.asgart_compute_scores_multi.restype = C.c_int32
     L.asgart_probe_hits.argtypes = [vp, vp, C.c_int64, C.POINTER(_Settings), vp, vp, vp, u64p]
     L.asgart_probe_hits.restype = C.c_int64
     L.asgart_get_stats.argtypes = [vp, C.c_uint32, C.POINTER(Stats)]
@@ -361,6 +371,17 @@ class Index:
                                                     int(complemented), _ptr(out)))
         return out
 
+    def compute_scores_shard(self, sds: np.ndarray, reversed_: bool = False, complemented: bool = False,
+                             shard: int = 0, n_shards: int = 1) -> np.ndarray:
+        """compute_scores for shard `shard` of `n_shards` (asgart_compute_scores_shard): `sds` is the FULL list, the
+        same on every rank; the duplications score_owners(sds, n_shards) gives to `shard` are scored, bit-equal to
+        compute_scores.  -> float32[len(sds)], NaN at the entries of the other shards."""
+        sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+        out = np.full(len(sds), np.nan, dtype=np.float32)
+        _check(load_library().asgart_compute_scores_shard(self._h, _ptr(sds), len(sds), int(reversed_),
+                                                          int(complemented), int(shard), int(n_shards), _ptr(out)))
+        return out
+
     def post_process(self, offs: np.ndarray, sds: np.ndarray, threads: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """FilterNs -> ReOrder -> ReduceOverlap -> Sort (reference src/bin/asgart.rs:738-747) on raw family arrays as
         search_duplications_raw returns them -> the same form (asgart_post_process: N counts on the GPU, the reduction
@@ -488,6 +509,36 @@ def search_duplications_multi(indices: Sequence[Index], chunks: Sequence[Tuple[i
     finally:
         L.asgart_families_free(h)
     return offs, sds
+
+
+def score_owners(sds: np.ndarray, n_shards: int) -> np.ndarray:
+    """asgart_score_owners (host code, no device needed): the shard of each duplication of an (n, 4) uint64 array under
+    the cost-balanced split that Index.compute_scores_shard uses -> int32[n]."""
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    out = np.zeros(len(sds), dtype=np.int32)
+    _check(load_library().asgart_score_owners(_ptr(sds), len(sds), int(n_shards), _ptr(out)))
+    return out
+
+
+def score_costs(sds: np.ndarray) -> np.ndarray:
+    """asgart_score_costs: the cost (device wave-steps) score_owners balances, per duplication -> uint64[n]."""
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    out = np.zeros(len(sds), dtype=np.uint64)
+    _check(load_library().asgart_score_costs(_ptr(sds), len(sds), _ptr(out)))
+    return out
+
+
+def compute_scores_multi(indices: Sequence[Index], sds: np.ndarray, reversed_: bool = False,
+                         complemented: bool = False) -> np.ndarray:
+    """asgart_compute_scores_multi: one shard per index replica, one host thread each -> float32[n], the array
+    Index.compute_scores gives."""
+    L = load_library()
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    out = np.empty(len(sds), dtype=np.float32)
+    arr = (C.c_void_p * len(indices))(*[i._h for i in indices])
+    _check(L.asgart_compute_scores_multi(arr, len(indices), _ptr(sds), len(sds), int(reversed_), int(complemented),
+                                         _ptr(out)))
+    return out
 
 
 def trim_cache(device: int = 0) -> int:

@@ -13,6 +13,12 @@
 #include "index.hpp"
 
 #include <algorithm>
+#include <functional>
+#include <new>
+#include <queue>
+#include <string>
+#include <thread>
+#include <utility>
 #include <vector>
 
 namespace asgart {
@@ -20,6 +26,22 @@ namespace {
 
 constexpr int kScoreThreads = 256;  // four duplications per workgroup
 constexpr int kScoreRows = 16;      // rows per lane
+constexpr uint32_t kBand = 64u * kScoreRows;  // rows of one band (a wave's 64 lanes)
+constexpr int kLongWaves = 16;                // waves of levenshtein_long_kernel's workgroup ...
+constexpr int kLongRows = kLongWaves + 2;     // ... and the boundary rows it has in flight
+// A duplication whose left arm has at least half a workgroup's bands goes to levenshtein_long_kernel, the rest to
+// levenshtein_kernel.  The dispatch (score_plan) and the cost model of the shards (score_cost) both read these.
+constexpr uint64_t kLongMinRows = (uint64_t)kBand * kLongWaves / 2u;
+
+__host__ __device__ inline bool score_is_long(uint64_t left_length) { return left_length + 1u >= kLongMinRows; }
+
+// steps per chunk of levenshtein_long_kernel for a right arm of n_steps - 63 bases: at most 2 kLongWaves chunks per band,
+// and >= 128 steps (a band's bottom row is stored 64 columns at a time, 62 steps late)
+__host__ __device__ inline uint32_t long_chunk_steps(uint64_t n_steps) {
+    uint32_t C = (uint32_t)((n_steps + 2u * kLongWaves - 1u) / (2u * kLongWaves));
+    C = (C + 63u) & ~63u;
+    return C > 128u ? C : 128u;
+}
 
 // utils::complement_nucleotide / structs::TR on the normalised alphabet; anything else is kept
 __device__ inline uint32_t complement_base(uint32_t c) {
@@ -250,15 +272,12 @@ __global__ __launch_bounds__(kScoreThreads) void levenshtein_kernel(const uint8_
 // chunks and band b+1 runs two chunks behind band b (its top boundary is band b's bottom row, whose
 // columns up to (c+1) C are complete after chunk c+1).  With at most 2 kLongWaves chunks per band a
 // wave finishes band b exactly when band b + kLongWaves may start, so every wave stays busy.
-constexpr int kLongWaves = 16;
-constexpr int kLongRows = kLongWaves + 2;  // boundary rows in flight
-
 __global__ __launch_bounds__(64 * kLongWaves) void levenshtein_long_kernel(
     const uint8_t *__restrict__ text, const asgart_proto_sd *__restrict__ sds, const uint32_t *__restrict__ list,
     uint64_t n_list, int reversed, int complemented, uint32_t *__restrict__ scratch, uint64_t scratch_stride,
     float *__restrict__ identity) {
     constexpr int R = kScoreRows;
-    constexpr uint32_t BAND = 64u * R;
+    constexpr uint32_t BAND = kBand;
     __shared__ uint32_t s_dist;
     const int lane = threadIdx.x & 63;
     const uint32_t w = threadIdx.x >> 6;
@@ -270,8 +289,7 @@ __global__ __launch_bounds__(64 * kLongWaves) void levenshtein_long_kernel(
         const RightArm rb{text + sd.right, lb, reversed, complemented};
         const uint32_t n_bands = (la + BAND - 1u) / BAND;
         const uint32_t n_steps = lb + 63u;
-        uint32_t C = (n_steps + 2u * kLongWaves - 1u) / (2u * kLongWaves);
-        C = max(128u, (C + 63u) & ~63u);  // >= 128: a band's bottom row is stored 64 columns at a time, 62 steps late
+        const uint32_t C = long_chunk_steps(n_steps);
         const uint32_t n_chunks = (n_steps + C - 1u) / C;  // <= 2 kLongWaves
         const uint32_t n_super = 2u * (n_bands - 1u) + n_chunks;
         uint32_t result = 0;
@@ -301,34 +319,145 @@ __global__ __launch_bounds__(64 * kLongWaves) void levenshtein_long_kernel(
     }
 }
 
-}  // namespace
-}  // namespace asgart
-
-extern "C" int32_t asgart_compute_scores(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
-                                         int32_t reversed, int32_t complemented, float *identity) {
-    using namespace asgart;
-    if (!idx || n_sd < 0 || (n_sd > 0 && (!sds || !identity))) {
-        set_error("asgart_compute_scores: bad argument");
-        return ASGART_E_ARG;
+// ---- a shard of a ComputeScore call: its duplications gathered out of the full list, on the device --------------
+// sub[k] = sds[owned[k]]; the Levenshtein kernels then walk sub through list[k] = k and write identity[k].
+__global__ __launch_bounds__(256) void gather_owned_kernel(const asgart_proto_sd *__restrict__ sds,
+                                                           const uint32_t *__restrict__ owned, uint64_t n_owned,
+                                                           asgart_proto_sd *__restrict__ sub, uint32_t *__restrict__ list) {
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_owned; k += (uint64_t)gridDim.x * blockDim.x) {
+        sub[k] = sds[owned[k]];
+        list[k] = (uint32_t)k;
     }
-    if (n_sd == 0) return 0;
+}
+
+// the kernels count rows, columns and distances in 32 bits
+bool arms_too_long(const asgart_proto_sd &sd) {
+    return sd.left_length >= 0xFFFFFFFFull || sd.right_length >= 0xFFFFFFFFull ||
+           sd.left_length + sd.right_length + 2u >= 0xFFFFFFFFull;
+}
+
+// What one duplication costs the device, in wave-steps (a step: one column of a band, 64 lanes x kScoreRows cells), the
+// way the kernels dispatch it.  Short: one wave walks ceil(la / kBand) bands of lb + 63 steps.  Long: kLongWaves waves
+// are held for the 2 (n_bands - 1) + n_chunks chunks of C steps of the band pipeline, its fill and drain included.
+// Inclusive ranges: la = left_length + 1, lb = right_length + 1 (la x lb DP cells).
+uint64_t score_cost(const asgart_proto_sd &sd) {
+    const uint64_t la = sd.left_length + 1u, lb = sd.right_length + 1u;
+    const uint64_t n_bands = (la + kBand - 1u) / kBand, n_steps = lb + 63u;
+    if (!score_is_long(sd.left_length)) return n_bands * n_steps;
+    const uint64_t C = long_chunk_steps(n_steps);
+    const uint64_t n_chunks = (n_steps + C - 1u) / C;
+    return (uint64_t)kLongWaves * (2u * (n_bands - 1u) + n_chunks) * C;
+}
+
+// Greedy longest first onto the least-loaded shard (ties: lower ordinal first, lower shard first).  Only the first
+// min(n_shards, n_sd) shards can receive anything: the heap holds those.
+void score_owners(const asgart_proto_sd *sds, int64_t n_sd, int32_t n_shards, int32_t *owner) {
+    std::vector<uint64_t> cost((size_t)n_sd);
+    std::vector<uint32_t> order((size_t)n_sd);
+    for (int64_t q = 0; q < n_sd; ++q) {
+        cost[(size_t)q] = score_cost(sds[q]);
+        order[(size_t)q] = (uint32_t)q;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cost[x] > cost[y]; });
+    using Load = std::pair<unsigned __int128, int32_t>;
+    std::priority_queue<Load, std::vector<Load>, std::greater<Load>> heap;
+    const int64_t used = std::min<int64_t>(n_shards, n_sd);
+    for (int32_t r = 0; r < (int32_t)used; ++r) heap.push(Load{0, r});
+    for (uint32_t q : order) {
+        Load l = heap.top();
+        heap.pop();
+        owner[q] = l.second;
+        l.first += cost[q];
+        heap.push(l);
+    }
+}
+
+// the reference slices [p ..= p + len] and panics past the end of the strand
+int32_t check_scores_input(const char *fn, const asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd) {
     const uint64_t n = (uint64_t)idx->n;
     for (int64_t q = 0; q < n_sd; ++q) {
         const asgart_proto_sd &sd = sds[q];
-        // the reference slices [p ..= p + len] and panics past the end of the strand
         if (sd.left > n || sd.left_length >= n - sd.left || sd.right > n || sd.right_length >= n - sd.right) {
-            set_error("asgart_compute_scores: duplication %lld reaches past the end of the text", (long long)q);
+            set_error("%s: duplication %lld reaches past the end of the text", fn, (long long)q);
             return ASGART_E_ARG;
         }
         if (sd.left_length == 0 && sd.right_length == 0) {
-            set_error("asgart_compute_scores: duplication %lld has two empty arms", (long long)q);
+            set_error("%s: duplication %lld has two empty arms", fn, (long long)q);
             return ASGART_E_ARG;
         }
-        if (sd.left_length + sd.right_length + 2u >= 0xFFFFFFFFull) {
-            set_error("asgart_compute_scores: arms of 2^32 bases are not supported");
+        if (arms_too_long(sd)) {
+            set_error("%s: arms of 2^32 bases are not supported", fn);
             return ASGART_E_CAP;
         }
     }
+    return 0;
+}
+
+// Long duplications (many bands) get a whole workgroup each, the rest one wave each; both lists are served largest first.
+struct ScorePlan {
+    std::vector<uint32_t> long_list, wave_list;  // ordinals into the caller's sds
+    uint64_t max_lb_long = 0, max_lb_wave = 0;   // longest right arm of each list (of the multi-band ones for wave_list)
+    unsigned grid_w = 0, grid_l = 0;
+    uint64_t stride_w = 0, stride_l = 0;
+    size_t scratch_w = 0, scratch_l = 0;         // u32 entries
+};
+
+ScorePlan score_plan(const asgart_proto_sd *sds, std::vector<uint32_t> order) {
+    ScorePlan p;
+    auto cells = [&](uint32_t q) { return (double)(sds[q].left_length + 1u) * (double)(sds[q].right_length + 1u); };
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells(x) > cells(y); });
+    for (uint32_t q : order) {
+        const asgart_proto_sd &sd = sds[q];
+        if (score_is_long(sd.left_length)) {
+            p.long_list.push_back(q);
+            p.max_lb_long = std::max<uint64_t>(p.max_lb_long, sd.right_length + 1u);
+        } else {
+            p.wave_list.push_back(q);
+            if (sd.left_length + 1u > kBand) p.max_lb_wave = std::max<uint64_t>(p.max_lb_wave, sd.right_length + 1u);
+        }
+    }
+    const unsigned waves_per_wg = kScoreThreads / 64;
+    p.grid_w = (unsigned)std::min<size_t>((p.wave_list.size() + waves_per_wg - 1) / waves_per_wg, 512);
+    p.grid_l = (unsigned)std::min<size_t>(p.long_list.size(), 256);
+    p.stride_w = p.max_lb_wave ? p.max_lb_wave + 64u : 0u;
+    p.stride_l = p.max_lb_long + 64u;
+    p.scratch_w = (size_t)p.stride_w * 2u * p.grid_w * waves_per_wg;
+    p.scratch_l = (size_t)p.stride_l * kLongRows * p.grid_l;
+    return p;
+}
+
+int32_t score_reserve(Workspace &w, const ScorePlan &p) {
+    RC_TRY(w.scratch.reserve((p.scratch_w + p.scratch_l) * 4u + 64));
+    return w.counters.reserve(1024);  // the search pipeline keeps its device counters here too
+}
+
+// d_list: the plan's long list, then its wave list, as indices into d_sds; identities go to d_identity[d_list[..]]
+int32_t score_launch(const asgart_index *idx, Workspace &w, hipStream_t s, const ScorePlan &p,
+                     const asgart_proto_sd *d_sds, const uint32_t *d_list, int32_t reversed, int32_t complemented,
+                     float *d_identity) {
+    unsigned long long *cursor = w.counters.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(cursor, 0, 8, s));
+    if (p.grid_l)
+        levenshtein_long_kernel<<<p.grid_l, 64 * kLongWaves, 0, s>>>(
+            idx->d_text, d_sds, d_list, (uint64_t)p.long_list.size(), reversed != 0, complemented != 0,
+            w.scratch.as<uint32_t>() + p.scratch_w, p.stride_l, d_identity);
+    if (p.grid_w)
+        levenshtein_kernel<<<p.grid_w, kScoreThreads, 0, s>>>(
+            idx->d_text, d_sds, d_list + p.long_list.size(), (uint64_t)p.wave_list.size(), reversed != 0,
+            complemented != 0, w.scratch.as<uint32_t>(), p.stride_w, cursor, d_identity);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Scores the duplications q with owner[q] == shard (owner NULL: all of them) on one of idx's call contexts; writes
+// identity[q] for those only.  Returns how many, < 0 on error.  The full list goes to the device once and the owned
+// ones are gathered there.
+int64_t score_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd, const int32_t *owner, int32_t shard,
+                    int32_t reversed, int32_t complemented, float *identity) {
+    std::vector<uint32_t> mine;
+    for (int64_t q = 0; q < n_sd; ++q)
+        if (owner[q] == shard) mine.push_back((uint32_t)q);
+    if (mine.empty()) return 0;
     REFUSE_POISONED(idx);
     HIP_TRY(hipSetDevice(idx->device));
     int which = 0;
@@ -340,55 +469,182 @@ extern "C" int32_t asgart_compute_scores(asgart_index *idx, const asgart_proto_s
     } unlock{idx, which};
     Workspace &w = cx.ws;
     hipStream_t s = cx.stream;
-    // Long duplications (many bands) get a whole workgroup each, the rest one wave each; both lists
-    // are served largest first.
-    std::vector<uint32_t> order((size_t)n_sd);
-    for (int64_t q = 0; q < n_sd; ++q) order[(size_t)q] = (uint32_t)q;
-    auto cells = [&](uint32_t q) { return (double)(sds[q].left_length + 1u) * (double)(sds[q].right_length + 1u); };
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells(x) > cells(y); });
-    const uint64_t long_rows = 64ull * kScoreRows * (uint64_t)kLongWaves / 2u;  // half a workgroup's bands
-    std::vector<uint32_t> long_list, wave_list;
-    uint64_t max_lb_long = 0, max_lb_wave = 0;
-    for (uint32_t q : order) {
-        const asgart_proto_sd &sd = sds[q];
-        if (sd.left_length + 1u >= long_rows) {
-            long_list.push_back(q);
-            max_lb_long = std::max<uint64_t>(max_lb_long, sd.right_length + 1u);
-        } else {
-            wave_list.push_back(q);
-            if (sd.left_length + 1u > 64u * (uint64_t)kScoreRows) max_lb_wave = std::max<uint64_t>(max_lb_wave, sd.right_length + 1u);
-        }
+    const ScorePlan p = score_plan(sds, mine);
+    std::vector<uint32_t> owned(p.long_list);  // the schedule, as ordinals into the full list
+    owned.insert(owned.end(), p.wave_list.begin(), p.wave_list.end());
+    const size_t m = owned.size();
+    // the buffers asgart_compute_scores uses: out_a = full list, then the gathered one; seg_vals = list, then ordinals
+    RC_TRY(w.out_a.reserve(((size_t)n_sd + m) * sizeof(asgart_proto_sd)));
+    RC_TRY(w.seg_vals.reserve(m * 8 + 64));
+    RC_TRY(w.out_b.reserve(m * sizeof(float) + 64));
+    RC_TRY(score_reserve(w, p));
+    const asgart_proto_sd *d_sds = w.out_a.as<asgart_proto_sd>();
+    asgart_proto_sd *d_sub = w.out_a.as<asgart_proto_sd>() + n_sd;
+    uint32_t *d_list = w.seg_vals.as<uint32_t>(), *d_owned = d_list + m;
+    HIP_TRY(hipMemcpyAsync(w.out_a.p, sds, (size_t)n_sd * sizeof(asgart_proto_sd), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_owned, owned.data(), m * 4, hipMemcpyHostToDevice, s));
+    const unsigned grid_g = (unsigned)std::min<size_t>((m + 255) / 256, 1024);
+    gather_owned_kernel<<<grid_g, 256, 0, s>>>(d_sds, d_owned, (uint64_t)m, d_sub, d_list);
+    HIP_TRY(hipGetLastError());
+    RC_TRY(score_launch(idx, w, s, p, d_sub, d_list, reversed, complemented, w.out_b.as<float>()));
+    std::vector<float> got(m);
+    HIP_TRY(read_back(got.data(), w.out_b.p, m * sizeof(float), s));
+    for (size_t k = 0; k < m; ++k) identity[owned[k]] = got[k];
+    return (int64_t)m;
+}
+
+int32_t check_shard_args(const char *fn, const asgart_proto_sd *sds, int64_t n_sd, int32_t n_shards, const void *out) {
+    if (n_sd < 0 || (n_sd > 0 && (!sds || !out))) {
+        set_error("%s: bad argument", fn);
+        return ASGART_E_ARG;
     }
-    const unsigned waves_per_wg = kScoreThreads / 64;
-    const unsigned grid_w = (unsigned)std::min<size_t>((wave_list.size() + waves_per_wg - 1) / waves_per_wg, 512);
-    const unsigned grid_l = (unsigned)std::min<size_t>(long_list.size(), 256);
-    const uint64_t stride_w = max_lb_wave ? max_lb_wave + 64u : 0u, stride_l = max_lb_long + 64u;
-    const size_t scratch_w = (size_t)stride_w * 2u * grid_w * waves_per_wg;          // u32 entries
-    const size_t scratch_l = (size_t)stride_l * kLongRows * grid_l;
+    if (n_shards < 1) {
+        set_error("%s: %d shards (at least 1)", fn, n_shards);
+        return ASGART_E_ARG;
+    }
+    if ((uint64_t)n_sd >= 0xFFFFFFFFull) {  // (ordinals are 32-bit)
+        set_error("%s: 2^32 duplications in one call are not supported", fn);
+        return ASGART_E_CAP;
+    }
+    for (int64_t q = 0; q < n_sd; ++q)
+        if (arms_too_long(sds[q])) {
+            set_error("%s: arms of 2^32 bases are not supported", fn);
+            return ASGART_E_CAP;
+        }
+    return 0;
+}
+
+}  // namespace
+}  // namespace asgart
+
+extern "C" int32_t asgart_compute_scores(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
+                                         int32_t reversed, int32_t complemented, float *identity) {
+    using namespace asgart;
+    if (!idx || n_sd < 0 || (n_sd > 0 && (!sds || !identity))) {
+        set_error("asgart_compute_scores: bad argument");
+        return ASGART_E_ARG;
+    }
+    if (n_sd == 0) return 0;
+    RC_TRY(check_scores_input("asgart_compute_scores", idx, sds, n_sd));
+    REFUSE_POISONED(idx);
+    HIP_TRY(hipSetDevice(idx->device));
+    int which = 0;
+    SearchCtx &cx = idx->acquire_one(&which);
+    struct Unlock {
+        asgart_index *i;
+        int w;
+        ~Unlock() { i->release_one(w); }
+    } unlock{idx, which};
+    Workspace &w = cx.ws;
+    hipStream_t s = cx.stream;
+    std::vector<uint32_t> all((size_t)n_sd);
+    for (int64_t q = 0; q < n_sd; ++q) all[(size_t)q] = (uint32_t)q;
+    const ScorePlan p = score_plan(sds, std::move(all));
     RC_TRY(w.out_a.reserve((size_t)n_sd * sizeof(asgart_proto_sd)));
     RC_TRY(w.out_b.reserve((size_t)n_sd * sizeof(float) + 64));
     RC_TRY(w.seg_vals.reserve((size_t)n_sd * 4 + 64));
-    RC_TRY(w.scratch.reserve((scratch_w + scratch_l) * 4u + 64));
-    RC_TRY(w.counters.reserve(1024));  // the search pipeline keeps its device counters here too
-    unsigned long long *cursor = w.counters.as<unsigned long long>();
+    RC_TRY(score_reserve(w, p));
     uint32_t *d_list = w.seg_vals.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(cursor, 0, 8, s));
     HIP_TRY(hipMemcpyAsync(w.out_a.p, sds, (size_t)n_sd * sizeof(asgart_proto_sd), hipMemcpyHostToDevice, s));
-    if (!long_list.empty())
-        HIP_TRY(hipMemcpyAsync(d_list, long_list.data(), long_list.size() * 4, hipMemcpyHostToDevice, s));
-    if (!wave_list.empty())
-        HIP_TRY(hipMemcpyAsync(d_list + long_list.size(), wave_list.data(), wave_list.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(stream_sync(s));  // the host vectors go out of use below
-    if (grid_l)
-        levenshtein_long_kernel<<<grid_l, 64 * kLongWaves, 0, s>>>(
-            idx->d_text, w.out_a.as<asgart_proto_sd>(), d_list, (uint64_t)long_list.size(), reversed != 0,
-            complemented != 0, w.scratch.as<uint32_t>() + scratch_w, stride_l, w.out_b.as<float>());
-    if (grid_w)
-        levenshtein_kernel<<<grid_w, kScoreThreads, 0, s>>>(
-            idx->d_text, w.out_a.as<asgart_proto_sd>(), d_list + long_list.size(), (uint64_t)wave_list.size(),
-            reversed != 0, complemented != 0, w.scratch.as<uint32_t>(), stride_w, cursor, w.out_b.as<float>());
-    HIP_TRY(hipGetLastError());
+    if (!p.long_list.empty())
+        HIP_TRY(hipMemcpyAsync(d_list, p.long_list.data(), p.long_list.size() * 4, hipMemcpyHostToDevice, s));
+    if (!p.wave_list.empty())
+        HIP_TRY(hipMemcpyAsync(d_list + p.long_list.size(), p.wave_list.data(), p.wave_list.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(stream_sync(s));  // (pageable host sources)
+    RC_TRY(score_launch(idx, w, s, p, w.out_a.as<asgart_proto_sd>(), d_list, reversed, complemented, w.out_b.as<float>()));
     HIP_TRY(read_back(identity, w.out_b.p, (size_t)n_sd * sizeof(float), s));
     HIP_TRY(stream_sync(s));
+    return 0;
+}
+
+extern "C" int32_t asgart_score_costs(const asgart_proto_sd *sds, int64_t n_sd, uint64_t *cost) {
+    using namespace asgart;
+    RC_TRY(check_shard_args("asgart_score_costs", sds, n_sd, 1, cost));
+    for (int64_t q = 0; q < n_sd; ++q) cost[q] = score_cost(sds[q]);
+    return 0;
+}
+
+extern "C" int32_t asgart_score_owners(const asgart_proto_sd *sds, int64_t n_sd, int32_t n_shards, int32_t *owner) {
+    using namespace asgart;
+    RC_TRY(check_shard_args("asgart_score_owners", sds, n_sd, n_shards, owner));
+    try {
+        score_owners(sds, n_sd, n_shards, owner);
+    } catch (const std::bad_alloc &) {
+        set_error("asgart_score_owners: out of host memory");
+        return ASGART_E_OOM;
+    }
+    return 0;
+}
+
+extern "C" int64_t asgart_compute_scores_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
+                                               int32_t reversed, int32_t complemented, int32_t shard, int32_t n_shards,
+                                               float *identity) {
+    using namespace asgart;
+    static const char *fn = "asgart_compute_scores_shard";
+    if (!idx) {
+        set_error("%s: bad argument", fn);
+        return ASGART_E_ARG;
+    }
+    RC_TRY(check_shard_args(fn, sds, n_sd, n_shards, identity));
+    if (shard < 0 || shard >= n_shards) {
+        set_error("%s: bad shard %d of %d", fn, shard, n_shards);
+        return ASGART_E_ARG;
+    }
+    if (n_sd == 0) return 0;
+    RC_TRY(check_scores_input(fn, idx, sds, n_sd));  // the whole list: every rank fails alike
+    try {
+        std::vector<int32_t> owner((size_t)n_sd);
+        score_owners(sds, n_sd, n_shards, owner.data());
+        return score_shard(idx, sds, n_sd, owner.data(), shard, reversed, complemented, identity);
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", fn);
+        return ASGART_E_OOM;
+    }
+}
+
+extern "C" int32_t asgart_compute_scores_multi(asgart_index *const *indices, int32_t n_devices,
+                                               const asgart_proto_sd *sds, int64_t n_sd, int32_t reversed,
+                                               int32_t complemented, float *identity) {
+    using namespace asgart;
+    static const char *fn = "asgart_compute_scores_multi";
+    if (!indices || n_devices < 1 || n_devices > 64) {
+        set_error("%s: bad argument: %d devices", fn, n_devices);
+        return ASGART_E_ARG;
+    }
+    for (int32_t r = 0; r < n_devices; ++r)
+        if (!indices[r] || indices[r]->n != indices[0]->n) {
+            set_error("%s: index %d is NULL or not a replica of index 0", fn, r);
+            return ASGART_E_ARG;
+        }
+    RC_TRY(check_shard_args(fn, sds, n_sd, n_devices, identity));
+    if (n_sd == 0) return 0;
+    RC_TRY(check_scores_input(fn, indices[0], sds, n_sd));
+    try {
+        std::vector<int32_t> owner((size_t)n_sd);
+        score_owners(sds, n_sd, n_devices, owner.data());
+        // one host thread per device, shard r of n_devices; the shards write disjoint entries of identity
+        std::vector<int64_t> rcs((size_t)n_devices, 0);
+        std::vector<std::string> errs((size_t)n_devices);
+        std::vector<std::thread> workers;
+        for (int32_t r = 0; r < n_devices; ++r)
+            workers.emplace_back([&, r]() {
+                try {
+                    rcs[r] = score_shard(indices[r], sds, n_sd, owner.data(), r, reversed, complemented, identity);
+                    if (rcs[r] < 0) errs[r] = asgart_last_error();  // the message is thread-local
+                } catch (const std::bad_alloc &) {
+                    rcs[r] = ASGART_E_OOM;
+                    errs[r] = "out of host memory";
+                }
+            });
+        for (auto &t : workers) t.join();
+        for (int32_t r = 0; r < n_devices; ++r)
+            if (rcs[r] < 0) {
+                set_error("%s: shard %d of %d: %s", fn, r, n_devices, errs[r].c_str());
+                return (int32_t)rcs[r];
+            }
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", fn);
+        return ASGART_E_OOM;
+    }
     return 0;
 }

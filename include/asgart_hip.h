@@ -316,6 +316,43 @@ void asgart_families_free(asgart_families *f);
 int32_t asgart_compute_scores(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
                               int32_t reversed, int32_t complemented, float *identity);
 
+/* ComputeScore over several GPUs.  The reference scores every duplication of a run in one loop
+ * (src/bin/asgart.rs:98-112); each identity depends on its own duplication alone, so the list splits by
+ * duplication and the shards' values are copied, never reduced: every value is bit-equal to what
+ * asgart_compute_scores gives for the same duplication.  The DP of one duplication is not split.
+ *
+ * asgart_score_owners: host code, needs no device.  owner[q] in [0, n_shards) for each of the n_sd
+ * duplications: greedy, longest first (ties: lower q first) onto the least-loaded shard (ties: lower shard
+ * first).  The load is the device time the Levenshtein kernels take for a duplication, in wave-steps, as
+ * asgart_score_costs reports it: its (left_length + 1) x (right_length + 1) DP cells rounded up to the
+ * shape of the kernel it is dispatched to (one wave per duplication, or a 16-wave band pipeline for left
+ * arms of 8192 rows and more, with the pipeline's fill and drain).  Bound: the most loaded shard costs at
+ * most total / n_shards + the largest single cost.  The result depends only on the lengths and n_shards.
+ * Errors: n_shards < 1 (ASGART_E_ARG), arms of 2^32 bases (ASGART_E_CAP). */
+int32_t asgart_score_owners(const asgart_proto_sd *sds, int64_t n_sd, int32_t n_shards, int32_t *owner);
+/* The cost model asgart_score_owners balances: cost[q] for each duplication (host code, needs no device). */
+int32_t asgart_score_costs(const asgart_proto_sd *sds, int64_t n_sd, uint64_t *cost);
+
+/* Replaces the ComputeScore loop (src/bin/asgart.rs:98-112) for shard `shard` of `n_shards` -- one process
+ * per GPU, index replicated: every rank passes the SAME full list; the call scores the duplications
+ * asgart_score_owners gives to `shard` and writes identity[q] for those only (the other entries are not
+ * touched).  The list goes to the device whole and the shard's duplications are gathered there, then
+ * scheduled longest first like asgart_compute_scores.  The whole list is validated as asgart_compute_scores
+ * validates it, so every rank fails alike.  Returns the number of duplications the shard owned, < 0 on
+ * error.  A gatherer copies each shard's values back to their input positions (asgart_amd/multi.py:
+ * compute_scores). */
+int64_t asgart_compute_scores_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
+                                    int32_t reversed, int32_t complemented, int32_t shard, int32_t n_shards,
+                                    float *identity);
+
+/* Replaces the same loop for ONE process over several GPUs, shaped like asgart_search_duplications_multi:
+ * indices[r] is a replica of the same text on device r (asgart_index_clone); one host thread per replica
+ * runs shard r of n_devices, and identity receives all n_sd values -- exactly asgart_compute_scores' array.
+ * The same index may appear more than once.  If a shard fails the call fails, and the message names the
+ * shard. */
+int32_t asgart_compute_scores_multi(asgart_index *const *indices, int32_t n_devices, const asgart_proto_sd *sds,
+                                    int64_t n_sd, int32_t reversed, int32_t complemented, float *identity);
+
 /* ---- the steps behind the search step ------------------------------------------
  * Replaces FilterNs, ReOrder, ReduceOverlap and Sort of the reference's step chain (src/bin/asgart.rs:33-96 with
  * ProtoSD::n_content src/structs.rs:454-467, reduce_overlap :481-562; order :738-747) for the families of one run,
