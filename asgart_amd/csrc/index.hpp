@@ -281,7 +281,7 @@ struct Options {
     int64_t test_genbits = 22;      // tests: width of the arm-resident kernels' table generation counter
     int64_t test_k8_delay = 0;      // tests: cycles K8's ranking wave waits in every step before it reads the free counts the arm
                                     // waves published (results must not depend on it: the counts are double-buffered by step parity)
-    int64_t tier_order = 3654217;   // launch order of the extension tiers, as decimal digits
+    int64_t tier_order = 3654217;   // launch order of the extension tiers, as decimal digits (a tier left out runs after them)
     int64_t grid[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // grid[t] > 0: workgroups of tier t (clamped to its maximum)
     int64_t ptab_depth = 0;         // 0: chosen from the text length
     int64_t force_wide = 0;         // tests: 64-bit slots and positions for a small text

@@ -989,7 +989,16 @@ struct SearchCall {
             HIP_TRY(hipGetLastError());
         }
         t_launch = std::chrono::steady_clock::now();
-        for (char c : tier_order) launch_tier(c - '0');
+        // every tier exactly once: first in the order the option gives (a digit repeated launches nothing more), then the
+        // tiers it leaves out -- option tier_order accepts any digits 1..7, and a tier that never ran would lose its segments
+        bool launched[kTiers + 1] = {};
+        for (char c : tier_order)
+            if (!launched[c - '0']) {
+                launched[c - '0'] = true;
+                launch_tier(c - '0');
+            }
+        for (int t = 1; t <= kTiers; ++t)
+            if (!launched[t]) launch_tier(t);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(cx.ev[12], st7));
         HIP_TRY(hipEventRecord(cx.ev[5], st2));
