@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "asgart_search_duplications_passes_shard", "asgart_families_keys",
     "asgart_index_export", "asgart_index_create_device", "asgart_trim_cache", "asgart_post_process",
     "asgart_debug_dump_stacks", "asgart_prepare_data", "asgart_score_owners", "asgart_score_costs",
-    "asgart_compute_scores_shard", "asgart_compute_scores_multi",
+    "asgart_compute_scores_shard", "asgart_compute_scores_multi", "asgart_tier_plan",
 )
 
 
@@ -178,6 +178,8 @@ def load_library() -> C.CDLL:
     L.asgart_score_owners.restype = C.c_int32
     L.asgart_score_costs.argtypes = [vp, C.c_int64, vp]
     L.asgart_score_costs.restype = C.c_int32
+    L.asgart_tier_plan.argtypes = [C.c_int32, vp, C.c_int64, vp, C.c_double, vp, vp]
+    L.asgart_tier_plan.restype = C.c_int32
     L.asgart_compute_scores_shard.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
     L.asgart_compute_scores_shard.restype = C.c_int64
     L.asgart_compute_scores_multi.argtypes = [C.POINTER(vp), C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, vp]
@@ -526,6 +528,19 @@ def score_costs(sds: np.ndarray) -> np.ndarray:
     out = np.zeros(len(sds), dtype=np.uint64)
     _check(load_library().asgart_score_costs(_ptr(sds), len(sds), _ptr(out)))
     return out
+
+
+def tier_plan(budget: int, n_work, tier_order: int, est_ms, main_ms: float = 0.0) -> Tuple[np.ndarray, np.ndarray]:
+    """asgart_tier_plan (host code, no device needed): the streams a search call puts its extension tiers on, for 7
+    tiers' work counts and estimated durations (ms) -> (stream_of int32[7]: 0 = the main stream, s = tier stream s,
+    -1 = no work; launch int32[7]: the tiers with work in launch order, 0 behind them)."""
+    work = np.ascontiguousarray(n_work, dtype=np.uint64).reshape(7)
+    est = np.ascontiguousarray(est_ms, dtype=np.float64).reshape(7)
+    stream_of = np.zeros(7, dtype=np.int32)
+    launch = np.zeros(7, dtype=np.int32)
+    _check(load_library().asgart_tier_plan(int(budget), _ptr(work), int(tier_order), _ptr(est), float(main_ms),
+                                           _ptr(stream_of), _ptr(launch)))
+    return stream_of, launch
 
 
 def compute_scores_multi(indices: Sequence[Index], sds: np.ndarray, reversed_: bool = False,

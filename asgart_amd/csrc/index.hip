@@ -23,8 +23,8 @@ namespace asgart {
 static thread_local char g_err[512] = "";
 thread_local bool tl_owns_pass_mu = false;
 
-// Runtime note.  The extension tiers of one call run on six HIP streams (twelve with
-// two calls in flight); ROCm maps streams onto the hardware queues the process may open (GPU_MAX_HW_QUEUES) and
+// Runtime note.  The extension tiers of one call run on up to six HIP streams, one per
+// hardware queue the process may open (GPU_MAX_HW_QUEUES, tier_plan); ROCm maps streams onto those queues and
 // kernels of streams that share a queue run one after the other.  How many queues a process gets is the host's
 // environment's to decide; the library never touches the process environment.
 void set_error(const char *fmt, ...) {
@@ -83,24 +83,105 @@ const OptDesc kOptions[] = {
 };
 }  // namespace
 
-// The main stream of a call context carries the chip-wide, short kernels of a call (probe search, scans, CSR
-// fill, placement, record sort) and its small copies; the extension tiers, whose persistent workgroups hold
-// their CU slots for tens of milliseconds, run on the other six.  The main stream gets the highest priority the
-// device offers: when two calls are in flight, the short kernels of one are dispatched into the first slots
-// the other's tiers give back instead of queueing behind the tiers' own backlog of workgroups.
+// The CSR fill runs on a tier stream beside the placement walk from this many queues on (create_ctx_streams).
+constexpr int kFillBesideQueues = 6;
+
+int hw_queue_budget() {
+    const char *q = getenv("GPU_MAX_HW_QUEUES");
+    if (!q || !*q) return 4;
+    char *end = nullptr;
+    const long v = strtol(q, &end, 10);
+    if (end == q) return 4;
+    return (int)std::min(32L, std::max(1L, v));
+}
+
+// The tiers' streams of a call.  Streams of one priority share the process's queues, and
+// kernels of streams on one queue run one after the other -- a tier behind another waits for that tier's longest
+// segment.  So a call gets at most one tier stream per queue (min(6, budget)) and tiers that must share one are put
+// behind each other knowingly: longest-processing-time packing of the tiers' estimated durations (each the longer of
+// its longest segment and its work spread over the compute units it can hold) onto the tier streams, and -- when the
+// process has two queues or more -- onto the main stream behind the runs over ranges.  Longest first (ties: the launch
+// order), each onto the least-loaded stream (ties: tier streams in order, then the main stream), and behind what that
+// stream already holds.  Every tier with work runs exactly once, the tiers option tier_order names and then the rest.
+// With one queue the plan is that single chain (the main stream stays free for the other call context).
+// Bound: the most loaded stream carries at most main_ms + total / (number of streams) + the largest single estimate.
+int32_t tier_plan(int budget, const uint64_t *n_work, int64_t tier_order, const double *est_ms, double main_ms,
+                  int32_t *stream_of, int32_t *launch) {
+    constexpr int kT = 7;
+    if (budget < 1 || !n_work || !est_ms || !stream_of || !launch || !(main_ms >= 0.0) || tier_order < 1 ||
+        tier_order > 7777777) {
+        set_error("asgart_tier_plan: bad argument");
+        return ASGART_E_ARG;
+    }
+    for (int t = 0; t < kT; ++t)
+        if (!(est_ms[t] >= 0.0) || est_ms[t] > 1e12) {
+            set_error("asgart_tier_plan: estimate of tier %d is not a finite duration", t + 1);
+            return ASGART_E_ARG;
+        }
+    int digits[kT] = {}, n_digits = 0;
+    for (int64_t v = tier_order; v; v /= 10) {
+        if (v % 10 < 1 || v % 10 > kT || n_digits == kT) {
+            set_error("asgart_tier_plan: tier_order digits must be tiers 1..7");
+            return ASGART_E_ARG;
+        }
+        digits[n_digits++] = (int)(v % 10);
+    }
+    int order[kT], n = 0;
+    bool seen[kT + 1] = {};
+    for (int i = n_digits - 1; i >= 0; --i)
+        if (!seen[digits[i]]) {
+            seen[digits[i]] = true;
+            if (n_work[digits[i] - 1]) order[n++] = digits[i];
+        }
+    for (int t = 1; t <= kT; ++t)
+        if (!seen[t] && n_work[t - 1]) order[n++] = t;
+    for (int i = 0; i < kT; ++i) stream_of[i] = -1;
+    int by_cost[kT], depth[kT + 1] = {}, slot[kT + 1] = {};
+    std::copy(order, order + n, by_cost);
+    std::stable_sort(by_cost, by_cost + n, [&](int a, int b) { return est_ms[a - 1] > est_ms[b - 1]; });
+    const int n_st = std::min(budget, SearchCtx::kMaxTierStreams);
+    const bool main_ok = budget >= 2;
+    double load[SearchCtx::kMaxTierStreams + 1] = {main_ms};
+    int on[SearchCtx::kMaxTierStreams + 1] = {};
+    for (int i = 0; i < n; ++i) {
+        int best = 1;
+        for (int q = 2; q <= n_st; ++q)
+            if (load[q] < load[best]) best = q;
+        if (main_ok && load[0] < load[best]) best = 0;
+        const int t = by_cost[i];
+        stream_of[t - 1] = best;
+        depth[t] = on[best]++;
+        load[best] += est_ms[t - 1];
+    }
+    // Launch: the first tier of every stream in the option's order, then the second ones, ...  Within a stream the
+    // longer estimate goes first, so that its longest segment starts at once (a tier behind another on one queue starts
+    // when that one has ended, and the tiers that hold whole compute units end late when they share the chip).  With
+    // one queue the chain is serial whatever its order, and it keeps the option's.
+    for (int i = 0; i < n; ++i) slot[order[i]] = budget == 1 ? i : depth[order[i]] * kT + i;
+    std::sort(order, order + n, [&](int a, int b) { return slot[a] < slot[b]; });
+    for (int i = 0; i < kT; ++i) launch[i] = i < n ? order[i] : 0;
+    return 0;
+}
+
+// The main stream of a call context carries the chip-wide, short kernels of a call (probe search, scans, placement,
+// record sort), its small copies and the runs over ranges; the extension tiers, whose persistent workgroups hold their
+// CU slots for tens of milliseconds, run on the tier streams (tier_plan).  The main stream gets the highest priority
+// the device offers: when two calls are in flight, the short kernels of one are dispatched into the first slots the
+// other's tiers give back instead of queueing behind the tiers' own backlog of workgroups.
 int32_t create_ctx_streams(SearchCtx &cx) {
     int least = 0, greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
     HIP_TRY(hipStreamCreateWithPriority(&cx.stream, hipStreamNonBlocking, greatest));
-    for (hipStream_t *st : {&cx.stream2, &cx.stream3, &cx.stream4, &cx.stream5, &cx.stream6, &cx.stream7})
-        HIP_TRY(hipStreamCreateWithPriority(st, hipStreamNonBlocking, least));
+    cx.n_tier_st = std::min(SearchCtx::kMaxTierStreams, hw_queue_budget());
+    for (int i = 0; i < cx.n_tier_st; ++i) HIP_TRY(hipStreamCreateWithPriority(&cx.tier_st[i], hipStreamNonBlocking, least));
     for (auto &e : cx.ev) HIP_TRY(hipEventCreate(&e));
-    // The CSR fill runs on stream2 beside the placement walk -- unless the process has been told to make do with few
-    // hardware queues (GPU_MAX_HW_QUEUES below 6: several processes sharing one device, bench.py's one-device mode): streams
-    // that share a queue run one after the other, and a tier stream used in the front put the tiers of two ranks on one
-    // device behind one another (283 instead of 74 ms for a rank's shard).
-    const char *q = getenv("GPU_MAX_HW_QUEUES");
-    cx.fill_stream = (q && *q && atoi(q) < 6) ? cx.stream : cx.stream2;
+    for (auto &e : cx.tier_ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventCreate(&cx.runs_ev));
+    // The CSR fill runs on a tier stream beside the placement walk only when every tier stream has a queue of its own
+    // (kFillBesideQueues); with fewer it stays on the main stream.  Measured on the GRCh38-shaped step
+    // (profiles/cfg4_tier_queues.json): with 4 queues the fill beside the walk gains nothing (138.6 against 138.9 ms;
+    // cluster_barren_kernel waits for the hit rows either way, and the fill itself runs 4 ms longer beside the walk).
+    cx.fill_stream = hw_queue_budget() >= kFillBesideQueues ? cx.tier_st[cx.n_tier_st - 1] : cx.stream;
     return 0;
 }
 
@@ -910,7 +991,8 @@ void asgart_index_destroy(asgart_index *idx) {
     for (int c = 0; c < kNumCtx; ++c) {
         SearchCtx &cx = idx->ctx[c];
         int j = 0;
-        for (hipStream_t st : {cx.stream, cx.stream2, cx.stream3, cx.stream4, cx.stream5, cx.stream6, cx.stream7}) {
+        for (int i = 0; i <= SearchCtx::kMaxTierStreams; ++i) {
+            const hipStream_t st = i ? cx.tier_st[i - 1] : cx.stream;
             ++j;
             if (!st) continue;
             const auto t1 = std::chrono::steady_clock::now();
@@ -947,16 +1029,24 @@ void asgart_index_destroy(asgart_index *idx) {
       return bounded_call(limit, [idx, dev]() {
             (void)hipSetDevice(dev);
             for (auto &cx : idx->ctx) {
-                for (auto &e : cx.ev)
+                auto destroy_event = [](hipEvent_t &e) {
                     if (e) {
                         (void)hipEventDestroy(e);
                         e = nullptr;
                     }
-                for (hipStream_t *st : {&cx.stream, &cx.stream2, &cx.stream3, &cx.stream4, &cx.stream5, &cx.stream6, &cx.stream7})
-                    if (*st) {
-                        (void)hipStreamDestroy(*st);
-                        *st = nullptr;
+                };
+                for (auto &e : cx.ev) destroy_event(e);
+                for (auto &e : cx.tier_ev) destroy_event(e);
+                destroy_event(cx.runs_ev);
+                auto destroy_stream = [](hipStream_t &st) {
+                    if (st) {
+                        (void)hipStreamDestroy(st);
+                        st = nullptr;
                     }
+                };
+                destroy_stream(cx.stream);
+                for (auto &st : cx.tier_st) destroy_stream(st);
+                cx.n_tier_st = 0;
             }
         });
     };
@@ -1475,6 +1565,11 @@ int32_t asgart_sa_read(asgart_index *idx, uint64_t lo, uint64_t hi, int64_t *out
     }
     HIP_TRY(stream_sync(idx->ctx[0].stream));
     return 0;
+}
+
+int32_t asgart_tier_plan(int32_t budget, const uint64_t *n_work, int64_t tier_order, const double *est_ms, double main_ms,
+                         int32_t *stream_of, int32_t *launch) {
+    return asgart::tier_plan(budget, n_work, tier_order, est_ms, main_ms, stream_of, launch);
 }
 
 }  // extern "C"

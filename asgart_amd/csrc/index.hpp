@@ -175,12 +175,21 @@ namespace asgart {
 // direct and the -RC run, reference src/bin/asgart.rs runs them as separate invocations) can be
 // in flight at once from two host threads; text, suffix array and keys are shared read-only.
 struct SearchCtx {
+    static constexpr int kMaxTierStreams = 6;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;  // concurrent extension tiers
-    hipStream_t stream5 = nullptr, stream6 = nullptr, stream7 = nullptr;
-    hipStream_t fill_stream = nullptr;  // where the CSR fill runs beside the placement walk: stream2, or the main stream when
-                                        // hardware queues are scarce (create_ctx_streams)
-    hipEvent_t ev[17] = {};
+    hipStream_t tier_st[kMaxTierStreams] = {};  // the extension tiers' streams: min(6, hw_queue_budget()) of them
+    int n_tier_st = 0;
+    hipStream_t fill_stream = nullptr;  // where the CSR fill runs: beside the placement walk on the last tier stream with 6
+                                        // queues or more, else on the main stream (create_ctx_streams)
+    hipEvent_t ev[17] = {};  // (5, 6, 8, 9, 10 and 12 are no longer recorded: the tiers have tier_ev)
+    hipEvent_t tier_ev[7] = {};  // tier t's launch (its early re-run included) is done: tier_ev[t - 1]
+    hipEvent_t runs_ev = nullptr;  // the runs over ranges are done (main stream)
+    // what the tier-to-stream plan of the next call with the same call_sig starts from (tier_plan): per tier the
+    // longer of its longest segment and its work spread over the compute units it can hold, in ms; [0]: the runs over
+    // ranges
+    uint64_t plan_sig = 0;
+    bool plan_known = false;
+    double plan_est[8] = {};
     Workspace ws;
     asgart_stats stats;
     RunParams last_rp;   // inputs of the last call, kept for the yardstick kernel
@@ -351,6 +360,14 @@ struct Options {
                                     // last heartbeats of its kernels instead of waiting forever; 0: wait forever
 };
 int32_t create_ctx_streams(SearchCtx &cx);
+// The normal-priority hardware queues this process may open: GPU_MAX_HW_QUEUES if it is set, otherwise HIP's default
+// of 4, clamped to 1..32 (the library reads the variable and never sets it).
+int hw_queue_budget();
+// The extension tiers' streams of one call (host code, asgart_tier_plan): stream_of[t - 1] = 0 for the main stream, s for
+// tier stream s (1 .. min(6, budget)), -1 for a tier without work; launch[] = the tiers with work in launch order (which
+// is also the order within each stream: longest estimate first), 0 behind them.
+int32_t tier_plan(int budget, const uint64_t *n_work, int64_t tier_order, const double *est_ms, double main_ms,
+                  int32_t *stream_of, int32_t *launch);
 template <class SlotT>
 int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_t n, SlotT *d_sap, uint32_t min_run, int k,
                               hipStream_t s);  // (sa_build.hip: only the runs of more than min_run equal keys; any slot width)  // the streams and events of one call context (current device)

@@ -327,6 +327,7 @@ struct SearchCall {
     ExtParams<SlotT> ep;
     char *scratch_override = nullptr;  // HBM slices of an early cascade launch
     hipStream_t tier_stream[kTiers + 1] = {};
+    bool tier_ran[kTiers + 1] = {};  // launched by run_tiers (its event in cx.tier_ev is this call's)
     uint64_t early_n[kTiers + 1] = {};
     double ms_tier2 = 0.0, ms_longest_tier = 0.0, ms_longest_segment = 0.0;
     uint64_t n_split_segments = 0, n_split_refused = 0;
@@ -907,7 +908,7 @@ struct SearchCall {
         ep.cursor = reinterpret_cast<unsigned long long *>(d_split + 24);
         ep.ovf_list = nullptr;
         ep.ovf_count = d_ctr + CT_OVF1 + 2;
-        ep.tier = 3;  // (statistics: with the long-segment tier)
+        ep.tier = kRunsStat;  // (statistics: a slot of their own; the debug output counts them with tier 3)
         ep.seg_slots = w.seg_slots.as<unsigned long long>();  // (slot block 0: no tier's)
         ep.hb = cx.d_hb ? cx.d_hb : nullptr;
         extend_k8_kernel<SlotT, kK8LongLayers<SlotT>, 1024, kHitBatch, kFastLongRows<SlotT>, 2, true><<<n_items, 1024, 0, s>>>(ep);
@@ -961,24 +962,35 @@ struct SearchCall {
         // back-fills CUs as workgroups retire, so the tails of one tier overlap the next.
         // The window bound guarantees that a segment fits its
         // tier, so the overflow lists normally stay empty (they feed the cascade below).
-        const hipStream_t st2 = cx.stream2, st3 = cx.stream3, st4 = cx.stream4, st5 = cx.stream5, st6 = cx.stream6, st7 = cx.stream7;
-        {
-            const hipStream_t streams[kTiers + 1] = {s, st7, st2, st3, st4, st5, st6, st2};
-            for (int t = 0; t <= kTiers; ++t) tier_stream[t] = streams[t];
+        // Which stream each tier runs on (tier_plan): streams that share a hardware queue run one after the other, so a
+        // call has one tier stream per queue it may open, and the tiers that must share a stream are packed by their
+        // estimated durations so that no chain outlasts the longest tier by much.
+        double est[kTiers + 1];
+        plan_estimates(est);
+        int32_t stream_of[kTiers], launch_seq[kTiers];
+        RC_TRY(tier_plan(cx.n_tier_st, n_t, opt.tier_order, est + 1, n_runs ? est[0] : 0.0, stream_of, launch_seq));
+        bool used[SearchCtx::kMaxTierStreams] = {};
+        tier_stream[0] = s;
+        for (int t = 1; t <= kTiers; ++t) {
+            tier_ran[t] = false;
+            tier_stream[t] = stream_of[t - 1] > 0 ? cx.tier_st[stream_of[t - 1] - 1] : s;
+            if (stream_of[t - 1] > 0) used[stream_of[t - 1] - 1] = true;
         }
-        HIP_TRY(hipStreamWaitEvent(st2, cx.ev[7], 0));
-        HIP_TRY(hipStreamWaitEvent(st3, cx.ev[7], 0));
-        HIP_TRY(hipStreamWaitEvent(st4, cx.ev[7], 0));
-        HIP_TRY(hipStreamWaitEvent(st5, cx.ev[7], 0));
-        HIP_TRY(hipStreamWaitEvent(st6, cx.ev[7], 0));
-        HIP_TRY(hipStreamWaitEvent(st7, cx.ev[7], 0));
+        for (int i = 0; i < cx.n_tier_st; ++i)
+            if (used[i]) HIP_TRY(hipStreamWaitEvent(cx.tier_st[i], cx.ev[7], 0));
+        if (opt.debug) {
+            fprintf(stderr, "[asgart] tier plan (%d tier streams; 0 = main stream behind %.1f ms of range runs):", cx.n_tier_st,
+                    n_runs ? est[0] : 0.0);
+            for (int i = 0; i < kTiers && launch_seq[i]; ++i)
+                fprintf(stderr, " t%d@%d ~%.1f ms", launch_seq[i], stream_of[launch_seq[i] - 1], est[launch_seq[i]]);
+            fprintf(stderr, "\n");
+        }
         // Launch order and grid sizes: workgroups are persistent and hold their LDS until the
         // tier's work list is exhausted, so whatever is dispatched first owns the CUs.  The
         // critical path of a pass is the longest tandem-array segment of the heavy tiers
         // (tens of thousands of probes, strictly serial): those tiers go first, the one-wave
         // tier last, and the heavy grids are sized so that every tier's longest segments
         // start at once instead of queueing behind another tier's bulk.
-        const std::string tier_order = std::to_string((long long)opt.tier_order);
         scratch_override = nullptr;
         if (n_runs) {
             // (room for one more run per cut segment: the rest behind the last cut that held, see below)
@@ -987,25 +999,19 @@ struct SearchCall {
             HIP_TRY(hipMemsetAsync(d_split + kOffMeta, 0, (size_t)n_runs * 64, s));  // run states
             launch_runs(n_runs);
             HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(cx.runs_ev, s));
         }
         t_launch = std::chrono::steady_clock::now();
-        // every tier exactly once: first in the order the option gives (a digit repeated launches nothing more), then the
-        // tiers it leaves out -- option tier_order accepts any digits 1..7, and a tier that never ran would lose its segments
-        bool launched[kTiers + 1] = {};
-        for (char c : tier_order)
-            if (!launched[c - '0']) {
-                launched[c - '0'] = true;
-                launch_tier(c - '0');
-            }
-        for (int t = 1; t <= kTiers; ++t)
-            if (!launched[t]) launch_tier(t);
+        // every tier with work exactly once, in the plan's launch order (tier_plan: the first tier of every stream in the
+        // order option tier_order gives, then the second ones; a tier the option leaves out would lose its segments if it
+        // never ran); each tier's event follows it on its stream
+        for (int i = 0; i < kTiers && launch_seq[i]; ++i) {
+            const int t = launch_seq[i];
+            launch_tier(t);
+            HIP_TRY(hipEventRecord(cx.tier_ev[t - 1], tier_stream[t]));
+            tier_ran[t] = true;
+        }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(cx.ev[12], st7));
-        HIP_TRY(hipEventRecord(cx.ev[5], st2));
-        HIP_TRY(hipEventRecord(cx.ev[6], st3));
-        HIP_TRY(hipEventRecord(cx.ev[8], st4));
-        HIP_TRY(hipEventRecord(cx.ev[9], st5));
-        HIP_TRY(hipEventRecord(cx.ev[10], st6));
         if (cx.progress && attempt == 0) {
             // Progress (reference src/automaton.rs:98 stores every probe's offset for a polled progress
             // bar): every probe of the call has been searched and its hits are materialised -- the
@@ -1021,8 +1027,10 @@ struct SearchCall {
         // the allowance): what they give up on need not wait for the other tiers to be re-run -- the longest
         // tier-3 segment of a GRCh38-shaped pass runs 60+ ms longer than tier 6, and in a two-genome run tier 6
         // runs seconds longer than tier 3.  The host waits for whichever of the two finishes first, reads its
-        // overflow count and launches the re-run behind it on the same stream (the main stream is idle
-        // meanwhile and has the highest priority); each such launch has its own counters and HBM slices.
+        // overflow count and launches the re-run behind it on the same stream; each such launch has its own counters
+        // and HBM slices.  The count is read on the main stream, so the re-run cannot start before the runs over
+        // ranges -- and any tier the plan put behind them -- have finished (a tier stream would make it wait for the
+        // tiers behind this one on that stream instead).
         for (int t = 0; t <= kTiers; ++t) early_n[t] = 0;
         {
             struct Early {
@@ -1030,7 +1038,7 @@ struct SearchCall {
                 hipEvent_t ev;
                 hipStream_t st;
                 bool pending;
-            } early[2] = {{3, 0, cx.ev[6], st3, false}, {6, 0, cx.ev[10], st6, false}};
+            } early[2] = {{3, 0, cx.tier_ev[2], tier_stream[3], false}, {6, 0, cx.tier_ev[5], tier_stream[6], false}};
             int n_pending = 0;
             unsigned early_polls = 0;
             Watchdog early_wd(idx, cx);
@@ -1039,9 +1047,10 @@ struct SearchCall {
                 int dst = E.src + 1;
                 while (dst < kTiers && (!tier_enabled(dst) || tier_cap[dst] <= tier_cap[E.src])) ++dst;
                 E.dst = dst;
-                // (a re-run in the HBM tier would share that tier's slices with its own list, if it has one)
-                E.pending = n_t[E.src - 1] && tier_stream[E.src] == E.st &&
-                            (dst < kTiers || !n_t[kTiers - 1]);
+                // (a re-run in the HBM tier would share that tier's slices with its own list, if it has one; a tier the
+                // plan put on the main stream is re-run by the regular cascade: reading its overflow count there would
+                // wait for the whole main stream)
+                E.pending = n_t[E.src - 1] && E.st != s && (dst < kTiers || !n_t[kTiers - 1]);
                 n_pending += E.pending ? 1 : 0;
             }
             // (If tier 3's re-run went to tier 6, its kernel would append to tier 6's overflow list while the host
@@ -1103,12 +1112,8 @@ struct SearchCall {
 
     // ---- the tiers are through: cuts checked, ranges joined up, refused segments run again --------------------------------------
     int32_t join_ranges() {
-        HIP_TRY(hipStreamWaitEvent(s, cx.ev[5], 0));
-        HIP_TRY(hipStreamWaitEvent(s, cx.ev[6], 0));
-        HIP_TRY(hipStreamWaitEvent(s, cx.ev[8], 0));
-        HIP_TRY(hipStreamWaitEvent(s, cx.ev[9], 0));
-        HIP_TRY(hipStreamWaitEvent(s, cx.ev[10], 0));
-        HIP_TRY(hipStreamWaitEvent(s, cx.ev[12], 0));
+        for (int t = 1; t <= kTiers; ++t)
+            if (tier_ran[t] && tier_stream[t] != s) HIP_TRY(hipStreamWaitEvent(s, cx.tier_ev[t - 1], 0));
         if (n_cuts) {
             validate_cuts_kernel<kDumpWords<SlotT>><<<n_cuts, 256, 0, s>>>(reinterpret_cast<const uint2 *>(d_split + kOffCuts),
                                                        reinterpret_cast<const uint32_t *>(d_split + kOffMeta), w.split_dump.as<uint32_t>(),
@@ -1296,28 +1301,32 @@ struct SearchCall {
             fprintf(stderr, "[asgart] all tiers and early re-runs done %.1f ms after the launches\n", since_launch());
             // how much of the chip each tier held: sum of its workgroups' lifetimes x the share of a compute unit one of
             // them occupies (workgroups per compute unit by LDS / registers: tiers 1..7 = 11, 8, 1, 4, 2, 1, 1)
-            static const double per_cu[kTiers] = {11, 8, 1, 4, 2, 1, 1};
+            const double *per_cu = kWgPerCU;
+            // (the runs over ranges count with tier 3, the long-segment tier whose kernel they run)
+            auto busy = [&](int t) { return (double)(h_ctr[CT_BUSY1 + t] + (t == 2 ? h_ctr[CT_BUSY1 + kRunsStat - 1] : 0ull)); };
+            auto wgs = [&](int t) { return h_ctr[CT_WGS1 + t] + (t == 2 ? h_ctr[CT_WGS1 + kRunsStat - 1] : 0ull); };
             double tot = 0.0;
             fprintf(stderr, "[asgart] compute-unit time held per tier (CU-ms; workgroups):");
             for (int t = 0; t < kTiers; ++t) {
-                const double cu_ms = (double)h_ctr[CT_BUSY1 + t] * 1e-5 / per_cu[t];
+                const double cu_ms = busy(t) * 1e-5 / per_cu[t];
                 tot += cu_ms;
-                fprintf(stderr, " %d: %.0f (%llu)", t + 1, cu_ms, (unsigned long long)h_ctr[CT_WGS1 + t]);
+                fprintf(stderr, " %d: %.0f (%llu)", t + 1, cu_ms, (unsigned long long)wgs(t));
             }
             fprintf(stderr, "  total %.0f = %.1f ms of the whole chip\n", tot, tot / 256.0);
             fprintf(stderr, "[asgart] per tier: hit-probes / hits per hit-probe / CU-microseconds per hit-probe:");
             for (int t = 0; t < kTiers; ++t) {
                 const double hp = (double)h_tp[t];
                 fprintf(stderr, " %d: %.0fK / %.1f / %.2f", t + 1, hp / 1e3, hp > 0 ? (double)h_th[t] / hp : 0.0,
-                        hp > 0 ? (double)h_ctr[CT_BUSY1 + t] * 1e-2 / per_cu[t] / hp : 0.0);
+                        hp > 0 ? busy(t) * 1e-2 / per_cu[t] / hp : 0.0);
             }
             fprintf(stderr, "\n");
         }
-        {   // the tier that ran longest (its early re-run included): the serial floor of this call's extension
+        {   // the longest chain of tiers on one stream (early re-runs included): the serial floor of this call's extension
             float longest = 0.f;
-            for (int e : {5, 6, 8, 9, 10, 12}) {
-                float t = 0.f;
-                if (hipEventElapsedTime(&t, cx.ev[7], cx.ev[e]) == hipSuccess) longest = std::max(longest, t);
+            for (int t = 1; t <= kTiers; ++t) {
+                float ms = 0.f;
+                if (!tier_ran[t]) continue;
+                if (hipEventElapsedTime(&ms, cx.ev[7], cx.tier_ev[t - 1]) == hipSuccess) longest = std::max(longest, ms);
                 else (void)hipGetLastError();
             }
             ms_longest_tier = longest;
@@ -1367,13 +1376,53 @@ struct SearchCall {
             return ASGART_E_CAP;
         }
         ms_longest_segment = 0.0;
-        for (int t = 0; t < kTiers; ++t) ms_longest_segment = std::max(ms_longest_segment, (double)h_ctr[CT_SEGMAX1 + t] * 1e-5);
+        for (int t = 0; t < kRunsStat; ++t) ms_longest_segment = std::max(ms_longest_segment, (double)h_ctr[CT_SEGMAX1 + t] * 1e-5);
         if (opt.debug) {
             fprintf(stderr, "[asgart] longest single segment per tier (ms):");
-            for (int t = 0; t < kTiers; ++t) fprintf(stderr, " %d: %.2f", t + 1, (double)h_ctr[CT_SEGMAX1 + t] * 1e-5);
+            for (int t = 0; t < kTiers; ++t)
+                fprintf(stderr, " %d: %.2f", t + 1,
+                        (double)std::max(h_ctr[CT_SEGMAX1 + t], t == 2 ? h_ctr[CT_SEGMAX1 + kRunsStat - 1] : 0ull) * 1e-5);
             fprintf(stderr, "\n");
         }
+        remember_plan_estimates();
         return 0;
+    }
+
+    // ---- the estimates of the tier plan (tier_plan) ---------------------------------------------------------------------------
+    // Workgroups of a tier's shape a compute unit holds (LDS / registers), and the compute units a tier's default grid can
+    // hold: tier 1's 2048 one-wave workgroups fill 186 of them, the others the whole chip.
+    static constexpr double kWgPerCU[kTiers] = {11, 8, 1, 4, 2, 1, 1};
+    static constexpr double kTierCUs[kTiers] = {2048.0 / 11.0, 256, 256, 256, 256, 256, 256};
+    // est[t]: tier t's estimated duration in ms, est[0]: the runs over ranges -- what the previous call with the same
+    // call_sig measured (remember_plan_estimates), else the GRCh38-shaped profile (profiles/r06_cfg4_tier_cu_seconds.json:
+    // the longest segments of tiers 2..6 -- tier 3's with the runs, which that profile counted with it --, tier 1's work
+    // over its compute units; tier 7 and the runs as tiers 6 and 3)
+    void plan_estimates(double *est) const {
+        static const double kProfile[kTiers + 1] = {67.0, 4.6, 51.8, 67.0, 35.5, 53.0, 33.0, 33.0};
+        const bool known = cx.plan_known && cx.plan_sig == call_sig;
+        for (int t = 0; t <= kTiers; ++t) est[t] = known && cx.plan_est[t] > 0.0 ? cx.plan_est[t] : kProfile[t];
+    }
+    // per tier that ran: the longer of its longest segment and its work spread over the compute units it can hold (the
+    // runs over ranges have a statistics slot of their own, kRunsStat, and their own estimate: their duration, est[0])
+    void remember_plan_estimates() {
+        if (!(cx.plan_known && cx.plan_sig == call_sig))
+            for (double &e : cx.plan_est) e = 0.0;
+        cx.plan_sig = call_sig;
+        cx.plan_known = true;
+        for (int t = 1; t <= kTiers; ++t) {
+            if (!tier_ran[t]) continue;
+            const double seg = (double)h_ctr[CT_SEGMAX1 + t - 1] * 1e-5;
+            const double spread = (double)h_ctr[CT_BUSY1 + t - 1] * 1e-5 / kWgPerCU[t - 1] / kTierCUs[t - 1];
+            cx.plan_est[t] = std::max(seg, spread);
+        }
+        float runs = 0.f;
+        if (n_runs) {
+            if (hipEventElapsedTime(&runs, cx.ev[7], cx.runs_ev) != hipSuccess) {
+                (void)hipGetLastError();
+                runs = 0.f;
+            }
+            cx.plan_est[0] = runs;
+        }
     }
 
     // ---- records -> reference order -> families per pass ----------------------------------------------------------------------

@@ -18,6 +18,7 @@
 namespace asgart {
 
 constexpr int kTiers = 7;  // extension tiers (see the placement in pipeline.hip)
+constexpr int kRunsStat = kTiers + 1;  // statistics slot (ExtParams::tier) of the runs over ranges: after the tiers'
 
 // device counters (u64 each)
 enum Counter {
@@ -1298,7 +1299,7 @@ struct RecAlloc {
 //                        call is one segment's duration; the longest per tier is the serial floor of the extension
 template <class PosT>
 __device__ inline void wg_begin(const ExtParams<PosT> &P) {
-    if (threadIdx.x == 0 && P.tier >= 1u && P.tier <= (uint32_t)kTiers) {
+    if (threadIdx.x == 0 && P.tier >= 1u && P.tier <= (uint32_t)kRunsStat) {
         atomicAdd(&P.ctr[CT_BUSY1 + P.tier - 1u], 0ull - wall_clock64());
     }
 }
@@ -1306,14 +1307,14 @@ __device__ inline void wg_begin(const ExtParams<PosT> &P) {
 // that fetches the segments and the thread that closes the last one need not be the same)
 template <class PosT>
 __device__ inline void seg_clock(const ExtParams<PosT> &P, bool last = false) {
-    if (!P.seg_slots || P.tier < 2u || P.tier > (uint32_t)kTiers) return;  // (tier 1: a million tiny segments)
+    if (!P.seg_slots || P.tier < 2u || P.tier > (uint32_t)kRunsStat) return;  // (tier 1: a million tiny segments)
     const unsigned long long now = wall_clock64();
     const unsigned long long prev = atomicExch(&P.seg_slots[blockIdx.x & 4095u], last ? 0ull : now);
     if (prev && now > prev) atomicMax(&P.ctr[CT_SEGMAX1 + P.tier - 1u], now - prev);
 }
 template <class PosT>
 __device__ inline void wg_busy(const ExtParams<PosT> &P) {
-    if (threadIdx.x == 0 && P.tier >= 1u && P.tier <= (uint32_t)kTiers) {
+    if (threadIdx.x == 0 && P.tier >= 1u && P.tier <= (uint32_t)kRunsStat) {
         seg_clock(P, true);  // (closes the last segment)
         atomicAdd(&P.ctr[CT_BUSY1 + P.tier - 1u], wall_clock64());
         atomicAdd(&P.ctr[CT_WGS1 + P.tier - 1u], 1ull);

@@ -87,9 +87,13 @@ typedef struct asgart_stats {
     uint64_t probes_filter_rejected; /* probes answered by the position bits alone                  */
     uint64_t search_bytes_wide_loads; /* ... of search_bytes, those loaded as whole-wave 16-byte-per-lane reads (text windows,
                                          position bits): what FETCH_SIZE counts at half on gfx950 (accounting pass only) */
-    double ms_longest_tier;   /* part of ms_extend: the extension tier that ran longest, from the launch of the tiers
-                                 (they run side by side) -- in practice the longest serial automaton segment of the
-                                 call, i.e. what sharding the probes over more GPUs cannot shorten              */
+    double ms_longest_tier;   /* part of ms_extend: the longest chain of extension tiers on one stream, from the
+                                 launch of the tiers to the end of the chain's last tier (early re-runs included) --
+                                 the tiers run side by side, one stream per hardware queue the process may open
+                                 (asgart_tier_plan), and tiers that share a stream run one after the other.  A tier
+                                 the plan puts on the main stream runs behind the runs over ranges, and its chain
+                                 counts them.  With a stream per tier this is the tier that ran longest: in practice
+                                 the longest serial automaton segment of the call                               */
     uint64_t passes;          /* passes (orientations) the call ran as ONE job: 1 for a plain call; n for the passes call
                                  when it fuses them (the counters above are then sums over the passes, the timings those
                                  of the one job)                                                                 */
@@ -332,6 +336,22 @@ int32_t asgart_compute_scores(asgart_index *idx, const asgart_proto_sd *sds, int
 int32_t asgart_score_owners(const asgart_proto_sd *sds, int64_t n_sd, int32_t n_shards, int32_t *owner);
 /* The cost model asgart_score_owners balances: cost[q] for each duplication (host code, needs no device). */
 int32_t asgart_score_costs(const asgart_proto_sd *sds, int64_t n_sd, uint64_t *cost);
+
+/* asgart_tier_plan: host code, needs no device.  The streams the extension tiers of one search call run on, as the
+ * call plans them: budget = the normal-priority hardware queues the process may open (GPU_MAX_HW_QUEUES, default 4;
+ * at least 1, above 32 counts as 32), n_work[t - 1] != 0 for each tier t = 1..7 with work, tier_order as the option,
+ * est_ms[t - 1] = tier t's estimated duration, main_ms = what the main stream carries ahead of the tiers (the runs
+ * over ranges).  The tiers with work are packed longest first (ties: launch order) onto the least-loaded of
+ * min(6, budget) tier streams (ties: lower stream first) and, with a budget of 2 or more, the main stream (after the
+ * tier streams on ties), each behind what its stream already holds.  Writes stream_of[t - 1]: 0 = the main stream,
+ * s = tier stream s (1-based), -1 = no work; launch[0..6] = the tiers with work in launch order, each once, 0 behind
+ * them: the first tier of every stream, then the second ones, ..., each rank in tier_order's order (the tiers it names,
+ * then the rest).  A budget of 1 gives one chain in tier_order's order.  Bound: the most
+ * loaded stream carries at most main_ms + total / streams + the largest single estimate.  The result depends only on
+ * the arguments.  Errors: budget < 1, a digit of tier_order outside 1..7, a negative or non-finite estimate
+ * (ASGART_E_ARG). */
+int32_t asgart_tier_plan(int32_t budget, const uint64_t *n_work, int64_t tier_order, const double *est_ms, double main_ms,
+                         int32_t *stream_of, int32_t *launch);
 
 /* Replaces the ComputeScore loop (src/bin/asgart.rs:98-112) for shard `shard` of `n_shards` -- one process
  * per GPU, index replicated: every rank passes the SAME full list; the call scores the duplications
