@@ -167,3 +167,71 @@ def test_short_and_empty_needles():
     assert idx.run([(0, 40)], oracle.make_settings(min_length=10)) == []      # L < k + step... few probes
     assert idx.run([(0, 20)], oracle.make_settings(min_length=1000)) == []    # L < M
     assert idx.run([], oracle.make_settings()) == []
+
+
+# ---- the corners of the run settings (tests/test_gpu_settings_edges.py holds the HIP path to the same) ----------------
+def _bucket_cache(strand, sa):
+    """B.cache_entry for every 8-mer at once (the same contract: the SA slots whose suffix starts with it), so that the
+    brute force's probes do not each scan the whole suffix array."""
+    first = {}
+    for r, x in enumerate(sa):
+        p8 = strand[x:x + 8]
+        if len(p8) == 8:
+            lo, hi = first.get(p8, (r, r))
+            assert hi == r, "an 8-mer's suffixes are not contiguous"
+            first[p8] = (lo, r + 1)
+    return lambda text, sa_, p8: first.get(bytes(p8), (0, 0))
+
+
+_EDGE_TEXTS = {}
+
+
+def _edge_text(k, t):
+    """A few-kb seeded text of the GPU module's generator (N-runs of 5001 bases), its suffix array checked suffix by
+    suffix, and the chunks plus chunks of k + step - 1 .. + 1 bases."""
+    from test_gpu_settings_edges import edge_genome, gap_for
+    if (k, t) not in _EDGE_TEXTS:
+        gap = gap_for(k, t)
+        text, meta = edge_genome(k, gap, seed=100 * k + t, unit=120, extra_quiet=(65,) if t > 66 else (), tandem=(13, 24))
+        strand = text + b"$"
+        sa = [int(x) for x in oracle.Index.build(strand).sa]
+        assert sorted(sa) == list(range(len(strand)))
+        assert all(strand[sa[r]:] < strand[sa[r + 1]:] for r in range(len(sa) - 1))   # sorted: the one suffix array
+        chunks = B.find_chunks(text)
+        assert [c[1] for c in chunks] == meta["chunk_lengths"]
+        _EDGE_TEXTS[(k, t)] = (strand, sa, chunks, gap)
+    return _EDGE_TEXTS[(k, t)]
+
+
+@pytest.mark.parametrize("mode", [(False, False), (True, False), (False, True), (True, True)])
+@pytest.mark.parametrize("k,t", [(8, 63), (8, 64), (8, 65), (8, 129), (9, 63), (9, 64), (9, 65), (9, 129)])
+def test_run_matches_bruteforce_at_setting_corners(k, t, mode, monkeypatch):
+    """k = 8 (the shortest probe) and 9, t* = ceil((gap + k) / step) at 63, 64, 65 and 129, min_length at 1, k - 1, k,
+    k + 1 and k + k/2 (a single hit can make a duplication), max_cardinality 0 (every probe with a hit skipped) and 1,
+    on texts with quiet stretches of t* - 1, t* and t* + 1 probes, chunk ends at the thresholds and chunks of
+    k + step - 1, k + step and k + step + 1 bases (the first two have no probe: the reference's
+    `needle.len() - probe_size - step_size` underflows at the first)."""
+    strand, sa, chunks, gap = _edge_text(k, t)
+    monkeypatch.setattr(B, "cache_entry", _bucket_cache(strand, sa))
+    idx = oracle.Index.build(strand, np.array(sa, dtype=np.int64))
+    step = k // 2
+    found = 0
+    for min_len, card in [(1, 500), (k - 1, 500), (k, 500), (k + 1, 500), (k + step, 500), (1, 0), (1, 1), (k + step, 1)]:
+        exp = B.run(strand, sa, chunks, k=k, gap=gap, min_len=min_len, max_card=card, reverse=mode[0], complement=mode[1])
+        st = oracle.make_settings(k=k, gap=gap, min_length=min_len, max_cardinality=card, reverse=mode[0],
+                                  complement=mode[1])
+        assert idx.run(chunks, st) == exp, (k, t, min_len, card)
+        found += len(exp)
+        if card == 0:
+            assert exp == []
+    # (at t* = 129 the random 8- and 9-mer hits of the text keep most segments alive to their chunk's end)
+    assert found > 0 or t > 100
+    # the short chunks alone: k + step - 1 and k + step bases have no probe, k + step + 1 one
+    short = [c for c in chunks if c[1] <= k + step + 1]
+    assert [c[1] for c in short] == [k + step - 1, k + step, k + step + 1]
+    for c in short:
+        st = oracle.make_settings(k=k, gap=gap, min_length=1, max_cardinality=500, reverse=mode[0], complement=mode[1])
+        exp = B.run(strand, sa, [c], k=k, gap=gap, min_len=1, max_card=500, reverse=mode[0], complement=mode[1])
+        assert idx.run([c], st) == exp
+        _, log = B.search_duplications(strand[c[0]:c[0] + c[1]], c[0], strand, sa, k, gap + k, 1, 500, False)
+        assert len(log) == (1 if c[1] == k + step + 1 else 0)
