@@ -23,7 +23,7 @@ import numpy as np
 __all__ = [
     "AsgartError", "RunSettings", "ProtoSD", "Strand", "Index", "Searcher", "SearchDuplications",
     "load_library", "library_path", "ABI_SYMBOLS", "sa_build64", "search_duplications_multi", "merge_shards",
-    "score_owners", "score_costs", "compute_scores_multi",
+    "score_owners", "score_costs", "compute_scores_multi", "Source",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "asgart_index_export", "asgart_index_create_device", "asgart_trim_cache", "asgart_post_process",
     "asgart_debug_dump_stacks", "asgart_prepare_data", "asgart_score_owners", "asgart_score_costs",
     "asgart_compute_scores_shard", "asgart_compute_scores_multi", "asgart_tier_plan",
+    "asgart_source_create", "asgart_source_destroy", "asgart_extract_sequences",
 )
 
 
@@ -129,6 +130,12 @@ def load_library() -> C.CDLL:
     L.asgart_prepare_data.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, C.c_int64, C.POINTER(C.c_int64),
                                       C.POINTER(vp)]
     L.asgart_prepare_data.restype = C.c_int32
+    L.asgart_source_create.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(vp)]
+    L.asgart_source_create.restype = C.c_int32
+    L.asgart_source_destroy.argtypes = [vp]
+    L.asgart_source_destroy.restype = None
+    L.asgart_extract_sequences.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_uint64, vp, C.POINTER(C.c_int64)]
+    L.asgart_extract_sequences.restype = C.c_int32
     L.asgart_debug_dump_stacks.argtypes = []
     L.asgart_debug_dump_stacks.restype = C.c_int32
     L.asgart_post_process.argtypes = [vp, vp, C.c_uint64, vp, C.c_int32, C.POINTER(vp)]
@@ -489,6 +496,93 @@ class Index:
         _check(L.asgart_probe_hits(self._h, _ptr(ch), len(chunks), C.byref(st), _ptr(status),
                                    _ptr(offs), _ptr(hits), C.byref(nh)))
         return status, offs, hits
+
+
+class Source:
+    """The raw bytes of a run's records on one GPU, what asgart-extract slices the duplicons' sequences from (reference
+    src/bin/asgart-extract.rs:17-29,110-131): asgart_source_create / asgart_extract_sequences.  Unlike Index.text it is
+    not normalised: soft-masked lower case and IUPAC letters stay as they are."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        self.n = 0
+
+    @classmethod
+    def from_records(cls, records, device: int = 0) -> "Source":
+        """records: the sequences in order, as (name, bytes) pairs (what prep.read_records yields) or bare byte
+        sequences."""
+        seqs = [_as_u8(r[1] if isinstance(r, tuple) else r) for r in records]
+        ptrs = (C.c_void_p * max(len(seqs), 1))(*[s_.ctypes.data for s_ in seqs])
+        lens = np.array([len(s_) for s_ in seqs], dtype=np.uint64)
+        self = cls()
+        _check(load_library().asgart_source_create(ptrs, _ptr(lens), len(seqs), device, C.byref(self._h)))
+        self.n = int(lens.sum())
+        return self
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            load_library().asgart_source_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def extract_piece(self, sds: np.ndarray, flags: np.ndarray, first: int, out: np.ndarray) -> Tuple[np.ndarray, int]:
+        """One asgart_extract_sequences call: the duplicons from `first` on that fit whole into `out` (uint8) ->
+        (end offsets in `out`, 2 per duplicon done, number done).  Raises AsgartError (ASGART_E_CAP: the first does not
+        fit; its `room` is the number of bytes that duplication needs)."""
+        sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+        flags = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        ends = np.zeros(2 * max(len(sds) - first, 1), dtype=np.uint64)
+        done = C.c_int64()
+        rc = load_library().asgart_extract_sequences(self._h, _ptr(sds), _ptr(flags), len(sds), int(first), _ptr(out),
+                                                     len(out), _ptr(ends), C.byref(done))
+        try:
+            _check(rc)
+        except AsgartError as err:
+            if rc == -4:
+                err.room = int(ends[1])
+            raise
+        return ends[:2 * done.value], int(done.value)
+
+    def extract(self, sds: np.ndarray, reversed_=False, complemented=False,
+                piece_bytes: int = 1 << 30) -> Tuple[np.ndarray, np.ndarray]:
+        """Both arms of every duplication of an (n, 4) uint64 array (left, right, left_length, right_length), left then
+        right for each; reversed_ / complemented: one flag for all, or one per duplication (the right arm only).
+        -> (ends uint64[2n]: cumulative end offsets, bytes uint8[ends[-1]]).  The library is called for pieces of at
+        most piece_bytes output bytes (a larger one for a duplication that needs more)."""
+        sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+        n = len(sds)
+        flags = (np.broadcast_to(np.asarray(reversed_, dtype=bool), (n,)).astype(np.uint8) |
+                 (np.broadcast_to(np.asarray(complemented, dtype=bool), (n,)).astype(np.uint8) << 1))
+        flags = np.ascontiguousarray(flags)
+        total = int(sds[:, 2].sum(dtype=np.uint64) + sds[:, 3].sum(dtype=np.uint64)) if n else 0
+        data = np.empty(total, dtype=np.uint8)
+        ends = np.zeros(2 * n, dtype=np.uint64)
+        first = pos = 0
+        while first < n:
+            cap = min(max(int(piece_bytes), 1), total - pos)
+            try:
+                e, done = self.extract_piece(sds, flags, first, data[pos:pos + cap])
+            except AsgartError as err:
+                if err.code != -4:   # ASGART_E_CAP: this duplication alone needs more than a piece
+                    raise
+                e, done = self.extract_piece(sds, flags, first, data[pos:pos + err.room])
+            if done == 0:
+                raise AsgartError(-4, f"asgart_extract_sequences: no progress at duplication {first}")
+            ends[2 * first:2 * (first + done)] = e + np.uint64(pos)
+            pos += int(e[-1]) if done else 0
+            first += done
+        return ends, data
 
 
 def search_duplications_multi(indices: Sequence[Index], chunks: Sequence[Tuple[int, int]],

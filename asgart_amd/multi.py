@@ -179,7 +179,7 @@ def _broadcast_array(a: Optional[np.ndarray], dist, device: Optional[str], src: 
 
 
 def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
-                        prefix: str = "") -> Optional[Tuple[str, str]]:
+                        prefix: str = "", with_sequences: bool = False) -> Optional[Tuple[str, str]]:
     """A whole `asgart` run (reference src/bin/asgart.rs:731-822) on the ranks of `dist`, rank r on GPU device_index:
     rank 0 prepares the input and builds the index, replicate_index copies it to every rank, each rank runs its shard of
     the search (asgart_search_duplications_passes_shard), gather_families merges the families on rank 0, rank 0 runs the
@@ -187,7 +187,9 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     (compute_scores) with compute_score.  Returns, on rank 0, (JSON text, output file name) -- the text is byte-equal to
     postprocess.to_json(postprocess.search_duplications(files, settings, device, compute_score)) on one GPU, the name
     postprocess.out_filename(files, settings, prefix) -- and None on the other ranks.  With world size 1 this is the
-    single-GPU driver.  `--trim` needs world size 1 (a trimmed index is not replicated)."""
+    single-GPU driver.  `--trim` needs world size 1 (a trimmed index is not replicated).  with_sequences: rank 0 also
+    fills left_seq / right_seq from the raw records it read (asgart_amd.Source on its GPU): the text `asgart` followed by
+    `asgart-extract -I` gives (extract.result_text), without its trailing newline."""
     from . import Index, Strand
     from .postprocess import out_filename, to_json_arrays
     from .prep import prepare_records, read_records, validate_trim
@@ -196,7 +198,7 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_duplications: --trim runs on one rank only")
     comm = f"cuda:{device_index}" if dist.get_backend() == "nccl" else None
-    index = strand = None
+    index = strand = records = None
     chunks = [None]
     try:
         if rank == 0:
@@ -219,7 +221,14 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
             ident = compute_scores(index, kept, settings.reverse, settings.complement, dist, comm)
         if rank != 0:
             return None
-        return to_json_arrays(post[0], post[1], strand, settings, ident), out_filename(files, settings, prefix)
+        seqs = None
+        if with_sequences:
+            from . import Source
+            from .extract import sequences
+
+            with Source.from_records(records, device_index) as src:
+                seqs = sequences(src, post[1], settings.reverse, settings.complement)
+        return to_json_arrays(post[0], post[1], strand, settings, ident, seqs), out_filename(files, settings, prefix)
     finally:
         if index is not None:
             index.close()
@@ -241,6 +250,8 @@ def _parse(argv):
     ap.add_argument("-C", "--complement", action="store_true")
     ap.add_argument("-S", "--skip-masked", action="store_true")
     ap.add_argument("--compute-score", action="store_true")
+    ap.add_argument("--with-sequences", action="store_true",
+                    help="fill left_seq / right_seq as asgart-extract --in-place does (python -m asgart_amd.extract)")
     ap.add_argument("--prefix", default="")
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
@@ -320,7 +331,8 @@ def rank_main(argv) -> int:
         settings = RunSettings.from_cli(k=args.probe_size, gap=args.max_gap, min_length=args.min_length,
                                         max_cardinality=args.max_cardinality, reverse=args.reverse,
                                         complement=args.complement, skip_masked=args.skip_masked)
-        out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix)
+        out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix,
+                                  args.with_sequences)
         if out is not None:
             text, name = out
             path = os.path.join(args.out_dir, name)

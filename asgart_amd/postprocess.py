@@ -14,7 +14,7 @@ against the oracle's C restatement.
 from __future__ import annotations
 
 import json
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -286,10 +286,12 @@ def post_process_arrays(index, offs: np.ndarray, sds: np.ndarray, threads: int =
     return index.post_process(offs, sds, threads)
 
 
-def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSettings, identity: Optional[np.ndarray] = None) -> str:
+def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSettings, identity: Optional[np.ndarray] = None,
+                   seqs: Optional[Tuple[Sequence[str], Sequence[str]]] = None) -> str:
     """`to_json(run_result(...))` for family arrays: the same bytes, one format operation per duplication (the
     chromosome of a position by bisection of the strand map, whose records follow one another: the reference's
-    first-match scan, src/structs.rs:85-90, finds the same record)."""
+    first-match scan, src/structs.rs:85-90, finds the same record).  seqs: (left, right) sequences of every
+    duplication, written into left_seq / right_seq (what asgart-extract --in-place fills) instead of null."""
     offs = np.asarray(offs, dtype=np.int64)
     sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
     starts = np.array([c.position for c in strand.map], dtype=np.uint64)
@@ -309,6 +311,8 @@ def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSetti
         il = ir = np.zeros(len(sds), dtype=np.int64)
         pl, pr_ = sds[:, 0], sds[:, 1]
     ident = [f32_repr(v) for v in identity] if identity is not None else None
+    if seqs is not None:
+        lseq, rseq = ([json.dumps(x, ensure_ascii=False) for x in side] for side in seqs)
     rev = "true" if settings.reverse else "false"
     comp = "true" if settings.complement else "false"
     sd_txt = []
@@ -325,8 +329,8 @@ def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSetti
             f'        "chr_right_position": {pr_[j]},\n'
             f'        "left_length": {LL[j]},\n'
             f'        "right_length": {RL[j]},\n'
-            '        "left_seq": null,\n'
-            '        "right_seq": null,\n'
+            f'        "left_seq": {lseq[j] if seqs is not None else "null"},\n'
+            f'        "right_seq": {rseq[j] if seqs is not None else "null"},\n'
             f'        "identity": {ident[j] if ident else "0.0"},\n'
             f'        "reversed": {rev},\n'
             f'        "complemented": {comp}\n'

@@ -386,6 +386,32 @@ int32_t asgart_compute_scores_multi(asgart_index *const *indices, int32_t n_devi
 int32_t asgart_post_process(asgart_index *idx, const uint64_t *fam_offsets, uint64_t n_families,
                             const asgart_proto_sd *sds, int32_t threads, asgart_families **out);
 
+/* ---- the sequences of the duplicons (asgart-extract) -------------------------------------------------------
+ * Replace the body of reference src/bin/asgart-extract.rs:110-200 behind its FASTA reader and JSON reader.
+ * A source is the raw bytes of every record of every file, concatenated in order as the FASTA reader returns them
+ * (:17-29, :110-117): NOT the normalised strand of the search (soft-masked lower case and IUPAC letters stay as they
+ * are); its positions are the search's global positions (normalisation keeps lengths, src/bin/asgart.rs:289-310).
+ * asgart_source_create takes the same record arrays as asgart_prepare_data and uploads them once to `device`
+ * (through pinned staging pieces); it needs no suffix array and is independent of any index. */
+typedef struct asgart_source asgart_source;
+int32_t asgart_source_create(const uint8_t *const *records, const uint64_t *record_lens, int64_t n_records,
+                             int32_t device, asgart_source **out);
+void asgart_source_destroy(asgart_source *src);
+/* The two arms of duplicons first, first + 1, ... of sds[n_sd] (global coordinates), left then right for each,
+ * packed into the host buffer out[out_cap] for as many WHOLE duplicons as fit:
+ *   left  = source[left .. left + left_length]                                                   (:123-125)
+ *   right = source[right .. right + right_length], reversed if flags[j] & 1, then complemented if flags[j] & 2 with
+ *           utils::complement_nucleotide (src/utils.rs:1-23: A<->T, G<->C keeping the case, N / n stay, any other
+ *           byte becomes N)                                                                      (:126-134)
+ * flags: one byte per duplicon of sds (NULL: all 0).  seq_ends[2 (j - first) + 0 / 1] receive the end offsets in
+ * `out` of the left / right arm of duplicon j, *n_done the number of duplicons extracted (call again with
+ * first + *n_done for the rest).  Errors: a duplicon whose first arm does not fit into out_cap (ASGART_E_CAP;
+ * seq_ends[0..1] then hold its ends: seq_ends[1] is the room it needs), an arm past the source (ASGART_E_ARG: the
+ * reference panics on the slice), a byte >= 0x80 in what is extracted (ASGART_E_ARG: the reference panics in
+ * String::from_utf8, :136-137).  Calls from several host threads on one source are safe (they take turns). */
+int32_t asgart_extract_sequences(asgart_source *src, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
+                                 int64_t first, uint8_t *out, uint64_t out_cap, uint64_t *seq_ends, int64_t *n_done);
+
 /* ---- finer-grained entry points mirroring the reference's inner API;
  *      used by the parity tests ------------------------------------------ */
 
