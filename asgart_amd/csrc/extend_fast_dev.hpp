@@ -1,7 +1,7 @@
 // extend_fast_dev.hpp -- "K6": the one-barrier arm-resident extension kernel.
 //
 // Same automaton as the other extension kernels (reference src/automaton.rs:57-204, representation of
-// pipeline_dev.hpp: only live arms are kept, winners by creation number, families by records),
+// extend_wave_dev.hpp: only live arms are kept, winners by creation number, families by records),
 // organised so that one processed hit-probe costs the workgroup ONE barrier, with loop-free
 // lookups and branch-free per-arm code, and a run of quiet probes costs nothing until the next
 // hit-probe:
@@ -38,7 +38,7 @@
 // Results are identical to the other extension kernels (tests force every segment through it).
 #pragma once
 
-#include "pipeline_dev.hpp"
+#include "extend_common_dev.hpp"
 
 namespace asgart {
 
@@ -79,21 +79,12 @@ template <class PosT, int S, int NT, int HB, int kRows = 1024, int kE = 4, bool 
 __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_fast_kernel(ExtParams<PosT> P) {  // (256 / 512 threads: four waves per SIMD, so that four / two workgroups share a compute unit)
     constexpr int CAP = S * NT;
     constexpr int NW = NT / 64;
-    constexpr uint32_t kNone = 0xFFFFFFFFu;    // best[]: no arm accepts this hit
-    constexpr uint32_t kNever = 0xFFFFFFFEu;   // what a candidate read of an idle lane returns: no creation number
-    // candidate register of an arm: up to three hit indices, 10 bits each, count in bits 30..31;
-    // kCoop: more than three, a window too wide for the table walk, or a probe whose stash overflowed
-    constexpr uint32_t kCoop = 0xFFFFFFFFu;
-    constexpr uint32_t kStash = 64;
     constexpr uint32_t kRowsLoop = 62;         // windows of up to this many rows are looked up by the arm itself (beyond the first two rows:
                                                // those whose occupancy bit is set)
     constexpr uint32_t kBitWords = (uint32_t)kRows / 32u;
-    constexpr bool kWidePos = sizeof(PosT) == 8;
-    // entry: 32-bit positions  [gen:22 | hit:10 | x:32];  64-bit positions  [gen:12 | hit:10 | x:42]
-    constexpr uint32_t kTagShift = kWidePos ? 42u : 32u;
-    constexpr uint32_t kGenMax = kWidePos ? 12u : 22u;
-    constexpr unsigned long long kPosMask = (1ull << kTagShift) - 1ull;
-    using WinT = typename std::conditional<kWidePos, uint64_t, uint32_t>::type;
+    using Tab = ArmTable<PosT>;  // (the layout of the hit-table entries)
+    using WinT = typename Tab::WinT;
+    constexpr bool kWidePos = Tab::kWidePos;
     static_assert(HB <= 1024 && S <= 8 && S * NW <= 128 && (kRows & (kRows - 1)) == 0 && (kE == 2 || kE == 4) && kRows >= 128 && kRows <= 2048, "shape");
     if (NT >= 1024) __builtin_amdgcn_s_setprio(3);
 
@@ -132,10 +123,8 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
     const uint64_t n_seg = *P.n_seg_ptr;
     const uint32_t k = (uint32_t)rp.k, step = (uint32_t)rp.step, G = rp.G;
     const uint32_t thr0 = arm_threshold(k, G);
-    // bucket width: the smallest power of two >= G + k (a young arm's window spans at most two rows)
-    uint32_t bsh = 3;
-    while ((1ull << bsh) < (unsigned long long)G + k) ++bsh;
-    const uint32_t kGenBits = min(kGenMax, max(2u, P.gen_bits));
+    const uint32_t bsh = bucket_shift(G, k);  // (a young arm's window spans at most two rows)
+    const uint32_t kGenBits = min(Tab::kGenMax, max(2u, P.gen_bits));
     const uint32_t cap_eff = min((uint32_t)CAP, P.cap_limit);
     const WinT w_loop = (WinT)(kRowsLoop - 1u) << bsh;  // windows up to this width span <= kRowsLoop rows
     RecAlloc rec_alloc;
@@ -175,12 +164,7 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
             seg_clock(P);
         }
         PROF_SEG_BEGIN();
-        const int c = chunk_of_uniform(rp.ch, g0);
-        const uint64_t cs = rp.ch.start[c], cl = rp.ch.len[c];
-        const bool seg_rev = (rp.mode_of(c) & 2u) != 0u;  // (the orientation of the chunk's pass)
-        const uint32_t pb = rp.ch.pbase[c];
-        const uint32_t chunk_end = rp.ch.pbase[c + 1];
-        const uint32_t g_end = min(chunk_end, rp.win_end(g0));  // (sharded calls: the window ends first)
+        const SegHeader sg = load_segment(rp, g0);
         // block-uniform bookkeeping
         uint32_t quiet = 0, pend = 0, fam_seq = 0, next_seq = 0;
         bool overflow = false, done = false, fam_open = false;
@@ -196,22 +180,8 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
             const unsigned long long em = __ballot(emit);
             if (!em) return;
             const unsigned long long at = rec_slot(rec_alloc, P, em, lane);
-            if (emit && at < P.rec_cap) {
-                const uint64_t ll = (uint64_t)le - (uint64_t)ls;
-                SdRec r;
-                r.g_start = g0;
-                r.fam_seq = fam_seq;
-                r.create_seq = seq;
-                r.pad = 0;
-                r.sd.left = seg_rev ? cs + cl - (uint64_t)ls - ll : (uint64_t)ls + cs;  // src/bin/asgart.rs:229-237
-                r.sd.right = rs;
-                r.sd.left_length = ll;
-                r.sd.right_length = (uint64_t)re - (uint64_t)rs;
-                P.recs[at] = r;
-            }
+            if (emit) write_record(P, at, g0, fam_seq, seq, 0u, sg.cs, sg.cl, sg.rev, ls, le, rs, re);
         };
-        auto tag_of = [&](unsigned long long e) { return (uint32_t)(e >> kTagShift); };
-        auto pos_of = [&](unsigned long long e) { return (PosT)(e & kPosMask); };
         // index the hits of one probe (cnt hits at s_hits[off..]) under generation `gen` in table tb, with
         // best[] / stash buffer bb; the TOP threads do it
         auto insert_hits = [&](uint32_t cnt, uint32_t off, uint32_t tb, uint32_t bb) {
@@ -219,7 +189,7 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
             for (uint32_t h = (uint32_t)(NT - 1 - tid); h < cnt; h += NT) {
                 const PosT x = s_hits[off + h];
                 s_best[bb][h] = kNone;
-                unsigned long long e = ((unsigned long long)(g10 | h) << kTagShift) | ((unsigned long long)x & kPosMask);
+                unsigned long long e = Tab::entry(g10 | h, x);
                 const uint32_t ri = ((uint32_t)((uint64_t)x >> bsh)) & (uint32_t)(kRows - 1);
                 unsigned long long *row = &s_tab[tb][ri * (uint32_t)kE];
                 atomicOr(&s_rowbits[bb][ri >> 5], 1u << (ri & 31u));
@@ -228,7 +198,7 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
                 for (int j = 0; j < kE; ++j) {
                     if (!placed) {
                         const unsigned long long old = atomicExch(&row[j], e);
-                        if (tag_of(old) - g10 >= 1024u) placed = true;  // displaced a stale entry: done
+                        if (Tab::tag_of(old) - g10 >= 1024u) placed = true;  // displaced a stale entry: done
                         else e = old;                                   // a hit of this probe: it moves on
                     }
                 }
@@ -303,8 +273,8 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
                         uint32_t ch = 0, nc = 0;
                         uint32_t *const sink = &s_sink[lane];
                         auto offer_w = [&](unsigned long long e, WinT wl) {
-                            const uint32_t d = tag_of(e) - g10;
-                            const WinT t = d < 1024u ? (WinT)(PosT)(pos_of(e) - lo) : ~(WinT)0;  // (no scalar AND of two masks)
+                            const uint32_t d = Tab::tag_of(e) - g10;
+                            const WinT t = d < 1024u ? (WinT)(PosT)(Tab::pos_of(e) - lo) : ~(WinT)0;  // (no scalar AND of two masks)
                             const bool ok = t < wl;
                             atomicMin(ok ? &s_best[bb][d & 1023u] : sink, key);
                             ch = ok ? ((ch << 10) | d) : ch;
@@ -777,36 +747,21 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
         // (Loading the next batch's per-probe words and hit rows ahead, in registers, was measured: the 1024-thread
         // shapes sit at their 128-register cap, the extra live values spill inside the probe loop, and the tandem
         // array went from 78 to 86 ms while the two-genome pass did not move.)
-        for (uint32_t g = g0; g < g_end && !done;) {
+        for (uint32_t g = g0; g < sg.g_end && !done;) {
             // ---- stage a batch of up to 64 probes (every wave computes the same masks) ----
             PROF_START();
-            const uint32_t nb = min(64u, g_end - g);
             if (tid == 0) heartbeat(P, g0, g);
-            const uint32_t f_l = (uint32_t)lane < nb ? P.p_filt[g + lane] : kSkipN;
-            const unsigned long long r_l = (uint32_t)lane < nb ? P.row_off[g + lane] : 0ull;
-            const unsigned long long r_hi = uni(P.row_off[g + nb]);
-            const unsigned long long base = lane_of(r_l, 0u);
-            unsigned long long r_next = __shfl_down(r_l, 1);
-            if ((uint32_t)lane + 1 >= nb) r_next = r_hi;
-            const bool fits = (uint32_t)lane < nb && r_next - base <= (unsigned long long)HB;
-            const unsigned long long fm = __ballot(fits);
-            uint32_t nbb = (~fm == 0ull) ? 64u : (uint32_t)(__ffsll((long long)~fm) - 1);
-            if (nbb > nb) nbb = nb;
-            if (nbb == 0) {  // one probe with more hits than the staging area: not for this kernel
+            const ProbeBatch bt = load_batch<HB>(P.p_filt, P.row_off, g, sg.g_end, lane);
+            if (bt.n == 0) {  // one probe with more hits than the staging area: not for this kernel
                 overflow = true;
                 break;
             }
-            const uint32_t rel_l = (uint32_t)(r_l - base);
-            const uint32_t tot = (uint32_t)((nbb == nb ? r_hi : lane_of(r_l, nbb)) - base);
-            if (tot) {  // (a batch of quiet probes stages nothing and needs no barrier)
+            if (bt.tot) {  // (a batch of quiet probes stages nothing and needs no barrier)
                 if (staged_before) lds_barrier();  // (the last B of the previous batch read the staged hits)
                 staged_before = true;
-                for (uint32_t r = tid; r < tot; r += NT) s_hits[r] = P.hits[base + r];
+                for (uint32_t r = tid; r < bt.tot; r += NT) s_hits[r] = P.hits[bt.base + r];
                 lds_barrier();
             }
-            const unsigned long long in_batch = nbb >= 64 ? ~0ull : ((1ull << nbb) - 1ull);
-            const unsigned long long hm = __ballot(f_l >= 1u && f_l < kPending) & in_batch;
-            const unsigned long long qm = __ballot(f_l == 0u) & in_batch;
             PROF_STOP(0);
             PROF_COUNT(1, 1);
             uint32_t pos = 0;
@@ -817,23 +772,20 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
                 bool have_cur = false;
                 Probe cur{0, 0, 0, 0, 0};
                 if (!done) {
-                    const unsigned long long hmr = pos >= 64 ? 0ull : (hm >> pos) << pos;
-                    const uint32_t b = hmr ? (uint32_t)(__ffsll((long long)hmr) - 1) : 64u;
-                    const unsigned long long upto = b >= 64 ? ~0ull : ((1ull << b) - 1ull);
-                    const unsigned long long from = pos >= 64 ? 0ull : ~((1ull << pos) - 1ull);
-                    const uint32_t q = (uint32_t)__popcll(qm & upto & from);
+                    uint32_t q;
+                    const uint32_t b = next_hit(bt, pos, q);
                     if (q) {  // folded into the next pass over the arms
                         quiet += q;
                         pend += q * step;
                         if (quiet >= rp.tstar) done = true;  // every arm is dead (gap >= G): the segment is over
                     }
-                    if (hmr && !done) {
+                    if (b < 64u && !done) {
                         have_cur = true;
                         quiet = 0;
                         pos = b + 1;
-                        cur.cnt = lane_of(f_l, b);
-                        cur.off = lane_of(rel_l, b);
-                        cur.i = (uint64_t)(g + b - pb + 1) * step;
+                        cur.cnt = lane_of(bt.f_l, b);
+                        cur.off = lane_of(bt.rel_l, b);
+                        cur.i = (uint64_t)(g + b - sg.pb + 1) * step;
                         cur.tb = par;
                         cur.bb = tri;
                     } else {
@@ -862,19 +814,17 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
                         // ... and goes on through the staged batch, without a barrier, while the next hit-probe is as
                         // sparse (the same accounting of the quiet probes in between as at the top of this loop)
                         for (;;) {
-                            const unsigned long long hmr = pos >= 64 ? 0ull : (hm >> pos) << pos;
-                            if (!hmr) break;
-                            const uint32_t b = (uint32_t)(__ffsll((long long)hmr) - 1);
-                            const unsigned long long span = ((1ull << b) - 1ull) & ~((1ull << pos) - 1ull);
-                            const uint32_t q = (uint32_t)__popcll(qm & span);
+                            uint32_t q;
+                            const uint32_t b = next_hit(bt, pos, q);
+                            if (b >= 64u) break;
                             if (q >= rp.tstar) break;  // (the segment ends there: left to the workgroup)
-                            const uint32_t cnt2 = lane_of(f_l, b);
+                            const uint32_t cnt2 = lane_of(bt.f_l, b);
                             if (cnt2 > kSoloHits || a_now + cnt2 > 64u) break;
                             pend = q * step;
                             Probe nx{0, 0, 0, 0, 0};
                             nx.cnt = cnt2;
-                            nx.off = lane_of(rel_l, b);
-                            nx.i = (uint64_t)(g + b - pb + 1) * step;
+                            nx.off = lane_of(bt.rel_l, b);
+                            nx.i = (uint64_t)(g + b - sg.pb + 1) * step;
                             pos = b + 1;
                             a_now = solo_probe(nx);
                             if (lane == 0) DBG_ADD(0, 1);
@@ -924,12 +874,12 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
                 PROF_STOP(4);
                 PROF_START();
                 {   // next hit probe of this staged batch, if any: the top threads index it in this interval
-                    const unsigned long long nxt = pos >= 64 ? 0ull : (hm >> pos) << pos;
+                    const unsigned long long nxt = pos >= 64 ? 0ull : (bt.hm >> pos) << pos;
                     const bool can_pre = nxt != 0ull && ((gen + 1u) >> kGenBits) == 0u;
                     if (can_pre) {
                         const uint32_t nb2 = (uint32_t)(__ffsll((long long)nxt) - 1);
                         ++gen;
-                        insert_hits(lane_of(f_l, nb2), lane_of(rel_l, nb2), par ^ 1u, (tri + 1u) % 3u);
+                        insert_hits(lane_of(bt.f_l, nb2), lane_of(bt.rel_l, nb2), par ^ 1u, (tri + 1u) % 3u);
                     }
                     pre_indexed = can_pre;
                 }
@@ -950,7 +900,7 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
                 }
             }
             if (overflow) break;
-            g += nbb;
+            g += bt.n;
         }
         if (!overflow) {
             // the age of the trailing quiet probes: whatever it kills is reported, and the family closes if
@@ -965,7 +915,7 @@ __global__ __launch_bounds__(NT, (NT == 512 || NT == 256) ? 4 : 1) void extend_f
                 total_free += lane_of(wave_incl_scan(fv2), 63u);
             }
             if (fam_open && total_free == (uint32_t)CAP) fam_open = false;
-            if (!done && g_end < chunk_end) {
+            if (!done && sg.g_end < sg.chunk_end) {
                 if (tid == 0) atomicAdd(&P.ctr[CT_RANOUT], 1ull);
             } else if (fam_open) {  // arms alive at the end of the chunk void their family (src/automaton.rs:201-203)
                 emit_records(tid == 0, (PosT)0, (PosT)0, (PosT)0, (PosT)0, kTombstone);

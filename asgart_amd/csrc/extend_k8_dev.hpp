@@ -2,7 +2,7 @@
 // (tier 3: the long dense segments, and every run over a range of a cut segment).
 //
 // Same automaton as the other extension kernels (reference src/automaton.rs:57-204; representation of
-// pipeline_dev.hpp: only live arms are kept, winners by creation number, families by records), same hit table and
+// extend_wave_dev.hpp: only live arms are kept, winners by creation number, families by records), same hit table and
 // per-arm code as K6 (extend_fast_dev.hpp).  What changes is who runs what.
 //
 // A wave issues at most one instruction every four cycles, so the time of a hit-probe is the length of the longest
@@ -117,7 +117,7 @@ constexpr uint32_t K8_STILL = 2u;      // the new arms of this block die of the 
 constexpr uint32_t K8_BIG = 4u;        // more than 64 new arms: the ranking wave offered for the first 64 only, every wave takes a
                                        // share of the others at the top of the next step (one extra barrier in such a step)
 
-// RANGE: a work item is not a segment but a RUN over part of one (struct RangeRun, pipeline_dev.hpp) --
+// RANGE: a work item is not a segment but a RUN over part of one (struct RangeRun, extend_common_dev.hpp) --
 // long segments cut into ranges that run side by side, each from an empty arm list some way in front of its cut.  What
 // differs from a whole segment: where the walk starts and stops; creation numbers that do not depend on what the run has
 // seen before (needle offset of the creating probe relative to the segment's first, then the hit's index: the same arm
@@ -129,20 +129,14 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
     constexpr int NW = NT / 64, NWA = NW - 2;  // waves; arm waves (then the RANKING wave and the PLANNING wave)
     constexpr int CAP = S * NWA * 64;
     constexpr int NE = S * NWA;                // (layer, wave) entries of the free counts
-    constexpr uint32_t kNone = 0xFFFFFFFFu;    // best[]: no arm accepts this hit
-    constexpr uint32_t kNever = 0xFFFFFFFEu;   // what a candidate read of an idle lane returns: no creation number
-    constexpr uint32_t kCoop = 0xFFFFFFFFu;    // candidate register: more than three / wide window / stash overflow
-    constexpr uint32_t kStash = 64;
     constexpr uint32_t kRowsWalk = 62;
     constexpr uint32_t kBitWords = (uint32_t)kRows / 32u;
-    constexpr bool kWidePos = sizeof(PosT) == 8;
-    constexpr uint32_t kTagShift = kWidePos ? 42u : 32u;
-    constexpr uint32_t kGenMax = kWidePos ? 12u : 22u;
-    constexpr unsigned long long kPosMask = (1ull << kTagShift) - 1ull;
+    using Tab = ArmTable<PosT>;  // (the layout of the hit-table entries)
+    using WinT = typename Tab::WinT;
+    constexpr bool kWidePos = Tab::kWidePos;
     constexpr uint32_t kTabBytes = (uint32_t)(kRows * kE * 8);  // one hit table
     constexpr uint32_t kCmdWords = 32;
     constexpr uint32_t kNewMax = kWidePos ? (uint32_t)HB / 2u : (uint32_t)HB;  // new arms of one probe (more: given up)
-    using WinT = typename std::conditional<kWidePos, uint64_t, uint32_t>::type;
     static_assert(!RANGE || S * NWA * 64 <= (int)kRunDumpCap, "runs over ranges: dump capacity");
     static_assert(NW >= 4 && HB <= 1024 && S <= 8 && NE <= 128 && (kRows & (kRows - 1)) == 0 && kE == 2 && kRows <= 2048 && CAP < 65536,
                   "shape");
@@ -211,8 +205,6 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
     if (tid == 0) s_never = kNever;
     lds_barrier();
 
-    auto tag_of = [&](unsigned long long e) { return (uint32_t)(e >> kTagShift); };
-    auto pos_of = [&](unsigned long long e) { return (PosT)(e & kPosMask); };
     char *const tab0 = reinterpret_cast<char *>(&s_tab[0][0]);
     char *const best0 = reinterpret_cast<char *>(&s_best[0][0]);
 
@@ -274,21 +266,11 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
             const unsigned long long em = __ballot(emit);
             if (!em) return;
             const unsigned long long at = rec_slot(rec_alloc, P, em, lane);
-            if (emit && at < P.rec_cap) {
-                const uint64_t cs = s_seg[1], cl = s_seg[2] & ~(1ull << 63);
-                const bool seg_rev = (s_seg[2] >> 63) != 0ull;  // (the orientation of the chunk's pass rides in the top bit)
-                const uint64_t ll = (uint64_t)le - (uint64_t)ls;
-                SdRec r;
-                r.g_start = (uint32_t)s_seg[0];
-                r.fam_seq = fam_seq;
-                r.create_seq = seq;
-                r.pad = RANGE ? (uint32_t)seg + 1u : 0u;  // (RANGE: the run, for the host's renumbering of its families)
-                r.sd.left = seg_rev ? cs + cl - (uint64_t)ls - ll : (uint64_t)ls + cs;  // src/bin/asgart.rs:229-237
-                r.sd.right = rs;
-                r.sd.left_length = ll;
-                r.sd.right_length = (uint64_t)re - (uint64_t)rs;
-                P.recs[at] = r;
-            }
+            // (the orientation of the chunk's pass rides in the top bit of its length; RANGE: pad names the run, for the
+            // host's renumbering of its families)
+            if (emit)
+                write_record(P, at, (uint32_t)s_seg[0], fam_seq, seq, RANGE ? (uint32_t)seg + 1u : 0u, s_seg[1], s_seg[2] & ~(1ull << 63),
+                             (s_seg[2] >> 63) != 0ull, ls, le, rs, re);
         };
         // index the hits of one probe under generation tag g10 in the table at byte offset tabo, winners at byte offset
         // besto, stash / occupancy bits bb; its rows are at s_hits[off..] or, when gsrc is set (the probe opens a batch
@@ -299,7 +281,7 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
             for (uint32_t h = me; h < cnt; h += NT) {
                 const PosT x = gsrc ? P.hits[gbase + h] : s_hits[off + h];
                 *reinterpret_cast<uint32_t *>(best0 + besto + 4u * h) = kNone;
-                unsigned long long e = ((unsigned long long)(g10 | h) << kTagShift) | ((unsigned long long)x & kPosMask);
+                unsigned long long e = Tab::entry(g10 | h, x);
                 const uint32_t ri = ((uint32_t)((uint64_t)x >> bsh)) & (uint32_t)(kRows - 1);
                 unsigned long long *row = reinterpret_cast<unsigned long long *>(tab0 + tabo + ri * (uint32_t)(kE * 8));
                 atomicOr(&s_rowbits[bb][ri >> 5], 1u << (ri & 31u));
@@ -308,7 +290,7 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
                 for (int j = 0; j < kE; ++j) {
                     if (!placed) {
                         const unsigned long long old = atomicExch(&row[j], e);
-                        if (tag_of(old) - g10 >= 1024u) placed = true;  // displaced a stale entry: done
+                        if (Tab::tag_of(old) - g10 >= 1024u) placed = true;  // displaced a stale entry: done
                         else e = old;                                   // a hit of this probe: it moves on
                     }
                 }
@@ -355,8 +337,8 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
             uint32_t ch = 0, nc = 0;
             uint32_t *const sink = &s_sink[lane];
             auto offer = [&](unsigned long long e, WinT wl) {
-                const uint32_t d = tag_of(e) - g10;
-                const WinT t = d < 1024u ? (WinT)(PosT)(pos_of(e) - lo) : ~(WinT)0;
+                const uint32_t d = Tab::tag_of(e) - g10;
+                const WinT t = d < 1024u ? (WinT)(PosT)(Tab::pos_of(e) - lo) : ~(WinT)0;
                 const bool ok = t < wl;
                 atomicMin(ok ? reinterpret_cast<uint32_t *>(best + 4u * (d & 1023u)) : sink, key);
                 ch = ok ? ((ch << 10) | d) : ch;
@@ -372,14 +354,14 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
                 uint32_t first = 0;
 #pragma unroll
                 for (int j = 3; j >= 0; --j) {
-                    const uint32_t d = tag_of(ee[j]) - g10;
-                    const WinT t = d < 1024u ? (WinT)(PosT)(pos_of(ee[j]) - lo) : ~(WinT)0;
+                    const uint32_t d = Tab::tag_of(ee[j]) - g10;
+                    const WinT t = d < 1024u ? (WinT)(PosT)(Tab::pos_of(ee[j]) - lo) : ~(WinT)0;
                     first = t < w_eff ? d : first;
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const uint32_t d = tag_of(ee[j]) - g10;
-                    const WinT t = d < 1024u ? (WinT)(PosT)(pos_of(ee[j]) - lo) : ~(WinT)0;
+                    const uint32_t d = Tab::tag_of(ee[j]) - g10;
+                    const WinT t = d < 1024u ? (WinT)(PosT)(Tab::pos_of(ee[j]) - lo) : ~(WinT)0;
                     const bool ok = t < w_eff;
                     ch = ok ? ((ch << 10) | d) : ch;
                     nc += ok ? 1u : 0u;
@@ -388,8 +370,8 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
                 if (K7_RARE(__ballot(nc > 1u) != 0ull)) {
 #pragma unroll
                     for (int j = 1; j < 4; ++j) {
-                        const uint32_t d = tag_of(ee[j]) - g10;
-                        const WinT t = d < 1024u ? (WinT)(PosT)(pos_of(ee[j]) - lo) : ~(WinT)0;
+                        const uint32_t d = Tab::tag_of(ee[j]) - g10;
+                        const WinT t = d < 1024u ? (WinT)(PosT)(Tab::pos_of(ee[j]) - lo) : ~(WinT)0;
                         atomicMin(t < w_eff ? reinterpret_cast<uint32_t *>(best + 4u * (d & 1023u)) : sink, key);
                     }
                 }
@@ -1059,55 +1041,34 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
             const RunParams &rp = P.rp;
             const uint32_t k = (uint32_t)rp.k, step = (uint32_t)rp.step, G = rp.G;
             const uint32_t thr0 = arm_threshold(k, G);
-            uint32_t bsh = 3;
-            while ((1ull << bsh) < (unsigned long long)G + k) ++bsh;
-                    const uint32_t kGenBits = min(kGenMax, max(2u, P.gen_bits));
+            const uint32_t bsh = bucket_shift(G, k);
+            const uint32_t kGenBits = min(Tab::kGenMax, max(2u, P.gen_bits));
             const uint32_t g0 = RANGE ? run.g_seg0 : P.seg_list[seg];
             if (lane == 0) {
-            heartbeat(P, g0, 0u);
-            seg_clock(P);
-        }
-            const int c = chunk_of_uniform(rp.ch, g0);
-            const uint64_t cs = rp.ch.start[c], cl = rp.ch.len[c];
-            const uint32_t pb = rp.ch.pbase[c];
-            const uint32_t chunk_end = rp.ch.pbase[c + 1];
-            const uint32_t w_end = min(chunk_end, rp.win_end(g0));  // (sharded calls: the window ends first)
-            const uint32_t g_end = RANGE ? min(w_end, run.g_stop) : w_end;
+                heartbeat(P, g0, 0u);
+                seg_clock(P);
+            }
+            const SegHeader sg = load_segment(rp, g0);
+            const uint32_t g_end = RANGE ? min(sg.g_end, run.g_stop) : sg.g_end;
             if (lane == 0) {
                 if constexpr (RANGE) s_end[3] = (uint32_t)wall_clock64();  // (the run's duration goes into its state: option debug)
                 s_seg[0] = g0;
-                s_seg[1] = cs;
-                s_seg[2] = cl | ((unsigned long long)((rp.mode_of(c) >> 1) & 1u) << 63);
+                s_seg[1] = sg.cs;
+                s_seg[2] = sg.cl | ((unsigned long long)sg.rev << 63);
             }
             uint32_t quiet = 0, pend = 0;
             bool done = false, giveup = false;
             uint32_t hbuf = 2;  // (the first batch moves it to 0)
             // ---- the batch under the cursor ---------------------------------------------------------------------
-            uint32_t g = RANGE ? run.g_begin : g0, nbb = 0, pos = 0, f_l = 0, rel_l = 0, tot = 0;
-            unsigned long long hm = 0, qm = 0, base = 0;
+            uint32_t g = RANGE ? run.g_begin : g0, pos = 0;
+            ProbeBatch bt{};
             bool staged = false;  // the rows of the batch under the cursor are in s_hits[hbuf] (or on their way)
-            auto load_batch = [&]() {  // -> false: a probe with more hits than the staging area
-                const uint32_t nb = min(64u, g_end - g);
+            auto open_batch = [&]() {  // -> false: a probe with more hits than the staging area
                 if (lane == 0) heartbeat(P, g0, g);
-                f_l = (uint32_t)lane < nb ? P.p_filt[g + lane] : kSkipN;
-                const unsigned long long r_l = (uint32_t)lane < nb ? P.row_off[g + lane] : 0ull;
-                const unsigned long long r_hi = uni(P.row_off[g + nb]);
-                base = lane_of(r_l, 0u);
-                unsigned long long r_next = __shfl_down(r_l, 1);
-                if ((uint32_t)lane + 1 >= nb) r_next = r_hi;
-                const bool fits = (uint32_t)lane < nb && r_next - base <= (unsigned long long)HB;
-                const unsigned long long fm = __ballot(fits);
-                nbb = (~fm == 0ull) ? 64u : (uint32_t)(__ffsll((long long)~fm) - 1);
-                if (nbb > nb) nbb = nb;
-                if (nbb == 0) return false;
-                rel_l = (uint32_t)(r_l - base);
-                tot = (uint32_t)((nbb == nb ? r_hi : lane_of(r_l, nbb)) - base);
-                const unsigned long long in_batch = nbb >= 64 ? ~0ull : ((1ull << nbb) - 1ull);
-                hm = __ballot(f_l >= 1u && f_l < kPending) & in_batch;
-                qm = __ballot(f_l == 0u) & in_batch;
+                bt = load_batch<HB>(P.p_filt, P.row_off, g, g_end, lane);
                 pos = 0;
                 staged = false;
-                return true;
+                return bt.n != 0u;
             };
             struct Probe {
                 uint32_t cnt, off, tb, bb, g10, pend;
@@ -1123,11 +1084,8 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
             bool opened = false;  // the probe just found opened a batch (its rows are to be staged)
             auto next_probe = [&](Probe &nx) -> bool {
                 for (;;) {
-                    const unsigned long long hmr = pos >= 64 ? 0ull : (hm >> pos) << pos;
-                    const uint32_t b = hmr ? (uint32_t)(__ffsll((long long)hmr) - 1) : 64u;
-                    const unsigned long long upto = b >= 64 ? ~0ull : ((1ull << b) - 1ull);
-                    const unsigned long long from = pos >= 64 ? 0ull : ~((1ull << pos) - 1ull);
-                    const uint32_t q = (uint32_t)__popcll(qm & upto & from);
+                    uint32_t q;
+                    const uint32_t b = next_hit(bt, pos, q);
                     if (q) {
                         quiet += q;
                         pend += q * step;
@@ -1136,7 +1094,7 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
                             return false;
                         }
                     }
-                    if (hmr) {
+                    if (b < 64u) {
                         quiet = 0;
                         pos = b + 1;
                         opened = false;
@@ -1145,16 +1103,16 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
                             opened = true;
                             staged = true;
                         }
-                        nx.cnt = lane_of(f_l, b);
-                        nx.off = hbuf * (uint32_t)HB + lane_of(rel_l, b);
-                        nx.i = (uint64_t)(g + b - pb + 1) * step;
+                        nx.cnt = lane_of(bt.f_l, b);
+                        nx.off = hbuf * (uint32_t)HB + lane_of(bt.rel_l, b);
+                        nx.i = (uint64_t)(g + b - sg.pb + 1) * step;
                         nx.pend = pend;
                         pend = 0;
                         return true;
                     }
-                    g += nbb;
+                    g += bt.n;
                     if (g >= g_end) return false;
-                    if (!load_batch()) {
+                    if (!open_batch()) {
                         giveup = true;
                         return false;
                     }
@@ -1213,8 +1171,8 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
                 Plan p{};
                 p.q = nx;
                 p.pre = opened ? K7_STAGE : 0u;
-                p.st_base = base;
-                p.st_tot = tot;
+                p.st_base = bt.base;
+                p.st_tot = bt.tot;
                 p.st_buf = hbuf;
                 p.flags = K7_CUR | (opened ? K7_LATE : 0u);
                 if (wrap) {
@@ -1254,7 +1212,7 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
             // ---- the first two steps are planned before the loop ---------------------------------------------------
             Plan p_cur{}, p_next{};
             p_cur.q = p_next.q = no_probe;
-            if (!load_batch()) giveup = true;
+            if (!open_batch()) giveup = true;
             if (giveup) p_cur.flags = K7_GIVEUP;
             else p_cur = advance(0u);  // (the segment starts with a hit-probe: its batch is staged and indexed below)
             if (lane == 0) {
@@ -1311,7 +1269,7 @@ __global__ __launch_bounds__(NT) void extend_k8_kernel(ExtParams<PosT> P) {
                     const Plan p_after = advance(nflags);
                     write_cmd(sc == 0u ? 2u : sc - 1u, p_after, Before{N(1), N(6), N(7), N(2), N(9)});
                     if ((p_after.flags & K7_LAST) && lane == 0) {  // (what the ranking wave needs when the segment is over)
-                        s_end[1] = (!done && g_end < chunk_end && (!RANGE || w_end == g_end)) ? 1u : 0u;
+                        s_end[1] = (!done && g_end < sg.chunk_end && (!RANGE || sg.g_end == g_end)) ? 1u : 0u;
                     }
                 }
                 if (npre & K7_STAGE) store_rows(st_tot, st_buf);

@@ -5,6 +5,8 @@
 // src/bin/asgart.rs:201-253 (chunk fan-out, needle preparation, automaton,
 // left fix-up, fold in chunk order).
 #include "pipeline_dev.hpp"
+#include "extend_wave_dev.hpp"
+#include "extend_heavy_dev.hpp"
 #include "extend_fast_dev.hpp"
 #include "extend_k8_dev.hpp"
 

@@ -1,117 +1,20 @@
-// pipeline_dev.hpp -- device kernels of the probe -> search -> extend pipeline.
+// pipeline_dev.hpp -- device kernels of the probe -> search -> extend pipeline, up to the extension: the front, the
+// placement of the segments onto the extension tiers, the cut planner of the runs over ranges.
 //
 //   K1 probe_count_kernel   one thread per probe: key, SA interval, filtered count
 //   K1b big_count_kernel    one wave per probe with a large interval (early exit)
 //   K2 scan_{reduce,mid,down}  row offsets + quiet-run segmentation
 //   K3 fill_{small,big}_kernel  filtered hits in SA order -> CSR
-//   K4 extend_kernel        one wavefront per independent automaton segment
+// The extension kernels have a file each (extend_{wave,heavy,fast,k8}_dev.hpp) over extend_common_dev.hpp.
 //
 // Reference semantics: src/automaton.rs:57-216 (see DESIGN.md for the proof
 // that a run of ceil(G/step) processed zero-hit probes empties the arm list,
 // which is what makes segments independent).
 #pragma once
 
-#include "search_dev.hpp"
-
-#include <type_traits>
+#include "extend_common_dev.hpp"
 
 namespace asgart {
-
-constexpr int kTiers = 7;  // extension tiers (see the placement in pipeline.hip)
-constexpr int kRunsStat = kTiers + 1;  // statistics slot (ExtParams::tier) of the runs over ranges: after the tiers'
-
-// device counters (u64 each)
-enum Counter {
-    CT_BIG = 0,       // entries in big_list
-    CT_SEG,           // entries in seg_list
-    CT_SCAN_TICKET,   // scan_segments_kernel: the next tile
-    CT_FAM,           // families emitted
-    CT_SD,            // ProtoSDs emitted
-    CT_OVF,           // segments that overflowed the arm capacity
-    CT_TOTAL_HITS,    // CSR size
-    CT_N_SKIPPED,
-    CT_CARD_SKIPPED,
-    CT_WITH_HITS,
-    CT_RAW_HITS,
-    CT_SEARCHED,
-    CT_BISECT,        // yardstick
-    CT_OVF_CURSOR,
-    CT_AMBIG,         // sharding: start decisions that need a longer look-back
-    CT_RANOUT,        // sharding: segments that ran past the look-ahead window
-    // 16..33 and 56..67: per-phase cycle sums of the diagnostic build (-DASGART_PROFILE_EXTEND)
-    CT_EARLY_N = 34,    // early cascade launches (of tiers 3 and 6): list lengths ...
-    CT_EARLY_CUR = 36,  // ... and work cursors
-    CT_RANK = 38,       // entries in rank_list (large intervals counted by bisection of the position-sorted lists)
-    CT_BIG0 = 39,       // entries of big_list that big_count_kernel counted (later ones were appended for the fill)
-    CT_ALG_BYTES = 68,  // accounting pass: bytes the probe-search kernels move by design
-    CT_FLT_REJECTED,    // accounting pass: probes answered by the position bits alone
-    CT_LONGSEG,         // placement: segments the lane-per-segment walk handed to the wave-per-segment kernel
-    CT_ALG_BYTES16,     // accounting pass: the part of CT_ALG_BYTES that is wide coalesced loads (16 bytes per lane)
-    CT_HIST_PEAK = 72,   // diagnostic build: log2 histograms per launch (16 bins each)
-    CT_HIST_PROBES = 88,
-    CT_N1 = 104,       // list lengths of the extension tiers 1..kTiers (kTiers entries)
-    CT_NF = 111,       // ... of a cascade launch
-    CT_CUR1 = 112,     // work cursors of the tiers (kTiers entries)
-    CT_CURF = 119,
-    CT_OVF1 = 120,     // segments tier t gave up on (kTiers entries; the last one has nowhere to go)
-    CT_BUSY1 = 128,    // per tier: sum over its workgroups of their lifetime, in 10-ns ticks (how much of the chip a tier holds:
-                       // persistent workgroups own their share of a compute unit from launch to exit) ...
-    CT_WGS1 = 136,     // ... and the number of workgroups summed
-    CT_TPROBES1 = 144, // placement statistics (option debug only): hit-probes per tier ...
-    CT_THITS1 = 152,   // ... and hits per tier
-    CT_SEGMAX1 = 160,  // per tier: the longest time one workgroup spent on ONE segment, in 10-ns ticks -- the serial floor of
-                       // the extension (what neither more compute units nor more GPUs shorten)
-    CT_CLUSTER_BARREN = 168,  // segments cluster_barren_kernel proved barren
-    CT_CLUSTER_CUR = 169,     // its work cursors (two launches)
-    CT_COUNT = 176
-};
-
-__device__ inline int chunk_of(const ChunkTable &ch, uint32_t g) {
-    // last c with pbase[c] <= g  (pbase non-decreasing; empty chunks repeat values)
-    int lo = 0, hi = ch.n_chunks;  // answer in [lo, hi)
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (ch.pbase[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// same for a wave-uniform probe number: keeps the bisection in scalar registers / scalar loads
-__device__ inline int chunk_of_uniform(const ChunkTable &ch, uint32_t g) {
-    g = __builtin_amdgcn_readfirstlane(g);
-    int lo = 0, hi = ch.n_chunks;
-    while (hi - lo > 1) {
-        const int mid = __builtin_amdgcn_readfirstlane((lo + hi) >> 1);
-        if (ch.pbase[mid] <= g) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
-
-// hit filter of src/automaton.rs:105-114
-__device__ inline bool keep_hit(uint64_t x, uint64_t i, uint64_t s, uint64_t L, bool reverse) {
-    if (!reverse) return x > i + s;  // implies x != i
-    return x != i && x >= s + L - i;
-}
-
-// Workgroup barrier for data exchanged through LDS only.  __syncthreads() also waits for the
-// wave's outstanding GLOBAL stores (vmcnt(0)): one record written to HBM would stall every wave
-// of the workgroup for a memory round trip at the next barrier.  The extension kernels never
-// read back what they store to global memory, so their per-probe barriers only drain LDS traffic.
-__device__ inline void lds_barrier() { __asm__ volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Wave-uniform values the compiler cannot prove uniform (read from LDS, or a lane of a vector):
-// forcing them into scalar registers keeps the per-probe bookkeeping and branches on the scalar
-// unit instead of exec-masked vector code and LDS permutes.
-__device__ inline uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ inline unsigned long long uni(unsigned long long v) {
-    return ((unsigned long long)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v);
-}
-__device__ inline uint32_t lane_of(uint32_t v, uint32_t l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
-}
-__device__ inline unsigned long long lane_of(unsigned long long v, uint32_t l) {
-    return ((unsigned long long)lane_of((uint32_t)(v >> 32), l) << 32) | lane_of((uint32_t)v, l);
-}
 
 // ---------------------------------------------------------------- K1 ---------
 // Probe search: one thread per probe, one workgroup per 256 consecutive probes.
@@ -633,33 +536,6 @@ __device__ inline ScanEl scan_combine(const ScanEl &a, const ScanEl &b) {
     return r;
 }
 
-// inclusive prefix sum across the 64 lanes of a wave (gfx9 DPP: row shifts + row broadcasts)
-__device__ inline uint32_t wave_incl_scan(uint32_t x) {
-#define ASGART_DPP_ADD(ctrl, rows) \
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, rows, 0xf, false)
-    ASGART_DPP_ADD(0x111, 0xf);  // row_shr:1
-    ASGART_DPP_ADD(0x112, 0xf);  // row_shr:2
-    ASGART_DPP_ADD(0x114, 0xf);  // row_shr:4
-    ASGART_DPP_ADD(0x118, 0xf);  // row_shr:8
-    ASGART_DPP_ADD(0x142, 0xa);  // row_bcast:15 -> rows 1, 3
-    ASGART_DPP_ADD(0x143, 0xc);  // row_bcast:31 -> rows 2, 3
-#undef ASGART_DPP_ADD
-    return x;
-}
-
-// inclusive running maximum across the 64 lanes of a wave (values >= 0: lanes without a source contribute 0)
-__device__ inline uint32_t wave_incl_max_scan(uint32_t x) {
-#define ASGART_DPP_MAX(ctrl, rows) \
-    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, rows, 0xf, false))
-    ASGART_DPP_MAX(0x111, 0xf);  // row_shr:1
-    ASGART_DPP_MAX(0x112, 0xf);  // row_shr:2
-    ASGART_DPP_MAX(0x114, 0xf);  // row_shr:4
-    ASGART_DPP_MAX(0x118, 0xf);  // row_shr:8
-    ASGART_DPP_MAX(0x142, 0xa);  // row_bcast:15 -> rows 1, 3
-    ASGART_DPP_MAX(0x143, 0xc);  // row_bcast:31 -> rows 2, 3
-#undef ASGART_DPP_MAX
-    return x;
-}
 
 constexpr int kScanBlock = 512;
 constexpr int kScanRounds = 16;                                  // rounds of 64 probes per wave and tile
@@ -1119,669 +995,6 @@ __global__ __launch_bounds__(256) void fill_big_kernel(IndexView<SlotT> ix, RunP
             }
         }
     }
-}
-
-// ---------------------------------------------------------------- K4 ---------
-// Seed-extension automaton, one wavefront per independent segment.
-//
-// Representation (equivalent to, not a transcription of, src/automaton.rs:87-200):
-//   * only LIVE (active) arms are kept.  An arm that turns inactive can never
-//     be extended again (try_extend_arms tests `a.active`, :68) and is only
-//     looked at once more, when its family is flushed (:182-200), so it is
-//     retired at once: written to the output list if len(right) >= M, dropped
-//     otherwise.  (The reference's `retain` at :173-179 removes a subset of the
-//     same arms; both removals are unobservable.)
-//   * the family is flushed when the live list becomes empty; its members are
-//     the retired arms, ordered by creation number (== position in the
-//     reference's `arms` vector).  The host sorts records by
-//     (segment start, family ordinal, creation number).
-//   * arms still live at the end of the chunk are dropped AND their family's
-//     retired members are void (:201-203): a tombstone record says so.
-//   * <= 64 live arms: one arm per lane, in registers; otherwise LDS arrays.
-//   * the hit rows of up to 64 consecutive probes are contiguous in the CSR and
-//     are staged through LDS with one coalesced load.
-constexpr uint32_t kTombstone = 0xFFFFFFFFu;
-
-// Diagnostic build only (-DASGART_PROFILE_EXTEND): per-phase cycle sums of the extension kernel
-// are added to ctr[16..]; never enabled in the shipped library.
-#ifdef ASGART_PROFILE_EXTEND
-#define PROF_DECL unsigned long long pf_t0 = 0, pf_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define PROF_START() pf_t0 = __builtin_amdgcn_s_memtime()
-#define PROF_STOP(slot) pf_acc[slot] += __builtin_amdgcn_s_memtime() - pf_t0
-#define PROF_COUNT(slot, v) pf_acc[slot] += (v)  // (slots 10, 11: sums of live arms and hits over the hit-probes)
-#define PROF_MAX(slot, v) pf_acc[slot] = pf_acc[slot] > (unsigned long long)(v) ? pf_acc[slot] : (unsigned long long)(v)
-#define PROF_SEG_BEGIN() const unsigned long long pf_seg0 = __builtin_amdgcn_s_memtime()
-#define PROF_FLUSH()                                                             \
-    do {                                                                         \
-        const unsigned long long pf_dt = __builtin_amdgcn_s_memtime() - pf_seg0; \
-        if (lane == 0 && atomicMax(&P.ctr[28], pf_dt) < pf_dt) {                 \
-            P.ctr[29] = g0;                                                      \
-            P.ctr[30] = ((unsigned long long)pf_acc[5] << 32) | pf_acc[3];       \
-            P.ctr[31] = ((unsigned long long)pf_acc[10] << 32) | pf_acc[11];     \
-            P.ctr[32] = pf_acc[0];                                               \
-            P.ctr[33] = pf_acc[6];                                               \
-            P.ctr[25] = pf_acc[9];                                               \
-            for (int pf_i = 0; pf_i < 12; ++pf_i) P.ctr[56 + pf_i] = pf_acc[pf_i]; \
-        }                                                                        \
-        if (lane == 0)                                                           \
-            for (int pf_i = 0; pf_i < 12; ++pf_i)                                \
-                if (pf_acc[pf_i]) atomicAdd(&P.ctr[16 + pf_i], pf_acc[pf_i]);     \
-        if (lane == 0) {                                                         \
-            int pf_b = 0;                                                        \
-            while (pf_b < 15 && (2ull << pf_b) <= pf_acc[9]) ++pf_b;             \
-            atomicAdd(&P.ctr[CT_HIST_PEAK + pf_b], 1ull);                        \
-            pf_b = 0;                                                            \
-            while (pf_b < 15 && (2ull << pf_b) <= pf_acc[5] + pf_acc[3]) ++pf_b; \
-            atomicAdd(&P.ctr[CT_HIST_PROBES + pf_b], pf_acc[5] + pf_acc[3]);     \
-        }                                                                        \
-        for (int pf_i = 0; pf_i < 12; ++pf_i) pf_acc[pf_i] = 0;                  \
-    } while (0)
-#define DBG_ADD(slot, v) atomicAdd(&P.ctr[40 + (slot)], (unsigned long long)(v))
-#else
-#define DBG_ADD(slot, v)
-#define PROF_DECL
-#define PROF_START()
-#define PROF_STOP(slot)
-#define PROF_COUNT(slot, v)
-#define PROF_MAX(slot, v)
-#define PROF_SEG_BEGIN()
-#define PROF_FLUSH()
-#endif
-constexpr int kHitBatch = 1024;  // LDS staging for the hit rows of one probe batch
-constexpr uint32_t kEscalateCost = 40000;  // sum of (live arms + hits) over LDS-path probes
-
-// A RUN over part of a long segment (extend_k8_kernel<..., RANGE = true>; plan_ranges_kernel makes them): the walk starts at
-// probe g_begin with no arm and stops in front of g_stop; records are written from probe emit_from on (the cut: a hit-probe;
-// what lies in front of it is the run's warm-up and belongs to the range before).
-struct RangeRun {
-    uint32_t g_begin, g_stop;  // [g_begin, g_stop) (g_stop = ~0u: to the segment's end)
-    uint32_t g_seg0;           // first probe of the segment (record key, chunk)
-    uint32_t emit_from;        // the cut this run reports from (g_seg0: from the start)
-    uint32_t flags;            // kRunNoEmit | kRunLast
-    uint32_t split;            // which split segment (struct SplitSeg)
-    uint32_t pad0, pad1;
-};
-constexpr uint32_t kRunNoEmit = 1u;    // a warm-up on its own: only its final state is wanted (what the run behind the cut starts from)
-constexpr uint32_t kRunLast = 2u;      // the run that reaches the segment's end
-constexpr uint32_t kRunDumpCap = 5120; // arms a run can leave alive (the long shape's slots)
-// per run two states, 8 words each (run_meta): [0] what it holds when it STOPS, [1] what it holds when it reaches its cut:
-// 0 arms written to run_dump  1 flushes since the cut  2 family open  3 probes a flush is still held back for  4 ([0] only) gave up
-// (more arms than slots, a probe with more hits than the staging area)
-// per run two dumps of kRunDumpCap arms (run_dump), kDumpWords per arm, the creation number first (32-bit positions: creation
-// number, left start, left end, right start | right end, threshold, gap, 0; 64-bit: creation number, threshold, gap, 0 | left
-// start, left end | right start, right end)
-template <class PosT> constexpr uint32_t kDumpWords = sizeof(PosT) == 4 ? 8u : 12u;
-struct SplitSeg {
-    uint32_t g_seg0, run_base, n_ranges, cut_base;  // runs run_base .. + n_ranges - 1: the ranges; cuts cut_base .. + n_ranges - 2
-    uint32_t span, hits, tier, warm;                // (what the placement knew of the segment; the warm-up its ranges got)
-};
-
-template <class PosT>
-struct ExtParams {
-    const RangeRun *runs;                 // (RANGE launches) the work list
-    uint32_t *run_meta, *run_dump;        // ... and what the runs leave behind (see RangeRun)
-    RunParams rp;
-    const uint32_t *p_filt;
-    const unsigned long long *row_off;
-    const PosT *hits;
-    const uint32_t *seg_list;
-    const unsigned long long *n_seg_ptr;  // device count of seg_list entries
-    unsigned long long *cursor;           // work-fetch cursor
-    SdRec *recs;
-    unsigned long long rec_cap;
-    uint32_t *ovf_list;                   // segments this launch gives up on go here (may be null)
-    unsigned long long *ovf_count;        // ... appended at *ovf_count (device counter)
-    char *scratch;                        // heavy global tier: per-workgroup arm storage
-    uint32_t gen_bits;                    // arm-resident kernels: bits of the table generation counter (tests shrink it)
-    uint32_t escalate_cost;               // one-wave tiers: give up after this much LDS-path work
-    uint32_t cap_limit;                   // effective live-arm capacity (<= CAP; tests lower it)
-    uint32_t heavy_cap;                   // K4b MODE 2 (tier 7): arm slots per workgroup in its HBM slice
-    uint32_t solo_hits;                   // K6: probes with up to this many hits may run on wave 0 alone (0: never)
-    uint32_t k8_delay;                    // K8 (tests): cycles the ranking wave waits before it reads the free counts
-    uint32_t tier;                        // the tier this launch runs as (statistics)
-    unsigned long long *seg_slots;        // 4096 words of this launch's tier: start time of the segment a workgroup is on (seg_clock)
-    unsigned long long *ctr;
-    unsigned long long *hb;               // heartbeat slots of this launch's tier (pinned host memory; null: none)
-};
-
-// a workgroup's sign of life (see SearchCtx::heartbeat): which segment it is on and how far
-template <class PosT>
-__device__ inline void heartbeat(const ExtParams<PosT> &P, uint32_t g0, uint32_t at) {
-    if (P.hb) {
-        unsigned long long *slot = P.hb + 2u * (blockIdx.x % 256u);
-        __builtin_nontemporal_store((unsigned long long)g0 | 1ull << 63, slot);
-        __builtin_nontemporal_store((unsigned long long)at, slot + 1);
-    }
-}
-
-// The whole predicate of try_extend_arms (src/automaton.rs:68-70) for an active arm with right
-// segment [rs, re], threshold thr, and a hit m = [x, x+k]:
-//     d_ss(a.right, m) < thr  &&  m.end > a.right.end
-// Because len(right) >= k always (an arm starts as [x0, x0+k] and re only grows), this is
-// exactly   re - k < x < re + thr   (thr >= 1), i.e. (x - lo) < w in unsigned arithmetic with
-// lo = re - k + 1, w = thr + k - 1:
-//   x <= re : x > re-k >= rs so m.start lies in [rs, re]            -> d_ss = 0 < thr
-//   x >  re : no containment, d_ss = min(x+k-rs, x-re) = x - re     -> accept iff x - re < thr
-// (thr == 0 accepts nothing.)  tests/test_oracle_golden.py checks the equivalence exhaustively
-// against the oracle's literal d_ss.
-template <class PosT>
-__device__ inline bool arm_accepts(PosT x, PosT re, uint32_t thr, uint32_t k) {
-    const PosT lo = (PosT)(re - k + 1u);
-    const uint64_t w = thr ? (uint64_t)thr + k - 1u : 0u;
-    return (uint64_t)(PosT)(x - lo) < w;
-}
-
-// max(e, (0.1 * len as f64) as i64)   (src/automaton.rs:69).  The double product truncates to
-// len / 10 for every len < 9e15 (0.1 rounds UP to 0.1000000000000000055, so the product can only
-// cross an integer boundary once len / 10 * 1.1e-16 reaches 0.1; checked for 3M values up to 2^40 in
-// tests/test_oracle_golden.py::test_tenth_threshold_is_integer_division), so the kernels divide.
-__device__ inline uint32_t arm_threshold(uint64_t left_len, uint32_t G) {
-    const uint64_t tenth = left_len <= 0xFFFFFFFFull ? (uint64_t)((uint32_t)left_len / 10u) : left_len / 10u;
-    const uint64_t thr = tenth > (uint64_t)G ? tenth : (uint64_t)G;
-    return thr > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)thr;
-}
-
-// Output records are appended to one device-wide list.  A global atomic WITH its return value costs
-// a full memory round trip (a microsecond on the critical path of a serial segment), so every wave
-// reserves kRecChunk slots at a time and hands them out from registers; what is left of a chunk
-// when the wave takes the next one (or exits) is marked void (g_start = kVoidStart: sorts last, the
-// host stops there).
-constexpr uint32_t kRecChunk = 32;
-constexpr uint32_t kVoidStart = 0xFFFFFFFFu;
-struct RecAlloc {
-    unsigned long long next = 0;  // wave-uniform
-    uint32_t left = 0;
-};
-// Statistics of the persistent workgroups, kept in DEVICE memory (not in registers: the 1024-thread shapes sit at their
-// 128-VGPR cap and every value that lives across the segment loop is a spill into it):
-//   wg_begin / wg_busy   the workgroup's lifetime goes into its tier's tally (- start, + end: two atomics per workgroup)
-//   seg_clock            called by ONE thread where the workgroup takes its next segment: the time since the previous
-//                        call is one segment's duration; the longest per tier is the serial floor of the extension
-template <class PosT>
-__device__ inline void wg_begin(const ExtParams<PosT> &P) {
-    if (threadIdx.x == 0 && P.tier >= 1u && P.tier <= (uint32_t)kRunsStat) {
-        atomicAdd(&P.ctr[CT_BUSY1 + P.tier - 1u], 0ull - wall_clock64());
-    }
-}
-// (the slots are zero when a launch starts -- the host clears them, and a workgroup leaves its slot zero -- : the thread
-// that fetches the segments and the thread that closes the last one need not be the same)
-template <class PosT>
-__device__ inline void seg_clock(const ExtParams<PosT> &P, bool last = false) {
-    if (!P.seg_slots || P.tier < 2u || P.tier > (uint32_t)kRunsStat) return;  // (tier 1: a million tiny segments)
-    const unsigned long long now = wall_clock64();
-    const unsigned long long prev = atomicExch(&P.seg_slots[blockIdx.x & 4095u], last ? 0ull : now);
-    if (prev && now > prev) atomicMax(&P.ctr[CT_SEGMAX1 + P.tier - 1u], now - prev);
-}
-template <class PosT>
-__device__ inline void wg_busy(const ExtParams<PosT> &P) {
-    if (threadIdx.x == 0 && P.tier >= 1u && P.tier <= (uint32_t)kRunsStat) {
-        seg_clock(P, true);  // (closes the last segment)
-        atomicAdd(&P.ctr[CT_BUSY1 + P.tier - 1u], wall_clock64());
-        atomicAdd(&P.ctr[CT_WGS1 + P.tier - 1u], 1ull);
-    }
-}
-template <class PosT>
-__device__ inline void rec_flush(RecAlloc &ra, const ExtParams<PosT> &P, int lane) {
-    if ((uint32_t)lane < ra.left && ra.next + (unsigned)lane < P.rec_cap) P.recs[ra.next + (unsigned)lane].g_start = kVoidStart;
-    ra.left = 0;
-}
-// all 64 lanes call; em = ballot of the emitting lanes (non-zero); returns this lane's slot
-template <class PosT>
-__device__ inline unsigned long long rec_slot(RecAlloc &ra, const ExtParams<PosT> &P, unsigned long long em, int lane) {
-    const uint32_t n = (uint32_t)__popcll(em);
-    if (n > ra.left) {
-        rec_flush(ra, P, lane);
-        const uint32_t take = n > kRecChunk ? n : kRecChunk;
-        unsigned long long b = 0;
-        if (lane == 0) b = atomicAdd(&P.ctr[CT_SD], (unsigned long long)take);
-        ra.next = lane_of(b, 0u);
-        ra.left = take;
-    }
-    const unsigned long long at = ra.next + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
-    ra.next += n;
-    ra.left -= n;
-    return at;
-}
-
-template <class PosT, int CAP>
-__global__ __launch_bounds__(64) void extend_kernel(ExtParams<PosT> P) {
-    __shared__ PosT s_ls[CAP], s_le[CAP], s_rs[CAP], s_re[CAP];
-    __shared__ uint32_t s_gap[CAP], s_thr[CAP], s_seq[CAP], s_pend[CAP];
-    __shared__ PosT s_hits[kHitBatch];
-    // candidate index of the LDS path: arms bucketed by right end (see "LDS path")
-    constexpr uint32_t HT = CAP <= 256 ? 256u : (CAP <= 1024 ? 1024u : 4096u);
-    __shared__ uint32_t s_head[HT];
-    __shared__ uint16_t s_next[CAP], s_wide[CAP];
-    __shared__ PosT s_wlo[CAP];      // wide arms, packed: accepts x iff (x - s_wlo[w]) < s_ww[w]
-    __shared__ uint32_t s_ww[CAP];
-    const int lane = threadIdx.x;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const RunParams &rp = P.rp;
-    const uint64_t n_seg = *P.n_seg_ptr;
-    const uint32_t k = (uint32_t)rp.k, step = (uint32_t)rp.step, G = rp.G;
-    const uint32_t thr0 = arm_threshold(k, G);
-    RecAlloc rec_alloc;
-    wg_begin(P);
-    PROF_DECL;
-
-    // Segments are fetched kFetch at a time (one contended global atomic per group).  The list is
-    // sorted longest first: in its head the members of a group are strided, so that the longest
-    // segments go to different waves instead of eight of them to the same one.
-    constexpr unsigned long long kFetch = 8;
-    const unsigned long long head_groups = min((unsigned long long)gridDim.x, n_seg / kFetch);
-    const unsigned long long head = head_groups * kFetch;
-    unsigned long long seg_base = 0;
-    uint32_t seg_j = (uint32_t)kFetch;
-    for (;;) {
-        if (seg_j == (uint32_t)kFetch) {
-            unsigned long long sb = 0;
-            if (lane == 0) sb = atomicAdd(P.cursor, kFetch);
-            seg_base = uni(sb);
-            seg_j = 0;
-        }
-        const uint32_t j = seg_j++;
-        const unsigned long long seg = seg_base < head ? seg_base / kFetch + (unsigned long long)j * head_groups
-                                                       : seg_base + j;
-        if (seg_base >= n_seg) break;
-        if (seg >= n_seg) continue;
-        const uint32_t g0 = P.seg_list[seg];
-        PROF_SEG_BEGIN();
-        if (lane == 0 && j == 0) {
-            heartbeat(P, g0, 0u);
-            seg_clock(P);
-        }  // (once per fetched group of segments)
-        const int c = chunk_of_uniform(rp.ch, g0);
-        const uint64_t cs = rp.ch.start[c], cl = rp.ch.len[c];
-        const bool seg_rev = (rp.mode_of(c) & 2u) != 0u;  // (the orientation of the chunk's pass)
-        const uint32_t pb = rp.ch.pbase[c];
-        const uint32_t chunk_end = rp.ch.pbase[c + 1];
-        const uint32_t g_end = min(chunk_end, rp.win_end(g0));  // (sharded calls: the window ends first)
-
-        // live arms: lane j holds arm j while in_regs (A <= 64), else s_*[0..A)
-        PosT r_ls = 0, r_le = 0, r_rs = 0, r_re = 0;
-        uint32_t r_gap = 0, r_thr = 0, r_seq = 0;
-        uint32_t A = 0, quiet = 0, fam_seq = 0, next_seq = 0, lds_cost = 0;
-        bool in_regs = true, overflow = false, done = false, fam_open = false;  // fam_open: a family is pending
-
-        // ---- helpers -------------------------------------------------------
-        auto emit_records = [&](bool emit, PosT ls, PosT le, PosT rs, PosT re, uint32_t seq) {
-            const unsigned long long em = __ballot(emit);
-            if (!em) return;
-            const unsigned long long at = rec_slot(rec_alloc, P, em, lane);
-            if (emit) {
-                if (at < P.rec_cap) {
-                    const uint64_t ll = (uint64_t)le - (uint64_t)ls;
-                    SdRec r;
-                    r.g_start = g0;
-                    r.fam_seq = fam_seq;
-                    r.create_seq = seq;
-                    r.pad = 0;
-                    // left fix-up, src/bin/asgart.rs:229-237
-                    r.sd.left = seg_rev ? cs + cl - (uint64_t)ls - ll : (uint64_t)ls + cs;
-                    r.sd.right = rs;
-                    r.sd.left_length = ll;
-                    r.sd.right_length = (uint64_t)re - (uint64_t)rs;
-                    P.recs[at] = r;
-                }
-            }
-        };
-        // the flush of src/automaton.rs:182-200: every arm inactive
-        auto maybe_close = [&]() {
-            if (fam_open && A == 0) {
-                ++fam_seq;
-                next_seq = 0;
-                fam_open = false;
-            }
-        };
-        // retire arms whose gap reached G (src/automaton.rs:166-171 + flush bookkeeping)
-        auto retire_regs = [&]() {
-            const bool dead = (uint32_t)lane < A && r_gap >= G;
-            if (!__ballot(dead)) return;
-            emit_records(dead && (uint64_t)(r_re - r_rs) >= rp.M, r_ls, r_le, r_rs, r_re, r_seq);
-            const bool alive = (uint32_t)lane < A && !dead;
-            const unsigned long long am = __ballot(alive);
-            if (alive) {
-                const int d = __popcll(am & lt_mask);
-                s_ls[d] = r_ls; s_le[d] = r_le; s_rs[d] = r_rs; s_re[d] = r_re;
-                s_gap[d] = r_gap; s_thr[d] = r_thr; s_seq[d] = r_seq;
-            }
-            __syncthreads();
-            A = (uint32_t)__popcll(am);
-            if ((uint32_t)lane < A) {
-                r_ls = s_ls[lane]; r_le = s_le[lane]; r_rs = s_rs[lane]; r_re = s_re[lane];
-                r_gap = s_gap[lane]; r_thr = s_thr[lane]; r_seq = s_seq[lane];
-            }
-            __syncthreads();
-        };
-        auto retire_lds = [&]() {
-            uint32_t w = 0;
-            bool any_dead = false;
-            for (uint32_t t0 = 0; t0 < A; t0 += 64) {
-                const uint32_t j = t0 + lane;
-                PosT ls = 0, le = 0, rs = 0, re = 0;
-                uint32_t gp = 0, th = 0, sq = 0;
-                bool valid = j < A;
-                if (valid) {
-                    ls = s_ls[j]; le = s_le[j]; rs = s_rs[j]; re = s_re[j];
-                    gp = s_gap[j]; th = s_thr[j]; sq = s_seq[j];
-                }
-                const bool dead = valid && gp >= G;
-                any_dead |= __ballot(dead) != 0ull;
-                emit_records(dead && (uint64_t)(re - rs) >= rp.M, ls, le, rs, re, sq);
-                const bool alive = valid && !dead;
-                const unsigned long long am = __ballot(alive);
-                __syncthreads();
-                if (alive && any_dead) {
-                    const uint32_t d = w + __popcll(am & lt_mask);
-                    s_ls[d] = ls; s_le[d] = le; s_rs[d] = rs; s_re[d] = re;
-                    s_gap[d] = gp; s_thr[d] = th; s_seq[d] = sq; s_pend[d] = 0;
-                }
-                w += __popcll(am);
-                __syncthreads();
-            }
-            A = w;
-        };
-        auto to_lds = [&]() {
-            if ((uint32_t)lane < A) {
-                s_ls[lane] = r_ls; s_le[lane] = r_le; s_rs[lane] = r_rs; s_re[lane] = r_re;
-                s_gap[lane] = r_gap; s_thr[lane] = r_thr; s_seq[lane] = r_seq; s_pend[lane] = 0;
-            }
-            __syncthreads();
-            in_regs = false;
-        };
-        auto to_regs = [&]() {
-            if ((uint32_t)lane < A) {
-                r_ls = s_ls[lane]; r_le = s_le[lane]; r_rs = s_rs[lane]; r_re = s_re[lane];
-                r_gap = s_gap[lane]; r_thr = s_thr[lane]; r_seq = s_seq[lane];
-            }
-            __syncthreads();
-            in_regs = true;
-        };
-        // q consecutive processed probes without hits
-        auto advance_quiet = [&](uint32_t q) {
-            quiet += q;
-            if (A > 0) {
-                const uint32_t add = q * step;
-                if (in_regs) {
-                    if ((uint32_t)lane < A) r_gap = r_gap + add < r_gap ? 0xFFFFFFFFu : r_gap + add;
-                    retire_regs();
-                } else {
-                    for (uint32_t j = lane; j < A; j += 64) {
-                        const uint32_t gp = s_gap[j];
-                        s_gap[j] = gp + add < gp ? 0xFFFFFFFFu : gp + add;
-                    }
-                    __syncthreads();
-                    PROF_STOP(7);
-                    PROF_START();
-                    retire_lds();
-                    if (A <= 32) to_regs();
-                    PROF_STOP(8);
-                }
-            }
-            maybe_close();
-            if (A == 0 && quiet >= rp.tstar) done = true;
-        };
-
-        for (uint32_t g = g0; g < g_end && !done;) {
-            // ---- stage a batch of up to 64 probes ------------------------------
-            PROF_START();
-            const uint32_t nb = min(64u, g_end - g);
-            const uint32_t f_l = (uint32_t)lane < nb ? P.p_filt[g + lane] : kSkipN;
-            const unsigned long long r_l = (uint32_t)lane < nb ? P.row_off[g + lane] : 0ull;
-            const unsigned long long r_hi = P.row_off[g + nb];
-            const unsigned long long base = __shfl(r_l, 0);
-            unsigned long long r_next = __shfl_down(r_l, 1);
-            if ((uint32_t)lane + 1 >= nb) r_next = r_hi;
-            const bool fits = (uint32_t)lane < nb && r_next - base <= (unsigned long long)kHitBatch;
-            const unsigned long long fm = __ballot(fits);
-            uint32_t nbb = (~fm == 0ull) ? 64u : (uint32_t)(__ffsll((long long)~fm) - 1);
-            if (nbb > nb) nbb = nb;
-            bool first_from_global = false;
-            if (nbb == 0) {  // a single row larger than the staging buffer
-                nbb = 1;
-                first_from_global = true;
-            }
-            const uint32_t rel_l = (uint32_t)(r_l - base);
-            if (!first_from_global) {
-                const unsigned long long end = nbb == nb ? r_hi : __shfl(r_l, (int)nbb);
-                const uint32_t tot = (uint32_t)(end - base);
-                // four loads per lane in flight per round trip; most batches need a single round
-                for (uint32_t r0 = 0; r0 < tot; r0 += 256u) {
-                    PosT tmp[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const uint32_t r = r0 + lane + 64u * u;
-                        tmp[u] = r < tot ? P.hits[base + r] : (PosT)0;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const uint32_t r = r0 + lane + 64u * u;
-                        if (r < tot) s_hits[r] = tmp[u];
-                    }
-                }
-            }
-            __syncthreads();
-            const unsigned long long in_batch = nbb >= 64 ? ~0ull : ((1ull << nbb) - 1ull);
-            const unsigned long long hm = __ballot(f_l >= 1u && f_l < kPending) & in_batch;
-            const unsigned long long qm = __ballot(f_l == 0u) & in_batch;
-            PROF_STOP(0);
-            PROF_COUNT(1, 1);
-            uint32_t pos = 0;
-            while (!done) {
-                const unsigned long long hmr = pos >= 64 ? 0ull : (hm >> pos) << pos;
-                if (!hmr) break;
-                const uint32_t b = (uint32_t)(__ffsll((long long)hmr) - 1);
-                {
-                    const unsigned long long range = ((1ull << b) - 1ull) & ~((1ull << pos) - 1ull);
-                    const uint32_t q = (uint32_t)__popcll(qm & range);
-                    if (q) {
-                        advance_quiet(q);
-                        if (done) break;
-                    }
-                }
-                quiet = 0;
-                pos = b + 1;
-                const uint32_t cnt = __shfl(f_l, (int)b);
-                const uint32_t off = __shfl(rel_l, (int)b);
-                const uint64_t i = (uint64_t)(g + b - pb + 1) * step;
-                const unsigned long long row = base + off;
-                if (in_regs && A + cnt <= 64u && !first_from_global) {
-                    // ---------------- register path -------------------------------
-                    PROF_START();
-                    PROF_COUNT(3, 1);
-                    PROF_MAX(9, A + cnt);
-                    bool pend = false;
-                    PosT pend_x = 0;
-                    uint32_t newc = 0;
-                    for (uint32_t t = 0; t < cnt; ++t) {
-                        const PosT x = s_hits[off + t];
-                        const bool ok = (uint32_t)lane < A && arm_accepts<PosT>(x, r_re, r_thr, k);
-                        const unsigned long long m = __ballot(ok);
-                        if (m) {  // ExtendArm on the first matching arm; last hit wins
-                            if (lane == __ffsll((long long)m) - 1) {
-                                pend = true;
-                                pend_x = x;
-                            }
-                        } else {  // NewArm
-                            if ((uint32_t)lane == A + newc) {
-                                r_ls = (PosT)i; r_le = (PosT)(i + k); r_rs = x; r_re = (PosT)(x + k);
-                                r_gap = step;  // not dirty: aged by this very probe
-                                r_thr = thr0;
-                                r_seq = next_seq + newc;
-                            }
-                            ++newc;
-                        }
-                    }
-                    if ((uint32_t)lane < A) {
-                        if (pend) {
-                            r_re = (PosT)(pend_x + k);
-                            r_le = (PosT)(i + k);
-                            r_thr = arm_threshold((uint64_t)(i + k) - (uint64_t)r_ls, G);
-                            r_gap = 0;
-                        } else {
-                            r_gap += step;
-                        }
-                    }
-                    A += newc;
-                    next_seq += newc;
-                    retire_regs();
-                    PROF_STOP(2);
-                } else {
-                    // ---------------- LDS path ------------------------------------
-                    if (in_regs) to_lds();
-                    // hand the segment to the block-cooperative heavy tier when it does not fit
-                    // this wave's LDS share, or keeps producing many-hit x many-arm probes
-                    lds_cost += A + cnt;
-                    if (A + cnt > min((uint32_t)CAP, P.cap_limit) || lds_cost > P.escalate_cost) {
-#ifdef ASGART_PROFILE_EXTEND
-                        if (lane == 0) printf("[light overflow] g0=%u g=%u A=%u cnt=%u cost=%u first_glob=%d\n", g0, g + b, A, cnt, lds_cost, (int)first_from_global);
-#endif
-                        overflow = true;
-                        done = true;
-                        break;
-                    }
-                    const uint32_t A_old = A;
-                    const bool from_lds = !first_from_global;
-                    PROF_COUNT(5, 1);
-                    PROF_COUNT(10, A_old);
-                    PROF_COUNT(11, cnt);
-                    PROF_MAX(9, A_old + cnt);
-                    PROF_START();
-                    // An arm accepts hit x iff  re - k < x < re + thr  (d_ss of src/automaton.rs:207-216
-                    // with m = [x, x+k) and len(right) >= k).  So instead of testing every arm
-                    // (automaton.rs:67-78) the arms whose thr is the floor G ("narrow") are hashed by
-                    // bucket(re) with bucket width G + k: a hit can only be accepted by narrow arms
-                    // in two buckets.  The few arms with a long left segment (thr > G) are kept in a
-                    // list and tested one by one.  The answer is the smallest accepting arm index.
-                    const uint32_t Wb = G + k;
-                    uint32_t hmask = 63u;  // table sized to the live arms (power of two <= HT)
-                    while (hmask + 1u < HT && hmask + 1u < 2u * A_old) hmask = (hmask << 1) | 1u;
-                    for (uint32_t h = lane; h <= hmask; h += 64) s_head[h] = 0xFFFFFFFFu;
-                    __syncthreads();
-                    uint32_t n_wide = 0;
-                    for (uint32_t t0 = 0; t0 < A_old; t0 += 64) {
-                        const uint32_t j = t0 + lane;
-                        const bool valid = j < A_old;
-                        const bool narrow = valid && s_thr[j] <= G;
-                        if (narrow) {
-                            const uint32_t b = (uint32_t)((uint64_t)s_re[j] / Wb);
-                            const uint32_t h = ((b * 2654435761u) >> 12) & hmask;
-                            s_next[j] = (uint16_t)atomicExch(&s_head[h], j);
-                        }
-                        const unsigned long long wm = __ballot(valid && !narrow);
-                        if (valid && !narrow) {
-                            const uint32_t d = n_wide + __popcll(wm & lt_mask);
-                            const uint32_t th = s_thr[j];
-                            const uint64_t wv = (uint64_t)th + k - 1u;
-                            s_wide[d] = (uint16_t)j;
-                            s_wlo[d] = (PosT)(s_re[j] - k + 1u);
-                            s_ww[d] = wv > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)wv;
-                        }
-                        n_wide += __popcll(wm);
-                    }
-                    __syncthreads();
-                    PROF_STOP(4);
-                    PROF_START();
-                    for (uint32_t t0 = 0; t0 < cnt; t0 += 64) {
-                        const uint32_t t = t0 + lane;
-                        const bool valid = t < cnt;
-                        PosT x = 0;
-                        if (valid) x = from_lds ? s_hits[off + t] : P.hits[row + t];
-                        uint32_t best = 0xFFFFFFFFu;
-                        if (valid) {
-                            // narrow candidates: re in (x - G, x + k)
-                            const uint64_t lo_re = (uint64_t)x + 1u > (uint64_t)G ? (uint64_t)x + 1u - G : 0u;
-                            const uint32_t b0 = (uint32_t)(lo_re / Wb);
-                            const uint32_t b1 = (uint32_t)(((uint64_t)x + k - 1u) / Wb);
-                            for (uint32_t b = b0; b <= b1; ++b) {
-                                uint32_t j = s_head[((b * 2654435761u) >> 12) & hmask];
-                                while (j != 0xFFFFFFFFu && j != 0xFFFFu) {
-                                    if (j < best && arm_accepts<PosT>(x, s_re[j], s_thr[j], k)) best = j;
-                                    j = s_next[j];
-                                }
-                            }
-                        }
-                        {   // wide arms: branch-free scan of the packed list (increasing arm index)
-                            uint32_t wbest = 0xFFFFFFFFu;
-                            uint32_t wdx = 0;
-                            for (; wdx + 4 <= n_wide; wdx += 4) {
-                                const uint32_t a0 = (uint64_t)(PosT)(x - s_wlo[wdx]) < s_ww[wdx] ? wdx : 0xFFFFFFFFu;
-                                const uint32_t a1 = (uint64_t)(PosT)(x - s_wlo[wdx + 1]) < s_ww[wdx + 1] ? wdx + 1 : 0xFFFFFFFFu;
-                                const uint32_t a2 = (uint64_t)(PosT)(x - s_wlo[wdx + 2]) < s_ww[wdx + 2] ? wdx + 2 : 0xFFFFFFFFu;
-                                const uint32_t a3 = (uint64_t)(PosT)(x - s_wlo[wdx + 3]) < s_ww[wdx + 3] ? wdx + 3 : 0xFFFFFFFFu;
-                                wbest = min(wbest, min(min(a0, a1), min(a2, a3)));
-                            }
-                            for (; wdx < n_wide; ++wdx)
-                                wbest = min(wbest, (uint64_t)(PosT)(x - s_wlo[wdx]) < s_ww[wdx] ? wdx : 0xFFFFFFFFu);
-                            if (valid && wbest != 0xFFFFFFFFu) best = min(best, (uint32_t)s_wide[wbest]);
-                        }
-                        const int found = best == 0xFFFFFFFFu ? -1 : (int)best;
-                        if (valid && found >= 0) atomicMax(&s_pend[found], t + 1u);
-                        const bool is_new = valid && found < 0;
-                        const unsigned long long m = __ballot(is_new);
-                        if (is_new) {
-                            const uint32_t d = A + __popcll(m & lt_mask);
-                            s_ls[d] = (PosT)i; s_le[d] = (PosT)(i + k); s_rs[d] = x;
-                            s_re[d] = (PosT)(x + k);
-                            s_gap[d] = step;
-                            s_thr[d] = thr0;
-                            s_seq[d] = next_seq + (d - A_old);
-                            s_pend[d] = 0;
-                        }
-                        A += __popcll(m);
-                    }
-                    next_seq += A - A_old;
-                    __syncthreads();
-                    PROF_STOP(6);
-                    PROF_START();
-                    for (uint32_t j = lane; j < A_old; j += 64) {
-                        const uint32_t pd = s_pend[j];
-                        if (pd) {
-                            s_pend[j] = 0;
-                            const PosT x = from_lds ? s_hits[off + pd - 1u] : P.hits[row + pd - 1u];
-                            s_re[j] = (PosT)(x + k);
-                            s_le[j] = (PosT)(i + k);
-                            s_thr[j] = arm_threshold((uint64_t)(i + k) - (uint64_t)s_ls[j], G);
-                            s_gap[j] = 0;
-                        } else {
-                            s_gap[j] += step;
-                        }
-                    }
-                    __syncthreads();
-                    PROF_STOP(7);
-                    PROF_START();
-                    retire_lds();
-                    if (A <= 32) to_regs();
-                    PROF_STOP(8);
-                }
-                // every hit of this probe extended an arm or created one
-                fam_open = true;
-                maybe_close();
-            }
-            if (!done) {
-                const unsigned long long range = pos >= 64 ? 0ull : ~((1ull << pos) - 1ull);
-                const uint32_t q = (uint32_t)__popcll(qm & range);
-                if (q) advance_quiet(q);
-            }
-            __syncthreads();
-            g += nbb;
-        }
-        // arms still alive at the end of the chunk are dropped together with the
-        // unflushed family they belong to (src/automaton.rs:201-203)
-        if (!done && g_end < chunk_end) {
-            // sharded call: the segment is not finished inside the look-ahead window
-            if (lane == 0) atomicAdd(&P.ctr[CT_RANOUT], 1ull);
-        } else if (!overflow && fam_open)
-            emit_records(lane == 0, (PosT)0, (PosT)0, (PosT)0, (PosT)0, kTombstone);
-        PROF_FLUSH();
-        if (overflow && lane == 0) {
-            const unsigned long long at = atomicAdd(P.ovf_count, 1ull);
-            if (P.ovf_list) P.ovf_list[at] = g0;
-        }
-        __syncthreads();
-    }
-    rec_flush(rec_alloc, P, lane);
-    wg_busy(P);
 }
 
 // ---------------------------------------------------------------- placement ---
@@ -2474,536 +1687,6 @@ __global__ void tier_bounds_kernel(const uint32_t *__restrict__ sorted_keys,
         return lo;
     };
     ctr[CT_N1 + t] = first_ge((uint32_t)t + 1u) - first_ge((uint32_t)t);
-}
-
-// ---------------------------------------------------------------- K4b --------
-// Block-cooperative extension kernel: ONE workgroup (NT = 256 or 1024 threads) per segment, for
-// the segments whose live-arm bound does not fit the one-wave kernel.  At genome scale these are
-// dense-repeat clusters and satellite tails: hundreds of hits per probe, hundreds to thousands of
-// live arms, most of them single-hit arms that die t* probes after they were born.
-//
-// Same results as extend_kernel, different bookkeeping:
-//   * arms live in SLOTS; a dead arm's slot goes on a free list and is reused, so there is no
-//     order-preserving compaction.  "First matching arm in list order" (src/automaton.rs:67-78)
-//     is the accepting arm with the smallest CREATION NUMBER (list order == creation order), so
-//     slot order is irrelevant.
-//   * per probe: (0) clear hash heads, (1) hash narrow arms by bucket(re) / list wide arms,
-//     (2) one thread per hit: two buckets + wide list -> best (creation number, slot),
-//     (3) ExtendArm = atomicMax of the hit index on the slot, NewArm = slot from the free list in
-//     hit order, (4) apply / age / retire in place.
-//   * MODE 2 keeps the arm arrays in an HBM scratch slice per workgroup (up to 16384
-//     live arms); the per-probe candidate index stays in LDS.
-constexpr int kHeavyThreads = 512;   // heavy tiers (1024 threads would cap VGPRs at 128 -> spills)
-constexpr int kMidThreads = 256;     // mid tier: 4 waves per segment, several workgroups per CU
-constexpr uint32_t kNoSeq = 0xFFFFFFFFu;  // s_seq value of an empty slot
-
-// MODE 0: every arm field in LDS.  MODE 1 ("hybrid"): everything a probe reads or updates (ls, le,
-// re, thr, seq, gap, pend) in LDS; rs, written once at creation and read once at retirement, in an
-// HBM scratch slice (no global access on the per-probe path: a pending global store would stall
-// every workgroup barrier); 16-bit gap/pend and an index-form wide list -> ~1.9x the capacity.
-// MODE 2: all fields in HBM scratch (last resort, up to 16384 live arms).
-// atomic max on a 32-bit or (LDS, packed pairs) 16-bit element
-__device__ inline void pend_max(uint32_t *a, uint32_t idx, uint32_t v) { atomicMax(&a[idx], v); }
-__device__ inline void pend_max(uint16_t *a, uint32_t idx, uint32_t v) {
-    // two 16-bit elements per word: the other half must be left untouched -> CAS loop
-    uint32_t *w = reinterpret_cast<uint32_t *>(a) + (idx >> 1);
-    const uint32_t sh = (idx & 1u) * 16u;
-    uint32_t old = *w;
-    for (;;) {
-        const uint32_t cur = (old >> sh) & 0xFFFFu;
-        if (cur >= v) break;
-        const uint32_t upd = (old & ~(0xFFFFu << sh)) | (v << sh);
-        const uint32_t prev = atomicCAS(w, old, upd);
-        if (prev == old) break;
-        old = prev;
-    }
-}
-
-template <class PosT, int CAP, int NT, int MODE>
-__global__ __launch_bounds__(NT) void extend_heavy_kernel(ExtParams<PosT> P) {
-    constexpr int NW = NT / 64;
-    constexpr bool PACKED_WIDE = MODE == 0;
-    constexpr int HCAP = MODE != 2 ? CAP : 1;  // hot fields in LDS
-    constexpr int CCAP = MODE == 0 ? CAP : 1;  // cold field (rs) in LDS
-    // MODE 2: the capacity is a launch parameter (P.heavy_cap: max_cardinality * (ceil(G / step) + 1) bounds the
-    // live arms of ANY segment -- every live arm was created or extended within the last t* + 1 processed probes,
-    // at most max_cardinality of them per probe), slots are 32-bit and the per-arm index lists live in the HBM slice
-    // as well; CAP is ignored.
-    const uint32_t cap_rt = MODE == 2 ? P.heavy_cap : (uint32_t)CAP;
-    constexpr uint32_t kSlotBits = MODE == 2 ? 24u : 20u;  // (creation number << kSlotBits) | slot
-    constexpr uint32_t kSlotMask = (1u << kSlotBits) - 1u;
-    using IdxT = typename std::conditional<MODE == 2, uint32_t, uint16_t>::type;
-    constexpr uint32_t kEndIdx = MODE == 2 ? 0xFFFFFFFFu : 0xFFFFu;
-    __shared__ PosT l_ls[HCAP], l_re[HCAP], l_le[HCAP], l_rs[CCAP];
-    // gap and pend are 16-bit in the hybrid tier (gap saturates; the host only uses that tier when
-    // G and max_cardinality fit): 24 B of LDS per arm instead of 32
-    using SmallT = typename std::conditional<MODE == 1, uint16_t, uint32_t>::type;
-    constexpr uint32_t kGapMax = MODE == 1 ? 0xFFFFu : 0xFFFFFFFFu;
-    __shared__ uint32_t l_thr[HCAP], l_seq[HCAP];
-    __shared__ SmallT l_gap[HCAP], l_pend[HCAP];
-    PosT *s_ls = l_ls, *s_le = l_le, *s_rs = l_rs, *s_re = l_re;
-    uint32_t *s_thr = l_thr, *s_seq = l_seq;
-    SmallT *s_gap = l_gap, *s_pend = l_pend;
-    IdxT *g_next = nullptr, *g_free = nullptr, *g_widx = nullptr;
-    if constexpr (MODE != 0) {
-        const size_t bytes = (size_t)cap_rt * (4 * sizeof(PosT) + (MODE == 2 ? 7 : 4) * sizeof(uint32_t));
-        char *b = P.scratch + (size_t)blockIdx.x * bytes;
-        PosT *g0p = reinterpret_cast<PosT *>(b);
-        s_rs = g0p + 2 * (size_t)cap_rt;
-        if constexpr (MODE == 2) {
-            s_ls = g0p;
-            s_le = g0p + cap_rt;
-            s_re = g0p + 3 * (size_t)cap_rt;
-            s_gap = reinterpret_cast<SmallT *>(g0p + 4 * (size_t)cap_rt);
-            s_thr = reinterpret_cast<uint32_t *>(s_gap + cap_rt);
-            s_seq = s_thr + cap_rt;
-            s_pend = reinterpret_cast<SmallT *>(s_seq + cap_rt);
-            g_next = reinterpret_cast<IdxT *>(s_pend + cap_rt);
-            g_free = g_next + cap_rt;
-            g_widx = g_free + cap_rt;
-        }
-    }
-    constexpr uint32_t HT = MODE == 2 ? 8192u : (CAP <= 1024 ? 1024u : (MODE == 1 ? 2048u : (CAP <= 4608 ? 4096u : 8192u)));
-    constexpr uint32_t WCAP = PACKED_WIDE ? (uint32_t)CAP : 1u;
-    __shared__ uint32_t s_head[HT];
-    __shared__ uint16_t l_next[MODE == 2 ? 1 : CAP];
-    __shared__ uint16_t l_free[MODE == 2 ? 1 : CAP];  // stack of empty slots below the high-water mark
-    __shared__ PosT s_ivlo[WCAP];     // wide arm w accepts x iff (x - s_ivlo[w]) < s_ivw[w]
-    __shared__ uint32_t s_ivw[WCAP];
-    __shared__ unsigned long long s_wkey[WCAP];  // (creation number << 20) | slot of wide arm w
-    __shared__ uint16_t l_widx[(PACKED_WIDE || MODE == 2) ? 1 : CAP];  // index form of the wide list
-    IdxT *s_next, *s_free, *s_widx;
-    if constexpr (MODE == 2) {
-        s_next = g_next; s_free = g_free; s_widx = g_widx;
-    } else {
-        s_next = l_next; s_free = l_free; s_widx = l_widx;
-    }
-    __shared__ PosT s_hits[kHitBatch];
-    __shared__ unsigned long long s_best[NT];  // per hit: (creation number << 20) | slot, or ~0
-    __shared__ uint32_t s_nwide, s_nfreed;
-    __shared__ uint32_t s_wcnt[NT / 64];
-    __shared__ unsigned long long s_bcast;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
-    const RunParams &rp = P.rp;
-    const uint64_t n_seg = *P.n_seg_ptr;
-    const uint32_t k = (uint32_t)rp.k, step = (uint32_t)rp.step, G = rp.G;
-    const uint32_t thr0 = arm_threshold(k, G);
-    uint32_t bsh = 3;  // bucket(re) = re >> bsh with 2^bsh >= G + k: a hit meets <= 2 buckets
-    while ((1ull << bsh) < (unsigned long long)G + k) ++bsh;
-    const uint32_t cap_eff = min(cap_rt, P.cap_limit);
-    RecAlloc rec_alloc;
-    wg_begin(P);
-    PROF_DECL;
-
-    for (;;) {
-        if (tid == 0) s_bcast = atomicAdd(P.cursor, 1ull);
-        __syncthreads();
-        const unsigned long long seg = s_bcast;
-        __syncthreads();
-        if (seg >= n_seg) break;
-        const uint32_t g0 = P.seg_list[seg];
-        if (tid == 0) {
-            heartbeat(P, g0, 0u);
-            seg_clock(P);
-        }
-        PROF_SEG_BEGIN();
-        const int c = chunk_of_uniform(rp.ch, g0);
-        const uint64_t cs = rp.ch.start[c], cl = rp.ch.len[c];
-        const bool seg_rev = (rp.mode_of(c) & 2u) != 0u;  // (the orientation of the chunk's pass)
-        const uint32_t pb = rp.ch.pbase[c];
-        const uint32_t chunk_end = rp.ch.pbase[c + 1];
-        const uint32_t g_end = min(chunk_end, rp.win_end(g0));  // (sharded calls: the window ends first)
-        // block-uniform state: A live arms in slots [0,H), n_free of them empty (on s_free)
-        uint32_t A = 0, H = 0, n_free = 0, quiet = 0, fam_seq = 0, next_seq = 0;
-        if (tid == 0) s_nfreed = 0;
-        bool overflow = false, done = false, fam_open = false;
-
-        auto emit_records = [&](bool emit, PosT ls, PosT le, PosT rs, PosT re, uint32_t seq) {
-            const unsigned long long em = __ballot(emit);
-            if (!em) return;
-            const unsigned long long at = rec_slot(rec_alloc, P, em, lane);
-            if (emit) {
-                if (at < P.rec_cap) {
-                    const uint64_t ll = (uint64_t)le - (uint64_t)ls;
-                    SdRec r;
-                    r.g_start = g0;
-                    r.fam_seq = fam_seq;
-                    r.create_seq = seq;
-                    r.pad = 0;
-                    r.sd.left = seg_rev ? cs + cl - (uint64_t)ls - ll : (uint64_t)ls + cs;
-                    r.sd.right = rs;
-                    r.sd.left_length = ll;
-                    r.sd.right_length = (uint64_t)re - (uint64_t)rs;
-                    P.recs[at] = r;
-                }
-            }
-        };
-        // Age every live arm by `add` (unless `extended` applies first), retire in place the ones
-        // whose gap reaches G.  i, off, row, from_lds describe the probe that may have extended
-        // arms (with_pend); block-uniform on exit: A, n_free, fam_seq, next_seq, H.
-        auto age_and_retire = [&](uint32_t add, bool with_pend, uint64_t i, uint32_t off,
-                                  unsigned long long row, bool from_lds) {
-            // s_nfreed was cleared at least one barrier ago (probe start / previous call's end)
-            for (uint32_t j0 = 0; j0 < H; j0 += NT) {
-                const uint32_t j = j0 + tid;
-                bool dead = false;
-                PosT ls = 0, le = 0, rs = 0, re = 0;
-                uint32_t sq = kNoSeq;
-                if (j < H && (sq = s_seq[j]) != kNoSeq) {
-                    const uint32_t pd = with_pend ? s_pend[j] : 0u;
-                    if (pd) {
-                        s_pend[j] = 0;
-                        const PosT x = from_lds ? s_hits[off + pd - 1u] : P.hits[row + pd - 1u];
-                        s_re[j] = (PosT)(x + k);
-                        s_le[j] = (PosT)(i + k);
-                        s_thr[j] = arm_threshold((uint64_t)(i + k) - (uint64_t)s_ls[j], G);
-                        s_gap[j] = 0;
-                    } else {
-                        const uint32_t gp = s_gap[j];
-                        const uint64_t sum_g = (uint64_t)gp + add;
-                        const uint32_t ng = sum_g > kGapMax ? kGapMax : (uint32_t)sum_g;
-                        s_gap[j] = (SmallT)ng;
-                        if (ng >= G) {
-                            dead = true;
-                            ls = s_ls[j]; le = s_le[j]; rs = s_rs[j]; re = s_re[j];
-                            s_seq[j] = kNoSeq;
-                            s_free[n_free + atomicAdd(&s_nfreed, 1u)] = (IdxT)j;
-                        }
-                    }
-                }
-                emit_records(dead && (uint64_t)(re - rs) >= rp.M, ls, le, rs, re, sq);
-            }
-            __syncthreads();
-            const uint32_t nd = s_nfreed;
-            __syncthreads();
-            if (tid == 0) s_nfreed = 0;  // visible after the next barrier, before the next use
-            A -= nd;
-            n_free += nd;
-            if (A == 0) {  // every slot is empty again
-                H = 0;
-                n_free = 0;
-            } else if (H > 2u * A + 128u) {
-                // Mostly holes (a long segment past its peak): pack the live arms into [0, A) so
-                // that the per-probe loops run over A slots again.  Slot order is free (matching
-                // goes by creation number).  Iteration by iteration: read, barrier, write below.
-                uint32_t w = 0;
-                for (uint32_t j0 = 0; j0 < H; j0 += NT) {
-                    const uint32_t j = j0 + tid;
-                    const bool live = j < H && s_seq[j] != kNoSeq;
-                    PosT ls = 0, le = 0, rs = 0, re = 0;
-                    uint32_t gp = 0, th = 0, sq = kNoSeq;
-                    if (live) {
-                        ls = s_ls[j]; le = s_le[j]; rs = s_rs[j]; re = s_re[j];
-                        gp = s_gap[j]; th = s_thr[j]; sq = s_seq[j];
-                    }
-                    // ordered prefix of `live` over the workgroup
-                    const unsigned long long lm = __ballot(live);
-                    if (lane == 0) s_wcnt[tid >> 6] = (uint32_t)__popcll(lm);
-                    __syncthreads();
-                    uint32_t before = 0, tot = 0;
-                    for (int wv = 0; wv < NW; ++wv) {
-                        const uint32_t v = s_wcnt[wv];
-                        if (wv < (tid >> 6)) before += v;
-                        tot += v;
-                    }
-                    if (j < H) s_seq[j] = kNoSeq;  // every slot of this stripe has been read
-                    __syncthreads();
-                    if (live) {
-                        const uint32_t d = w + before + (uint32_t)__popcll(lm & lt_mask);
-                        s_ls[d] = ls; s_le[d] = le; s_rs[d] = rs; s_re[d] = re;
-                        s_gap[d] = (SmallT)gp; s_thr[d] = th; s_seq[d] = sq; s_pend[d] = 0;
-                    }
-                    w += tot;
-                    __syncthreads();
-                }
-                H = A;
-                n_free = 0;
-            }
-        };
-        // the flush of src/automaton.rs:182-200: every arm inactive
-        auto maybe_close = [&]() {
-            if (fam_open && A == 0) {
-                ++fam_seq;
-                next_seq = 0;
-                fam_open = false;
-            }
-        };
-        auto advance_quiet = [&](uint32_t q) {
-            quiet += q;
-            if (A > 0) age_and_retire(q * step, false, 0, 0, 0, true);
-            maybe_close();
-            if (A == 0 && quiet >= rp.tstar) done = true;
-        };
-
-        for (uint32_t g = g0; g < g_end && !done;) {
-            // ---- stage a batch of up to 64 probes (every wave computes the same masks) ----
-            PROF_START();
-            const uint32_t nb = min(64u, g_end - g);
-            if (tid == 0) heartbeat(P, g0, g);
-            const uint32_t f_l = (uint32_t)lane < nb ? P.p_filt[g + lane] : kSkipN;
-            const unsigned long long r_l = (uint32_t)lane < nb ? P.row_off[g + lane] : 0ull;
-            const unsigned long long r_hi = P.row_off[g + nb];
-            const unsigned long long base = __shfl(r_l, 0);
-            unsigned long long r_next = __shfl_down(r_l, 1);
-            if ((uint32_t)lane + 1 >= nb) r_next = r_hi;
-            const bool fits = (uint32_t)lane < nb && r_next - base <= (unsigned long long)kHitBatch;
-            const unsigned long long fm = __ballot(fits);
-            uint32_t nbb = (~fm == 0ull) ? 64u : (uint32_t)(__ffsll((long long)~fm) - 1);
-            if (nbb > nb) nbb = nb;
-            bool first_from_global = false;
-            if (nbb == 0) {
-                nbb = 1;
-                first_from_global = true;
-            }
-            const uint32_t rel_l = (uint32_t)(r_l - base);
-            if (!first_from_global) {
-                const unsigned long long end = nbb == nb ? r_hi : __shfl(r_l, (int)nbb);
-                const uint32_t tot = (uint32_t)(end - base);
-                for (uint32_t r = tid; r < tot; r += NT) s_hits[r] = P.hits[base + r];
-            }
-            __syncthreads();
-            const unsigned long long in_batch = nbb >= 64 ? ~0ull : ((1ull << nbb) - 1ull);
-            const unsigned long long hm = __ballot(f_l >= 1u && f_l < kPending) & in_batch;
-            const unsigned long long qm = __ballot(f_l == 0u) & in_batch;
-            PROF_STOP(0);
-            PROF_COUNT(1, 1);
-            uint32_t pos = 0;
-            while (!done) {
-                const unsigned long long hmr = pos >= 64 ? 0ull : (hm >> pos) << pos;
-                if (!hmr) break;
-                const uint32_t b = (uint32_t)(__ffsll((long long)hmr) - 1);
-                {
-                    const unsigned long long range = ((1ull << b) - 1ull) & ~((1ull << pos) - 1ull);
-                    const uint32_t q = (uint32_t)__popcll(qm & range);
-                    if (q) {
-                        advance_quiet(q);
-                        if (done) break;
-                    }
-                }
-                quiet = 0;
-                pos = b + 1;
-                const uint32_t cnt = __shfl(f_l, (int)b);
-                const uint32_t off = __shfl(rel_l, (int)b);
-                const uint64_t i = (uint64_t)(g + b - pb + 1) * step;
-                const unsigned long long row = base + off;
-                if (A + cnt > cap_eff) {
-                    overflow = true;
-                    done = true;
-                    break;
-                }
-                const bool from_lds = !first_from_global;
-                PROF_COUNT(5, 1);
-                PROF_COUNT(10, A);
-                PROF_COUNT(11, cnt);
-                PROF_MAX(9, A + cnt);
-                PROF_START();
-                // ---- (0)+(1) candidate index over the live arms ------------------------------
-                uint32_t hmask = 63u;
-                while (hmask + 1u < HT && hmask + 1u < 2u * A) hmask = (hmask << 1) | 1u;
-                for (uint32_t h = tid; h <= hmask; h += NT) s_head[h] = 0xFFFFFFFFu;
-                if (tid == 0) s_nwide = 0;
-                __syncthreads();
-                for (uint32_t j0 = 0; j0 < H; j0 += NT) {
-                    const uint32_t j = j0 + tid;
-                    uint32_t sq = kNoSeq, th = 0;
-                    PosT re = 0;
-                    if (j < H && (sq = s_seq[j]) != kNoSeq) {
-                        th = s_thr[j];
-                        re = s_re[j];
-                    }
-                    const bool live = sq != kNoSeq;
-                    if (live && th <= G) {
-                        const uint32_t bkt = (uint32_t)((uint64_t)re >> bsh);
-                        s_next[j] = (IdxT)atomicExch(&s_head[((bkt * 2654435761u) >> 12) & hmask], j);
-                    }
-                    // wide arms: one LDS atomic per wave, not per arm
-                    const bool wide = live && th > G;
-                    const unsigned long long wm = __ballot(wide);
-                    if (wm) {
-                        const int leader = __ffsll((long long)wm) - 1;
-                        uint32_t wbase = 0;
-                        if (lane == leader) wbase = atomicAdd(&s_nwide, (uint32_t)__popcll(wm));
-                        wbase = __shfl(wbase, leader);
-                        const uint32_t d = wbase + (uint32_t)__popcll(wm & lt_mask);
-                        if (wide) {
-                            if constexpr (PACKED_WIDE) {
-                                const uint64_t wv = (uint64_t)th + k - 1u;
-                                s_ivlo[d] = (PosT)(re - k + 1u);
-                                s_ivw[d] = wv > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)wv;
-                                s_wkey[d] = ((unsigned long long)sq << kSlotBits) | j;
-                            } else {
-                                s_widx[d] = (IdxT)j;
-                            }
-                        }
-                    }
-                }
-                __syncthreads();
-                PROF_STOP(2);
-                PROF_START();
-                const uint32_t n_wide = s_nwide;
-                const uint32_t seq_base = next_seq;
-                for (uint32_t t0 = 0; t0 < cnt; t0 += NT) {
-                    const uint32_t ct = min((uint32_t)NT, cnt - t0);
-                    if (t0) __syncthreads();
-                    // ---- (2) narrow arms: one thread per hit, two buckets ----------------------
-                    PosT hx = 0;
-                    if ((uint32_t)tid < ct) {
-                        hx = from_lds ? s_hits[off + t0 + tid] : P.hits[row + t0 + tid];
-                        const uint64_t lo_re = (uint64_t)hx + 1u > (uint64_t)G ? (uint64_t)hx + 1u - G : 0u;
-                        const uint32_t b0 = (uint32_t)(lo_re >> bsh);
-                        const uint32_t b1 = (uint32_t)(((uint64_t)hx + k - 1u) >> bsh);
-                        unsigned long long best = ~0ull;
-                        for (uint32_t bkt = b0; bkt <= b1; ++bkt) {
-                            uint32_t j = s_head[((bkt * 2654435761u) >> 12) & hmask];
-                            while (j != 0xFFFFFFFFu && j != kEndIdx) {
-                                if (arm_accepts<PosT>(hx, s_re[j], s_thr[j], k))
-                                    best = min(best, ((unsigned long long)s_seq[j] << kSlotBits) | j);
-                                j = s_next[j];
-                            }
-                        }
-                        s_best[tid] = best;
-                    }
-                    __syncthreads();
-                    PROF_STOP(4);
-                    PROF_START();
-                    // ---- wide arms: thread = (hit, part of the packed list), branch-free --------
-                    if (n_wide) {
-                        const uint32_t Hr = (ct + 63u) & ~63u;  // hits rounded up to waves
-                        const uint32_t NP = NT / Hr;            // list parts
-                        const uint32_t tl = (uint32_t)tid % Hr, part = (uint32_t)tid / Hr;
-                        const bool valid = tl < ct && part < NP;
-                        PosT x = 0;
-                        if (valid) x = from_lds ? s_hits[off + t0 + tl] : P.hits[row + t0 + tl];
-                        if (part < NP) {  // wave-uniform
-                            const uint32_t j0 = (uint32_t)((uint64_t)n_wide * part / NP);
-                            const uint32_t j1 = (uint32_t)((uint64_t)n_wide * (part + 1) / NP);
-                            unsigned long long found = ~0ull;
-                            // 8 independent LDS load chains in flight per thread (the scan is
-                            // latency-bound otherwise), smallest accepting key wins
-                            uint32_t j = j0;
-                            if constexpr (PACKED_WIDE) {
-                                for (; j + 8 <= j1; j += 8) {
-                                    PosT lo8[8];
-                                    uint32_t w8[8];
-                                    unsigned long long k8[8];
-#pragma unroll
-                                    for (int u = 0; u < 8; ++u) {
-                                        lo8[u] = s_ivlo[j + u];
-                                        w8[u] = s_ivw[j + u];
-                                        k8[u] = s_wkey[j + u];
-                                    }
-#pragma unroll
-                                    for (int u = 0; u < 8; ++u)
-                                        found = min(found, (uint64_t)(PosT)(x - lo8[u]) < w8[u] ? k8[u] : ~0ull);
-                                }
-                                for (; j < j1; ++j)
-                                    found = min(found, (uint64_t)(PosT)(x - s_ivlo[j]) < s_ivw[j] ? s_wkey[j] : ~0ull);
-                            } else {
-                                for (; j + 8 <= j1; j += 8) {
-                                    uint32_t sl8[8], th8[8], sq8[8];
-                                    PosT re8[8];
-#pragma unroll
-                                    for (int u = 0; u < 8; ++u) sl8[u] = s_widx[j + u];
-#pragma unroll
-                                    for (int u = 0; u < 8; ++u) {
-                                        re8[u] = s_re[sl8[u]];
-                                        th8[u] = s_thr[sl8[u]];
-                                        sq8[u] = s_seq[sl8[u]];
-                                    }
-#pragma unroll
-                                    for (int u = 0; u < 8; ++u) {
-                                        const unsigned long long key = ((unsigned long long)sq8[u] << kSlotBits) | sl8[u];
-                                        found = min(found, arm_accepts<PosT>(x, re8[u], th8[u], k) ? key : ~0ull);
-                                    }
-                                }
-                                for (; j < j1; ++j) {
-                                    const uint32_t slot = s_widx[j];
-                                    const unsigned long long key = ((unsigned long long)s_seq[slot] << kSlotBits) | slot;
-                                    found = min(found, arm_accepts<PosT>(x, s_re[slot], s_thr[slot], k) ? key : ~0ull);
-                                }
-                            }
-                            if (valid && found != ~0ull) atomicMin(&s_best[tl], found);
-                        }
-                        __syncthreads();
-                    }
-                    PROF_STOP(8);
-                    PROF_START();
-                    // ---- (3) ExtendArm / NewArm, one thread per hit -----------------------------
-                    const bool mine = (uint32_t)tid < ct;
-                    unsigned long long best = ~0ull;
-                    if (mine) {
-                        best = s_best[tid];
-                        if (best != ~0ull) pend_max(s_pend, (uint32_t)(best & kSlotMask), t0 + tid + 1u);
-                    }
-                    // unmatched hits become arms
-                    const bool is_new = mine && best == ~0ull;
-                    // rank of this hit among the new arms, in hit order (= creation order): every
-                    // wave recomputes the per-group counts from s_best (no barrier)
-                    uint32_t before = 0, n_new = 0;
-                    for (uint32_t c0 = 0; c0 < ct; c0 += 64) {
-                        const uint32_t hidx = c0 + lane;
-                        const bool un = hidx < ct && s_best[hidx] == ~0ull;
-                        const unsigned long long nm = __ballot(un);
-                        const uint32_t pc = (uint32_t)__popcll(nm);
-                        if (c0 < ((uint32_t)tid & ~63u)) before += pc;
-                        else if (c0 == ((uint32_t)tid & ~63u)) before += (uint32_t)__popcll(nm & lt_mask);
-                        n_new += pc;
-                    }
-                    if (is_new) {
-                        // reuse empty slots first (top of the stack), then grow the high-water mark
-                        const uint32_t slot = before < n_free ? (uint32_t)s_free[n_free - 1u - before]
-                                                              : H + (before - n_free);
-                        s_ls[slot] = (PosT)i; s_le[slot] = (PosT)(i + k); s_rs[slot] = hx;
-                        s_re[slot] = (PosT)(hx + k);
-                        s_gap[slot] = 0;  // aged to `step` by this very probe in (4)
-                        s_thr[slot] = thr0;
-                        s_seq[slot] = next_seq + before;
-                        s_pend[slot] = 0;
-                    }
-                    if (n_new <= n_free) {
-                        n_free -= n_new;
-                    } else {
-                        H += n_new - n_free;
-                        n_free = 0;
-                    }
-                    A += n_new;
-                    next_seq += n_new;
-                    __syncthreads();
-                }
-                (void)seq_base;
-                PROF_STOP(6);
-                PROF_START();
-                // ---- (4) apply ExtendArm (last hit in SA order wins), age, retire -----------------
-                age_and_retire(step, true, i, off, row, from_lds);
-                fam_open = true;
-                maybe_close();
-                PROF_STOP(7);
-            }
-            if (!done) {
-                const unsigned long long range = pos >= 64 ? 0ull : ~((1ull << pos) - 1ull);
-                const uint32_t q = (uint32_t)__popcll(qm & range);
-                if (q) advance_quiet(q);
-            }
-            __syncthreads();
-            g += nbb;
-        }
-        if (!done && g_end < chunk_end) {
-            if (tid == 0) atomicAdd(&P.ctr[CT_RANOUT], 1ull);
-        } else if (!overflow && fam_open) {
-            emit_records(tid == 0, (PosT)0, (PosT)0, (PosT)0, (PosT)0, kTombstone);
-        }
-        if (overflow && tid == 0) {
-            const unsigned long long at = atomicAdd(P.ovf_count, 1ull);
-            if (P.ovf_list) P.ovf_list[at] = g0;
-        }
-        if (tid < 64) {
-            PROF_FLUSH();
-        }
-        __syncthreads();
-    }
-    rec_flush(rec_alloc, P, lane);
-    wg_busy(P);
 }
 
 // yardstick: sum over searched probes of ceil(log2(b_p + 1)), b_p = size of the

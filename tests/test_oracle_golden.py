@@ -59,7 +59,7 @@ def test_tenth_threshold_is_integer_division():
 
 def test_interval_form_of_the_arm_predicate():
     """The HIP kernels test `re - k < x < re + thr` instead of evaluating d_ss
-    (pipeline_dev.hpp: arm_accepts).  Check it against the oracle's literal d_ss
+    (extend_common_dev.hpp: arm_accepts).  Check it against the oracle's literal d_ss
     (src/automaton.rs:68-70,207-216) for every small configuration with len(right) >= k."""
     k = 8
     for rs in (0, 5, 40):

@@ -1,5 +1,5 @@
-// Unit check of the wave-level helpers of extend_fast_dev.hpp on the GPU: the DPP inclusive scan and the
-// n-th-set-bit select, against host loops.  Build + run: hipcc --offload-arch=gfx950 -I asgart_amd/csrc
+// Unit check of the wave-level helpers of the arm-resident kernels on the GPU: the DPP inclusive scan (device_base.hpp)
+// and the n-th-set-bit select (extend_fast_dev.hpp), against host loops.  Build + run: hipcc --offload-arch=gfx950 -I asgart_amd/csrc
 // -I include tools/test_wave_scan.hip -o /tmp/tws && /tmp/tws
 #include "extend_fast_dev.hpp"
 
