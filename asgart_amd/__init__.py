@@ -23,7 +23,7 @@ import numpy as np
 __all__ = [
     "AsgartError", "RunSettings", "ProtoSD", "Strand", "Index", "Searcher", "SearchDuplications",
     "load_library", "library_path", "ABI_SYMBOLS", "sa_build64", "search_duplications_multi", "merge_shards",
-    "score_owners", "score_costs", "compute_scores_multi", "Source",
+    "score_owners", "score_costs", "compute_scores_multi", "Source", "compute_scores_flags_multi", "orientation_flags",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "asgart_debug_dump_stacks", "asgart_prepare_data", "asgart_score_owners", "asgart_score_costs",
     "asgart_compute_scores_shard", "asgart_compute_scores_multi", "asgart_tier_plan",
     "asgart_source_create", "asgart_source_destroy", "asgart_extract_sequences",
+    "asgart_compute_scores_flags", "asgart_compute_scores_flags_shard", "asgart_compute_scores_flags_multi",
 )
 
 
@@ -191,6 +192,12 @@ def load_library() -> C.CDLL:
     L.asgart_compute_scores_shard.restype = C.c_int64
     L.asgart_compute_scores_multi.argtypes = [C.POINTER(vp), C.c_int32, vp, C.c_int64, C.c_int32, C.c_int32, vp]
     L.asgart_compute_scores_multi.restype = C.c_int32
+    L.asgart_compute_scores_flags.argtypes = [vp, vp, vp, C.c_int64, vp]
+    L.asgart_compute_scores_flags.restype = C.c_int32
+    L.asgart_compute_scores_flags_shard.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
+    L.asgart_compute_scores_flags_shard.restype = C.c_int64
+    L.asgart_compute_scores_flags_multi.argtypes = [C.POINTER(vp), C.c_int32, vp, vp, C.c_int64, vp]
+    L.asgart_compute_scores_flags_multi.restype = C.c_int32
     L.asgart_probe_hits.argtypes = [vp, vp, C.c_int64, C.POINTER(_Settings), vp, vp, vp, u64p]
     L.asgart_probe_hits.restype = C.c_int64
     L.asgart_get_stats.argtypes = [vp, C.c_uint32, C.POINTER(Stats)]
@@ -389,6 +396,26 @@ class Index:
         out = np.full(len(sds), np.nan, dtype=np.float32)
         _check(load_library().asgart_compute_scores_shard(self._h, _ptr(sds), len(sds), int(reversed_),
                                                           int(complemented), int(shard), int(n_shards), _ptr(out)))
+        return out
+
+    def compute_scores_flags(self, sds: np.ndarray, flags: Optional[np.ndarray]) -> np.ndarray:
+        """compute_scores with one flag byte per duplication (asgart_compute_scores_flags): flags uint8[n], bit 0
+        reversed, bit 1 complemented (None: all zero).  Entry q is bit-equal to compute_scores with q's two flags."""
+        sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+        flags = _score_flags(flags, len(sds))
+        out = np.empty(len(sds), dtype=np.float32)
+        _check(load_library().asgart_compute_scores_flags(self._h, _ptr(sds), _ptr(flags), len(sds), _ptr(out)))
+        return out
+
+    def compute_scores_flags_shard(self, sds: np.ndarray, flags: Optional[np.ndarray], shard: int = 0,
+                                   n_shards: int = 1) -> np.ndarray:
+        """compute_scores_shard with one flag byte per duplication (asgart_compute_scores_flags_shard): the same owners,
+        NaN at the entries of the other shards."""
+        sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+        flags = _score_flags(flags, len(sds))
+        out = np.full(len(sds), np.nan, dtype=np.float32)
+        _check(load_library().asgart_compute_scores_flags_shard(self._h, _ptr(sds), _ptr(flags), len(sds), int(shard),
+                                                                int(n_shards), _ptr(out)))
         return out
 
     def post_process(self, offs: np.ndarray, sds: np.ndarray, threads: int = 0) -> Tuple[np.ndarray, np.ndarray]:
@@ -647,6 +674,35 @@ def compute_scores_multi(indices: Sequence[Index], sds: np.ndarray, reversed_: b
     arr = (C.c_void_p * len(indices))(*[i._h for i in indices])
     _check(L.asgart_compute_scores_multi(arr, len(indices), _ptr(sds), len(sds), int(reversed_), int(complemented),
                                          _ptr(out)))
+    return out
+
+
+def _score_flags(flags, n: int) -> Optional[np.ndarray]:
+    """The flag bytes of a compute_scores_flags* call: uint8[n], or None."""
+    if flags is None:
+        return None
+    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != n:
+        raise ValueError(f"{len(flags)} flag bytes for {n} duplications")
+    return flags
+
+
+def orientation_flags(reversed_, complemented, n: Optional[int] = None) -> np.ndarray:
+    """The flag bytes (bit 0 reversed, bit 1 complemented) of asgart_compute_scores_flags and asgart_extract_sequences
+    for two booleans or boolean arrays; n: broadcast to that many duplications."""
+    f = np.asarray(reversed_, dtype=bool).astype(np.uint8) | (np.asarray(complemented, dtype=bool).astype(np.uint8) << 1)
+    return np.ascontiguousarray(np.broadcast_to(f, (n,)) if n is not None else f)
+
+
+def compute_scores_flags_multi(indices: Sequence[Index], sds: np.ndarray, flags: Optional[np.ndarray]) -> np.ndarray:
+    """asgart_compute_scores_flags_multi: compute_scores_multi with one flag byte per duplication -> float32[n], the
+    array Index.compute_scores_flags gives."""
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = _score_flags(flags, len(sds))
+    out = np.empty(len(sds), dtype=np.float32)
+    arr = (C.c_void_p * len(indices))(*[i._h for i in indices])
+    _check(load_library().asgart_compute_scores_flags_multi(arr, len(indices), _ptr(sds), _ptr(flags), len(sds),
+                                                            _ptr(out)))
     return out
 
 

@@ -10,6 +10,8 @@
 // goes through an HBM scratch row, read and written 64 columns at a time.  Long duplications get a
 // workgroup of 16 waves that walk 16 consecutive bands as a pipeline (see levenshtein_long_kernel).  Integer work, bit-exact by
 // construction; the identity is formed in f64 like the reference and narrowed to f32.
+// The orientation of the right arm is per duplication (asgart_compute_scores_flags*: one flag byte each) or per call
+// (asgart_compute_scores*: the same kernels without a flag array).
 #include "index.hpp"
 
 #include <algorithm>
@@ -68,6 +70,14 @@ struct RightArm {
         return complemented ? complement_base(c) : c;
     }
 };
+
+// The orientation of duplication `item`: its flag byte (bit 0 reversed, bit 1 complemented, the encoding of
+// asgart_extract_sequences) or, without a flag array, the call's two constants.  `item` is the same in every lane of
+// the wave that picked the duplication up, so the byte is read once and kept in a scalar register.
+__device__ inline uint32_t orientation_of(const uint8_t *flags, uint32_t item, int reversed, int complemented) {
+    const uint32_t f = flags ? (uint32_t)flags[item] : (reversed ? 1u : 0u) | (complemented ? 2u : 0u);
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)f);
+}
 
 // one lane's share of a band of 64 x R rows
 struct BandState {
@@ -161,7 +171,8 @@ __device__ inline float identity_of(const asgart_proto_sd &sd, uint32_t dist) {
 __global__ __launch_bounds__(kScoreThreads) void levenshtein_kernel(const uint8_t *__restrict__ text,
                                                                     const asgart_proto_sd *__restrict__ sds,
                                                                     const uint32_t *__restrict__ list, uint64_t n_list,
-                                                                    int reversed, int complemented,
+                                                                    const uint8_t *__restrict__ flags, int reversed0,
+                                                                    int complemented0,
                                                                     uint32_t *__restrict__ scratch, uint64_t scratch_stride,
                                                                     unsigned long long *__restrict__ cursor,
                                                                     float *__restrict__ identity) {
@@ -180,6 +191,8 @@ __global__ __launch_bounds__(kScoreThreads) void levenshtein_kernel(const uint8_
         const uint32_t la = (uint32_t)sd.left_length + 1u, lb = (uint32_t)sd.right_length + 1u;
         const uint8_t *A = text + sd.left;
         const uint8_t *B = text + sd.right;
+        const uint32_t orient = orientation_of(flags, item, reversed0, complemented0);
+        const bool reversed = orient & 1u, complemented = orient & 2u;
         auto b_at = [&](uint32_t j) -> uint32_t {  // j-th base of the right arm after reverse/complement
             const uint32_t c = B[reversed ? lb - 1u - j : j];
             return complemented ? complement_base(c) : c;
@@ -274,8 +287,8 @@ __global__ __launch_bounds__(kScoreThreads) void levenshtein_kernel(const uint8_
 // wave finishes band b exactly when band b + kLongWaves may start, so every wave stays busy.
 __global__ __launch_bounds__(64 * kLongWaves) void levenshtein_long_kernel(
     const uint8_t *__restrict__ text, const asgart_proto_sd *__restrict__ sds, const uint32_t *__restrict__ list,
-    uint64_t n_list, int reversed, int complemented, uint32_t *__restrict__ scratch, uint64_t scratch_stride,
-    float *__restrict__ identity) {
+    uint64_t n_list, const uint8_t *__restrict__ flags, int reversed0, int complemented0, uint32_t *__restrict__ scratch,
+    uint64_t scratch_stride, float *__restrict__ identity) {
     constexpr int R = kScoreRows;
     constexpr uint32_t BAND = kBand;
     __shared__ uint32_t s_dist;
@@ -286,7 +299,8 @@ __global__ __launch_bounds__(64 * kLongWaves) void levenshtein_long_kernel(
         const uint32_t item = list[pos];
         const asgart_proto_sd sd = sds[item];
         const uint32_t la = (uint32_t)sd.left_length + 1u, lb = (uint32_t)sd.right_length + 1u;
-        const RightArm rb{text + sd.right, lb, reversed, complemented};
+        const uint32_t orient = orientation_of(flags, item, reversed0, complemented0);
+        const RightArm rb{text + sd.right, lb, (int)(orient & 1u), (int)(orient >> 1)};
         const uint32_t n_bands = (la + BAND - 1u) / BAND;
         const uint32_t n_steps = lb + 63u;
         const uint32_t C = long_chunk_steps(n_steps);
@@ -320,12 +334,16 @@ __global__ __launch_bounds__(64 * kLongWaves) void levenshtein_long_kernel(
 }
 
 // ---- a shard of a ComputeScore call: its duplications gathered out of the full list, on the device --------------
-// sub[k] = sds[owned[k]]; the Levenshtein kernels then walk sub through list[k] = k and write identity[k].
+// sub[k] = sds[owned[k]], with its flag byte when the call has flags (sub_flags[k] = flags[owned[k]]); the Levenshtein
+// kernels then walk sub through list[k] = k and write identity[k].
 __global__ __launch_bounds__(256) void gather_owned_kernel(const asgart_proto_sd *__restrict__ sds,
+                                                           const uint8_t *__restrict__ flags,
                                                            const uint32_t *__restrict__ owned, uint64_t n_owned,
-                                                           asgart_proto_sd *__restrict__ sub, uint32_t *__restrict__ list) {
+                                                           asgart_proto_sd *__restrict__ sub,
+                                                           uint8_t *__restrict__ sub_flags, uint32_t *__restrict__ list) {
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_owned; k += (uint64_t)gridDim.x * blockDim.x) {
         sub[k] = sds[owned[k]];
+        if (flags) sub_flags[k] = flags[owned[k]];
         list[k] = (uint32_t)k;
     }
 }
@@ -393,6 +411,22 @@ int32_t check_scores_input(const char *fn, const asgart_index *idx, const asgart
     return 0;
 }
 
+// The orientations of one call: a flag byte per duplication (bit 0 reversed, bit 1 complemented), or one pair for all.
+struct Orientations {
+    const uint8_t *flags;  // host, one per duplication of the call's list; NULL: the two constants below
+    int32_t reversed, complemented;
+};
+
+int32_t check_flags(const char *fn, const uint8_t *flags, int64_t n_sd) {
+    for (int64_t q = 0; flags && q < n_sd; ++q)
+        if (flags[q] & ~3u) {
+            set_error("%s: duplication %lld has flag byte %u (bit 0 reversed, bit 1 complemented)", fn, (long long)q,
+                      (unsigned)flags[q]);
+            return ASGART_E_ARG;
+        }
+    return 0;
+}
+
 // Long duplications (many bands) get a whole workgroup each, the rest one wave each; both lists are served largest first.
 struct ScorePlan {
     std::vector<uint32_t> long_list, wave_list;  // ordinals into the caller's sds
@@ -431,20 +465,21 @@ int32_t score_reserve(Workspace &w, const ScorePlan &p) {
     return w.counters.reserve(1024);  // the search pipeline keeps its device counters here too
 }
 
-// d_list: the plan's long list, then its wave list, as indices into d_sds; identities go to d_identity[d_list[..]]
+// d_list: the plan's long list, then its wave list, as indices into d_sds (and into d_flags, the device copy of
+// o.flags; NULL without); identities go to d_identity[d_list[..]]
 int32_t score_launch(const asgart_index *idx, Workspace &w, hipStream_t s, const ScorePlan &p,
-                     const asgart_proto_sd *d_sds, const uint32_t *d_list, int32_t reversed, int32_t complemented,
+                     const asgart_proto_sd *d_sds, const uint32_t *d_list, const uint8_t *d_flags, const Orientations &o,
                      float *d_identity) {
     unsigned long long *cursor = w.counters.as<unsigned long long>();
     HIP_TRY(hipMemsetAsync(cursor, 0, 8, s));
     if (p.grid_l)
         levenshtein_long_kernel<<<p.grid_l, 64 * kLongWaves, 0, s>>>(
-            idx->d_text, d_sds, d_list, (uint64_t)p.long_list.size(), reversed != 0, complemented != 0,
+            idx->d_text, d_sds, d_list, (uint64_t)p.long_list.size(), d_flags, o.reversed != 0, o.complemented != 0,
             w.scratch.as<uint32_t>() + p.scratch_w, p.stride_l, d_identity);
     if (p.grid_w)
         levenshtein_kernel<<<p.grid_w, kScoreThreads, 0, s>>>(
-            idx->d_text, d_sds, d_list + p.long_list.size(), (uint64_t)p.wave_list.size(), reversed != 0,
-            complemented != 0, w.scratch.as<uint32_t>(), p.stride_w, cursor, d_identity);
+            idx->d_text, d_sds, d_list + p.long_list.size(), (uint64_t)p.wave_list.size(), d_flags, o.reversed != 0,
+            o.complemented != 0, w.scratch.as<uint32_t>(), p.stride_w, cursor, d_identity);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -453,7 +488,7 @@ int32_t score_launch(const asgart_index *idx, Workspace &w, hipStream_t s, const
 // identity[q] for those only.  Returns how many, < 0 on error.  The full list goes to the device once and the owned
 // ones are gathered there.
 int64_t score_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd, const int32_t *owner, int32_t shard,
-                    int32_t reversed, int32_t complemented, float *identity) {
+                    const Orientations &o, float *identity) {
     std::vector<uint32_t> mine;
     for (int64_t q = 0; q < n_sd; ++q)
         if (owner[q] == shard) mine.push_back((uint32_t)q);
@@ -473,20 +508,23 @@ int64_t score_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
     std::vector<uint32_t> owned(p.long_list);  // the schedule, as ordinals into the full list
     owned.insert(owned.end(), p.wave_list.begin(), p.wave_list.end());
     const size_t m = owned.size();
-    // the buffers asgart_compute_scores uses: out_a = full list, then the gathered one; seg_vals = list, then ordinals
+    // the buffers score_all uses: out_a = full list, then the gathered one; seg_vals = list, then ordinals, then the
+    // flag bytes of the full list and of the gathered one
     RC_TRY(w.out_a.reserve(((size_t)n_sd + m) * sizeof(asgart_proto_sd)));
-    RC_TRY(w.seg_vals.reserve(m * 8 + 64));
+    RC_TRY(w.seg_vals.reserve(m * 8 + (size_t)n_sd + m + 64));
     RC_TRY(w.out_b.reserve(m * sizeof(float) + 64));
     RC_TRY(score_reserve(w, p));
     const asgart_proto_sd *d_sds = w.out_a.as<asgart_proto_sd>();
     asgart_proto_sd *d_sub = w.out_a.as<asgart_proto_sd>() + n_sd;
     uint32_t *d_list = w.seg_vals.as<uint32_t>(), *d_owned = d_list + m;
+    uint8_t *d_flags = o.flags ? (uint8_t *)(d_owned + m) : nullptr, *d_sub_flags = o.flags ? d_flags + n_sd : nullptr;
     HIP_TRY(hipMemcpyAsync(w.out_a.p, sds, (size_t)n_sd * sizeof(asgart_proto_sd), hipMemcpyHostToDevice, s));
+    if (o.flags) HIP_TRY(hipMemcpyAsync(d_flags, o.flags, (size_t)n_sd, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_owned, owned.data(), m * 4, hipMemcpyHostToDevice, s));
     const unsigned grid_g = (unsigned)std::min<size_t>((m + 255) / 256, 1024);
-    gather_owned_kernel<<<grid_g, 256, 0, s>>>(d_sds, d_owned, (uint64_t)m, d_sub, d_list);
+    gather_owned_kernel<<<grid_g, 256, 0, s>>>(d_sds, d_flags, d_owned, (uint64_t)m, d_sub, d_sub_flags, d_list);
     HIP_TRY(hipGetLastError());
-    RC_TRY(score_launch(idx, w, s, p, d_sub, d_list, reversed, complemented, w.out_b.as<float>()));
+    RC_TRY(score_launch(idx, w, s, p, d_sub, d_list, d_sub_flags, o, w.out_b.as<float>()));
     std::vector<float> got(m);
     HIP_TRY(read_back(got.data(), w.out_b.p, m * sizeof(float), s));
     for (size_t k = 0; k < m; ++k) identity[owned[k]] = got[k];
@@ -514,18 +552,16 @@ int32_t check_shard_args(const char *fn, const asgart_proto_sd *sds, int64_t n_s
     return 0;
 }
 
-}  // namespace
-}  // namespace asgart
-
-extern "C" int32_t asgart_compute_scores(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
-                                         int32_t reversed, int32_t complemented, float *identity) {
-    using namespace asgart;
+// asgart_compute_scores[_flags]: the whole list on one call context
+int32_t score_all(const char *fn, asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd, const Orientations &o,
+                  float *identity) {
     if (!idx || n_sd < 0 || (n_sd > 0 && (!sds || !identity))) {
-        set_error("asgart_compute_scores: bad argument");
+        set_error("%s: bad argument", fn);
         return ASGART_E_ARG;
     }
     if (n_sd == 0) return 0;
-    RC_TRY(check_scores_input("asgart_compute_scores", idx, sds, n_sd));
+    RC_TRY(check_flags(fn, o.flags, n_sd));
+    RC_TRY(check_scores_input(fn, idx, sds, n_sd));
     REFUSE_POISONED(idx);
     HIP_TRY(hipSetDevice(idx->device));
     int which = 0;
@@ -542,19 +578,34 @@ extern "C" int32_t asgart_compute_scores(asgart_index *idx, const asgart_proto_s
     const ScorePlan p = score_plan(sds, std::move(all));
     RC_TRY(w.out_a.reserve((size_t)n_sd * sizeof(asgart_proto_sd)));
     RC_TRY(w.out_b.reserve((size_t)n_sd * sizeof(float) + 64));
-    RC_TRY(w.seg_vals.reserve((size_t)n_sd * 4 + 64));
+    RC_TRY(w.seg_vals.reserve((size_t)n_sd * 5 + 64));  // the list, then the flag bytes
     RC_TRY(score_reserve(w, p));
     uint32_t *d_list = w.seg_vals.as<uint32_t>();
+    uint8_t *d_flags = o.flags ? (uint8_t *)(d_list + n_sd) : nullptr;
     HIP_TRY(hipMemcpyAsync(w.out_a.p, sds, (size_t)n_sd * sizeof(asgart_proto_sd), hipMemcpyHostToDevice, s));
+    if (o.flags) HIP_TRY(hipMemcpyAsync(d_flags, o.flags, (size_t)n_sd, hipMemcpyHostToDevice, s));
     if (!p.long_list.empty())
         HIP_TRY(hipMemcpyAsync(d_list, p.long_list.data(), p.long_list.size() * 4, hipMemcpyHostToDevice, s));
     if (!p.wave_list.empty())
         HIP_TRY(hipMemcpyAsync(d_list + p.long_list.size(), p.wave_list.data(), p.wave_list.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(stream_sync(s));  // (pageable host sources)
-    RC_TRY(score_launch(idx, w, s, p, w.out_a.as<asgart_proto_sd>(), d_list, reversed, complemented, w.out_b.as<float>()));
+    RC_TRY(score_launch(idx, w, s, p, w.out_a.as<asgart_proto_sd>(), d_list, d_flags, o, w.out_b.as<float>()));
     HIP_TRY(read_back(identity, w.out_b.p, (size_t)n_sd * sizeof(float), s));
     HIP_TRY(stream_sync(s));
     return 0;
+}
+
+}  // namespace
+}  // namespace asgart
+
+extern "C" int32_t asgart_compute_scores(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
+                                         int32_t reversed, int32_t complemented, float *identity) {
+    return asgart::score_all("asgart_compute_scores", idx, sds, n_sd, {nullptr, reversed, complemented}, identity);
+}
+
+extern "C" int32_t asgart_compute_scores_flags(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags,
+                                               int64_t n_sd, float *identity) {
+    return asgart::score_all("asgart_compute_scores_flags", idx, sds, n_sd, {flags, 0, 0}, identity);
 }
 
 extern "C" int32_t asgart_score_costs(const asgart_proto_sd *sds, int64_t n_sd, uint64_t *cost) {
@@ -576,11 +627,10 @@ extern "C" int32_t asgart_score_owners(const asgart_proto_sd *sds, int64_t n_sd,
     return 0;
 }
 
-extern "C" int64_t asgart_compute_scores_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
-                                               int32_t reversed, int32_t complemented, int32_t shard, int32_t n_shards,
-                                               float *identity) {
+// asgart_compute_scores[_flags]_shard
+static int64_t score_one_shard(const char *fn, asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
+                               const asgart::Orientations &o, int32_t shard, int32_t n_shards, float *identity) {
     using namespace asgart;
-    static const char *fn = "asgart_compute_scores_shard";
     if (!idx) {
         set_error("%s: bad argument", fn);
         return ASGART_E_ARG;
@@ -591,22 +641,34 @@ extern "C" int64_t asgart_compute_scores_shard(asgart_index *idx, const asgart_p
         return ASGART_E_ARG;
     }
     if (n_sd == 0) return 0;
-    RC_TRY(check_scores_input(fn, idx, sds, n_sd));  // the whole list: every rank fails alike
+    RC_TRY(check_flags(fn, o.flags, n_sd));          // the whole list: every rank fails alike
+    RC_TRY(check_scores_input(fn, idx, sds, n_sd));
     try {
         std::vector<int32_t> owner((size_t)n_sd);
         score_owners(sds, n_sd, n_shards, owner.data());
-        return score_shard(idx, sds, n_sd, owner.data(), shard, reversed, complemented, identity);
+        return score_shard(idx, sds, n_sd, owner.data(), shard, o, identity);
     } catch (const std::bad_alloc &) {
         set_error("%s: out of host memory", fn);
         return ASGART_E_OOM;
     }
 }
 
-extern "C" int32_t asgart_compute_scores_multi(asgart_index *const *indices, int32_t n_devices,
-                                               const asgart_proto_sd *sds, int64_t n_sd, int32_t reversed,
-                                               int32_t complemented, float *identity) {
+extern "C" int64_t asgart_compute_scores_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
+                                               int32_t reversed, int32_t complemented, int32_t shard, int32_t n_shards,
+                                               float *identity) {
+    return score_one_shard("asgart_compute_scores_shard", idx, sds, n_sd, {nullptr, reversed, complemented}, shard,
+                           n_shards, identity);
+}
+
+extern "C" int64_t asgart_compute_scores_flags_shard(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags,
+                                                     int64_t n_sd, int32_t shard, int32_t n_shards, float *identity) {
+    return score_one_shard("asgart_compute_scores_flags_shard", idx, sds, n_sd, {flags, 0, 0}, shard, n_shards, identity);
+}
+
+// asgart_compute_scores[_flags]_multi
+static int32_t score_devices(const char *fn, asgart_index *const *indices, int32_t n_devices, const asgart_proto_sd *sds,
+                             int64_t n_sd, const asgart::Orientations &o, float *identity) {
     using namespace asgart;
-    static const char *fn = "asgart_compute_scores_multi";
     if (!indices || n_devices < 1 || n_devices > 64) {
         set_error("%s: bad argument: %d devices", fn, n_devices);
         return ASGART_E_ARG;
@@ -618,6 +680,7 @@ extern "C" int32_t asgart_compute_scores_multi(asgart_index *const *indices, int
         }
     RC_TRY(check_shard_args(fn, sds, n_sd, n_devices, identity));
     if (n_sd == 0) return 0;
+    RC_TRY(check_flags(fn, o.flags, n_sd));
     RC_TRY(check_scores_input(fn, indices[0], sds, n_sd));
     try {
         std::vector<int32_t> owner((size_t)n_sd);
@@ -629,7 +692,7 @@ extern "C" int32_t asgart_compute_scores_multi(asgart_index *const *indices, int
         for (int32_t r = 0; r < n_devices; ++r)
             workers.emplace_back([&, r]() {
                 try {
-                    rcs[r] = score_shard(indices[r], sds, n_sd, owner.data(), r, reversed, complemented, identity);
+                    rcs[r] = score_shard(indices[r], sds, n_sd, owner.data(), r, o, identity);
                     if (rcs[r] < 0) errs[r] = asgart_last_error();  // the message is thread-local
                 } catch (const std::bad_alloc &) {
                     rcs[r] = ASGART_E_OOM;
@@ -647,4 +710,17 @@ extern "C" int32_t asgart_compute_scores_multi(asgart_index *const *indices, int
         return ASGART_E_OOM;
     }
     return 0;
+}
+
+extern "C" int32_t asgart_compute_scores_multi(asgart_index *const *indices, int32_t n_devices,
+                                               const asgart_proto_sd *sds, int64_t n_sd, int32_t reversed,
+                                               int32_t complemented, float *identity) {
+    return score_devices("asgart_compute_scores_multi", indices, n_devices, sds, n_sd, {nullptr, reversed, complemented},
+                         identity);
+}
+
+extern "C" int32_t asgart_compute_scores_flags_multi(asgart_index *const *indices, int32_t n_devices,
+                                                     const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
+                                                     float *identity) {
+    return score_devices("asgart_compute_scores_flags_multi", indices, n_devices, sds, n_sd, {flags, 0, 0}, identity);
 }

@@ -11,7 +11,9 @@ in the CPU tests and on one-GPU boxes):
 `--compute-score` splits the same way, by duplication (asgart_score_owners: cost-balanced, the same on every rank):
 compute_scores gathers the (input ordinal, identity) pairs of every rank and puts them back in input order.
 search_duplications is a whole run on N ranks, FASTA files to the RunResult JSON text; `python -m asgart_amd.multi
---gpus N files...` starts the ranks and writes the reference's output file.
+--gpus N files...` starts the ranks and writes the reference's output file.  search_orientations is a run over a list
+of orientations with everything built once (`--orientations direct,RC [--merged NAME]`): one file per orientation, each
+the bytes of its own run, and the merged result asgart-slice makes of them.
 """
 from __future__ import annotations
 
@@ -149,33 +151,37 @@ def gather_scores(ordinals: np.ndarray, values: np.ndarray, n: int, dist, device
 
 
 def compute_scores(index, sds: np.ndarray, reversed_: bool, complemented: bool, dist, device: Optional[str] = None,
-                   dst: int = 0) -> Optional[np.ndarray]:
+                   dst: int = 0, flags: Optional[np.ndarray] = None) -> Optional[np.ndarray]:
     """ComputeScore (reference src/bin/asgart.rs:98-112) on every rank of `dist`: each rank passes the same full (n, 4)
     list and scores the duplications asgart_score_owners gives it (Index.compute_scores_shard); rank `dst` receives the
     identities of all ranks in input order -- float32[n], bit-equal to Index.compute_scores on one GPU -- and the other
     ranks None.  `index` is the rank's replica (anything with compute_scores_shard).  device: where the collective's
-    tensors live ("cuda:<i>" for RCCL, None for gloo)."""
+    tensors live ("cuda:<i>" for RCCL, None for gloo).  flags: one byte per duplication (bit 0 reversed, bit 1
+    complemented; Index.compute_scores_flags_shard) instead of the two booleans -- the owners do not depend on them."""
     from . import score_owners
 
     sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
     world, rank = dist.get_world_size(), dist.get_rank()
-    ident = index.compute_scores_shard(sds, reversed_, complemented, shard=rank, n_shards=world)
+    if flags is None:
+        ident = index.compute_scores_shard(sds, reversed_, complemented, shard=rank, n_shards=world)
+    else:
+        ident = index.compute_scores_flags_shard(sds, flags, shard=rank, n_shards=world)
     mine = np.flatnonzero(score_owners(sds, world) == rank)
     return gather_scores(mine, ident[mine], len(sds), dist, device, dst)
 
 
-def _broadcast_array(a: Optional[np.ndarray], dist, device: Optional[str], src: int = 0) -> np.ndarray:
-    """An (n, 4) uint64 array from rank `src` to every rank."""
+def _broadcast_array(a: Optional[np.ndarray], dist, device: Optional[str], src: int = 0, cols: int = 4) -> np.ndarray:
+    """An (n, cols) uint64 array from rank `src` to every rank."""
     import torch
 
     dev = torch.device(device) if device else torch.device("cpu")
     n = torch.tensor([len(a) if dist.get_rank() == src else 0], dtype=torch.int64, device=dev)
     dist.broadcast(n, src=src)
-    t = torch.zeros(int(n.item()) * 4 + 1, dtype=torch.int64, device=dev)
+    t = torch.zeros(int(n.item()) * cols + 1, dtype=torch.int64, device=dev)
     if dist.get_rank() == src and len(a):
         t[:-1] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).reshape(-1)).to(dev)
     dist.broadcast(t, src=src)
-    return t[:-1].cpu().numpy().view(np.uint64).reshape(-1, 4)
+    return t[:-1].cpu().numpy().view(np.uint64).reshape(-1, cols)
 
 
 def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
@@ -234,6 +240,93 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
             index.close()
 
 
+def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool, bool]], settings, dist,
+                        device_index: int, compute_score: bool = False, prefix: str = "",
+                        with_sequences: bool = False):
+    """One run over several orientations of one strand -- what the reference needs one `asgart` invocation per
+    orientation and an `asgart-slice` merge for.  orientations: one to four distinct (reverse, complement) pairs in the
+    user's order; `settings` supplies everything else (its own two flags are ignored).  Built ONCE: the records read and
+    prepared, the index, its replicas; ONE fused search over the settings of every orientation
+    (asgart_search_duplications_passes[_shard]); then per orientation, as the reference runs them per invocation (families
+    of different orientations are never reduced against each other), gather_families and, on rank 0, post_process.  With
+    compute_score the survivors of all orientations, concatenated in the given order with their flag bytes, are
+    broadcast once and scored by ONE Index.compute_scores_flags_shard per rank; with_sequences is one Source and one
+    extraction over the same list.  Returns, on rank 0, ([(JSON text, out_filename(files, its settings, prefix)) per
+    orientation], merged JSON text) and None elsewhere: each text is byte-equal to search_duplications with that
+    orientation, the merged one to postprocess.merge_results over those files in that order (RunResult::from_files,
+    reference src/structs.rs:114-141: strand and settings of the first, every duplication with the flags of its own
+    run).  dist None: one process, one GPU, no collective.  `--trim` needs one rank."""
+    from dataclasses import replace
+
+    from . import Index, Strand, merge_shards, orientation_flags
+    from .postprocess import out_filename, to_json_arrays
+    from .prep import prepare_records, read_records, validate_trim
+
+    orientations = [(bool(r), bool(c)) for r, c in orientations]
+    if not 1 <= len(orientations) <= 4 or len(set(orientations)) != len(orientations):
+        raise ValueError("multi.search_orientations: one to four distinct (reverse, complement) pairs")
+    sts = [replace(settings, reverse=r, complement=c) for r, c in orientations]
+    world, rank = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
+    if settings.trim is not None and world > 1:
+        raise ValueError("multi.search_orientations: --trim runs on one rank only")
+    comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
+    index = strand = records = None
+    chunks = [None]
+    try:
+        if rank == 0:
+            records = [rec for f in files for rec in read_records(f)]
+            pr = prepare_records(records, settings.skip_masked)
+            strand = Strand(", ".join(files), pr.data, pr.map)
+            trim = validate_trim(settings.trim, len(pr.data))
+            index = Index(strand.data, None, device_index, trim=trim)
+            chunks = [list(pr.chunks)]
+        if dist is not None:
+            dist.broadcast_object_list(chunks, src=0)
+        if world > 1:
+            index = replicate_index(index, dist, device_index)
+        raw = index.search_duplications_passes(chunks[0], sts, shard=rank, n_shards=world, with_keys=True)
+        posts = []
+        for offs, sds, keys in raw:
+            got = gather_families(offs, sds, dist, comm, keys=keys) if dist is not None else \
+                merge_shards([(offs, sds, keys)])
+            posts.append(index.post_process(*got) if rank == 0 else None)
+        kept = flags = None
+        if rank == 0:
+            kept = np.concatenate([p[1] for p in posts]).reshape(-1, 4)
+            flags = np.concatenate([orientation_flags(r, c, len(p[1])) for (r, c), p in zip(orientations, posts)])
+        ident = None
+        if compute_score:
+            if dist is not None:   # the duplications and their flag bytes travel as one (n, 5) array
+                both = _broadcast_array(np.column_stack([kept, flags.astype(np.uint64)]) if rank == 0 else None, dist,
+                                        comm, cols=5)
+                ident = compute_scores(index, both[:, :4], False, False, dist, comm, flags=both[:, 4].astype(np.uint8))
+            else:
+                ident = index.compute_scores_flags_shard(kept, flags, shard=0, n_shards=1)
+        if rank != 0:
+            return None
+        seqs = None
+        if with_sequences:
+            from . import Source
+            from .extract import sequences
+
+            with Source.from_records(records, device_index) as src:
+                seqs = sequences(src, kept, (flags & 1).astype(bool), (flags >> 1 & 1).astype(bool))
+        out = []
+        lo = 0
+        for st, (offs, sds) in zip(sts, posts):
+            hi = lo + len(sds)
+            part = None if seqs is None else (seqs[0][lo:hi], seqs[1][lo:hi])
+            out.append((to_json_arrays(offs, sds, strand, st, None if ident is None else ident[lo:hi], part),
+                        out_filename(files, st, prefix)))
+            lo = hi
+        sizes = np.concatenate([np.diff(p[0].astype(np.int64)) for p in posts])
+        all_offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+        return out, to_json_arrays(all_offs, kept, strand, sts[0], ident, seqs, flags)
+    finally:
+        if index is not None:
+            index.close()
+
+
 def _parse(argv):
     import argparse
 
@@ -256,9 +349,27 @@ def _parse(argv):
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
                     help="every rank on device 0 over gloo (also the choice when there are fewer GPUs than ranks)")
+    def orientation_list(text):
+        from .postprocess import parse_orientations
+
+        try:
+            return parse_orientations(text)
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e))
+
+    ap.add_argument("--orientations", type=orientation_list, metavar="LIST",
+                    help="several orientations in ONE run, e.g. direct,RC (tokens direct, R, C, RC; no repeats): one "
+                         "file per orientation under the reference's names; not together with -R / -C")
+    ap.add_argument("--merged", metavar="NAME",
+                    help="with --orientations: also write the merged result (asgart-slice's RunResult::from_files over "
+                         "those files, in the order given) to NAME in --out-dir")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
+    if args.orientations and (args.reverse or args.complement):
+        ap.error("--orientations names the orientations: not together with -R / -C")
+    if args.merged and not args.orientations:
+        ap.error("--merged needs --orientations")
     return args
 
 
@@ -331,10 +442,15 @@ def rank_main(argv) -> int:
         settings = RunSettings.from_cli(k=args.probe_size, gap=args.max_gap, min_length=args.min_length,
                                         max_cardinality=args.max_cardinality, reverse=args.reverse,
                                         complement=args.complement, skip_masked=args.skip_masked)
-        out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix,
-                                  args.with_sequences)
-        if out is not None:
-            text, name = out
+        if args.orientations:
+            out = search_orientations(args.files, args.orientations, settings, dist, device_index, args.compute_score,
+                                      args.prefix, args.with_sequences)
+            texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])
+        else:
+            out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix,
+                                      args.with_sequences)
+            texts = None if out is None else [out]
+        for text, name in texts or []:
             path = os.path.join(args.out_dir, name)
             with open(path, "w", encoding="utf-8") as fh:
                 fh.write(text)

@@ -287,11 +287,13 @@ def post_process_arrays(index, offs: np.ndarray, sds: np.ndarray, threads: int =
 
 
 def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSettings, identity: Optional[np.ndarray] = None,
-                   seqs: Optional[Tuple[Sequence[str], Sequence[str]]] = None) -> str:
+                   seqs: Optional[Tuple[Sequence[str], Sequence[str]]] = None, flags: Optional[np.ndarray] = None) -> str:
     """`to_json(run_result(...))` for family arrays: the same bytes, one format operation per duplication (the
     chromosome of a position by bisection of the strand map, whose records follow one another: the reference's
     first-match scan, src/structs.rs:85-90, finds the same record).  seqs: (left, right) sequences of every
-    duplication, written into left_seq / right_seq (what asgart-extract --in-place fills) instead of null."""
+    duplication, written into left_seq / right_seq (what asgart-extract --in-place fills) instead of null.  flags: one
+    byte per duplication (bit 0 reversed, bit 1 complemented) for a result merged from several runs (merge_results);
+    default: the settings' two flags on every duplication."""
     offs = np.asarray(offs, dtype=np.int64)
     sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
     starts = np.array([c.position for c in strand.map], dtype=np.uint64)
@@ -313,8 +315,13 @@ def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSetti
     ident = [f32_repr(v) for v in identity] if identity is not None else None
     if seqs is not None:
         lseq, rseq = ([json.dumps(x, ensure_ascii=False) for x in side] for side in seqs)
-    rev = "true" if settings.reverse else "false"
-    comp = "true" if settings.complement else "false"
+    if flags is None:
+        flags = np.full(len(sds), int(bool(settings.reverse)) | int(bool(settings.complement)) << 1, dtype=np.uint8)
+    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != len(sds):
+        raise ValueError(f"{len(flags)} flag bytes for {len(sds)} duplications")
+    rev = [("false", "true")[f & 1] for f in flags.tolist()]
+    comp = [("false", "true")[f >> 1 & 1] for f in flags.tolist()]
     sd_txt = []
     L, R, LL, RL = (sds[:, j].tolist() for j in range(4))
     il, ir, pl, pr_ = il.tolist(), ir.tolist(), pl.tolist(), pr_.tolist()
@@ -332,8 +339,8 @@ def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSetti
             f'        "left_seq": {lseq[j] if seqs is not None else "null"},\n'
             f'        "right_seq": {rseq[j] if seqs is not None else "null"},\n'
             f'        "identity": {ident[j] if ident else "0.0"},\n'
-            f'        "reversed": {rev},\n'
-            f'        "complemented": {comp}\n'
+            f'        "reversed": {rev[j]},\n'
+            f'        "complemented": {comp[j]}\n'
             '      }')
     fams = []
     for f in range(len(offs) - 1):
@@ -354,6 +361,56 @@ def out_filename(files: Sequence[str], settings: RunSettings, prefix: str = "") 
          ("R" if settings.reverse else "") + ("C" if settings.complement else "")
     trim = f"_{settings.trim[0]}-{settings.trim[1]}" if settings.trim else ""
     return f"{prefix}{radix}{rc}{trim}.json"
+
+
+def merge_parsed(results: Sequence[dict]) -> dict:
+    """RunResult::from_files (src/structs.rs:114-141) on parsed results (extract.parse_result): strand and settings of
+    the first, the families of all one after the other, every duplication as its own file has it.  Different
+    strand.name: ValueError with the reference's message (:120-128)."""
+    for res in results:
+        if res["strand"]["name"] != results[0]["strand"]["name"]:
+            raise ValueError("Trying to combine ASGART files from different sources: "
+                             f"`{res['strand']['name']}` and `{results[0]['strand']['name']}`")
+    return {"strand": results[0]["strand"], "settings": results[0]["settings"],
+            "families": [fam for res in results for fam in res["families"]]}
+
+
+def merge_results(paths: Sequence[str]) -> str:
+    """What asgart-slice makes of several result files before it filters (RunResult::from_files): the JSON text (to_json)
+    of the merged result, e.g. of the direct and the -RC run over one strand, whoever wrote the files."""
+    from .extract import read_result
+
+    if not paths:
+        raise ValueError("merge_results: no input file")
+    return to_json(merge_parsed([read_result(p) for p in paths]))
+
+
+ORIENTATION_TOKENS = {"direct": (False, False), "R": (True, False), "C": (False, True), "RC": (True, True)}
+
+
+def parse_orientations(text: str) -> List[Tuple[bool, bool]]:
+    """`direct,RC` -> [(False, False), (True, True)]: (reverse, complement) pairs in the order given.  Tokens direct,
+    R, C, RC; one to four of them, none twice (ValueError)."""
+    out = []
+    for tok in text.split(","):
+        if tok not in ORIENTATION_TOKENS:
+            raise ValueError(f"unknown orientation `{tok}` (one of {', '.join(ORIENTATION_TOKENS)})")
+        if ORIENTATION_TOKENS[tok] in out:
+            raise ValueError(f"orientation `{tok}` given twice")
+        out.append(ORIENTATION_TOKENS[tok])
+    return out
+
+
+def search_orientations(strands_files: Sequence[str], orientations: Sequence[Tuple[bool, bool]], settings: RunSettings,
+                        device: int = 0, compute_score: bool = False):
+    """One run over several orientations on one GPU (multi.search_orientations without a process group): the input read
+    and the index built once, ONE fused search over all orientations, one score call over all survivors.
+    -> ([(JSON text, output file name) per orientation], merged JSON text): each text is what
+    to_json(search_duplications(files, settings with that orientation, device, compute_score)) gives, the merged one
+    what merge_results gives for those files in that order."""
+    from .multi import search_orientations as run
+
+    return run(strands_files, orientations, settings, None, device, compute_score)
 
 
 def search_duplications(strands_files: Sequence[str], settings: RunSettings, device: int = 0,

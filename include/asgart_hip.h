@@ -373,6 +373,20 @@ int64_t asgart_compute_scores_shard(asgart_index *idx, const asgart_proto_sd *sd
 int32_t asgart_compute_scores_multi(asgart_index *const *indices, int32_t n_devices, const asgart_proto_sd *sds,
                                     int64_t n_sd, int32_t reversed, int32_t complemented, float *identity);
 
+/* The same three with ONE FLAG BYTE PER DUPLICATION instead of one pair of flags per call: ProtoSD::levenshtein
+ * (reference src/structs.rs:439-452) reads `reversed` / `complemented` of the duplication it scores, so a list that
+ * holds the duplications of several runs over one strand (the direct and the -RC one, as asgart-slice merges their
+ * files, src/structs.rs:114-141) is scored in one call.  flags[q]: bit 0 reversed, bit 1 complemented, the encoding of
+ * asgart_extract_sequences; NULL means all zero; any other bit set is ASGART_E_ARG (checked over the whole list, on
+ * every shard).  identity[q] is bit-equal to what the call above gives for duplication q with q's two flags.  The
+ * owners (asgart_score_owners) and the schedule do not look at the flags. */
+int32_t asgart_compute_scores_flags(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
+                                    float *identity);
+int64_t asgart_compute_scores_flags_shard(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags,
+                                          int64_t n_sd, int32_t shard, int32_t n_shards, float *identity);
+int32_t asgart_compute_scores_flags_multi(asgart_index *const *indices, int32_t n_devices, const asgart_proto_sd *sds,
+                                          const uint8_t *flags, int64_t n_sd, float *identity);
+
 /* ---- the steps behind the search step ------------------------------------------
  * Replaces FilterNs, ReOrder, ReduceOverlap and Sort of the reference's step chain (src/bin/asgart.rs:33-96 with
  * ProtoSD::n_content src/structs.rs:454-467, reduce_overlap :481-562; order :738-747) for the families of one run,
