@@ -42,6 +42,8 @@ ABI_SYMBOLS = (
     "asgart_compute_scores_shard", "asgart_compute_scores_multi", "asgart_tier_plan",
     "asgart_source_create", "asgart_source_destroy", "asgart_extract_sequences",
     "asgart_compute_scores_flags", "asgart_compute_scores_flags_shard", "asgart_compute_scores_flags_multi",
+    "asgart_fasta_read", "asgart_fasta_counts", "asgart_fasta_copy", "asgart_fasta_read_text", "asgart_fasta_index",
+    "asgart_fasta_source", "asgart_fasta_free", "asgart_fasta_timings", "asgart_fasta_geometry",
 )
 
 
@@ -137,6 +139,24 @@ def load_library() -> C.CDLL:
     L.asgart_source_destroy.restype = None
     L.asgart_extract_sequences.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_uint64, vp, C.POINTER(C.c_int64)]
     L.asgart_extract_sequences.restype = C.c_int32
+    L.asgart_fasta_read.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.asgart_fasta_read.restype = C.c_int32
+    L.asgart_fasta_counts.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), u64p]
+    L.asgart_fasta_counts.restype = C.c_int32
+    L.asgart_fasta_copy.argtypes = [vp, vp, vp, vp]
+    L.asgart_fasta_copy.restype = C.c_int32
+    L.asgart_fasta_read_text.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
+    L.asgart_fasta_read_text.restype = C.c_int32
+    L.asgart_fasta_index.argtypes = [vp, C.POINTER(vp)]
+    L.asgart_fasta_index.restype = C.c_int32
+    L.asgart_fasta_source.argtypes = [vp, C.POINTER(vp)]
+    L.asgart_fasta_source.restype = C.c_int32
+    L.asgart_fasta_free.argtypes = [vp]
+    L.asgart_fasta_free.restype = None
+    L.asgart_fasta_timings.argtypes = [vp, C.POINTER(C.c_double)]
+    L.asgart_fasta_timings.restype = C.c_int32
+    L.asgart_fasta_geometry.argtypes = [u64p, u64p, u64p]
+    L.asgart_fasta_geometry.restype = None
     L.asgart_debug_dump_stacks.argtypes = []
     L.asgart_debug_dump_stacks.restype = C.c_int32
     L.asgart_post_process.argtypes = [vp, vp, C.c_uint64, vp, C.c_int32, C.POINTER(vp)]

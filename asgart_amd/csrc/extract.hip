@@ -10,6 +10,7 @@
 // spread over as many workgroups as their length asks for), and the copy of one piece to the host runs beside the
 // gather of the next.
 #include "common.hpp"
+#include "prep.hpp"
 
 #include <algorithm>
 
@@ -175,6 +176,61 @@ struct asgart_source {
     }
 };
 
+namespace asgart {
+
+// A source of n bytes on the current device with its streams, events and staging buffers, its text still empty.
+static int32_t source_new(uint64_t n, int32_t device, asgart_source **out) {
+    asgart_source *src = new asgart_source;
+    src->device = device;
+    src->n = n;
+    const int32_t rc = [&]() -> int32_t {
+        HIP_TRY(hipStreamCreateWithFlags(&src->s_gather, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&src->s_copy, hipStreamNonBlocking));
+        for (int k = 0; k < 2; ++k) {
+            HIP_TRY(hipEventCreateWithFlags(&src->ev_gather[k], hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&src->ev_copy[k], hipEventDisableTiming));
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&src->h_stage[k]), (size_t)kStage, hipHostMallocDefault));
+        }
+        RC_TRY(src->d_bad.reserve(64));
+        return 0;
+    }();
+    if (rc != 0) {
+        src->release();
+        delete src;
+        return rc;
+    }
+    *out = src;
+    return 0;
+}
+
+// A source over bytes that are on the device already (fasta.hip: the raw strand the FASTA reader wrote): `text` holds
+// n bytes and room for the pad behind them; the source takes the buffer over (text is left empty) -- on success only.
+int32_t source_adopt(DevBuf &text, uint64_t n, int32_t device, asgart_source **out) {
+    if (text.cap < (size_t)n + kPad) {
+        set_error("source_adopt: the buffer lacks the %u bytes of pad", kPad);
+        return ASGART_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(device));
+    asgart_source *src = nullptr;
+    RC_TRY(source_new(n, device, &src));
+    const int32_t rc = [&]() -> int32_t {
+        HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(text.p) + n, 0, kPad, src->s_copy));
+        HIP_TRY(stream_sync(src->s_copy));
+        return 0;
+    }();
+    if (rc != 0) {
+        src->release();
+        delete src;
+        return rc;
+    }
+    src->text = text;
+    text = DevBuf();
+    *out = src;
+    return 0;
+}
+
+}  // namespace asgart
+
 namespace {
 
 // The raw records into src->text through the two pinned staging buffers: the copy of one staging buffer runs while
@@ -235,21 +291,10 @@ extern "C" int32_t asgart_source_create(const uint8_t *const *records, const uin
         return ASGART_E_HIP;
     }
     HIP_TRY(hipSetDevice(device));
-    asgart_source *src = new asgart_source;
-    src->device = device;
-    src->n = n;
-    const int32_t rc = [&]() -> int32_t {
-        HIP_TRY(hipStreamCreateWithFlags(&src->s_gather, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&src->s_copy, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) {
-            HIP_TRY(hipEventCreateWithFlags(&src->ev_gather[k], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&src->ev_copy[k], hipEventDisableTiming));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&src->h_stage[k]), (size_t)kStage, hipHostMallocDefault));
-        }
-        RC_TRY(src->text.reserve((size_t)n + kPad));
-        RC_TRY(src->d_bad.reserve(64));
-        return upload_records(src, records, record_lens, n_records);
-    }();
+    asgart_source *src = nullptr;
+    RC_TRY(source_new(n, device, &src));
+    int32_t rc = src->text.reserve((size_t)n + kPad);
+    if (rc == 0) rc = upload_records(src, records, record_lens, n_records);
     if (rc != 0) {
         src->release();
         delete src;

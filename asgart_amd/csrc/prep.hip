@@ -8,20 +8,12 @@
 // the device anyway, so the raw bytes are uploaded once, normalised in place by one streaming kernel, the long N-runs
 // are found there, and the index is built from the same device buffer.
 #include "index.hpp"
+#include "prep.hpp"
 
 #include <algorithm>
 
 namespace asgart {
 namespace {
-
-constexpr uint64_t kNRunThreshold = 5000;  // reference src/bin/asgart.rs:326
-
-// (:291-301) c -> upper case unless skip_masked; then anything outside ATGCN -> N
-__device__ inline uint32_t norm_byte(uint32_t c, bool skip_masked) {
-    if (!skip_masked && c >= 'a' && c <= 'z') c -= 32u;
-    const bool ok = c == 'A' || c == 'T' || c == 'G' || c == 'C' || c == 'N';
-    return ok ? c : (uint32_t)'N';
-}
 
 __global__ __launch_bounds__(256) void normalise_kernel(uint8_t *__restrict__ text, uint64_t n, int skip_masked) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 16u;
@@ -106,6 +98,82 @@ __global__ __launch_bounds__(64) void nrun_extent_kernel(const uint8_t *__restri
 }
 
 }  // namespace
+
+int32_t find_long_n_runs(const char *who, const uint8_t *d_text, uint64_t n_bases, const uint64_t *d_off,
+                         int64_t n_records, hipStream_t s, std::vector<uint64_t> &runs) {
+    constexpr unsigned long long kCandCap = 1ull << 22;
+    DevBuf d_cand, d_runs, d_cnt;
+    runs.clear();
+    const int32_t rc = [&]() -> int32_t {
+        RC_TRY(d_cand.reserve((size_t)kCandCap * 8));
+        RC_TRY(d_runs.reserve((size_t)kCandCap * 16));
+        RC_TRY(d_cnt.reserve(64));
+        HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 64, s));
+        unsigned long long *cnt = d_cnt.as<unsigned long long>();
+        nrun_candidates_kernel<<<(unsigned)std::min<uint64_t>((n_bases + 255) / 256 + 1, 1u << 16), 256, 0, s>>>(
+            d_text, n_bases, d_off, (int)n_records, d_cand.as<uint64_t>(), kCandCap, cnt);
+        HIP_TRY(hipGetLastError());
+        unsigned long long h_cnt[2] = {0, 0};
+        HIP_TRY(read_back(h_cnt, cnt, 8, s));
+        if (h_cnt[0] > kCandCap) {
+            set_error("%s: more than %llu candidate N-runs", who, kCandCap);
+            return ASGART_E_CAP;
+        }
+        if (h_cnt[0]) {
+            nrun_extent_kernel<<<(unsigned)std::min<unsigned long long>(h_cnt[0], 4096ull), 64, 0, s>>>(
+                d_text, d_off, (int)n_records, d_cand.as<uint64_t>(), h_cnt[0], d_runs.as<uint64_t>(), cnt + 1);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(read_back(h_cnt + 1, cnt + 1, 8, s));
+            runs.resize((size_t)h_cnt[1] * 2);
+            if (h_cnt[1]) HIP_TRY(read_back(runs.data(), d_runs.p, (size_t)h_cnt[1] * 16, s));
+        }
+        return 0;
+    }();
+    d_cand.release();
+    d_runs.release();
+    d_cnt.release();
+    return rc;
+}
+
+void chunks_from_runs(const uint64_t *off, int64_t n_records, const std::vector<uint64_t> &h_runs,
+                      std::vector<uint64_t> &chunks) {
+    // chunks per record: the pieces between its long runs (src/bin/asgart.rs:317-366), in record order (:375-395)
+    std::vector<std::pair<uint64_t, uint64_t>> runs(h_runs.size() / 2);
+    for (size_t j = 0; j < runs.size(); ++j) runs[j] = {h_runs[2 * j], h_runs[2 * j + 1]};
+    std::sort(runs.begin(), runs.end());
+    chunks.clear();
+    size_t j = 0;
+    auto push = [&](uint64_t a, uint64_t len) {
+        chunks.push_back(a);
+        chunks.push_back(len);
+    };
+    for (int64_t r = 0; r < n_records; ++r) {
+        const uint64_t r0 = off[r], r1 = off[r + 1];
+        const size_t before = chunks.size();
+        uint64_t a = r0;
+        while (j < runs.size() && runs[j].first < r1) {
+            if (runs[j].first > a) push(a, runs[j].first - a);
+            a = runs[j].second;
+            ++j;
+        }
+        if (r1 > a) push(a, r1 - a);
+        if (chunks.size() == before) push(r0, r1 - r0);  // (`if chunks.is_empty() { chunks.push((0, len)) }`)
+    }
+}
+
+int32_t finish_text(uint8_t *d_text, uint64_t n_bases, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(d_text + n_bases, '$', 1, s));
+    HIP_TRY(hipMemsetAsync(d_text + n_bases + 1, 0, 64, s));
+    return 0;
+}
+
+int32_t index_over_text(const uint8_t *d_text, uint64_t n, int32_t device, asgart_index **out) {
+    asgart::Options opt;
+    options_from_env(opt);
+    const bool wide = n >= 0xFFFFFF00ull || opt.force_wide != 0;
+    return asgart_index_create_device(d_text, (int64_t)n, nullptr, (int64_t)n, wide ? 8 : 4, device, out);
+}
+
 }  // namespace asgart
 
 using namespace asgart;
@@ -115,7 +183,7 @@ extern "C" int32_t asgart_prepare_data(const uint8_t *const *records, const uint
                                        int64_t chunks_cap, int64_t *n_chunks, asgart_index **index_out) {
     if (index_out) *index_out = nullptr;
     if (n_chunks) *n_chunks = 0;
-    if (!records || !record_lens || n_records <= 0 || !n_chunks || (chunks_cap && !chunks) || n_records > (1 << 24)) {
+    if (!records || !record_lens || n_records <= 0 || !n_chunks || (chunks_cap && !chunks) || n_records > kMaxRecords) {
         set_error("asgart_prepare_data: bad argument");
         return ASGART_E_ARG;
     }
@@ -135,75 +203,31 @@ extern "C" int32_t asgart_prepare_data(const uint8_t *const *records, const uint
         set_error("asgart_prepare_data: no usable device %d (there is no CPU fallback)", device);
         return ASGART_E_HIP;
     }
-    DevBuf d_text, d_off, d_cand, d_runs, d_cnt;
+    DevBuf d_text, d_off;
     hipStream_t s = nullptr;
     std::vector<uint64_t> h_runs;
-    constexpr unsigned long long kCandCap = 1ull << 22;
     int32_t rc = [&]() -> int32_t {
         HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         RC_TRY(d_text.reserve((size_t)n + 64));
         RC_TRY(d_off.reserve(((size_t)n_records + 1) * 8));
-        RC_TRY(d_cand.reserve((size_t)kCandCap * 8));
-        RC_TRY(d_runs.reserve((size_t)kCandCap * 16));
-        RC_TRY(d_cnt.reserve(64));
         uint8_t *text = d_text.as<uint8_t>();
         for (int64_t r = 0; r < n_records; ++r)
             if (record_lens[r])
                 HIP_TRY(hipMemcpyAsync(text + off[(size_t)r], records[r], (size_t)record_lens[r], hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), ((size_t)n_records + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 64, s));
         const unsigned grid = (unsigned)std::min<uint64_t>((n_bases + 256u * 16u - 1) / (256u * 16u) + 1, 1u << 16);
         normalise_kernel<<<grid, 256, 0, s>>>(text, n_bases, skip_masked);
-        HIP_TRY(hipMemsetAsync(text + n_bases, '$', 1, s));
-        HIP_TRY(hipMemsetAsync(text + n, 0, 64, s));
-        unsigned long long *cnt = d_cnt.as<unsigned long long>();
-        nrun_candidates_kernel<<<(unsigned)std::min<uint64_t>((n_bases + 255) / 256 + 1, 1u << 16), 256, 0, s>>>(
-            text, n_bases, d_off.as<uint64_t>(), (int)n_records, d_cand.as<uint64_t>(), kCandCap, cnt);
-        HIP_TRY(hipGetLastError());
-        unsigned long long h_cnt[2] = {0, 0};
-        HIP_TRY(read_back(h_cnt, cnt, 8, s));
-        if (h_cnt[0] > kCandCap) {
-            set_error("asgart_prepare_data: more than %llu candidate N-runs", kCandCap);
-            return ASGART_E_CAP;
-        }
-        if (h_cnt[0]) {
-            nrun_extent_kernel<<<(unsigned)std::min<unsigned long long>(h_cnt[0], 4096ull), 64, 0, s>>>(
-                text, d_off.as<uint64_t>(), (int)n_records, d_cand.as<uint64_t>(), h_cnt[0], d_runs.as<uint64_t>(), cnt + 1);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(read_back(h_cnt + 1, cnt + 1, 8, s));
-            h_runs.resize((size_t)h_cnt[1] * 2);
-            if (h_cnt[1]) HIP_TRY(read_back(h_runs.data(), d_runs.p, (size_t)h_cnt[1] * 16, s));
-        }
+        RC_TRY(finish_text(text, n_bases, s));
+        RC_TRY(find_long_n_runs("asgart_prepare_data", text, n_bases, d_off.as<uint64_t>(), n_records, s, h_runs));
         if (text_out) HIP_TRY(read_back(text_out, text, (size_t)n, s));
         HIP_TRY(stream_sync(s));
         return 0;
     }();
-    int64_t nc = 0;
     if (rc == 0) {
-        // chunks per record: the pieces between its long runs (src/bin/asgart.rs:317-366), in record order (:375-395)
-        std::vector<std::pair<uint64_t, uint64_t>> runs(h_runs.size() / 2);
-        for (size_t j = 0; j < runs.size(); ++j) runs[j] = {h_runs[2 * j], h_runs[2 * j + 1]};
-        std::sort(runs.begin(), runs.end());
-        size_t j = 0;
-        auto push = [&](uint64_t a, uint64_t len) {
-            if (nc < chunks_cap) {
-                chunks[2 * nc] = a;
-                chunks[2 * nc + 1] = len;
-            }
-            ++nc;
-        };
-        for (int64_t r = 0; r < n_records; ++r) {
-            const uint64_t r0 = off[(size_t)r], r1 = off[(size_t)r + 1];
-            const int64_t before = nc;
-            uint64_t a = r0;
-            while (j < runs.size() && runs[j].first < r1) {
-                if (runs[j].first > a) push(a, runs[j].first - a);
-                a = runs[j].second;
-                ++j;
-            }
-            if (r1 > a) push(a, r1 - a);
-            if (nc == before) push(r0, r1 - r0);  // (`if chunks.is_empty() { chunks.push((0, len)) }`)
-        }
+        std::vector<uint64_t> all;
+        chunks_from_runs(off.data(), n_records, h_runs, all);
+        const int64_t nc = (int64_t)(all.size() / 2);
+        if (chunks_cap) memcpy(chunks, all.data(), (size_t)std::min(nc, chunks_cap) * 16);
         *n_chunks = nc;
         if (nc > chunks_cap && chunks_cap) {
             set_error("asgart_prepare_data: %lld chunks, room for %lld (call again with a larger array)", (long long)nc,
@@ -211,17 +235,9 @@ extern "C" int32_t asgart_prepare_data(const uint8_t *const *records, const uint
             rc = ASGART_E_CAP;
         }
     }
-    if (rc == 0 && index_out) {
-        asgart::Options opt;
-        options_from_env(opt);
-        const bool wide = n >= 0xFFFFFF00ull || opt.force_wide != 0;
-        rc = asgart_index_create_device(d_text.p, (int64_t)n, nullptr, (int64_t)n, wide ? 8 : 4, device, index_out);
-    }
+    if (rc == 0 && index_out) rc = index_over_text(d_text.as<uint8_t>(), n, device, index_out);
     d_text.release();
     d_off.release();
-    d_cand.release();
-    d_runs.release();
-    d_cnt.release();
     if (s) (void)hipStreamDestroy(s);
     return rc;
 }

@@ -103,6 +103,20 @@ def read_source(paths: Sequence[str]) -> List[np.ndarray]:
     return [seq for p in paths for _, seq in read_records(p)]
 
 
+def open_source(paths: Sequence[str], device: int = 0):
+    """The Source of the files' records (:17-29, :110-117), read on the GPU (prep.read_fasta_gpu: the mapped files are
+    uploaded once and parsed there); files without any record give the empty source the host reader gives."""
+    from . import AsgartError, Source
+    from .prep import read_fasta_gpu
+
+    try:
+        return read_fasta_gpu(paths, device=device, want_index=False, want_source=True)[2]
+    except AsgartError as e:
+        if e.code != -1 or "no record" not in str(e):
+            raise
+    return Source.from_records(read_source(paths), device)
+
+
 def duplications(result: dict) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Every duplicon of the result in family order -> (sds uint64[n, 4], reversed bool[n], complemented bool[n])."""
     sds = [sd for fam in result["families"] for sd in fam]
@@ -190,11 +204,11 @@ def main(argv=None) -> int:
     except FileNotFoundError as e:
         print(f"error: {e}", file=sys.stderr)
         return 1
-    from . import AsgartError, Source
+    from . import AsgartError
 
     sds, rev, comp = duplications(result)
     try:
-        with Source.from_records(read_source(paths), args.device) as src:
+        with open_source(paths, args.device) as src:
             left, right = sequences(src, sds, rev, comp)
     except AsgartError as e:
         print(f"error: {e}", file=sys.stderr)

@@ -184,8 +184,56 @@ def _broadcast_array(a: Optional[np.ndarray], dist, device: Optional[str], src: 
     return t[:-1].cpu().numpy().view(np.uint64).reshape(-1, cols)
 
 
+def _choose_reader(reader: Optional[str], settings) -> str:
+    """reader=None: the device reader whenever the run has no --trim (a trimmed index is built on the host)."""
+    if reader is None:
+        return "device" if settings.trim is None else "host"
+    if reader not in ("device", "host"):
+        raise ValueError("reader: 'device' or 'host'")
+    if reader == "device" and settings.trim is not None:
+        raise ValueError("--trim runs with the host reader")
+    return reader
+
+
+def _read_input(files: Sequence[str], settings, device_index: int, reader: str, with_sequences: bool):
+    """Rank 0's input step -> (strand, chunks, index, records or None, source or None).
+    reader "device": one prep.read_fasta_gpu over the mapped files -- the strand stays on the GPU (strand.data is None),
+    the index is built from it there and, with_sequences, the Source is the raw strand of the same read.  A run whose
+    files hold no record at all is refused by the library and goes through the host reader like every run did before.
+    reader "host": prep.read_records and prep.prepare_records, the text uploaded by Index()."""
+    from . import AsgartError, Index, Strand
+    from .prep import prepare_records, read_fasta_gpu, read_records, validate_trim
+
+    names = ", ".join(files)                                     # file_names, src/bin/asgart.rs:437
+    if reader == "device":
+        try:
+            pr, index, source = read_fasta_gpu(files, settings.skip_masked, device_index, want_text=False,
+                                               want_index=True, want_source=with_sequences)
+            return Strand(names, None, pr.map), list(pr.chunks), index, None, source
+        except AsgartError as e:
+            if e.code != -1 or "no record" not in str(e):
+                raise
+    records = [rec for f in files for rec in read_records(f)]
+    pr = prepare_records(records, settings.skip_masked)
+    strand = Strand(names, pr.data, pr.map)
+    trim = validate_trim(settings.trim, len(pr.data))            # prepare_data's checks, :432-463
+    return strand, list(pr.chunks), Index(strand.data, None, device_index, trim=trim), records, None
+
+
+def _sequences(source, records, device_index: int, sds, reversed_, complemented):
+    """left_seq / right_seq of the duplications from the run's Source (device reader) or its records (host reader)."""
+    from . import Source
+    from .extract import sequences
+
+    if source is not None:
+        return sequences(source, sds, reversed_, complemented)
+    with Source.from_records(records, device_index) as src:
+        return sequences(src, sds, reversed_, complemented)
+
+
 def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
-                        prefix: str = "", with_sequences: bool = False) -> Optional[Tuple[str, str]]:
+                        prefix: str = "", with_sequences: bool = False,
+                        reader: Optional[str] = None) -> Optional[Tuple[str, str]]:
     """A whole `asgart` run (reference src/bin/asgart.rs:731-822) on the ranks of `dist`, rank r on GPU device_index:
     rank 0 prepares the input and builds the index, replicate_index copies it to every rank, each rank runs its shard of
     the search (asgart_search_duplications_passes_shard), gather_families merges the families on rank 0, rank 0 runs the
@@ -195,25 +243,22 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     postprocess.out_filename(files, settings, prefix) -- and None on the other ranks.  With world size 1 this is the
     single-GPU driver.  `--trim` needs world size 1 (a trimmed index is not replicated).  with_sequences: rank 0 also
     fills left_seq / right_seq from the raw records it read (asgart_amd.Source on its GPU): the text `asgart` followed by
-    `asgart-extract -I` gives (extract.result_text), without its trailing newline."""
-    from . import Index, Strand
+    `asgart-extract -I` gives (extract.result_text), without its trailing newline.  reader: "device" (the default
+    without --trim) reads the files on rank 0's GPU (prep.read_fasta_gpu: index and Source from one upload), "host" with
+    prep.read_records as before; the text is the same either way."""
     from .postprocess import out_filename, to_json_arrays
-    from .prep import prepare_records, read_records, validate_trim
 
     world, rank = dist.get_world_size(), dist.get_rank()
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_duplications: --trim runs on one rank only")
+    reader = _choose_reader(reader, settings)
     comm = f"cuda:{device_index}" if dist.get_backend() == "nccl" else None
-    index = strand = records = None
+    index = strand = records = source = None
     chunks = [None]
     try:
         if rank == 0:
-            records = [rec for f in files for rec in read_records(f)]
-            pr = prepare_records(records, settings.skip_masked)
-            strand = Strand(", ".join(files), pr.data, pr.map)       # file_names, src/bin/asgart.rs:437
-            trim = validate_trim(settings.trim, len(pr.data))        # prepare_data's checks, :432-463
-            index = Index(strand.data, None, device_index, trim=trim)
-            chunks = [list(pr.chunks)]
+            strand, chunk_list, index, records, source = _read_input(files, settings, device_index, reader, with_sequences)
+            chunks = [chunk_list]
         dist.broadcast_object_list(chunks, src=0)
         if world > 1:
             index = replicate_index(index, dist, device_index)
@@ -229,20 +274,18 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
             return None
         seqs = None
         if with_sequences:
-            from . import Source
-            from .extract import sequences
-
-            with Source.from_records(records, device_index) as src:
-                seqs = sequences(src, post[1], settings.reverse, settings.complement)
+            seqs = _sequences(source, records, device_index, post[1], settings.reverse, settings.complement)
         return to_json_arrays(post[0], post[1], strand, settings, ident, seqs), out_filename(files, settings, prefix)
     finally:
+        if source is not None:
+            source.close()
         if index is not None:
             index.close()
 
 
 def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool, bool]], settings, dist,
                         device_index: int, compute_score: bool = False, prefix: str = "",
-                        with_sequences: bool = False):
+                        with_sequences: bool = False, reader: Optional[str] = None):
     """One run over several orientations of one strand -- what the reference needs one `asgart` invocation per
     orientation and an `asgart-slice` merge for.  orientations: one to four distinct (reverse, complement) pairs in the
     user's order; `settings` supplies everything else (its own two flags are ignored).  Built ONCE: the records read and
@@ -255,12 +298,11 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     orientation], merged JSON text) and None elsewhere: each text is byte-equal to search_duplications with that
     orientation, the merged one to postprocess.merge_results over those files in that order (RunResult::from_files,
     reference src/structs.rs:114-141: strand and settings of the first, every duplication with the flags of its own
-    run).  dist None: one process, one GPU, no collective.  `--trim` needs one rank."""
+    run).  dist None: one process, one GPU, no collective.  `--trim` needs one rank.  reader: as search_duplications."""
     from dataclasses import replace
 
-    from . import Index, Strand, merge_shards, orientation_flags
+    from . import merge_shards, orientation_flags
     from .postprocess import out_filename, to_json_arrays
-    from .prep import prepare_records, read_records, validate_trim
 
     orientations = [(bool(r), bool(c)) for r, c in orientations]
     if not 1 <= len(orientations) <= 4 or len(set(orientations)) != len(orientations):
@@ -269,17 +311,14 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
+    reader = _choose_reader(reader, settings)
     comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
-    index = strand = records = None
+    index = strand = records = source = None
     chunks = [None]
     try:
         if rank == 0:
-            records = [rec for f in files for rec in read_records(f)]
-            pr = prepare_records(records, settings.skip_masked)
-            strand = Strand(", ".join(files), pr.data, pr.map)
-            trim = validate_trim(settings.trim, len(pr.data))
-            index = Index(strand.data, None, device_index, trim=trim)
-            chunks = [list(pr.chunks)]
+            strand, chunk_list, index, records, source = _read_input(files, settings, device_index, reader, with_sequences)
+            chunks = [chunk_list]
         if dist is not None:
             dist.broadcast_object_list(chunks, src=0)
         if world > 1:
@@ -306,11 +345,7 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
             return None
         seqs = None
         if with_sequences:
-            from . import Source
-            from .extract import sequences
-
-            with Source.from_records(records, device_index) as src:
-                seqs = sequences(src, kept, (flags & 1).astype(bool), (flags >> 1 & 1).astype(bool))
+            seqs = _sequences(source, records, device_index, kept, (flags & 1).astype(bool), (flags >> 1 & 1).astype(bool))
         out = []
         lo = 0
         for st, (offs, sds) in zip(sts, posts):
@@ -323,6 +358,8 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
         all_offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
         return out, to_json_arrays(all_offs, kept, strand, sts[0], ident, seqs, flags)
     finally:
+        if source is not None:
+            source.close()
         if index is not None:
             index.close()
 
@@ -345,6 +382,9 @@ def _parse(argv):
     ap.add_argument("--compute-score", action="store_true")
     ap.add_argument("--with-sequences", action="store_true",
                     help="fill left_seq / right_seq as asgart-extract --in-place does (python -m asgart_amd.extract)")
+    ap.add_argument("--host-reader", action="store_true",
+                    help="read and prepare the FASTA files on the host (prep.read_records) instead of on rank 0's GPU; "
+                         "the result is the same")
     ap.add_argument("--prefix", default="")
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
@@ -442,13 +482,14 @@ def rank_main(argv) -> int:
         settings = RunSettings.from_cli(k=args.probe_size, gap=args.max_gap, min_length=args.min_length,
                                         max_cardinality=args.max_cardinality, reverse=args.reverse,
                                         complement=args.complement, skip_masked=args.skip_masked)
+        reader = "host" if args.host_reader else None
         if args.orientations:
             out = search_orientations(args.files, args.orientations, settings, dist, device_index, args.compute_score,
-                                      args.prefix, args.with_sequences)
+                                      args.prefix, args.with_sequences, reader)
             texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])
         else:
             out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix,
-                                      args.with_sequences)
+                                      args.with_sequences, reader)
             texts = None if out is None else [out]
         for text, name in texts or []:
             path = os.path.join(args.out_dir, name)

@@ -407,10 +407,11 @@ def search_orientations(strands_files: Sequence[str], orientations: Sequence[Tup
     and the index built once, ONE fused search over all orientations, one score call over all survivors.
     -> ([(JSON text, output file name) per orientation], merged JSON text): each text is what
     to_json(search_duplications(files, settings with that orientation, device, compute_score)) gives, the merged one
-    what merge_results gives for those files in that order."""
+    what merge_results gives for those files in that order.  Like search_duplications below it reads the files with the
+    host reader: these two are what the drivers' texts are compared with."""
     from .multi import search_orientations as run
 
-    return run(strands_files, orientations, settings, None, device, compute_score)
+    return run(strands_files, orientations, settings, None, device, compute_score, reader="host")
 
 
 def search_duplications(strands_files: Sequence[str], settings: RunSettings, device: int = 0,

@@ -6,12 +6,14 @@ N-runs longer than 5000 (:317-366), concatenation with per-record chunk offsets
 (:375-395) and the final '$' (:430).  prepare_records is the numpy statement of it (host only: what the CPU tests
 and the oracle comparisons use); prepare_records_gpu is the product path: the same step behind the C ABI
 (asgart_prepare_data: normalisation and N-run detection as kernels over the uploaded bytes, the index built from
-the same device buffer).
+the same device buffer).  read_fasta_gpu is the whole of it from the files on (asgart_fasta_read: the FASTA parsing
+too runs on the GPU, over the mapped file bytes); parse_fasta_bytes states the reader's rules in numpy, without a loop
+over lines: what the tests pin against read_records and compare large inputs with.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Iterable, List, Sequence, Tuple
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -62,6 +64,8 @@ class Prepared:
     data: np.ndarray                      # concatenated, normalised, '$'-terminated
     chunks: List[Tuple[int, int]]         # global (start, len)
     map: List[Start]
+    records: Optional[np.ndarray] = None  # read_fasta_gpu: the record table (FASTA_RECORD rows)
+    timings: Optional[dict] = None        # read_fasta_gpu: milliseconds of the library call (asgart_fasta_timings)
 
 
 def prepare_records(records: Sequence[Tuple[str, np.ndarray]], skip_masked: bool = False) -> Prepared:
@@ -150,3 +154,158 @@ def read_records(path: str) -> Iterable[Tuple[str, np.ndarray]]:
                 buf.append(line)
     if name is not None:
         yield name, np.frombuffer(b"".join(buf), dtype=np.uint8)
+
+
+# One row per record, as asgart_fasta_record (include/asgart_hip.h): which file, where its header line lies in it
+# ('>' included, line end excluded), where the record lies in the strand.
+FASTA_RECORD = np.dtype([("file", np.uint64), ("header_offset", np.uint64), ("header_len", np.uint64),
+                         ("start", np.uint64), ("len", np.uint64)])
+
+
+def parse_fasta_bytes(buf, file: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """The bytes of ONE FASTA file -> (record table: FASTA_RECORD rows with `start` counted from this file's first
+    record, raw: the sequence bytes of its records, concatenated).  The rules of read_records, vectorised:
+    lines end at LF only; a CR is dropped iff only CRs lie between it and the next LF or the end of the file; a line
+    whose first byte is '>' is a header and starts a record; everything in front of the first header is ignored."""
+    b = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf
+    n = len(b)
+    if n == 0:
+        return np.zeros(0, dtype=FASTA_RECORD), np.zeros(0, dtype=np.uint8)
+    is_nl, is_cr = b == 10, b == 13
+    line_start = np.empty(n, dtype=bool)
+    line_start[0] = True
+    line_start[1:] = is_nl[:-1]
+    header_start = line_start & (b == ord(">"))
+    starts = np.flatnonzero(line_start)
+    in_header = np.repeat(header_start[starts], np.diff(np.append(starts, n)))     # per byte: the kind of its line
+    seen = np.cumsum(header_start) > 0
+    other = np.flatnonzero(~is_cr)                        # a CR is dropped iff the next byte that is not one is LF / EOF
+    nxt = np.searchsorted(other, np.arange(n))
+    nxt_pos = np.append(other, n)[nxt]
+    ends_line = (nxt_pos == n) | np.append(is_nl, True)[nxt_pos]
+    keep = ~in_header & seen & ~is_nl & ~(is_cr & ends_line)
+    kept_before = np.concatenate(([0], np.cumsum(keep)))
+    hoff = np.flatnonzero(header_start)
+    nl_pos = np.append(np.flatnonzero(is_nl), n)
+    hend = nl_pos[np.searchsorted(nl_pos, hoff)]
+    table = np.zeros(len(hoff), dtype=FASTA_RECORD)
+    table["file"] = file
+    table["header_offset"] = hoff
+    table["header_len"] = hend - hoff
+    table["start"] = kept_before[hoff]
+    table["len"] = np.diff(np.append(kept_before[hoff], kept_before[n]))
+    return table, b[keep]
+
+
+def record_names(bufs: Sequence, table: np.ndarray) -> List[str]:
+    """The ids of the records of a table: the first whitespace-separated token behind the '>' of each header line
+    ("" if there is none), UTF-8, cut out of the files' own bytes (bufs[file])."""
+    names = []
+    for f, o, ln in zip(table["file"].tolist(), table["header_offset"].tolist(), table["header_len"].tolist()):
+        tok = bytes(bufs[f][o + 1:o + ln]).split()
+        names.append(tok[0].decode() if tok else "")
+    return names
+
+
+def parsed_records(bufs: Sequence) -> List[Tuple[str, np.ndarray]]:
+    """parse_fasta_bytes over several files' bytes -> (name, raw sequence) per record: what read_records yields."""
+    out = []
+    for buf in bufs:
+        table, raw = parse_fasta_bytes(buf)
+        s0 = table["start"].astype(np.int64)
+        for name, a, ln in zip(record_names([buf], table), s0.tolist(), table["len"].tolist()):
+            out.append((name, raw[a:a + ln]))
+    return out
+
+
+def _map_file(f):
+    """A path -> a read-only mapping of the file (an empty file: empty bytes); anything else is taken as its bytes."""
+    import mmap
+    import os
+
+    if isinstance(f, (str, os.PathLike)):
+        with open(f, "rb") as fh:
+            if os.fstat(fh.fileno()).st_size == 0:
+                return b""
+            return mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+    return f
+
+
+def read_fasta_gpu(files: Sequence, skip_masked: bool = False, device: int = 0, want_text: bool = False,
+                   want_index: bool = True, want_source: bool = False):
+    """prepare_data from the files on, through the library (asgart_fasta_read): -> (Prepared, Index or None, Source or
+    None).  files: paths (mapped, not read into Python objects) or bytes-like objects holding a file's bytes.  The bytes
+    are copied to the GPU once; the parsing, the raw strand (the Source), the normalised strand, the chunks and the suffix
+    sort happen there.  Prepared.data is the strand only with want_text; Prepared.map carries the names, cut out of the
+    mapped bytes with the record table (Prepared.records).  Raises AsgartError (code -1: no record in any file)."""
+    import ctypes as C
+
+    from . import Index, Source, _check, _ptr, load_library
+
+    L = load_library()
+    maps = [_map_file(f) for f in files]
+    views = [np.frombuffer(m, dtype=np.uint8) if not isinstance(m, np.ndarray) else np.ascontiguousarray(m, dtype=np.uint8)
+             for m in maps]
+    ptrs = (C.c_void_p * max(len(views), 1))(*[v.ctypes.data if len(v) else None for v in views])
+    lens = np.array([len(v) for v in views], dtype=np.uint64)
+    h = C.c_void_p()
+    idx = src = None
+    try:
+        _check(L.asgart_fasta_read(ptrs, _ptr(lens), len(views), 1 if skip_masked else 0, device, C.byref(h)))
+        n_rec, n_chunks, n_text = C.c_int64(), C.c_int64(), C.c_uint64()
+        _check(L.asgart_fasta_counts(h, C.byref(n_rec), C.byref(n_chunks), C.byref(n_text)))
+        table = np.zeros(n_rec.value, dtype=FASTA_RECORD)
+        chunks = np.zeros((n_chunks.value, 2), dtype=np.uint64)
+        text = np.empty(n_text.value, dtype=np.uint8) if want_text else None
+        _check(L.asgart_fasta_copy(h, _ptr(table), _ptr(chunks), _ptr(text)))
+        ms = (C.c_double * 4)()
+        _check(L.asgart_fasta_timings(h, ms))
+        starts = [Start(name, int(a), int(ln)) for name, a, ln in
+                  zip(record_names(views, table), table["start"].tolist(), table["len"].tolist())]
+        pr = Prepared(text, [(int(a), int(b)) for a, b in chunks], starts, table,
+                      dict(zip(("total", "stage", "h2d", "kernels"), ms)))
+        if want_index:
+            ih = C.c_void_p()
+            _check(L.asgart_fasta_index(h, C.byref(ih)))
+            idx = Index.__new__(Index)
+            idx.text, idx.n, idx.trim, idx._h = text, int(n_text.value), None, ih
+        if want_source:
+            src = Source()
+            _check(L.asgart_fasta_source(h, C.byref(src._h)))
+            src.n = int(n_text.value) - 1
+        return pr, idx, src
+    except BaseException:
+        for o in (idx, src):
+            if o is not None:
+                o.close()
+        raise
+    finally:
+        if h.value:
+            L.asgart_fasta_free(h)
+        del views
+        for m in maps:
+            if hasattr(m, "close") and not isinstance(m, (bytes, bytearray, memoryview, np.ndarray)):
+                try:
+                    m.close()
+                except BufferError:
+                    pass
+
+
+def fasta_read_text(h, lo: int, hi: int) -> np.ndarray:
+    """Bytes [lo, hi) of the normalised strand of an asgart_fasta handle (tests of very large inputs)."""
+    from . import _check, _ptr, load_library
+
+    out = np.empty(hi - lo, dtype=np.uint8)
+    _check(load_library().asgart_fasta_read_text(h, lo, hi, _ptr(out)))
+    return out
+
+
+def fasta_geometry() -> Tuple[int, int, int]:
+    """(file bytes per workgroup, file bytes per staging piece, bytes per output store) of the library's FASTA reader."""
+    import ctypes as C
+
+    from . import load_library
+
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    load_library().asgart_fasta_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)

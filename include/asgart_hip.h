@@ -426,6 +426,53 @@ void asgart_source_destroy(asgart_source *src);
 int32_t asgart_extract_sequences(asgart_source *src, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
                                  int64_t first, uint8_t *out, uint64_t out_cap, uint64_t *seq_ends, int64_t *n_done);
 
+/* ---- FASTA files read on the GPU ---------------------------------------------------------------------------
+ * Replace the FASTA reader in front of prepare_data and prepare_data itself (reference src/bin/asgart.rs:273-430: bio's
+ * fasta::Reader and the per-record loop at :278-313, normalisation :289-301, find_chunks_to_process :317-366,
+ * concatenation :375-395, '$' :430) and the reader of asgart-extract (src/bin/asgart-extract.rs:17-29, :110-117).
+ * files[i] / file_lens[i] are the bytes of FASTA file i as they are on disk (for instance a read-only mapping); they are
+ * copied to `device` through pinned pieces and parsed there:
+ *   - lines end at '\n'; a '\r' is dropped iff only '\r's lie between it and the next '\n' or the end of the file (so
+ *     "\r\n" ends a line, a '\r' with another byte behind it on its line is sequence and normalises to N);
+ *   - a line whose first byte is '>' starts a record; '>' elsewhere is sequence; what precedes a file's first header
+ *     line is ignored; blank lines add nothing; a last line without '\n' counts; a record may be empty;
+ *   - the records of all files in the order given are one strand; N-runs are measured in the record, not in the lines.
+ * The result holds, on the device, the raw strand (every record's bytes as they are: what asgart_source holds) and the
+ * normalised strand with its '$' (Strand.data); on the host the record table and the chunks.  Names are the host's:
+ * record r's header line is file_lens-checked bytes [header_offset, header_offset + header_len) of file `file`, '>'
+ * included, line end excluded (a trailing '\r' may be part of it: the id is the first whitespace-separated token).
+ * Errors: NULL / no files and no record in any file (ASGART_E_ARG, before the device is looked at), no usable device
+ * (ASGART_E_HIP), more than 2^24 records (ASGART_E_CAP, as asgart_prepare_data).  No device memory stays behind. */
+typedef struct asgart_fasta asgart_fasta;
+typedef struct asgart_fasta_record {
+    uint64_t file;           /* index into files[]                                   */
+    uint64_t header_offset;  /* of the '>' in that file                              */
+    uint64_t header_len;     /* bytes of the header line, without its '\n'           */
+    uint64_t start;          /* Start.position: first base in the strand (:375-395)  */
+    uint64_t len;            /* Start.length; may be 0                               */
+} asgart_fasta_record;
+int32_t asgart_fasta_read(const uint8_t *const *files, const uint64_t *file_lens, int64_t n_files, int32_t skip_masked,
+                          int32_t device, asgart_fasta **out);
+/* *n_text: bytes of the normalised strand, '$' included.  Any of the three may be NULL. */
+int32_t asgart_fasta_counts(const asgart_fasta *f, int64_t *n_records, int64_t *n_chunks, uint64_t *n_text);
+/* records[n_records], chunks[2 * n_chunks] ((start, len) pairs, record order: what asgart_search_duplications takes),
+ * text[n_text]; each nullable.  asgart_fasta_read_text copies bytes [lo, hi) of the normalised strand only. */
+int32_t asgart_fasta_copy(const asgart_fasta *f, asgart_fasta_record *records, uint64_t *chunks, uint8_t *text);
+int32_t asgart_fasta_read_text(const asgart_fasta *f, uint64_t lo, uint64_t hi, uint8_t *out);
+/* An index over the normalised strand (copied device to device), its suffixes sorted on the GPU: what
+ * asgart_index_create builds from Strand.data (src/bin/asgart.rs:141-155), without the text visiting the host. */
+int32_t asgart_fasta_index(asgart_fasta *f, asgart_index **out);
+/* The raw strand as a source for asgart_extract_sequences, without another upload: the source takes the buffer over,
+ * so this succeeds once per result (then ASGART_E_ARG); the source outlives asgart_fasta_free. */
+int32_t asgart_fasta_source(asgart_fasta *f, asgart_source **out);
+void asgart_fasta_free(asgart_fasta *f);
+/* Milliseconds of the asgart_fasta_read call behind f: [0] the whole call, [1] host copies into the pinned pieces,
+ * [2] host -> device copies and [3] kernels (sums over the pieces, HIP events; [2] and [3] overlap each other and [1]). */
+int32_t asgart_fasta_timings(const asgart_fasta *f, double *ms4);
+/* Sizes the reader works in, for tests that place line ends on its seams: file bytes per workgroup, file bytes per
+ * staging piece, bytes per output store. */
+void asgart_fasta_geometry(uint64_t *tile_bytes, uint64_t *piece_bytes, uint64_t *vector_bytes);
+
 /* ---- finer-grained entry points mirroring the reference's inner API;
  *      used by the parity tests ------------------------------------------ */
 

@@ -1,11 +1,12 @@
 """One run over several orientations (multi.search_orientations) against one multi.search_duplications run per
 orientation -- the way to the same files without it -- on a synth.config_genome input, one GPU, one rank.
 
-    python tools/orientations_bench.py [cfg4] [direct,RC] [out.json]
+    python tools/orientations_bench.py [cfg4] [direct,RC] [out.json] [device|host]
 
 Both ways start from the same FASTA files (written to a temporary directory first) and end with the JSON texts, with and
-without --compute-score.  Wall time of each way, split into prepare (FASTA reader + prepare_records), index
-(Index.__init__: upload, suffix sort), search, post-process and score by timing those calls from outside; `other` is the
+without --compute-score.  The last argument chooses the drivers' reader (default: theirs, the device reader).  Wall time
+of each way, split into prepare (host reader: read_records + prepare_records; device reader: prep.read_fasta_gpu, which
+ends with the index built, so `index` is then part of `prepare`), index (Index.__init__: upload, suffix sort), search, post-process and score by timing those calls from outside; `other` is the
 rest (JSON writer, gathers).  The texts of the two ways are compared byte for byte.  Prints one JSON line and writes it
 to out.json (default profiles/orientations_<cfg>.json).
 """
@@ -23,7 +24,7 @@ import asgart_amd  # noqa: E402
 from asgart_amd import multi, postprocess, prep, synth  # noqa: E402
 
 CONFIGS = {"cfg4": (4, 1.0), "cfg3": (3, 1.0), "cfg2": (2, 1.0), "tiny": (2, 0.05)}
-PHASES = {"prepare": [(prep, "read_records"), (prep, "prepare_records")],
+PHASES = {"prepare": [(prep, "read_records"), (prep, "prepare_records"), (prep, "read_fasta_gpu")],
           "index": [(asgart_amd.Index, "__init__")],
           "search": [(asgart_amd.Index, "search_duplications_passes")],
           "post_process": [(asgart_amd.Index, "post_process")],
@@ -77,6 +78,7 @@ def main():
     name = sys.argv[1] if len(sys.argv) > 1 else "cfg4"
     toks = sys.argv[2] if len(sys.argv) > 2 else "direct,RC"
     out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", f"orientations_{name}.json")
+    reader = sys.argv[4] if len(sys.argv) > 4 else None
     cfg, scale = CONFIGS[name]
     orientations = postprocess.parse_orientations(toks)
     base = asgart_amd.RunSettings.from_cli()
@@ -84,7 +86,7 @@ def main():
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29517")
     dist.init_process_group("gloo", rank=0, world_size=1)
-    res = {"workload": name, "orientations": toks.split(","), "bases": int(sum(len(s) for _, s in recs)), "runs": []}
+    res = {"workload": name, "reader": reader or "device", "orientations": toks.split(","), "bases": int(sum(len(s) for _, s in recs)), "runs": []}
     ok = True
     try:
         with tempfile.TemporaryDirectory() as tmp:
@@ -95,16 +97,18 @@ def main():
             del recs
             files = [path]
             # warm-up: code objects, allocator pools, the process group
-            multi.search_duplications(files, base, dist, 0, compute_score=True)
+            multi.search_duplications(files, base, dist, 0, compute_score=True, reader=reader)
             for score in (False, True):
                 singles, single_t = [], []
                 for r, c in orientations:
                     st = replace(base, reverse=r, complement=c)
-                    (text, _), t = timed_run(lambda: multi.search_duplications(files, st, dist, 0, compute_score=score))
+                    (text, _), t = timed_run(lambda: multi.search_duplications(files, st, dist, 0, compute_score=score,
+                                                                                        reader=reader))
                     singles.append(text)
                     single_t.append(t)
                 (per, merged), one_t = timed_run(
-                    lambda: multi.search_orientations(files, orientations, base, dist, 0, compute_score=score))
+                    lambda: multi.search_orientations(files, orientations, base, dist, 0, compute_score=score,
+                                                      reader=reader))
                 same = [text for text, _ in per] == singles
                 ok = ok and same
                 total = {k: round(sum(t[k] for t in single_t), 3) for k in single_t[0]}
