@@ -171,6 +171,22 @@ struct Workspace {
 }  // namespace asgart
 
 namespace asgart {
+// The events of a call context (SearchCtx::ev), each recorded when the stage it names has been queued; the tiers and the
+// runs over ranges have tier_ev and runs_ev.
+enum CtxEvent {
+    EV_SEARCH,        // the probe search begins
+    EV_PROBE_COUNT,   // ... its first kernel, the probe count, is through
+    EV_SEARCHED,      // ... and all of it
+    EV_SCANNED,       // scans + segmentation
+    EV_FILL,          // the CSR fill begins (fill stream)
+    EV_HIT_ROWS,      // ... the hit rows are filled
+    EV_BARREN,        // barren by position begins: segments of up to 1 024 hits
+    EV_BARREN_SMALL,  // ... those are through, segments of up to 16 384 hits
+    EV_BARREN_BIG,    // ... and those
+    EV_TIERS,         // the extension tiers may start: everything they read is there
+    EV_EXTENDED,      // the extension is over
+    EV_COUNT
+};
 // Everything one search call mutates.  The index owns two of them so that two passes (say the
 // direct and the -RC run, reference src/bin/asgart.rs runs them as separate invocations) can be
 // in flight at once from two host threads; text, suffix array and keys are shared read-only.
@@ -181,7 +197,7 @@ struct SearchCtx {
     int n_tier_st = 0;
     hipStream_t fill_stream = nullptr;  // where the CSR fill runs: beside the placement walk on the last tier stream with 6
                                         // queues or more, else on the main stream (create_ctx_streams)
-    hipEvent_t ev[17] = {};  // (5, 6, 8, 9, 10 and 12 are no longer recorded: the tiers have tier_ev)
+    hipEvent_t ev[EV_COUNT] = {};
     hipEvent_t tier_ev[7] = {};  // tier t's launch (its early re-run included) is done: tier_ev[t - 1]
     hipEvent_t runs_ev = nullptr;  // the runs over ranges are done (main stream)
     // what the tier-to-stream plan of the next call with the same call_sig starts from (tier_plan): per tier the

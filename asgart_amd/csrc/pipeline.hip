@@ -15,6 +15,7 @@
 #include <chrono>
 #include <string>
 #include <thread>
+#include <utility>
 
 namespace asgart {
 
@@ -63,32 +64,97 @@ namespace asgart {
 #define PROF_TIER(tag, stream, n)
 #endif
 
-// default launch order / grid sizes of the extension tiers (see the launch site)
-constexpr uint64_t kGrid1 = 256ull * 8ull, kGrid2 = 256ull * 3ull;
-// Arm slots of the arm-resident shapes (S arms per thread x NT threads; 64-bit positions hold fewer).
-// tier 2, the one-wave shape: 8 x 64 = 512 live arms per wave, probes with up to 512 hits
-template <class SlotT> constexpr int kWaveArmsLayers = sizeof(SlotT) == 4 ? 8 : 5;
-// tiers 4 and 5: 4 arms per thread x 256 / 512 threads, cold fields in LDS
-template <class SlotT> constexpr int kMidArmsLayers = sizeof(SlotT) == 4 ? 4 : 2;
-constexpr int kWaveArmsHits = 512;
-constexpr uint64_t kGrid2Arms = 256ull * 8ull;
-// tier 6 on the one-barrier kernel (extend_fast_dev.hpp): 5 x 1024 arm slots (64-bit positions: 4 x 1024, a smaller table)
-template <class SlotT> constexpr int kFastHeavyLayers = sizeof(SlotT) == 4 ? 5 : 4;
-template <class SlotT> constexpr int kFastLongRows = sizeof(SlotT) == 4 ? 2048 : 1024;
-// tier 3 and the runs over ranges on the kernel with specialised waves (extend_k8_dev.hpp): two of the sixteen waves hold
-// no arms, so the shape has S x 896 slots: 5 x 896 (64-bit positions: 4 x 896)
-template <class SlotT> constexpr int kK8LongLayers = sizeof(SlotT) == 4 ? 5 : 4;
-constexpr uint32_t kK8LongSlots = 896;
-// (A half shape -- 512 threads, 5 x 384 slots, 75 KB of LDS, two workgroups per compute unit -- was measured in round 6:
-// 37 % less compute-unit time per hit-probe, 25 % more wall time, and the 208 segments of a GRCh38-sized step whose arms
-// do not fit it fall to tier 6's kernel, one of them for 145 ms: the step doubled.  DESIGN_HISTORY.md.)
-constexpr int kArmCapSmall = 256;   // live arms per wave in LDS, common case
+// ---- the extension tiers ---------------------------------------------------------------------------------------------------
+// What a tier is, stated once.  Placement (place), every launch (launch_kernel), the statistics (finish_tiers) and the
+// estimates of the tier plan (plan_estimates) read this table and nothing else; which stream a tier runs on is tier_plan's
+// business.
+enum class TierKernel {
+    none,          // the tier stays empty
+    wave,          // extend_kernel: one wave per segment, arms in registers / LDS arrays
+    fast,          // extend_fast_kernel: arm-resident, one barrier per step
+    k8,            // extend_k8_kernel: arm-resident, specialised waves (two of the sixteen hold no arms)
+    heavy_lds,     // extend_heavy_kernel MODE 0: arms in LDS arrays (launch_shape takes MODE from the order of these three)
+    heavy_hybrid,  // ... MODE 1: hot fields in LDS, (rs, le) in HBM scratch; 16-bit gap / pend
+    heavy_hbm      // ... MODE 2: arms in HBM scratch, a slice of heavy_cap arms per workgroup
+};
+static_assert((int)TierKernel::heavy_hybrid == (int)TierKernel::heavy_lds + 1 && (int)TierKernel::heavy_hbm == (int)TierKernel::heavy_lds + 2,
+              "extend_heavy_kernel's MODE is the distance from heavy_lds");
+struct TierShape {
+    TierKernel kernel;
+    int threads;              // per workgroup
+    int layers, slots;        // arm layers (arms per thread) x arm-holding slots per layer: the arms it holds
+    int hits, rows;           // hits staged per probe; table rows (arm-resident kernels)
+    int wg_per_cu;            // workgroups of this shape a compute unit holds (LDS / registers)
+    int grid;                 // default grid
+    int64_t Options::*widen;  // the option that lets it accept segments whose arm BOUND is that percentage of cap() (null: none)
+    bool early;               // what it gives up on is re-run as soon as it has ended (run_tiers)
+    double profile_ms;        // its duration before a call has measurements (plan_estimates)
+    constexpr uint32_t cap() const { return (uint32_t)(layers * slots); }
+};
+// shape[t][0]: tier t of the arm-resident set, shape[t][1]: of the LDS-array set, which takes over with
+// max_cardinality > 1024, option arms_kernel = 0 (tests) or a text of 2^42 bases (the arm-resident kernels pack a
+// position into 42 bits of a table entry).  shape[0]: the runs over ranges of the cut segments.
+template <class SlotT>
+struct TierTable {
+    static constexpr bool k32 = sizeof(SlotT) == 4;  // 64-bit positions: fewer arms per thread, smaller tables
+    static constexpr int kLong = k32 ? 2048 : 1024;  // table rows of the long shapes
+    // (an empty entry is never placed into and never launched: launch_kernel refuses)
+    static constexpr TierShape kNone = {TierKernel::none, 0, 0, 0, 0, 0, 1, 0, nullptr, false, 0.0};
+    static constexpr TierShape kWave = {TierKernel::wave, 64, 1, 256, kHitBatch, 0, 11, 256 * 8, nullptr, false, 4.6};
+    static constexpr TierShape kHbm = {TierKernel::heavy_hbm, kHeavyThreads, 1, 1, kHitBatch, 0, 1, 256, nullptr, false, 33.0};
+    static constexpr TierShape kK8 = {TierKernel::k8, 1024, k32 ? 5 : 4, 896, kHitBatch, kLong, 1, 256, &Options::cap3_pct, true, 67.0};
+    // profile_ms: the GRCh38-shaped profile (profiles/r06_cfg4_tier_cu_seconds.json: the longest segments of tiers 2..6
+    // -- tier 3's with the runs, which that profile counted with it --, tier 1's work over its compute units; tier 7 and
+    // the runs as tiers 6 and 3)
+    // {kernel, threads, layers, slots, hits, rows, wg_per_cu, grid, widen, early, profile_ms}
+    static constexpr TierShape shape[kTiers + 1][2] = {
+        // the runs over ranges: tier 3's kernel, one workgroup per run (no default grid)
+        {{kK8.kernel, kK8.threads, kK8.layers, kK8.slots, kK8.hits, kK8.rows, 1, 0, nullptr, false, 67.0}, kNone},
+        // 1: the common case; placement never puts a segment busier than kTier1MaxSum on a single wave
+        {kWave, kWave},
+        // 2: one wave, probes with up to 512 hits | the block-cooperative kernel, 256 threads per segment
+        {{TierKernel::fast, 64, k32 ? 8 : 5, 64, 512, 256, 8, 256 * 8, nullptr, false, 51.8},
+         {TierKernel::heavy_lds, kMidThreads, 1, 768, kHitBatch, 0, 3, 256 * 3, nullptr, false, 51.8}},
+        // 3: the LONG DENSE segments.  It accepts what tier 6 would accept by the bound (a long segment is no less safe
+        // there), but never more than cap3_pct of its own capacity: with 64-bit positions it holds fewer arms than tier 6,
+        // and what it gives up on is re-run from the start.  (The bound of a tandem array is three to four times what it
+        // really holds.)
+        // (A half shape -- 512 threads, 5 x 384 slots, 75 KB of LDS, two workgroups per compute unit -- was measured in
+        // round 6: 37 % less compute-unit time per hit-probe, 25 % more wall time, and the 208 segments of a GRCh38-sized
+        // step whose arms do not fit it fall to tier 6's kernel, one of them for 145 ms: the step doubled.
+        // DESIGN_HISTORY.md.)
+        {kK8, kNone},
+        // 4: cold fields in LDS, probes with up to 512 hits | 32-bit positions: 3072 * 40 B + hits + scratch = 128 KiB of
+        // LDS, 64-bit: 2048 * 60 B + hits + scratch = 132 KiB
+        {{TierKernel::fast, 256, k32 ? 4 : 2, 256, 512, 512, 4, 256 * 4, &Options::cap45_pct, false, 35.5},
+         {TierKernel::heavy_lds, kHeavyThreads, 1, k32 ? 2432 : 1664, kHitBatch, 0, 1, 256, nullptr, false, 35.5}},
+        // 5
+        {{TierKernel::fast, 512, k32 ? 4 : 2, 512, kHitBatch, 1024, 2, 256 * 2, &Options::cap45_pct, false, 53.0}, kNone},
+        // 6: the long sparse segments.  The window bound is pessimistic for tandem arrays (hits extend arms there) and the
+        // HBM tier is several times slower per probe: tier 6 also takes segments whose bound exceeds its capacity, by up
+        // to 40 % (a real overflow falls through the cascade).  With 64-bit positions the HBM tier is an order of
+        // magnitude slower per probe and the bound three to four times what a segment really holds -- at cfg5 every
+        // segment that went to tier 7 by its bound peaked below 4 096 arms: cap6w_pct.  | by 7/5, in place()
+        {{TierKernel::fast, 1024, k32 ? 5 : 4, 1024, kHitBatch, kLong, 1, 256, k32 ? &Options::cap6_pct : &Options::cap6w_pct, true, 33.0},
+         {TierKernel::heavy_hybrid, kHeavyThreads, 1, k32 ? 4608 : 3072, kHitBatch, 0, 1, 256, nullptr, true, 33.0}},
+        // 7: whatever is left (place() sizes its slices and its grid, at most this one, by the bound on the live arms of
+        // ANY segment)
+        {kHbm, kHbm},
+    };
+    static constexpr int kRunsTier = 3;  // the tier whose kernel the runs run and whose statistics they are counted with
+};
+template <class SlotT>
+constexpr bool tier_caps(int set, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t c4, uint32_t c5, uint32_t c6) {
+    const uint32_t want[kTiers] = {0, c1, c2, c3, c4, c5, c6};
+    for (int t = 1; t < kTiers; ++t)
+        if (TierTable<SlotT>::shape[t][set].cap() != want[t]) return false;
+    return true;
+}
+static_assert(tier_caps<uint32_t>(0, 256, 512, 4480, 1024, 2048, 5120) && tier_caps<uint64_t>(0, 256, 320, 3584, 512, 1024, 4096),
+              "capacities of the arm-resident set");
+static_assert(tier_caps<uint32_t>(1, 256, 768, 0, 2432, 0, 4608) && tier_caps<uint64_t>(1, 256, 768, 0, 1664, 0, 3072),
+              "capacities of the LDS-array set");
 constexpr uint32_t kTier1MaxSum = 20000;  // placement: busier segments never run on a single wave
-constexpr int kArmCapMid = 768;     // second tier: block-cooperative kernel, 256 threads per segment
-constexpr int kArmCapHybrid32 = 4608;   // tier 4: hot fields in LDS, (rs, le) in HBM scratch
-constexpr int kArmCapHybrid64 = 3072;
-constexpr int kArmCapBig32 = 2432;  // heavy tier, 32-bit positions: 3072*40 B + hits + scratch = 128 KiB
-constexpr int kArmCapBig64 = 1664;  // heavy tier, 64-bit positions: 2048*60 B + hits + scratch = 132 KiB
 
 static inline unsigned grid_for(uint64_t n, unsigned block = 256) {
     return (unsigned)((n + block - 1) / block);
@@ -283,7 +349,8 @@ struct SearchCall {
     const Options opt;           // options cannot change while this call holds a context
     static constexpr size_t kCtrBytes = (size_t)CT_COUNT * 8;
     static constexpr size_t kSplitMirror = 512 << 10;  // (option split: host copy of Workspace::split_buf)
-    static constexpr int caph = sizeof(SlotT) == 4 ? kArmCapHybrid32 : kArmCapHybrid64;
+    using Tiers = TierTable<SlotT>;
+    static constexpr int caph = (int)Tiers::shape[6][1].cap();  // (its HBM scratch is reserved whichever set runs)
     // ---- set up once (setup) --------------------------------------------------------------------------------------------
     bool nothing_to_do = true;
     size_t ch_bytes = 0;
@@ -326,8 +393,7 @@ struct SearchCall {
     size_t region = 0;
     char *scratch6 = nullptr, *scratch7 = nullptr;
     // ---- the tiers (run_tiers .. finish_tiers) ---------------------------------------------------------------------------
-    ExtParams<SlotT> ep;
-    char *scratch_override = nullptr;  // HBM slices of an early cascade launch
+    ExtParams<SlotT> base{};  // what every launch of this attempt shares (run_tiers); launch_kernel adds the work list
     hipStream_t tier_stream[kTiers + 1] = {};
     bool tier_ran[kTiers + 1] = {};  // launched by run_tiers (its event in cx.tier_ev is this call's)
     uint64_t early_n[kTiers + 1] = {};
@@ -345,7 +411,14 @@ struct SearchCall {
 
     uint32_t pass_of_probe(uint32_t g) const { return std::min<uint32_t>(g / K, (uint32_t)n_passes - 1u); }
     uint32_t pass_offset(uint32_t g) const { return lo_lim + (g - pass_of_probe(g) * K); }  // from the start of its pass
+    const TierShape &shape(int t) const { return Tiers::shape[t][arms_kernel ? 0 : 1]; }  // (t = 0: the runs over ranges)
     bool tier_enabled(int t) const { return t >= 1 && t <= kTiers && tier_cap[t] != 0; }
+    // where what tier src gave up on is run again: the next tier that is in use and holds more arms
+    int next_holding_more(int src) const {
+        int dst = src + 1;
+        while (dst < kTiers && (!tier_enabled(dst) || tier_cap[dst] <= tier_cap[src])) ++dst;
+        return dst;
+    }
     double since_launch() const {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_launch).count();
     }
@@ -529,21 +602,21 @@ struct SearchCall {
 
         if (opt.test_stall_s > 0) stall_kernel<<<1, 64, 0, s>>>((unsigned long long)opt.test_stall_s * 100000000ull);
         // ---- K1: probe search + filtered counts -----------------------------------
-        HIP_TRY(hipEventRecord(cx.ev[0], s));
+        HIP_TRY(hipEventRecord(cx.ev[EV_SEARCH], s));
         probe_count_kernel<SlotT, false><<<rp.n_tiles((uint32_t)kProbeBlock), kProbeThreads, 0, s>>>(
             ix, rp, p_lo, p_raw, p_filt, big_list, rank_list, d_ctr);
-        HIP_TRY(hipEventRecord(cx.ev[11], s));
+        HIP_TRY(hipEventRecord(cx.ev[EV_PROBE_COUNT], s));
         collect_pending_kernel<<<std::min<uint32_t>(rp.n_tiles((uint32_t)kCollectTile), 256u * 8u), kCollectBlock, 0, s>>>(
             rp, p_filt, big_list, rank_list, d_ctr);
         big_count_kernel<SlotT, false><<<2048, 256, 0, s>>>(ix, rp, p_lo, p_raw, p_filt, big_list, d_ctr);
         // (after big_count_kernel: what it appends to big_list is for the fill only)
         if (ix.sap)
             rank_count_kernel<SlotT, false><<<2048, 256, 0, s>>>(ix, rp, p_lo, p_raw, p_filt, rank_list, big_list, d_ctr);
-        HIP_TRY(hipEventRecord(cx.ev[1], s));
+        HIP_TRY(hipEventRecord(cx.ev[EV_SEARCHED], s));
         // ---- K2: scans + segmentation ----------------------------------------------
         HIP_TRY(hipMemsetAsync(scan_desc, 0, (size_t)n_blk * 16, s));
         scan_segments_kernel<<<std::min<uint32_t>(n_blk, 256u * 2u), kScanBlock, 0, s>>>(rp, p_filt, scan_desc, n_blk, row_off, seg_list, d_ctr);
-        HIP_TRY(hipEventRecord(cx.ev[2], s));
+        HIP_TRY(hipEventRecord(cx.ev[EV_SCANNED], s));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr, kCtrBytes, hipMemcpyDeviceToHost, s));
         RC_TRY(wd_sync(idx, cx, s, "the probe search and the scans"));
@@ -561,16 +634,16 @@ struct SearchCall {
         // ---- K3: CSR fill -----------------------------------------------------------
         // On a stream of its own (idle until the tiers are launched; the main stream has just been drained): the placement
         // walk, which reads the per-probe counts only, runs beside it -- the fill is bound by the suffix-array intervals it
-        // gathers, the walk by its round trips.  Whoever needs the hit rows waits for ev[3].
+        // gathers, the walk by its round trips.  Whoever needs the hit rows waits for ev[EV_HIT_ROWS].
         RC_TRY(w.hits.reserve((size_t)(total_hits + 64) * sizeof(SlotT)));
         hits = w.hits.as<SlotT>();
         hipStream_t sf = cx.fill_stream;
-        HIP_TRY(hipEventRecord(cx.ev[16], sf));
+        HIP_TRY(hipEventRecord(cx.ev[EV_FILL], sf));
         fill_small_kernel<SlotT><<<rp.n_tiles(256u), 256, 0, sf>>>(ix, rp, p_lo, p_raw, p_filt, row_off, hits);
         if (h_ctr[CT_BIG])
             fill_big_kernel<SlotT><<<2048, 256, 0, sf>>>(ix, rp, p_lo, p_raw, p_filt, row_off, hits,
                                                          big_list, d_ctr);
-        HIP_TRY(hipEventRecord(cx.ev[3], sf));
+        HIP_TRY(hipEventRecord(cx.ev[EV_HIT_ROWS], sf));
         HIP_TRY(hipGetLastError());
 
         return 0;
@@ -608,53 +681,19 @@ struct SearchCall {
         RC_TRY(w.seg_vals.reserve((size_t)n_seg * 4 * 2));
         uint32_t *kbuf = w.seg_keys.as<uint32_t>(), *vbuf = w.seg_vals.as<uint32_t>();
         HIP_TRY(hipMemsetAsync(d_ctr + CT_N1, 0, (size_t)(CT_COUNT - CT_N1) * 8, s));
-        // ---- the tiers ------------------------------------------------------------------------
-        //  1  one wave per segment, arms in registers / LDS arrays (extend_kernel)                 <= 256 arms
-        //  2  arm-resident, one wave, 8 per CU (K6 8x64)                                           <= 512
-        //  3  arm-resident, specialised waves, 1024 threads (K8 5x896): the LONG DENSE segments    <= 4480 * 1.6 (by the bound)
-        //  4  arm-resident, 256 threads, 4 workgroups per CU (K6 4x256)                            <= 1024
-        //  5  arm-resident, 512 threads, 2 per CU (K6 4x512)                                       <= 2048
-        //  6  arm-resident, 1024 threads, 1 per CU (K6 5x1024): the long sparse segments           <= 5120 * 1.4 (by the bound)
-        //  7  arms in HBM scratch (extend_heavy_kernel MODE 2)                                     any
-        // (64-bit positions: 5x64 / 4x896 / 2x256 / 2x512 / 4x1024.)
-        // Streams: the short chip-wide kernels on the call's high-priority main stream; tiers 1..6 on six
-        // low-priority streams of their own, tier 7 behind tier 2.
-        // With max_cardinality > 1024 (or ASGART_ARMS_KERNEL=0, tests) the LDS-array kernels (extend_heavy_kernel) take
-        // tiers 2, 4 and 6 (768 / 2432 / 4608 * 1.4 arms) and tiers 3 and 5 stay empty; the small
-        // shapes 2 and 4 stage 512 hits per probe and are skipped when max_cardinality > 512.
-        // (the arm-resident kernels pack a position into 42 bits of a table entry)
+        // ---- the tiers (TierTable): what each accepts ---------------------------------------------
         arms_kernel = rp.C <= (uint64_t)kHitBatch && opt.arms_kernel != 0 && (uint64_t)idx->n < (1ull << 42);
-        const bool arms_small = arms_kernel && rp.C <= (uint64_t)kWaveArmsHits;
-        for (int t = 0; t <= kTiers; ++t) tier_cap[t] = 0;
-        tier_cap[1] = kArmCapSmall;
-        tier_cap[kTiers] = 0xFFFFFFFFu;  // (tier 7 takes whatever is left)
-        if (arms_kernel) {
-            if (arms_small) {
-                tier_cap[2] = (uint32_t)kWaveArmsLayers<SlotT> * 64u;
-                tier_cap[4] = (uint32_t)((uint64_t)(kMidArmsLayers<SlotT> * 256) * (uint64_t)opt.cap45_pct / 100u);
-            }
-            tier_cap[3] = (uint32_t)kK8LongLayers<SlotT> * kK8LongSlots;
-            tier_cap[5] = (uint32_t)((uint64_t)(kMidArmsLayers<SlotT> * 512) * (uint64_t)opt.cap45_pct / 100u);
-            // the window bound is pessimistic for tandem arrays (hits extend arms there) and the HBM
-            // tier is several times slower per probe: tier 6 also takes segments whose bound exceeds
-            // its capacity by up to 40 % (a real overflow falls through the cascade)
-            // (64-bit positions on the one-barrier kernel: the HBM tier is an order of magnitude slower per probe and the
-            // bound three to four times what a segment really holds -- at cfg5 every segment that went to tier 7 by its
-            // bound peaked below 4 096 arms: tier 6 accepts up to cap6w_pct of its capacity)
-            const uint64_t pct6 = sizeof(SlotT) == 8 ? (uint64_t)opt.cap6w_pct : (uint64_t)opt.cap6_pct;
-            tier_cap[6] = (uint32_t)((uint64_t)(kFastHeavyLayers<SlotT> * 1024) * pct6 / 100u);
-            // tier 3 accepts what tier 6 would accept by the bound (a long segment is no less safe there), but
-            // never more than the same allowance over its own capacity (with 64-bit positions it holds fewer
-            // arms than tier 6, and what it gives up on is re-run from the start)
-            // (the bound of a tandem array is three to four times what it really holds: the one-barrier kernel, a fifth
-            // faster per probe on such segments, takes them up to cap3_pct of its capacity)
-            tier_cap[3] = std::min<uint32_t>(std::max(tier_cap[3], tier_cap[6]),
-                                             (uint32_t)((uint64_t)tier_cap[3] * (uint64_t)opt.cap3_pct / 100u));
-        } else {
-            tier_cap[2] = kArmCapMid;
-            tier_cap[4] = sizeof(SlotT) == 4 ? kArmCapBig32 : kArmCapBig64;
-            tier_cap[6] = (rp.G >= 0xFFF0u || rp.C >= 0xFFF0u) ? 0u : (uint32_t)caph * 7 / 5;  // 16-bit gap/pend
+        for (int t = 1; t <= kTiers; ++t) {
+            const TierShape &sh = shape(t);
+            // (an arm-resident shape stages the whole hit row of a probe: it is skipped when max_cardinality exceeds that)
+            const bool usable = sh.kernel != TierKernel::none && !(arms_kernel && rp.C > (uint64_t)sh.hits);
+            tier_cap[t] = usable ? (uint32_t)((uint64_t)sh.cap() * (uint64_t)(sh.widen ? opt.*sh.widen : 100) / 100u) : 0u;
         }
+        tier_cap[kTiers] = 0xFFFFFFFFu;  // (tier 7 takes whatever is left)
+        if (arms_kernel)  // (tier 3: what tier 6 accepts, within its own allowance)
+            tier_cap[3] = std::min(std::max(shape(3).cap(), tier_cap[6]), tier_cap[3]);
+        else              // (the hybrid kernel: 40 % over by the bound as well; 16-bit gap / pend)
+            tier_cap[6] = (rp.G >= 0xFFF0u || rp.C >= 0xFFF0u) ? 0u : tier_cap[6] * 7 / 5;
         PlaceParams pp;
         pp.long3 = pp.long3_big = pp.dense3 = pp.dense6 = 0;
         pp.stats = opt.debug ? 1u : 0u;
@@ -689,7 +728,7 @@ struct SearchCall {
                 pp.long3 = pp.long3_big = 1;
                 pp.dense3 = pp.dense6 = 0;
             }
-            pp.cap[0] = (uint32_t)std::min<int64_t>(opt.cap1, kArmCapSmall);
+            pp.cap[0] = (uint32_t)std::min<int64_t>(opt.cap1, shape(1).cap());
         }
         int force_eff = force_tier;  // a forced tier that has no kernel in this mode: the next one that has
         while (force_eff > 1 && force_eff < kTiers && !tier_enabled(force_eff)) ++force_eff;
@@ -705,18 +744,18 @@ struct SearchCall {
                 rp, p_filt, seg_list, d_ctr + CT_LONGSEG, long_list, kbuf, vbuf, pp, d_ctr);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamWaitEvent(s, cx.ev[3], 0));  // the hit rows (front(): filled beside the walk above)
+        HIP_TRY(hipStreamWaitEvent(s, cx.ev[EV_HIT_ROWS], 0));  // the hit rows (front(): filled beside the walk above)
         if (cluster_barren) {
-            HIP_TRY(hipEventRecord(cx.ev[13], s));
+            HIP_TRY(hipEventRecord(cx.ev[EV_BARREN], s));
             // barren by position (cluster_barren_kernel): a wave per segment, two bitmap sizes (2 KB: 32 waves per compute
             // unit; 16 KB: 9)
             cluster_barren_kernel<SlotT, 16384><<<256 * 32, 64, 0, s>>>(rp, pp, row_off, hits, seg_list, d_ctr + CT_SEG, kbuf, 1u, 1024u,
                                                                        d_ctr + CT_CLUSTER_CUR, d_ctr);
-            HIP_TRY(hipEventRecord(cx.ev[14], s));
+            HIP_TRY(hipEventRecord(cx.ev[EV_BARREN_SMALL], s));
             cluster_barren_kernel<SlotT, 131072><<<256 * 9, 64, 0, s>>>(rp, pp, row_off, hits, seg_list, d_ctr + CT_SEG, kbuf, 1025u,
                                                                        16384u, d_ctr + CT_CLUSTER_CUR + 1, d_ctr);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(cx.ev[15], s));
+            HIP_TRY(hipEventRecord(cx.ev[EV_BARREN_BIG], s));
         }
         if (split_on) {
             SplitParams sp{};
@@ -812,9 +851,9 @@ struct SearchCall {
                     (unsigned long long)n_seg - placed, (unsigned long long)h_ctr[CT_CLUSTER_BARREN]);
             if (cluster_barren) {
                 float ms_a = 0.f, ms_b = 0.f, ms_p = 0.f;
-                (void)hipEventElapsedTime(&ms_a, cx.ev[13], cx.ev[14]);
-                (void)hipEventElapsedTime(&ms_b, cx.ev[14], cx.ev[15]);
-                (void)hipEventElapsedTime(&ms_p, cx.ev[16], cx.ev[13]);
+                (void)hipEventElapsedTime(&ms_a, cx.ev[EV_BARREN], cx.ev[EV_BARREN_SMALL]);
+                (void)hipEventElapsedTime(&ms_b, cx.ev[EV_BARREN_SMALL], cx.ev[EV_BARREN_BIG]);
+                (void)hipEventElapsedTime(&ms_p, cx.ev[EV_FILL], cx.ev[EV_BARREN]);
                 fprintf(stderr, "[asgart] hit rows filled, placement walk beside it: %.2f ms; barren by position: segments of up to 1 024 hits %.2f ms, up to 16 384 hits %.2f ms\n",
                         ms_p, ms_a, ms_b);
             }
@@ -838,97 +877,96 @@ struct SearchCall {
         const size_t per_wg6 = (size_t)caph * (4 * sizeof(SlotT) + 16);
         const size_t per_wg = std::max(per_wg6, per_wg7);
         n_wg7 = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(256, (16ull << 30) / (4 * per_wg)));
-        const unsigned n_wg_region = per_wg6 * 256 > per_wg * n_wg7 ? 256u : n_wg7;  // (a region serves either kind of launch)
-        region = std::max(per_wg6 * 256, per_wg * (size_t)n_wg7);
-        (void)n_wg_region;
+        region = std::max(per_wg6 * 256, per_wg * (size_t)n_wg7);  // (a region serves either kind of launch)
         RC_TRY(w.scratch.reserve(region * 4));  // tier 6, tier 7, and one region per early cascade launch
         scratch6 = w.scratch.as<char>();
         scratch7 = scratch6 + region;
         return 0;
     }
 
-    // one launch of tier `tier`'s kernel over the list described by ep
-    void launch_kernel(int tier, uint64_t n_items, hipStream_t st) {
-        // option grid<t> may shrink a tier's grid; the workgroup kernels (tiers 3..7) never get
-        // more workgroups than their default (HBM scratch is reserved for that many)
-        ep.tier = (uint32_t)tier;
-        ep.seg_slots = w.seg_slots.as<unsigned long long>() + (size_t)4096 * (size_t)(tier & 7);
-        ep.hb = cx.d_hb ? cx.d_hb + (size_t)2 * SearchCtx::kHbSlots * (size_t)(tier & 7) : nullptr;
-        auto grid = [&](uint64_t dflt) -> unsigned {
-            uint64_t g = dflt;
-            if (opt.grid[tier] > 0) g = tier >= 3 ? std::min<uint64_t>(dflt, (uint64_t)opt.grid[tier]) : (uint64_t)opt.grid[tier];
-            return (unsigned)std::min<uint64_t>(n_items, g);
-        };
-        switch (tier) {
-        case 1:
-            extend_kernel<SlotT, kArmCapSmall><<<grid(kGrid1), 64, 0, st>>>(ep);
-            break;
-        case 2:
-            if (arms_kernel)
-                extend_fast_kernel<SlotT, kWaveArmsLayers<SlotT>, 64, kWaveArmsHits, 256, 2><<<grid(kGrid2Arms), 64, 0, st>>>(ep);
-            else
-                extend_heavy_kernel<SlotT, kArmCapMid, kMidThreads, 0><<<grid(kGrid2), kMidThreads, 0, st>>>(ep);
-            break;
-        case 3:  // (arm-resident kernels only: the long dense segments)
-            extend_k8_kernel<SlotT, kK8LongLayers<SlotT>, 1024, kHitBatch, kFastLongRows<SlotT>, 2><<<grid(256), 1024, 0, st>>>(ep);
-            break;
-        case 4:
-            if (arms_kernel)
-                extend_fast_kernel<SlotT, kMidArmsLayers<SlotT>, 256, kWaveArmsHits, 512, 2><<<grid(256 * 4), 256, 0, st>>>(ep);
-            else if constexpr (sizeof(SlotT) == 4)
-                extend_heavy_kernel<SlotT, kArmCapBig32, kHeavyThreads, 0><<<grid(256), kHeavyThreads, 0, st>>>(ep);
-            else
-                extend_heavy_kernel<SlotT, kArmCapBig64, kHeavyThreads, 0><<<grid(256), kHeavyThreads, 0, st>>>(ep);
-            break;
-        case 5:  // (arm-resident kernels only)
-            extend_fast_kernel<SlotT, kMidArmsLayers<SlotT>, 512, kHitBatch, 1024, 2><<<grid(256 * 2), 512, 0, st>>>(ep);
-            break;
-        case 6:
-            if (scratch_override) ep.scratch = scratch_override;
-            if (arms_kernel)  // 5 x 1024 slots; 64-bit positions: 4 x 1024 with a smaller table
-                extend_fast_kernel<SlotT, kFastHeavyLayers<SlotT>, 1024, kHitBatch, kFastLongRows<SlotT>, 2><<<grid(256), 1024, 0, st>>>(ep);
-            else
-                extend_heavy_kernel<SlotT, caph, kHeavyThreads, 1><<<grid(256), kHeavyThreads, 0, st>>>(ep);
-            ep.scratch = scratch6;
-            break;
-        default:
-            ep.scratch = scratch_override ? scratch_override : scratch7;
-            extend_heavy_kernel<SlotT, 1, kHeavyThreads, 2><<<grid(n_wg7), kHeavyThreads, 0, st>>>(ep);
-            ep.scratch = scratch6;
-            break;
+    // What one launch works through.  Every launch site builds its own: nothing is inherited from an earlier launch.
+    struct WorkList {
+        const uint32_t *list;             // the segments (the runs over ranges: null, the runs are the list)
+        const unsigned long long *count;  // device count of the entries
+        unsigned long long *cursor;       // work-fetch cursor
+        int ovf_into;                     // what the launch gives up on goes where tier ovf_into's own goes
+        uint32_t cap_limit;               // test_cap(), or 0xFFFFFFFF for a re-run of what overflowed
+        char *scratch = nullptr;          // HBM region of the LDS-array kernels (null: the tier's own)
+    };
+    // option test_cap_limit (tests): shrink the tiers' capacity to exercise the cascade
+    uint32_t test_cap() const { return opt.test_cap_limit >= 0 ? (uint32_t)opt.test_cap_limit : 0xFFFFFFFFu; }
+
+    // the kernel of one table entry: its template arguments are the entry's
+    template <int T, int SET>
+    static void launch_shape(const ExtParams<SlotT> &p, unsigned grid, hipStream_t st) {
+        constexpr TierShape sh = Tiers::shape[T][SET];
+        constexpr int cap = (int)sh.cap();
+        if constexpr (sh.kernel == TierKernel::wave)
+            extend_kernel<SlotT, cap><<<grid, sh.threads, 0, st>>>(p);
+        else if constexpr (sh.kernel == TierKernel::fast)
+            extend_fast_kernel<SlotT, sh.layers, sh.threads, sh.hits, sh.rows, 2><<<grid, sh.threads, 0, st>>>(p);
+        else if constexpr (sh.kernel == TierKernel::k8)
+            extend_k8_kernel<SlotT, sh.layers, sh.threads, sh.hits, sh.rows, 2, T == 0><<<grid, sh.threads, 0, st>>>(p);
+        else if constexpr (sh.kernel != TierKernel::none)
+            extend_heavy_kernel<SlotT, cap, sh.threads, (int)sh.kernel - (int)TierKernel::heavy_lds><<<grid, sh.threads, 0, st>>>(p);
+    }
+    template <int... I>
+    static void launch_entry(int entry, std::integer_sequence<int, I...>, const ExtParams<SlotT> &p, unsigned grid, hipStream_t st) {
+        ((entry == I ? launch_shape<I / 2, I % 2>(p, grid, st) : void()), ...);
+    }
+
+    // one launch of tier `tier`'s kernel (0: the runs over ranges) over the first n_items of wl
+    int32_t launch_kernel(int tier, const WorkList &wl, uint64_t n_items, hipStream_t st) {
+        const bool runs = tier == 0;
+        if (shape(tier).kernel == TierKernel::none) {  // (cannot happen: place() gives such a tier no segments and cuts no ranges)
+            set_error("internal: tier %d has no kernel in this set, its %llu work items would be lost", tier, (unsigned long long)n_items);
+            return ASGART_E_CAP;
         }
+        // (statistics, segment clocks, heartbeats: the runs have a slot of their own and block 0, no tier's; the debug
+        // output counts them with tier 3)
+        const uint32_t stat = runs ? (uint32_t)kRunsStat : (uint32_t)tier;
+        ExtParams<SlotT> p = base;
+        p.runs = runs ? reinterpret_cast<const RangeRun *>(d_split + kOffRuns) : nullptr;
+        p.run_meta = runs ? reinterpret_cast<uint32_t *>(d_split + kOffMeta) : nullptr;
+        p.run_dump = runs ? w.split_dump.as<uint32_t>() : nullptr;
+        p.seg_list = wl.list;
+        p.n_seg_ptr = wl.count;
+        p.cursor = wl.cursor;
+        p.ovf_list = runs || wl.ovf_into >= kTiers ? nullptr : ovf[wl.ovf_into - 1];
+        p.ovf_count = d_ctr + CT_OVF1 + wl.ovf_into - 1;  // appended behind what is already there
+        // (tiers 6 and 7, whose LDS-array kernels keep arms in HBM: the region named, else their own; the others: tier 6's)
+        p.scratch = wl.scratch && tier >= 6 ? wl.scratch : tier == kTiers ? scratch7 : scratch6;
+        p.cap_limit = wl.cap_limit;
+        p.tier = stat;
+        p.seg_slots = w.seg_slots.as<unsigned long long>() + (size_t)4096 * (size_t)(stat & 7);
+        p.hb = cx.d_hb ? cx.d_hb + (size_t)2 * SearchCtx::kHbSlots * (size_t)(stat & 7) : nullptr;
+        // a workgroup per run; tier 7: as many as its HBM slices (place()).  Option grid<t> may shrink a tier's grid; the
+        // workgroup kernels (tiers 3..7) never get more workgroups than their default (HBM scratch is reserved for that many)
+        uint64_t g = runs ? n_items : tier == kTiers ? (uint64_t)n_wg7 : (uint64_t)shape(tier).grid;
+        if (!runs && opt.grid[tier] > 0) g = tier >= 3 ? std::min<uint64_t>(g, (uint64_t)opt.grid[tier]) : (uint64_t)opt.grid[tier];
+        launch_entry(2 * tier + (arms_kernel ? 0 : 1), std::make_integer_sequence<int, 2 * (kTiers + 1)>{}, p,
+                     (unsigned)std::min<uint64_t>(n_items, g), st);
+        return 0;
     }
 
-    // the runs over ranges of the cut segments: first, on the main stream (idle while the tiers run) -- they are the
-    // longest work items of the call, one workgroup each
-    void launch_runs(uint32_t n_items) {  // the runs from the work cursor on, one workgroup each
-        ep.runs = reinterpret_cast<const RangeRun *>(d_split + kOffRuns);
-        ep.run_meta = reinterpret_cast<uint32_t *>(d_split + kOffMeta);
-        ep.run_dump = w.split_dump.as<uint32_t>();
-        ep.seg_list = nullptr;
-        ep.n_seg_ptr = reinterpret_cast<const unsigned long long *>(d_split);
-        ep.cursor = reinterpret_cast<unsigned long long *>(d_split + 24);
-        ep.ovf_list = nullptr;
-        ep.ovf_count = d_ctr + CT_OVF1 + 2;
-        ep.tier = kRunsStat;  // (statistics: a slot of their own; the debug output counts them with tier 3)
-        ep.seg_slots = w.seg_slots.as<unsigned long long>();  // (slot block 0: no tier's)
-        ep.hb = cx.d_hb ? cx.d_hb : nullptr;
-        extend_k8_kernel<SlotT, kK8LongLayers<SlotT>, 1024, kHitBatch, kFastLongRows<SlotT>, 2, true><<<n_items, 1024, 0, s>>>(ep);
+    // the runs over ranges of the cut segments from the work cursor on, one workgroup each, on the main stream (idle while
+    // the tiers run) -- they are the longest work items of the call.  What a run gives up on is the host's to run again
+    // (join_ranges): no overflow list, tier 3's count.
+    int32_t launch_runs(uint32_t n_items) {
+        return launch_kernel(0, WorkList{nullptr, reinterpret_cast<const unsigned long long *>(d_split),
+                                  reinterpret_cast<unsigned long long *>(d_split + 24), Tiers::kRunsTier, test_cap()}, n_items, s);
     }
 
-    void launch_tier(int tier) {
-        if (tier < 1 || tier > kTiers || !n_t[tier - 1]) return;
-        ep.seg_list = order + seg_off[tier - 1];
-        ep.n_seg_ptr = d_ctr + CT_N1 + (tier - 1);
-        ep.cursor = d_ctr + CT_CUR1 + (tier - 1);
-        ep.ovf_list = tier < kTiers ? ovf[tier - 1] : nullptr;
-        ep.ovf_count = d_ctr + CT_OVF1 + (tier - 1);
-        launch_kernel(tier, n_t[tier - 1], tier_stream[tier]);
+    int32_t launch_tier(int tier) {
+        if (tier < 1 || tier > kTiers || !n_t[tier - 1]) return 0;
+        const int i = tier - 1;
+        RC_TRY(launch_kernel(tier, WorkList{order + seg_off[i], d_ctr + CT_N1 + i, d_ctr + CT_CUR1 + i, tier, test_cap()}, n_t[i], tier_stream[tier]));
     #ifdef ASGART_PROFILE_EXTEND
         char tag[8];
         snprintf(tag, sizeof tag, "%d", tier);
         PROF_TIER(tag, tier_stream[tier], n_t[tier - 1]);
     #endif
+        return 0;
     }
 
     // ---- every tier and the runs over ranges, launched together; early re-runs of what tiers 3 and 6 give up on ----------------
@@ -940,23 +978,19 @@ struct SearchCall {
         HIP_TRY(hipMemsetAsync(d_ctr + CT_BUSY1, 0, (size_t)(CT_COUNT - CT_BUSY1) * 8, s));
         RC_TRY(w.seg_slots.reserve((size_t)8 * 4096 * 8));
         HIP_TRY(hipMemsetAsync(w.seg_slots.p, 0, (size_t)8 * 4096 * 8, s));
-        HIP_TRY(hipEventRecord(cx.ev[7], s));
-        ep.rp = rp;
-        ep.p_filt = p_filt;
-        ep.row_off = row_off;
-        ep.hits = hits;
-        ep.recs = w.fam_sds.as<SdRec>();
-        ep.rec_cap = rec_cap;
-        ep.scratch = scratch6;
-        // option test_cap_limit (tests): shrink the tiers' capacity to exercise the cascade
-        ep.cap_limit = opt.test_cap_limit >= 0 ? (uint32_t)opt.test_cap_limit : 0xFFFFFFFFu;
-        ep.escalate_cost = 0xFFFFFFFFu;
-        ep.heavy_cap = (uint32_t)heavy_cap64;
-        ep.solo_hits = opt.solo == 1 ? 16u : (uint32_t)opt.solo;  // (1: the default of 16 hits; other values: that many)
-        ep.gen_bits = (uint32_t)opt.test_genbits;
-        ep.k8_delay = (uint32_t)opt.test_k8_delay;
-        ep.ctr = d_ctr;
-        ep.hb = nullptr;
+        HIP_TRY(hipEventRecord(cx.ev[EV_TIERS], s));
+        base.rp = rp;
+        base.p_filt = p_filt;
+        base.row_off = row_off;
+        base.hits = hits;
+        base.recs = w.fam_sds.as<SdRec>();
+        base.rec_cap = rec_cap;
+        base.escalate_cost = 0xFFFFFFFFu;  // (one-wave tiers: never give up for the work done)
+        base.heavy_cap = (uint32_t)heavy_cap64;
+        base.solo_hits = opt.solo == 1 ? 16u : (uint32_t)opt.solo;  // (1: the default of 16 hits; other values: that many)
+        base.gen_bits = (uint32_t)opt.test_genbits;
+        base.k8_delay = (uint32_t)opt.test_k8_delay;
+        base.ctr = d_ctr;
         RC_TRY(cx.heartbeat(opt.watchdog_s > 0));
         if (cx.h_hb) memset(cx.h_hb, 0, (size_t)SearchCtx::kHbTiers * SearchCtx::kHbSlots * 16);
         // The tiers are launched together on separate streams, each with a grid that can fill
@@ -979,7 +1013,7 @@ struct SearchCall {
             if (stream_of[t - 1] > 0) used[stream_of[t - 1] - 1] = true;
         }
         for (int i = 0; i < cx.n_tier_st; ++i)
-            if (used[i]) HIP_TRY(hipStreamWaitEvent(cx.tier_st[i], cx.ev[7], 0));
+            if (used[i]) HIP_TRY(hipStreamWaitEvent(cx.tier_st[i], cx.ev[EV_TIERS], 0));
         if (opt.debug) {
             fprintf(stderr, "[asgart] tier plan (%d tier streams; 0 = main stream behind %.1f ms of range runs):", cx.n_tier_st,
                     n_runs ? est[0] : 0.0);
@@ -993,13 +1027,12 @@ struct SearchCall {
         // (tens of thousands of probes, strictly serial): those tiers go first, the one-wave
         // tier last, and the heavy grids are sized so that every tier's longest segments
         // start at once instead of queueing behind another tier's bulk.
-        scratch_override = nullptr;
         if (n_runs) {
             // (room for one more run per cut segment: the rest behind the last cut that held, see below)
             RC_TRY(w.split_dump.reserve((size_t)(n_runs + n_splits) * 2 * kRunDumpCap * kDumpWords<SlotT> * 4));
             HIP_TRY(hipMemsetAsync(d_split + 24, 0, 8, s));                         // work cursor
             HIP_TRY(hipMemsetAsync(d_split + kOffMeta, 0, (size_t)n_runs * 64, s));  // run states
-            launch_runs(n_runs);
+            RC_TRY(launch_runs(n_runs));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(cx.runs_ev, s));
         }
@@ -1009,7 +1042,7 @@ struct SearchCall {
         // never ran); each tier's event follows it on its stream
         for (int i = 0; i < kTiers && launch_seq[i]; ++i) {
             const int t = launch_seq[i];
-            launch_tier(t);
+            RC_TRY(launch_tier(t));
             HIP_TRY(hipEventRecord(cx.tier_ev[t - 1], tier_stream[t]));
             tier_ran[t] = true;
         }
@@ -1021,7 +1054,7 @@ struct SearchCall {
             // A host that pipelines calls (bench.py) issues the next one when it sees this: its search
             // phases then run beside this call's extension, whose tail is a few serial segments.
             if (!progress_given) {
-                RC_TRY(wd_event_sync(idx, cx, cx.ev[3], "the hit rows"));  // probe search, scans and CSR fill are done
+                RC_TRY(wd_event_sync(idx, cx, cx.ev[EV_HIT_ROWS], "the hit rows"));  // probe search, scans and CSR fill are done
                 signal_progress();
             }
         }
@@ -1036,23 +1069,22 @@ struct SearchCall {
         for (int t = 0; t <= kTiers; ++t) early_n[t] = 0;
         {
             struct Early {
-                int src, dst;
-                hipEvent_t ev;
-                hipStream_t st;
+                int src, dst;  // (src's event, cx.tier_ev, follows the re-run on src's stream)
                 bool pending;
-            } early[2] = {{3, 0, cx.tier_ev[2], tier_stream[3], false}, {6, 0, cx.tier_ev[5], tier_stream[6], false}};
-            int n_pending = 0;
+                char phase[24];  // (what the watchdog names)
+            } early[2] = {};  // (two sets of counters, CT_EARLY_N, and of HBM regions, place(); a third tier waits for the cascade)
+            int n_early = 0, n_pending = 0;
             unsigned early_polls = 0;
             Watchdog early_wd(idx, cx);
-            for (int e = 0; e < 2; ++e) {
-                Early &E = early[e];
-                int dst = E.src + 1;
-                while (dst < kTiers && (!tier_enabled(dst) || tier_cap[dst] <= tier_cap[E.src])) ++dst;
-                E.dst = dst;
+            for (int t = 1; t < kTiers; ++t) {
+                if (!shape(t).early || n_early == 2) continue;
+                Early &E = early[n_early++];
+                E = Early{t, next_holding_more(t), false, {}};
+                snprintf(E.phase, sizeof E.phase, "extension tier %d", t);
                 // (a re-run in the HBM tier would share that tier's slices with its own list, if it has one; a tier the
                 // plan put on the main stream is re-run by the regular cascade: reading its overflow count there would
                 // wait for the whole main stream)
-                E.pending = n_t[E.src - 1] && E.st != s && (dst < kTiers || !n_t[kTiers - 1]);
+                E.pending = n_t[t - 1] && tier_stream[t] != s && (E.dst < kTiers || !n_t[kTiers - 1]);
                 n_pending += E.pending ? 1 : 0;
             }
             // (If tier 3's re-run went to tier 6, its kernel would append to tier 6's overflow list while the host
@@ -1065,10 +1097,10 @@ struct SearchCall {
             }
             while (n_pending) {
                 bool progressed = false;
-                for (int e = 0; e < 2; ++e) {
+                for (int e = 0; e < n_early; ++e) {
                     Early &E = early[e];
                     if (!E.pending) continue;
-                    const hipError_t q = hipEventQuery(E.ev);
+                    const hipError_t q = hipEventQuery(cx.tier_ev[E.src - 1]);
                     if (q == hipErrorNotReady) {
                         (void)hipGetLastError();
                         continue;
@@ -1086,26 +1118,17 @@ struct SearchCall {
                     if (!n_e) continue;
                     early_n[E.src] = n_e;
                     // the count the launch works on is fixed now (the list itself may still grow)
-                    HIP_TRY(hipMemcpyAsync(d_ctr + CT_EARLY_N + e, h_scalar + 1 + e, 8, hipMemcpyHostToDevice, E.st));
-                    ep.seg_list = ovf[E.src - 1];
-                    ep.n_seg_ptr = d_ctr + CT_EARLY_N + e;
-                    ep.cursor = d_ctr + CT_EARLY_CUR + e;
-                    ep.ovf_list = E.dst < kTiers ? ovf[E.dst - 1] : nullptr;
-                    ep.ovf_count = d_ctr + CT_OVF1 + E.dst - 1;
-                    ep.escalate_cost = 0xFFFFFFFFu;
-                    ep.cap_limit = 0xFFFFFFFFu;
-                    scratch_override = scratch6 + region * (size_t)(2 + e);
-                    launch_kernel(E.dst, n_e, E.st);
-                    scratch_override = nullptr;
+                    HIP_TRY(hipMemcpyAsync(d_ctr + CT_EARLY_N + e, h_scalar + 1 + e, 8, hipMemcpyHostToDevice, tier_stream[E.src]));
+                    RC_TRY(launch_kernel(E.dst, WorkList{ovf[E.src - 1], d_ctr + CT_EARLY_N + e, d_ctr + CT_EARLY_CUR + e, E.dst, 0xFFFFFFFFu,
+                                                         scratch6 + region * (size_t)(2 + e)}, n_e, tier_stream[E.src]));
                     HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipEventRecord(E.ev, E.st));
+                    HIP_TRY(hipEventRecord(cx.tier_ev[E.src - 1], tier_stream[E.src]));
                 }
                 if (n_pending && !progressed) {
                     std::this_thread::sleep_for(std::chrono::microseconds(50));
                     // (the same watchdog as every other wait of the call -- one look at the heartbeats, never a blocking
                     // wait: the other tier's early re-run must not wait for this one's stream to drain)
-                    if ((++early_polls & 0x3FFu) == 0 && early_wd.expired(early[0].pending ? "extension tier 3" : "extension tier 6"))
-                        return ASGART_E_HIP;
+                    if ((++early_polls & 0x3FFu) == 0 && early_wd.expired(early[early[0].pending ? 0 : 1].phase)) return ASGART_E_HIP;
                 }
             }
         }
@@ -1252,7 +1275,7 @@ struct SearchCall {
                 HIP_TRY(hipMemcpyAsync(d_split, h_scalar + 8, 8, hipMemcpyHostToDevice, s));
                 HIP_TRY(hipMemcpyAsync(d_split + 24, h_scalar + 9, 8, hipMemcpyHostToDevice, s));
                 HIP_TRY(hipMemsetAsync(d_split + kOffMeta + (size_t)n_runs * 64, 0, (size_t)n_tail * 64, s));
-                launch_runs(n_tail);
+                RC_TRY(launch_runs(n_tail));
                 HIP_TRY(hipMemcpyAsync(h_split + kOffMeta + (size_t)n_runs * 64, d_split + kOffMeta + (size_t)n_runs * 64, (size_t)n_tail * 64,
                                        hipMemcpyDeviceToHost, s));
                 HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr, kCtrBytes, hipMemcpyDeviceToHost, s));
@@ -1281,13 +1304,10 @@ struct SearchCall {
                 *h_scalar = n_again;
                 HIP_TRY(hipMemcpyAsync(d_ctr + CT_NF, h_scalar, 8, hipMemcpyHostToDevice, s));
                 HIP_TRY(hipMemsetAsync(d_ctr + CT_CURF, 0, 8, s));
-                ep.seg_list = reinterpret_cast<const uint32_t *>(d_split + kOffAgain);
-                ep.n_seg_ptr = d_ctr + CT_NF;
-                ep.cursor = d_ctr + CT_CURF;
-                ep.ovf_list = ovf[3 - 1];
-                ep.ovf_count = d_ctr + CT_OVF1 + 3 - 1;  // (what the whole segment overflows goes the way of tier 3's own)
-                ep.escalate_cost = 0xFFFFFFFFu;
-                launch_kernel(3, n_again, s);
+                // (what the whole segment overflows goes the way of tier 3's own.  cap_limit is the option's, as in the tail
+                // runs above and in tier 3's own launch -- whether or not an early re-run came before)
+                RC_TRY(launch_kernel(Tiers::kRunsTier, WorkList{reinterpret_cast<const uint32_t *>(d_split + kOffAgain), d_ctr + CT_NF,
+                                                                d_ctr + CT_CURF, Tiers::kRunsTier, test_cap()}, n_again, s));
                 HIP_TRY(hipGetLastError());
             }
             HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr, kCtrBytes, hipMemcpyDeviceToHost, s));
@@ -1296,30 +1316,35 @@ struct SearchCall {
         return 0;
     }
 
+    // tier t's busy time or workgroups (ct1: CT_BUSY1, CT_WGS1) and its longest segment, the runs over ranges counted with
+    // the long-segment tier whose kernel they run
+    unsigned long long tier_sum(int ct1, int t) const { return h_ctr[ct1 + t - 1] + (t == Tiers::kRunsTier ? h_ctr[ct1 + kRunsStat - 1] : 0ull); }
+    unsigned long long tier_longest(int t) const { return std::max(h_ctr[CT_SEGMAX1 + t - 1], t == Tiers::kRunsTier ? h_ctr[CT_SEGMAX1 + kRunsStat - 1] : 0ull); }
+    // The statistics and the plan's estimates count every tier with the ARM-RESIDENT set's workgroups per compute unit,
+    // compute units and profile, whichever set runs: so they always have, and with the LDS-array set's own figures
+    // (3, 1, 1 for tiers 2, 4, 6) tier_plan would pack the streams of such a call differently.
+    static const TierShape &stat_shape(int t) { return Tiers::shape[t][0]; }
+
     // ---- statistics of the tiers; the cascade: what tier t gave up on is re-run by the next tier that holds more ------------------
     int32_t finish_tiers() {
         PROF_DUMP("concurrent tiers");
         if (opt.debug) {
             fprintf(stderr, "[asgart] all tiers and early re-runs done %.1f ms after the launches\n", since_launch());
             // how much of the chip each tier held: sum of its workgroups' lifetimes x the share of a compute unit one of
-            // them occupies (workgroups per compute unit by LDS / registers: tiers 1..7 = 11, 8, 1, 4, 2, 1, 1)
-            const double *per_cu = kWgPerCU;
-            // (the runs over ranges count with tier 3, the long-segment tier whose kernel they run)
-            auto busy = [&](int t) { return (double)(h_ctr[CT_BUSY1 + t] + (t == 2 ? h_ctr[CT_BUSY1 + kRunsStat - 1] : 0ull)); };
-            auto wgs = [&](int t) { return h_ctr[CT_WGS1 + t] + (t == 2 ? h_ctr[CT_WGS1 + kRunsStat - 1] : 0ull); };
+            // them occupies
             double tot = 0.0;
             fprintf(stderr, "[asgart] compute-unit time held per tier (CU-ms; workgroups):");
-            for (int t = 0; t < kTiers; ++t) {
-                const double cu_ms = busy(t) * 1e-5 / per_cu[t];
+            for (int t = 1; t <= kTiers; ++t) {
+                const double cu_ms = (double)tier_sum(CT_BUSY1, t) * 1e-5 / stat_shape(t).wg_per_cu;
                 tot += cu_ms;
-                fprintf(stderr, " %d: %.0f (%llu)", t + 1, cu_ms, (unsigned long long)wgs(t));
+                fprintf(stderr, " %d: %.0f (%llu)", t, cu_ms, tier_sum(CT_WGS1, t));
             }
             fprintf(stderr, "  total %.0f = %.1f ms of the whole chip\n", tot, tot / 256.0);
             fprintf(stderr, "[asgart] per tier: hit-probes / hits per hit-probe / CU-microseconds per hit-probe:");
-            for (int t = 0; t < kTiers; ++t) {
-                const double hp = (double)h_tp[t];
-                fprintf(stderr, " %d: %.0fK / %.1f / %.2f", t + 1, hp / 1e3, hp > 0 ? (double)h_th[t] / hp : 0.0,
-                        hp > 0 ? busy(t) * 1e-2 / per_cu[t] / hp : 0.0);
+            for (int t = 1; t <= kTiers; ++t) {
+                const double hp = (double)h_tp[t - 1];
+                fprintf(stderr, " %d: %.0fK / %.1f / %.2f", t, hp / 1e3, hp > 0 ? (double)h_th[t - 1] / hp : 0.0,
+                        hp > 0 ? (double)tier_sum(CT_BUSY1, t) * 1e-2 / stat_shape(t).wg_per_cu / hp : 0.0);
             }
             fprintf(stderr, "\n");
         }
@@ -1328,7 +1353,7 @@ struct SearchCall {
             for (int t = 1; t <= kTiers; ++t) {
                 float ms = 0.f;
                 if (!tier_ran[t]) continue;
-                if (hipEventElapsedTime(&ms, cx.ev[7], cx.tier_ev[t - 1]) == hipSuccess) longest = std::max(longest, ms);
+                if (hipEventElapsedTime(&ms, cx.ev[EV_TIERS], cx.tier_ev[t - 1]) == hipSuccess) longest = std::max(longest, ms);
                 else (void)hipGetLastError();
             }
             ms_longest_tier = longest;
@@ -1351,19 +1376,11 @@ struct SearchCall {
             const uint64_t skip = early_n[src];
             const uint64_t n_ovf = h_ctr[CT_OVF1 + src - 1] - skip;
             if (!n_ovf) continue;
-            int dst = src + 1;
-            while (dst < kTiers && (!tier_enabled(dst) || tier_cap[dst] <= tier_cap[src])) ++dst;
+            const int dst = next_holding_more(src);
             *h_scalar = n_ovf;  // (the previous cascade launch has been waited for)
             HIP_TRY(hipMemcpyAsync(d_ctr + CT_NF, h_scalar, 8, hipMemcpyHostToDevice, s));
             HIP_TRY(hipMemsetAsync(d_ctr + CT_CURF, 0, 8, s));
-            ep.seg_list = ovf[src - 1] + skip;
-            ep.n_seg_ptr = d_ctr + CT_NF;
-            ep.cursor = d_ctr + CT_CURF;
-            ep.ovf_list = dst < kTiers ? ovf[dst - 1] : nullptr;
-            ep.ovf_count = d_ctr + CT_OVF1 + dst - 1;  // appended behind what is already there
-            ep.escalate_cost = 0xFFFFFFFFu;
-            ep.cap_limit = 0xFFFFFFFFu;
-            launch_kernel(dst, n_ovf, s);
+            RC_TRY(launch_kernel(dst, WorkList{ovf[src - 1] + skip, d_ctr + CT_NF, d_ctr + CT_CURF, dst, 0xFFFFFFFFu}, n_ovf, s));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(h_ctr, d_ctr, kCtrBytes, hipMemcpyDeviceToHost, s));
             RC_TRY(wd_sync(idx, cx, s, "a re-run of overflowed segments"));
@@ -1381,9 +1398,7 @@ struct SearchCall {
         for (int t = 0; t < kRunsStat; ++t) ms_longest_segment = std::max(ms_longest_segment, (double)h_ctr[CT_SEGMAX1 + t] * 1e-5);
         if (opt.debug) {
             fprintf(stderr, "[asgart] longest single segment per tier (ms):");
-            for (int t = 0; t < kTiers; ++t)
-                fprintf(stderr, " %d: %.2f", t + 1,
-                        (double)std::max(h_ctr[CT_SEGMAX1 + t], t == 2 ? h_ctr[CT_SEGMAX1 + kRunsStat - 1] : 0ull) * 1e-5);
+            for (int t = 1; t <= kTiers; ++t) fprintf(stderr, " %d: %.2f", t, (double)tier_longest(t) * 1e-5);
             fprintf(stderr, "\n");
         }
         remember_plan_estimates();
@@ -1391,21 +1406,15 @@ struct SearchCall {
     }
 
     // ---- the estimates of the tier plan (tier_plan) ---------------------------------------------------------------------------
-    // Workgroups of a tier's shape a compute unit holds (LDS / registers), and the compute units a tier's default grid can
-    // hold: tier 1's 2048 one-wave workgroups fill 186 of them, the others the whole chip.
-    static constexpr double kWgPerCU[kTiers] = {11, 8, 1, 4, 2, 1, 1};
-    static constexpr double kTierCUs[kTiers] = {2048.0 / 11.0, 256, 256, 256, 256, 256, 256};
     // est[t]: tier t's estimated duration in ms, est[0]: the runs over ranges -- what the previous call with the same
-    // call_sig measured (remember_plan_estimates), else the GRCh38-shaped profile (profiles/r06_cfg4_tier_cu_seconds.json:
-    // the longest segments of tiers 2..6 -- tier 3's with the runs, which that profile counted with it --, tier 1's work
-    // over its compute units; tier 7 and the runs as tiers 6 and 3)
+    // call_sig measured (remember_plan_estimates), else the table's profile
     void plan_estimates(double *est) const {
-        static const double kProfile[kTiers + 1] = {67.0, 4.6, 51.8, 67.0, 35.5, 53.0, 33.0, 33.0};
         const bool known = cx.plan_known && cx.plan_sig == call_sig;
-        for (int t = 0; t <= kTiers; ++t) est[t] = known && cx.plan_est[t] > 0.0 ? cx.plan_est[t] : kProfile[t];
+        for (int t = 0; t <= kTiers; ++t) est[t] = known && cx.plan_est[t] > 0.0 ? cx.plan_est[t] : stat_shape(t).profile_ms;
     }
-    // per tier that ran: the longer of its longest segment and its work spread over the compute units it can hold (the
-    // runs over ranges have a statistics slot of their own, kRunsStat, and their own estimate: their duration, est[0])
+    // per tier that ran: the longer of its longest segment and its work spread over the compute units its default grid can
+    // hold -- tier 1's 2048 one-wave workgroups fill 186 of them, the others the whole chip (the runs over ranges have a
+    // statistics slot of their own, kRunsStat, and their own estimate: their duration, est[0])
     void remember_plan_estimates() {
         if (!(cx.plan_known && cx.plan_sig == call_sig))
             for (double &e : cx.plan_est) e = 0.0;
@@ -1414,12 +1423,13 @@ struct SearchCall {
         for (int t = 1; t <= kTiers; ++t) {
             if (!tier_ran[t]) continue;
             const double seg = (double)h_ctr[CT_SEGMAX1 + t - 1] * 1e-5;
-            const double spread = (double)h_ctr[CT_BUSY1 + t - 1] * 1e-5 / kWgPerCU[t - 1] / kTierCUs[t - 1];
+            const TierShape &sh = stat_shape(t);
+            const double spread = (double)h_ctr[CT_BUSY1 + t - 1] * 1e-5 / sh.wg_per_cu / std::min(256.0, (double)sh.grid / sh.wg_per_cu);
             cx.plan_est[t] = std::max(seg, spread);
         }
         float runs = 0.f;
         if (n_runs) {
-            if (hipEventElapsedTime(&runs, cx.ev[7], cx.runs_ev) != hipSuccess) {
+            if (hipEventElapsedTime(&runs, cx.ev[EV_TIERS], cx.runs_ev) != hipSuccess) {
                 (void)hipGetLastError();
                 runs = 0.f;
             }
@@ -1429,7 +1439,7 @@ struct SearchCall {
 
     // ---- records -> reference order -> families per pass ----------------------------------------------------------------------
     int32_t records() {
-        HIP_TRY(hipEventRecord(cx.ev[4], s));
+        HIP_TRY(hipEventRecord(cx.ev[EV_EXTENDED], s));
         const uint64_t n_rec = h_ctr[CT_SD];
         if (n_rec) {
             void *hp = nullptr;
@@ -1527,13 +1537,13 @@ struct SearchCall {
         // ---- stats ------------------------------------------------------------------
         asgart_stats &stt = cx.stats;
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[0], cx.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[EV_SEARCH], cx.ev[EV_SEARCHED]));
         stt.ms_search = ms;
-        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[1], cx.ev[2]));
+        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[EV_SEARCHED], cx.ev[EV_SCANNED]));
         stt.ms_scan = ms;
-        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[16], cx.ev[3]));
+        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[EV_FILL], cx.ev[EV_HIT_ROWS]));
         stt.ms_fill = ms;
-        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[3], cx.ev[4]));
+        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[EV_HIT_ROWS], cx.ev[EV_EXTENDED]));
         stt.ms_extend = ms;
         stt.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() -
                                                                 t_host0).count();
@@ -1559,11 +1569,10 @@ struct SearchCall {
         stt.ms_longest_segment = ms_longest_segment;
         stt.split_segments = n_split_segments;
         stt.split_refused = n_split_refused;
-        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[0], cx.ev[11]));
+        HIP_TRY(hipEventElapsedTime(&ms, cx.ev[EV_SEARCH], cx.ev[EV_PROBE_COUNT]));
         stt.ms_probe_count = ms;
         cx.has_last = true;
         cx.raw_done = false;
-        return 0;
         return 0;
     }
 
@@ -1583,7 +1592,7 @@ struct SearchCall {
                 continue;
             }
             // (the hit rows are being filled on a stream of their own; place() waits for them where it needs them)
-            if (want_csr || !(fam_out && n_seg)) HIP_TRY(hipStreamWaitEvent(s, cx.ev[3], 0));
+            if (want_csr || !(fam_out && n_seg)) HIP_TRY(hipStreamWaitEvent(s, cx.ev[EV_HIT_ROWS], 0));
             if (want_csr) RC_TRY(csr_out());
             if (fam_out && n_seg) {
                 RC_TRY(place());
@@ -1605,7 +1614,7 @@ struct SearchCall {
                 }
                 RC_TRY(records());
             } else {
-                HIP_TRY(hipEventRecord(cx.ev[4], s));
+                HIP_TRY(hipEventRecord(cx.ev[EV_EXTENDED], s));
                 RC_TRY(wd_sync(idx, cx, s, "the hit rows"));
             }
             break;

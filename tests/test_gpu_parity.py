@@ -1457,6 +1457,51 @@ def test_long_segments_as_ranges_equal_whole_segments(hiplib, shape, wide, monke
     assert joined > 0 and refused > 0, (shape, joined, refused)
 
 
+def test_refused_ranges_run_whole_under_a_small_cap_limit(hiplib):
+    """A refused range run re-run as a whole segment while option test_cap_limit is small: the runs over ranges, the one
+    more run behind the last cut that held and the whole segment again are all launched with test_cap_limit, like tier
+    3's own launch, and what they give up on goes the cascade's way.  Cases of the ranges test above, every multi-hit
+    segment forced through the long shape.  What guards the path is the equality: families, ProtoSDs and keys equal to
+    the uncut run without the limit and to the oracle, both orientations as single calls.  That a call refuses a cut
+    segment AND re-runs overflowed segments only shows that the cases reach the path (with a limit of 24 arms tier 3's
+    own launch overflows as well, so the counts do not tell which launch gave up)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import fuzz_k8
+
+    both = 0
+    for seed in (4, 101, 123):
+        text, cli, genbits = fuzz_k8.make_case(seed)
+        chunks = [(0, len(text) - 1)]
+        oidx = oracle.Index.build(text)
+        with asgart_amd.Index(text, oidx.sa) as idx:
+            idx.set_option("force_tier", 3)
+            idx.set_option("test_genbits", genbits)
+            sts = [asgart_amd.RunSettings.from_cli(reverse=rc, complement=rc, **cli) for rc in (False, True)]
+            idx.set_option("split", 0)
+            idx.set_option("test_cap_limit", -1)
+            whole = [idx.search_duplications_raw(chunks, st, with_keys=True) for st in sts]
+            for rc, got in zip((False, True), whole):
+                key = ("ranges", seed) if not rc else ("ranges", seed, rc)
+                if key not in _ORACLE_CACHE:
+                    _ORACLE_CACHE[key] = oidx.run_raw(chunks, oracle.make_settings(reverse=rc, complement=rc, **cli), threads=4)
+                eo, es = _ORACLE_CACHE[key]
+                assert np.array_equal(got[0], eo) and np.array_equal(got[1], es), (seed, rc, cli)
+            idx.set_option("split", 1)
+            idx.set_option("split_len", 256)
+            idx.set_option("split_warm", 128)
+            idx.set_option("split_min", 512)
+            idx.set_option("split_warm_max", 0)
+            idx.set_option("test_cap_limit", 24)
+            for j, st in enumerate(sts):
+                got = idx.search_duplications_raw(chunks, st, with_keys=True)
+                stt = idx.stats()
+                print(f"seed {seed} pass {j}: split_segments {stt.split_segments} split_refused {stt.split_refused} "
+                      f"overflow_segments {stt.overflow_segments}")
+                assert all(np.array_equal(a, b) for a, b in zip(got, whole[j])), (seed, j, cli)
+                both += 1 if stt.split_refused > 0 and stt.overflow_segments > 0 else 0
+    assert both > 0
+
+
 @pytest.mark.parametrize("block", range(6))
 def test_randomised_cut_cases_against_the_oracle(hiplib, block, monkeypatch):
     """The randomised evidence of the range scheme, on the driver's box: 60 cases of tools/fuzz_k8.py (tandem arrays of
