@@ -44,6 +44,7 @@ ABI_SYMBOLS = (
     "asgart_compute_scores_flags", "asgart_compute_scores_flags_shard", "asgart_compute_scores_flags_multi",
     "asgart_fasta_read", "asgart_fasta_counts", "asgart_fasta_copy", "asgart_fasta_read_text", "asgart_fasta_index",
     "asgart_fasta_source", "asgart_fasta_free", "asgart_fasta_timings", "asgart_fasta_geometry",
+    "asgart_index_set_tail_up", "asgart_tier_segments", "asgart_tier_profile",
 )
 
 
@@ -222,6 +223,13 @@ def load_library() -> C.CDLL:
     L.asgart_probe_hits.restype = C.c_int64
     L.asgart_get_stats.argtypes = [vp, C.c_uint32, C.POINTER(Stats)]
     L.asgart_get_stats.restype = C.c_int32
+    if hasattr(L, "asgart_tier_segments"):   # (ASGART_LIB may name an older build of the library: benchmarks against a parent)
+        L.asgart_index_set_tail_up.argtypes = [vp, C.c_int32, C.c_int64]
+        L.asgart_index_set_tail_up.restype = C.c_int32
+        L.asgart_tier_segments.argtypes = [vp, vp]
+        L.asgart_tier_segments.restype = C.c_int32
+        L.asgart_tier_profile.argtypes = [vp, vp]
+        L.asgart_tier_profile.restype = C.c_int32
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []
@@ -383,6 +391,17 @@ class Index:
     def set_option(self, name: str, value: int):
         """Tuning / test option (include/asgart_hip.h: asgart_index_set_option)."""
         _check(load_library().asgart_index_set_option(self._h, name.encode(), int(value)))
+
+    def set_tail_up(self, mode: int, hits: int = 0):
+        """The tail rule of the placement (include/asgart_hip.h: asgart_index_set_tail_up): mode 0 off, 1 where tiers share
+        a stream (the default), 2 always; hits > 0 replaces the tier table's thresholds (tests)."""
+        _check(load_library().asgart_index_set_tail_up(self._h, int(mode), int(hits)))
+
+    def tier_segments(self) -> Tuple[np.ndarray, int]:
+        """-> (segments placed per tier 1..7 by the last search call as uint64[7], how many the tail rule moved up)."""
+        out = np.zeros(8, dtype=np.uint64)
+        _check(load_library().asgart_tier_segments(self._h, _ptr(out)))
+        return out[:7].copy(), int(out[7])
 
     def check_sa(self) -> int:
         """GPU verifier of the resident suffix array: number of violating slots (0 = valid)."""
@@ -682,6 +701,15 @@ def tier_plan(budget: int, n_work, tier_order: int, est_ms, main_ms: float = 0.0
     _check(load_library().asgart_tier_plan(int(budget), _ptr(work), int(tier_order), _ptr(est), float(main_ms),
                                            _ptr(stream_of), _ptr(launch)))
     return stream_of, launch
+
+
+def tier_profile() -> Tuple[np.ndarray, np.ndarray]:
+    """asgart_tier_profile (host code): (profile_ms float64[8]: [0] the runs over ranges, [t] tier t's estimated duration
+    before a call has measurements; tail_hits uint64[8]: tier t's threshold of the tail rule, 0 = none)."""
+    ms = np.zeros(8, dtype=np.float64)
+    hits = np.zeros(8, dtype=np.uint64)
+    _check(load_library().asgart_tier_profile(_ptr(ms), _ptr(hits)))
+    return ms, hits
 
 
 def compute_scores_multi(indices: Sequence[Index], sds: np.ndarray, reversed_: bool = False,

@@ -54,6 +54,7 @@ enum Counter {
                        // the extension (what neither more compute units nor more GPUs shorten)
     CT_CLUSTER_BARREN = 168,  // segments cluster_barren_kernel proved barren
     CT_CLUSTER_CUR = 169,     // its work cursors (two launches)
+    CT_TAIL_UP = 171,         // placement: segments the tail rule moved to the next tier that holds more (place_tier)
     CT_COUNT = 176
 };
 

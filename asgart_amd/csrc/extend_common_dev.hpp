@@ -176,12 +176,25 @@ __device__ inline void wg_begin(const ExtParams<PosT> &P) {
 }
 // (the slots are zero when a launch starts -- the host clears them, and a workgroup leaves its slot zero -- : the thread
 // that fetches the segments and the thread that closes the last one need not be the same)
+#ifdef ASGART_SEG_TOP
+constexpr unsigned long long kSegTopMin = 200000;  // (diagnostic build: 2 ms; the log holds 511 segments per tier)
+constexpr uint32_t kSegTopWords = 512;
+#endif
 template <class PosT>
 __device__ inline void seg_clock(const ExtParams<PosT> &P, bool last = false) {
     if (!P.seg_slots || P.tier < 2u || P.tier > (uint32_t)kRunsStat) return;  // (tier 1: a million tiny segments)
     const unsigned long long now = wall_clock64();
     const unsigned long long prev = atomicExch(&P.seg_slots[blockIdx.x & 4095u], last ? 0ull : now);
     if (prev && now > prev) atomicMax(&P.ctr[CT_SEGMAX1 + P.tier - 1u], now - prev);
+#ifdef ASGART_SEG_TOP
+    // diagnostic build (make segtop; never shipped): every segment of kSegTopMin ticks and more is also logged, per tier, in
+    // block 1 of the segment slots (tier 1 keeps no segment clock): 512 words per statistics slot, [count | durations]
+    if (prev && now > prev && now - prev >= kSegTopMin) {
+        unsigned long long *log = P.seg_slots - (size_t)4096 * (P.tier & 7u) + 4096 + (size_t)kSegTopWords * (P.tier & 7u);
+        const unsigned long long at = atomicAdd(log, 1ull);
+        if (at + 1u < kSegTopWords) log[1u + at] = now - prev;
+    }
+#endif
 }
 template <class PosT>
 __device__ inline void wg_busy(const ExtParams<PosT> &P) {

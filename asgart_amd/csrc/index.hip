@@ -1280,6 +1280,7 @@ int32_t asgart_index_clone(asgart_index *src, int32_t device, asgart_index **out
     idx->trim_end = src->trim_end;
     idx->wide = src->wide;
     idx->opt = src->opt;
+    idx->tail_up = src->tail_up;
     idx->h_tail = src->h_tail;
     for (auto &cx : idx->ctx) memset(&cx.stats, 0, sizeof(cx.stats));
     src->acquire_all();  // the source's buffers must not change under the copy
@@ -1404,6 +1405,22 @@ int32_t asgart_index_set_option(asgart_index *idx, const char *name, int64_t val
     if (rc == 0 && !strcmp(name, "test_fail_alloc")) asgart::fail_alloc_countdown().store(value);  // (process-wide)
     idx->release_all();
     return rc;
+}
+
+int32_t asgart_index_set_tail_up(asgart_index *idx, int32_t mode, int64_t hits) {
+    if (!idx) {
+        set_error("index is NULL");
+        return ASGART_E_ARG;
+    }
+    if (mode < 0 || mode > 2 || hits < 0 || hits > (1ll << 31)) {
+        set_error("asgart_index_set_tail_up: mode %d outside [0, 2] or %lld hits outside [0, 2^31]", (int)mode, (long long)hits);
+        return ASGART_E_ARG;
+    }
+    idx->acquire_all();  // never changes under a running call
+    idx->tail_up.mode = mode;
+    idx->tail_up.hits = hits;
+    idx->release_all();
+    return 0;
 }
 
 int64_t asgart_index_check_sa(asgart_index *idx) {

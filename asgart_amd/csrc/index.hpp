@@ -208,6 +208,7 @@ struct SearchCtx {
     double plan_est[8] = {};
     Workspace ws;
     asgart_stats stats;
+    uint64_t tier_segments[8] = {};  // of the last call: segments placed per tier 1..7; [7]: how many of them the tail rule moved up
     RunParams last_rp;   // inputs of the last call, kept for the yardstick kernel
     bool has_last = false;
     bool raw_done = false;  // asgart_stats.raw_hits of the last call has been summed up (asgart_get_stats does it on demand)
@@ -375,6 +376,12 @@ struct Options {
     int64_t watchdog_s = 120;       // a search call whose device work makes no progress for this many seconds returns ASGART_E_HIP with the
                                     // last heartbeats of its kernels instead of waiting forever; 0: wait forever
 };
+// The tail rule of the placement (place_tier, pipeline_dev.hpp; the thresholds are TierTable's, pipeline.hip), set with
+// asgart_index_set_tail_up.  (Not an entry of the option table above.)
+struct TailUp {
+    int32_t mode = 1;  // 0: off; 1: on in calls with fewer tier streams than arm-resident tiers that can hold work; 2: always on (tests)
+    int64_t hits = 0;  // tests: > 0 replaces the table's thresholds -- for tiers 2, 4 and 5, whichever the table gives one
+};
 int32_t create_ctx_streams(SearchCtx &cx);
 // The normal-priority hardware queues this process may open: GPU_MAX_HW_QUEUES if it is set, otherwise HIP's default
 // of 4, clamped to 1..32 (the library reads the variable and never sets it).
@@ -474,6 +481,7 @@ struct asgart_index {
                                         // index's streams and buffers, every later call is refused
     double tail_ms[4] = {-1.0, -1.0, -1.0, -1.0};  // per orientation (reverse * 2 + complement): shortest extension time of an unsharded call so far
     asgart::Options opt;
+    asgart::TailUp tail_up;
     asgart::SearchCtx ctx[asgart::kNumCtx];
     int last_ctx = 0;  // context of the most recent search call (asgart_get_stats)
     std::mutex mu;

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <string>
 #include <thread>
 #include <utility>
@@ -89,6 +90,8 @@ struct TierShape {
     int64_t Options::*widen;  // the option that lets it accept segments whose arm BOUND is that percentage of cap() (null: none)
     bool early;               // what it gives up on is re-run as soon as it has ended (run_tiers)
     double profile_ms;        // its duration before a call has measurements (plan_estimates)
+    uint32_t tail_hits = 0;   // > 0: the tail rule's threshold (place_tier): segments with this many hits and more leave the tier
+    double tail_profile_ms = 0.0;  // ... and its duration without them: what replaces profile_ms in a call where the rule is in force
     constexpr uint32_t cap() const { return (uint32_t)(layers * slots); }
 };
 // shape[t][0]: tier t of the arm-resident set, shape[t][1]: of the LDS-array set, which takes over with
@@ -100,13 +103,20 @@ struct TierTable {
     static constexpr int kLong = k32 ? 2048 : 1024;  // table rows of the long shapes
     // (an empty entry is never placed into and never launched: launch_kernel refuses)
     static constexpr TierShape kNone = {TierKernel::none, 0, 0, 0, 0, 0, 1, 0, nullptr, false, 0.0};
-    static constexpr TierShape kWave = {TierKernel::wave, 64, 1, 256, kHitBatch, 0, 11, 256 * 8, nullptr, false, 4.6};
-    static constexpr TierShape kHbm = {TierKernel::heavy_hbm, kHeavyThreads, 1, 1, kHitBatch, 0, 1, 256, nullptr, false, 33.0};
-    static constexpr TierShape kK8 = {TierKernel::k8, 1024, k32 ? 5 : 4, 896, kHitBatch, kLong, 1, 256, &Options::cap3_pct, true, 67.0};
-    // profile_ms: the GRCh38-shaped profile (profiles/r06_cfg4_tier_cu_seconds.json: the longest segments of tiers 2..6
-    // -- tier 3's with the runs, which that profile counted with it --, tier 1's work over its compute units; tier 7 and
-    // the runs as tiers 6 and 3)
-    // {kernel, threads, layers, slots, hits, rows, wg_per_cu, grid, widen, early, profile_ms}
+    static constexpr TierShape kWave = {TierKernel::wave, 64, 1, 256, kHitBatch, 0, 11, 256 * 8, nullptr, false, 3.4};
+    static constexpr TierShape kHbm = {TierKernel::heavy_hbm, kHeavyThreads, 1, 1, kHitBatch, 0, 1, 256, nullptr, false, 56.6};
+    static constexpr TierShape kK8 = {TierKernel::k8, 1024, k32 ? 5 : 4, 896, kHitBatch, kLong, 1, 256, &Options::cap3_pct, true, 56.6};
+    // profile_ms: the GRCh38-shaped profile (profiles/tail_up_ab.json; the rows of tiers 2 and 5 and of the runs as
+    // profiles/r06_cfg4_tier_cu_seconds.json had them, which the new measurements bear out): the longest segments of tiers
+    // 2, 4 and 5, tier 1's work over its compute units, the runs' duration; tiers 3 and 6 (tier 7 as tier 6) the longer of
+    // their longest segment and the step's 14.5 CU-seconds spread over the chip (remember_plan_estimates).
+    // tail_hits of tier 4 (place_tier; 32-bit positions only: nothing of that size with 64-bit positions is measured).  What
+    // stays in tier 4 runs behind another tier, which ends 56-60 ms after the launches, and should end with the runs at 67 ms:
+    // about 7 ms, well inside the quarter of the runs that bounds a thresholded tier.  Tier 4's segments on its own kernel,
+    // ms / hits by rank: 35.5 / 471 K, 21.1 / 223 K, 13.1 / 145 K, 9.0 / 97 K, 7.05 / 35 K -> 36 000 hits.  Measured: 58 of
+    // 9 543 segments move, what stays takes 8.7 ms (tail_profile_ms: tier 4's estimate in a call where its threshold is in
+    // force; profile_ms where it is not).  Tiers 2 and 5 keep their segments (DESIGN_HISTORY.md has the whole derivation).
+    // {kernel, threads, layers, slots, hits, rows, wg_per_cu, grid, widen, early, profile_ms[, tail_hits, tail_profile_ms]}
     static constexpr TierShape shape[kTiers + 1][2] = {
         // the runs over ranges: tier 3's kernel, one workgroup per run (no default grid)
         {{kK8.kernel, kK8.threads, kK8.layers, kK8.slots, kK8.hits, kK8.rows, 1, 0, nullptr, false, 67.0}, kNone},
@@ -126,7 +136,7 @@ struct TierTable {
         {kK8, kNone},
         // 4: cold fields in LDS, probes with up to 512 hits | 32-bit positions: 3072 * 40 B + hits + scratch = 128 KiB of
         // LDS, 64-bit: 2048 * 60 B + hits + scratch = 132 KiB
-        {{TierKernel::fast, 256, k32 ? 4 : 2, 256, 512, 512, 4, 256 * 4, &Options::cap45_pct, false, 35.5},
+        {{TierKernel::fast, 256, k32 ? 4 : 2, 256, 512, 512, 4, 256 * 4, &Options::cap45_pct, false, 35.5, k32 ? 36000u : 0u, 8.7},
          {TierKernel::heavy_lds, kHeavyThreads, 1, k32 ? 2432 : 1664, kHitBatch, 0, 1, 256, nullptr, false, 35.5}},
         // 5
         {{TierKernel::fast, 512, k32 ? 4 : 2, 512, kHitBatch, 1024, 2, 256 * 2, &Options::cap45_pct, false, 53.0}, kNone},
@@ -135,8 +145,8 @@ struct TierTable {
         // to 40 % (a real overflow falls through the cascade).  With 64-bit positions the HBM tier is an order of
         // magnitude slower per probe and the bound three to four times what a segment really holds -- at cfg5 every
         // segment that went to tier 7 by its bound peaked below 4 096 arms: cap6w_pct.  | by 7/5, in place()
-        {{TierKernel::fast, 1024, k32 ? 5 : 4, 1024, kHitBatch, kLong, 1, 256, k32 ? &Options::cap6_pct : &Options::cap6w_pct, true, 33.0},
-         {TierKernel::heavy_hybrid, kHeavyThreads, 1, k32 ? 4608 : 3072, kHitBatch, 0, 1, 256, nullptr, true, 33.0}},
+        {{TierKernel::fast, 1024, k32 ? 5 : 4, 1024, kHitBatch, kLong, 1, 256, k32 ? &Options::cap6_pct : &Options::cap6w_pct, true, 56.6},
+         {TierKernel::heavy_hybrid, kHeavyThreads, 1, k32 ? 4608 : 3072, kHitBatch, 0, 1, 256, nullptr, true, 56.6}},
         // 7: whatever is left (place() sizes its slices and its grid, at most this one, by the bound on the live arms of
         // ANY segment)
         {kHbm, kHbm},
@@ -347,6 +357,7 @@ struct SearchCall {
     const int64_t n_chunks;      // entries of the chunk table: the chunk list once per pass
     const uint64_t k, step, n;
     const Options opt;           // options cannot change while this call holds a context
+    const TailUp tail_up;        // (nor the tail rule's settings)
     static constexpr size_t kCtrBytes = (size_t)CT_COUNT * 8;
     static constexpr size_t kSplitMirror = 512 << 10;  // (option split: host copy of Workspace::split_buf)
     using Tiers = TierTable<SlotT>;
@@ -380,6 +391,7 @@ struct SearchCall {
     size_t n_hrec = 0;
     bool arms_kernel = false, split_on = false;
     uint32_t tier_cap[kTiers + 1] = {};
+    uint32_t tail_hits[kTiers + 1] = {};  // the tail rule's thresholds of THIS call (0: tier t keeps its segments), place()
     char *d_split = nullptr;
     const uint32_t *order = nullptr;
     uint64_t n_t[kTiers] = {}, seg_off[kTiers + 1] = {};
@@ -407,18 +419,14 @@ struct SearchCall {
           n_shards(n_shards_), want_csr(want_csr_), fams(fams_), status_out(status_out_), rowoff_out(rowoff_out_),
           hits_out(hits_out_), w(cx_.ws), s(cx_.stream), st(&sts_[0]), fam_out(fams_ != nullptr),
           n_chunks(n_chunks_pass_ * (int64_t)n_passes_), k(sts_[0].probe_size), step(sts_[0].probe_size / 2),
-          n((uint64_t)idx_->n), opt(idx_->opt) {}
+          n((uint64_t)idx_->n), opt(idx_->opt), tail_up(idx_->tail_up) {}
 
     uint32_t pass_of_probe(uint32_t g) const { return std::min<uint32_t>(g / K, (uint32_t)n_passes - 1u); }
     uint32_t pass_offset(uint32_t g) const { return lo_lim + (g - pass_of_probe(g) * K); }  // from the start of its pass
     const TierShape &shape(int t) const { return Tiers::shape[t][arms_kernel ? 0 : 1]; }  // (t = 0: the runs over ranges)
     bool tier_enabled(int t) const { return t >= 1 && t <= kTiers && tier_cap[t] != 0; }
     // where what tier src gave up on is run again: the next tier that is in use and holds more arms
-    int next_holding_more(int src) const {
-        int dst = src + 1;
-        while (dst < kTiers && (!tier_enabled(dst) || tier_cap[dst] <= tier_cap[src])) ++dst;
-        return dst;
-    }
+    int next_holding_more(int src) const { return asgart::next_holding_more(tier_cap + 1, src); }
     double since_launch() const {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_launch).count();
     }
@@ -730,6 +738,19 @@ struct SearchCall {
             }
             pp.cap[0] = (uint32_t)std::min<int64_t>(opt.cap1, shape(1).cap());
         }
+        {   // the tail rule (place_tier): by default only where tiers must share a stream -- with a stream per arm-resident
+            // tier every launch lasts as long as its own longest segment and nothing waits behind it
+            int n_resident = 0;
+            for (int t = 2; t < kTiers; ++t)
+                n_resident += tier_enabled(t) && (shape(t).kernel == TierKernel::fast || shape(t).kernel == TierKernel::k8) ? 1 : 0;
+            const bool on = tail_up.mode == 2 || (tail_up.mode == 1 && cx.n_tier_st < n_resident);
+            for (int t = 1; t < kTiers; ++t) {
+                // (arm-resident shapes only: the LDS-array set keeps its segments whatever the settings)
+                const bool source = (t == 2 || t == 4 || t == 5) && shape(t).kernel == TierKernel::fast;
+                const uint32_t thr = !source ? 0u : tail_up.hits > 0 ? (uint32_t)std::min<int64_t>(tail_up.hits, 0xFFFFFFFFll) : shape(t).tail_hits;
+                pp.tail_hits[t - 1] = tail_hits[t] = on && tier_enabled(t) ? thr : 0u;
+            }
+        }
         int force_eff = force_tier;  // a forced tier that has no kernel in this mode: the next one that has
         while (force_eff > 1 && force_eff < kTiers && !tier_enabled(force_eff)) ++force_eff;
         pp.sum1 = kTier1MaxSum;
@@ -810,6 +831,21 @@ struct SearchCall {
                         t % 2 ? "hits" : "probe positions", g0, info.y & 0x7FFFFFFFu, (info.y >> 31) ? "" : " (cut short by the window)", info.x);
             }
             (void)hipFree(d_top);
+            // ... and the hit totals of the 48 richest segments every tier runs whole (its list is sorted by them: they start first)
+            std::vector<uint32_t> h_keys((size_t)n_seg);
+            std::vector<uint2> h_info((size_t)n_seg);
+            (void)hipMemcpy(h_keys.data(), kbuf, (size_t)n_seg * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(h_info.data(), pp.seg_info, (size_t)n_seg * sizeof(uint2), hipMemcpyDeviceToHost);
+            for (uint32_t t = 1; t < (uint32_t)kTiers; ++t) {
+                std::vector<uint32_t> rich;
+                for (size_t sj = 0; sj < (size_t)n_seg; ++sj)
+                    if (h_keys[sj] >> 29 == t) rich.push_back(h_info[sj].x);
+                const size_t top = std::min<size_t>(rich.size(), 48);
+                std::partial_sort(rich.begin(), rich.begin() + top, rich.end(), std::greater<uint32_t>());
+                fprintf(stderr, "[asgart] tier %u, run whole, the most hits:", t + 1);
+                for (size_t i = 0; i < top; ++i) fprintf(stderr, " %u", rich[i]);
+                fprintf(stderr, "\n");
+            }
         }
         order = nullptr;
         const uint32_t *sorted_keys = nullptr;
@@ -824,7 +860,9 @@ struct SearchCall {
             seg_off[t + 1] = seg_off[t] + n_t[t];
             h_tp[t] = h_ctr[CT_TPROBES1 + t];
             h_th[t] = h_ctr[CT_THITS1 + t];
+            cx.tier_segments[t] = n_t[t];
         }
+        cx.tier_segments[kTiers] = h_ctr[CT_TAIL_UP];
         h_split_hdr = reinterpret_cast<const unsigned long long *>(h_split);
         n_runs = split_on ? (uint32_t)h_split_hdr[0] : 0u;
         n_cuts = split_on ? (uint32_t)h_split_hdr[1] : 0u;
@@ -849,6 +887,8 @@ struct SearchCall {
             }
             fprintf(stderr, "; %llu barren (no arm can reach min_duplication_length: not run), %llu of them by the positions of their hits\n",
                     (unsigned long long)n_seg - placed, (unsigned long long)h_ctr[CT_CLUSTER_BARREN]);
+            fprintf(stderr, "[asgart] tail rule: thresholds (hits) of tiers 2, 4, 5: %u %u %u; %llu segment(s) moved to the next tier that holds more\n",
+                    pp.tail_hits[1], pp.tail_hits[3], pp.tail_hits[4], (unsigned long long)h_ctr[CT_TAIL_UP]);
             if (cluster_barren) {
                 float ms_a = 0.f, ms_b = 0.f, ms_p = 0.f;
                 (void)hipEventElapsedTime(&ms_a, cx.ev[EV_BARREN], cx.ev[EV_BARREN_SMALL]);
@@ -1401,6 +1441,21 @@ struct SearchCall {
             for (int t = 1; t <= kTiers; ++t) fprintf(stderr, " %d: %.2f", t, (double)tier_longest(t) * 1e-5);
             fprintf(stderr, "\n");
         }
+#ifdef ASGART_SEG_TOP
+        if (opt.debug) {  // diagnostic build: the 48 longest segments per tier (seg_clock's log)
+            std::vector<unsigned long long> log(4096);
+            HIP_TRY(hipMemcpy(log.data(), w.seg_slots.as<unsigned long long>() + 4096, log.size() * 8, hipMemcpyDeviceToHost));
+            for (int stat = 2; stat <= kRunsStat; ++stat) {
+                unsigned long long *l = log.data() + (size_t)kSegTopWords * (stat & 7);
+                const size_t n_log = (size_t)std::min<unsigned long long>(l[0], kSegTopWords - 1);
+                std::sort(l + 1, l + 1 + n_log, std::greater<unsigned long long>());
+                fprintf(stderr, "[asgart] %s%d: %llu segments of %.1f ms and more; the longest (ms):", stat == kRunsStat ? "runs, as tier " : "tier ",
+                        stat == kRunsStat ? Tiers::kRunsTier : stat, l[0], (double)kSegTopMin * 1e-5);
+                for (size_t i = 0; i < std::min<size_t>(n_log, 48); ++i) fprintf(stderr, " %.2f", (double)l[1 + i] * 1e-5);
+                fprintf(stderr, "\n");
+            }
+        }
+#endif
         remember_plan_estimates();
         return 0;
     }
@@ -1408,17 +1463,28 @@ struct SearchCall {
     // ---- the estimates of the tier plan (tier_plan) ---------------------------------------------------------------------------
     // est[t]: tier t's estimated duration in ms, est[0]: the runs over ranges -- what the previous call with the same
     // call_sig measured (remember_plan_estimates), else the table's profile
+    // (what remembered estimates belong to: the call's settings and chunks, and the thresholds its placement moved tails by)
+    uint64_t plan_sig() const {
+        uint64_t sig = call_sig;
+        for (int t = 1; t <= kTiers; ++t) sig = (sig ^ tail_hits[t]) * 1099511628211ull;
+        return sig;
+    }
     void plan_estimates(double *est) const {
-        const bool known = cx.plan_known && cx.plan_sig == call_sig;
-        for (int t = 0; t <= kTiers; ++t) est[t] = known && cx.plan_est[t] > 0.0 ? cx.plan_est[t] : stat_shape(t).profile_ms;
+        const bool known = cx.plan_known && cx.plan_sig == plan_sig();
+        for (int t = 0; t <= kTiers; ++t) {
+            const TierShape &sh = stat_shape(t);
+            // (a tier whose tail this call moved away: the profile's figure for what is left of it)
+            const double profile = tail_hits[t] && sh.tail_hits && sh.tail_profile_ms > 0.0 ? sh.tail_profile_ms : sh.profile_ms;
+            est[t] = known && cx.plan_est[t] > 0.0 ? cx.plan_est[t] : profile;
+        }
     }
     // per tier that ran: the longer of its longest segment and its work spread over the compute units its default grid can
     // hold -- tier 1's 2048 one-wave workgroups fill 186 of them, the others the whole chip (the runs over ranges have a
     // statistics slot of their own, kRunsStat, and their own estimate: their duration, est[0])
     void remember_plan_estimates() {
-        if (!(cx.plan_known && cx.plan_sig == call_sig))
+        if (!(cx.plan_known && cx.plan_sig == plan_sig()))
             for (double &e : cx.plan_est) e = 0.0;
-        cx.plan_sig = call_sig;
+        cx.plan_sig = plan_sig();
         cx.plan_known = true;
         for (int t = 1; t <= kTiers; ++t) {
             if (!tier_ran[t]) continue;
@@ -1435,6 +1501,17 @@ struct SearchCall {
             }
             cx.plan_est[0] = runs;
         }
+        // The launches whose workgroups hold whole compute units (tier 3, tier 6, tier 7, the runs) get a unit only when
+        // nothing else is left on it, and a GRCh38-shaped step is bound by compute-unit time: such a launch does not end
+        // before the chip has served the compute-unit time of everything that starts with it, however short its own
+        // longest segment (tier 6: 33.6 ms of longest segment, 36 ms of whole-unit work spread over the chip, traced at
+        // 0-59 ms beside the other tiers, whose 14.4 CU-seconds are 56 ms of the chip).
+        double chip_ms = 0.0;
+        auto ran = [&](int t) { return t ? tier_ran[t] : n_runs != 0; };
+        for (int t = 0; t <= kTiers; ++t)
+            if (ran(t)) chip_ms += (double)h_ctr[CT_BUSY1 + (t ? t : kRunsStat) - 1] * 1e-5 / stat_shape(t).wg_per_cu / 256.0;
+        for (int t = 0; t <= kTiers; ++t)
+            if (ran(t) && stat_shape(t).wg_per_cu == 1) cx.plan_est[t] = std::max(cx.plan_est[t], chip_ms);
     }
 
     // ---- records -> reference order -> families per pass ----------------------------------------------------------------------
@@ -2106,6 +2183,31 @@ int64_t asgart_probe_hits(asgart_index *idx, const uint64_t *chunks, int64_t n_c
         if (!hv.empty()) memcpy(hits, hv.data(), hv.size() * 8);
     }
     return (int64_t)st.size();
+}
+
+int32_t asgart_tier_segments(asgart_index *idx, uint64_t *out) {
+    if (!idx || !out) {
+        set_error("bad argument");
+        return ASGART_E_ARG;
+    }
+    idx->acquire_all();
+    const SearchCtx &cx = idx->ctx[idx->last_ctx];
+    for (int i = 0; i < 8; ++i) out[i] = cx.has_last ? cx.tier_segments[i] : 0;
+    idx->release_all();
+    return 0;
+}
+
+int32_t asgart_tier_profile(double *profile_ms, uint64_t *tail_hits) {
+    if (!profile_ms || !tail_hits) {
+        set_error("bad argument");
+        return ASGART_E_ARG;
+    }
+    for (int t = 0; t <= kTiers; ++t) {
+        const TierShape &sh = TierTable<uint32_t>::shape[t][0];
+        profile_ms[t] = sh.tail_hits && sh.tail_profile_ms > 0.0 ? sh.tail_profile_ms : sh.profile_ms;
+        tail_hits[t] = TierTable<uint32_t>::shape[t][0].tail_hits;
+    }
+    return 0;
 }
 
 int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out) {

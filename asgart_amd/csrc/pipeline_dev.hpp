@@ -1021,6 +1021,8 @@ struct PlaceParams {
                                 // tandem arrays); the sparse long ones (a chromosome against its homologue: a few hits per
                                 // probe, mostly run by one wave alone) go to tier 6's kernel -- set when tier 3 runs the
                                 // kernel with a control wave, whose step costs the same whatever the probe holds
+    uint32_t tail_hits[kTiers - 1];  // tail_hits[t - 1] > 0 (tiers 2, 4, 5): a segment its arm bound sends to tier t goes, with at least this
+                                // many hits, to the next tier that holds more instead (the tail rule, place_tier); 0: tier t keeps its own
 };
 
 // A segment that cannot emit anything need not run.  A family holds the arms whose RIGHT segment is at least M long
@@ -1057,10 +1059,25 @@ __device__ inline uint32_t placement_key(int tier, unsigned long long sum, uint3
     return (((uint32_t)tier - 1u) << 29) | low;
 }
 
+// The next tier above src that is in use and holds more arms than src (cap[t - 1]: tier t's capacity, 0: not in use; tier
+// kTiers takes whatever is left); tier `skip` is passed over.  Where the cascade re-runs what src gave up on (skip = 0), and
+// where the tail rule sends a long segment (skip = 3).
+__host__ __device__ inline int next_holding_more(const uint32_t *cap, int src, int skip = 0) {
+    int dst = src + 1;
+    while (dst < kTiers && (dst == skip || cap[dst - 1] == 0u || cap[dst - 1] <= cap[src - 1])) ++dst;
+    return dst;
+}
+
 // Tier of a segment from its live-arm bound, hit total and processed-probe count.  With long3 set,
 // tier 3 (lowest per-probe latency, one workgroup of 1024 threads per CU) only takes the long
 // segments whose serial chain is the critical path of a pass; everything else goes by capacity.
-__device__ inline int place_tier(uint32_t bound, unsigned long long sum, uint32_t n_probes, const PlaceParams &pp) {
+// The tail rule: a launch lasts as long as its longest segment, and a stream that carries two launches (a call has fewer
+// hardware queues than tiers) runs the second one's longest segment behind the first one's.  The few segments that make up
+// the tail of a thresholded tier -- those with tail_hits hits and more -- go to the next arm-resident workgroup tier (4, 5,
+// 6) that holds more, whose launch a longer segment bounds anyway.  More capacity is always safe; tier 3 is never entered
+// this way (long3 / dense3 / dense6 decide that, above and below).  *tail_up: the rule moved the segment.
+__device__ inline int place_tier(uint32_t bound, unsigned long long sum, uint32_t n_probes, const PlaceParams &pp, bool *tail_up) {
+    *tail_up = false;
     if (bound <= pp.cap[0] && sum <= pp.sum1) return 1;
     // tier 6 pays ~3x tier 3's time per probe (many arms per thread): its segments count as long
     // from a quarter of the threshold on
@@ -1073,6 +1090,13 @@ __device__ inline int place_tier(uint32_t bound, unsigned long long sum, uint32_
         if (t == 3 && pp.long3) continue;
         if (bound <= pp.cap[t - 1]) {
             if (t == 6 && pp.dense6 && bound <= pp.cap[2] && sum >= (unsigned long long)pp.dense6 * n_probes) return 3;
+            if (pp.tail_hits[t - 1] && sum >= (unsigned long long)pp.tail_hits[t - 1]) {
+                const int up = next_holding_more(pp.cap, t, 3);
+                if (up >= 4 && up <= 6) {
+                    *tail_up = true;
+                    return up;
+                }
+            }
             return t;
         }
     }
@@ -1142,9 +1166,11 @@ __global__ __launch_bounds__(64) void seg_stats_lanes_kernel(RunParams rp, const
         if (g >= g_end) done = true;
         if (have && done) {
             if (rp.tstar > 64u) bound = 0xFFFFFFFFu;  // no estimate for huge gap settings: largest tier
-            int tier = place_tier(bound, sum, n_probes, pp);
+            bool tail_up;
+            int tier = place_tier(bound, sum, n_probes, pp, &tail_up);
             if (mx > 1 && pp.force_tier > tier) tier = min(pp.force_tier, kTiers);
             if ((by_quiet || !window_cut) && segment_is_barren(pp, n_hit, g - g0)) tier = kTierBarren;
+            if (tail_up && tier != kTierBarren) atomicAdd(&ctr[CT_TAIL_UP], 1ull);
             keys[sidx] = placement_key(tier, sum, g0);
             vals[sidx] = g0;
             if (pp.seg_info)
@@ -1255,9 +1281,11 @@ __global__ __launch_bounds__(64) void seg_stats_kernel(RunParams rp, const uint3
         }
         if (rp.tstar > 64u) bound = 0xFFFFFFFFu;
         if (lane == 0) {
-            int tier = place_tier(bound, sum, n_probes, pp);
+            bool tail_up;
+            int tier = place_tier(bound, sum, n_probes, pp, &tail_up);
             if (mx > 1 && pp.force_tier > tier) tier = min(pp.force_tier, kTiers);
             if ((done || !window_cut) && segment_is_barren(pp, n_hit, min(g_stop, g_end) - g0)) tier = kTierBarren;
+            if (tail_up && tier != kTierBarren) atomicAdd(&ctr[CT_TAIL_UP], 1ull);
             keys[sidx] = placement_key(tier, sum, g0);
             vals[sidx] = g0;
             if (pp.seg_info)

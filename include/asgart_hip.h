@@ -209,6 +209,16 @@ int32_t asgart_index_create_trim(const uint8_t *T, int64_t n, const int64_t *SA,
  * only).  Blocks until no call is in flight. */
 int32_t asgart_index_set_option(asgart_index *idx, const char *name, int64_t value);
 
+/* The tail rule of the placement.  A call with fewer hardware queues than extension tiers runs some tiers behind each
+ * other on one stream, and the second one's longest segment then starts when the first one's has ended.  The rule moves
+ * the few segments that make up the tail of tier 2, 4 or 5 (those with at least the tier's threshold of hits; the thresholds
+ * are part of the tier table, asgart_tier_profile) to the next arm-resident workgroup tier that holds more arms (4, 5 or 6,
+ * never tier 3), whose launch a longer segment bounds anyway.  mode 0: off; 1 (the default): on in calls with fewer tier
+ * streams than arm-resident tiers that can hold work; 2: always on.  hits > 0 replaces the table's thresholds (tests).
+ * RESULTS NEVER DEPEND ON EITHER.  Blocks until no call is in flight.  ASGART_E_ARG: mode outside 0..2, hits outside
+ * 0..2^31. */
+int32_t asgart_index_set_tail_up(asgart_index *idx, int32_t mode, int64_t hits);
+
 /* O(n) verifier of the suffix array held by the index, on the GPU: SA must be a permutation of
  * 0..n-1 whose adjacent suffixes are in strictly increasing bytewise order (the same rank trick as
  * the CPU oracle's checker).  Returns the number of violating slots (0 = valid), < 0 on error.
@@ -508,6 +518,16 @@ int64_t asgart_probe_hits(asgart_index *idx, const uint64_t *chunks, int64_t n_c
  * `flags` extra (untimed) kernels also fill bisect_steps, the accounting fields and raw_hits; with
  * ASGART_STATS_RAW_HITS raw_hits alone (the probes the position filter answered are looked up for it). */
 int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out);
+
+/* Segments per extension tier as the last search call on this index placed them: out[t - 1] for tier t = 1..7 (barren
+ * segments, which are not run, are in none); out[7] = the segments the tail rule moved up (counted before the barren test
+ * by position and option force_tier). */
+int32_t asgart_tier_segments(asgart_index *idx, uint64_t *out);
+/* The tier table's figures a call starts from (host code, needs no device): profile_ms[0] = the runs over ranges,
+ * profile_ms[t] = tier t's estimated duration on the GRCh38-shaped profile (what asgart_tier_plan is fed before a call
+ * has measurements of its own), for a thresholded tier what is left of it where the tail rule is in force; tail_hits[t] =
+ * tier t's threshold of the tail rule, 0 = none (8 entries each). */
+int32_t asgart_tier_profile(double *profile_ms, uint64_t *tail_hits);
 
 /* Thread-local message of the last error returned on this thread. */
 const char *asgart_last_error(void);
