@@ -37,6 +37,8 @@ class FilterNs:
             cr = csum[sd.right + sd.right_length + 1] - csum[sd.right]
             a = np.float32(cl) / np.float32(sd.left_length)
             b = np.float32(cr) / np.float32(sd.right_length)
+            if a != a or b != b:  # f32::max ignores a NaN operand (0 / 0 of an empty arm)
+                return b if a != a else a
             return max(a, b)
 
         out = []

@@ -26,7 +26,9 @@ static float n_content(const sd_t *sd, const uint8_t *strand) { /* structs.rs:45
         cr += (strand[p] == 'n' || strand[p] == 'N');
     float a = (float)cl / (float)sd->left_length;
     float b = (float)cr / (float)sd->right_length;
-    return a > b ? a : b; /* f32::max */
+    if (a != a) return b; /* f32::max ignores a NaN operand (0 / 0 of an empty arm), whichever side it is on */
+    if (b != b) return a;
+    return a > b ? a : b;
 }
 
 static int subsegment(uint64_t xs, uint64_t xl, uint64_t ys, uint64_t yl) { /* asgart.rs:482-487 */
