@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "asgart_fasta_read", "asgart_fasta_counts", "asgart_fasta_copy", "asgart_fasta_read_text", "asgart_fasta_index",
     "asgart_fasta_source", "asgart_fasta_free", "asgart_fasta_timings", "asgart_fasta_geometry",
     "asgart_index_set_tail_up", "asgart_tier_segments", "asgart_tier_profile",
+    "asgart_slice_families", "asgart_slice_counts", "asgart_slice_copy", "asgart_slice_timings", "asgart_slice_free",
 )
 
 
@@ -230,6 +231,17 @@ def load_library() -> C.CDLL:
         L.asgart_tier_segments.restype = C.c_int32
         L.asgart_tier_profile.argtypes = [vp, vp]
         L.asgart_tier_profile.restype = C.c_int32
+    if hasattr(L, "asgart_slice_families"):
+        L.asgart_slice_families.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp, C.POINTER(vp)]
+        L.asgart_slice_families.restype = C.c_int32
+        L.asgart_slice_counts.argtypes = [vp, u64p, u64p]
+        L.asgart_slice_counts.restype = None
+        L.asgart_slice_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.asgart_slice_copy.restype = None
+        L.asgart_slice_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_slice_timings.restype = C.c_int32
+        L.asgart_slice_free.argtypes = [vp]
+        L.asgart_slice_free.restype = None
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []

@@ -231,9 +231,34 @@ def _sequences(source, records, device_index: int, sds, reversed_, complemented)
         return sequences(src, sds, reversed_, complemented)
 
 
+def _check_slice(slice_options, fmt: str) -> bool:
+    """Whether a run is sliced at all; everything about the options that can be refused before the run starts is (on every
+    rank: the format, conflicting options, patterns that do not compile or are too many)."""
+    from .slice import FORMATS, _masks
+
+    if fmt not in FORMATS:
+        raise ValueError(f"unknown format `{fmt}` (one of {', '.join(FORMATS)})")
+    if slice_options is None:
+        return fmt != "json"
+    slice_options.check()
+    for what in ("keep", "restrict", "exclude"):
+        _masks([], getattr(slice_options, what + "_fragments"), slice_options.regexp, what)
+    return slice_options.active() or fmt != "json"
+
+
+def _slice_run(post, strand, settings, slice_options, device_index: int):
+    """Rank 0, behind post_process: the result as arrays (what its JSON file would parse to), sliced on the GPU.
+    -> (the sliced ResultArrays, the surviving duplications in the run's own coordinates: what is scored and extracted)."""
+    from .slice import ResultArrays, SliceOptions, apply_arrays
+
+    arrays = ResultArrays.from_run(post[0], post[1], strand, settings)
+    cut, keys = apply_arrays(arrays, slice_options or SliceOptions(), device_index, with_keys=True)
+    return cut, np.ascontiguousarray(arrays.sds[keys])
+
+
 def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
-                        prefix: str = "", with_sequences: bool = False,
-                        reader: Optional[str] = None) -> Optional[Tuple[str, str]]:
+                        prefix: str = "", with_sequences: bool = False, reader: Optional[str] = None,
+                        slice_options=None, fmt: str = "json") -> Optional[Tuple[str, str]]:
     """A whole `asgart` run (reference src/bin/asgart.rs:731-822) on the ranks of `dist`, rank r on GPU device_index:
     rank 0 prepares the input and builds the index, replicate_index copies it to every rank, each rank runs its shard of
     the search (asgart_search_duplications_passes_shard), gather_families merges the families on rank 0, rank 0 runs the
@@ -245,37 +270,71 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     fills left_seq / right_seq from the raw records it read (asgart_amd.Source on its GPU): the text `asgart` followed by
     `asgart-extract -I` gives (extract.result_text), without its trailing newline.  reader: "device" (the default
     without --trim) reads the files on rank 0's GPU (prep.read_fasta_gpu: index and Source from one upload), "host" with
-    prep.read_records as before; the text is the same either way."""
+    prep.read_records as before; the text is the same either way.
+    slice_options (slice.SliceOptions) / fmt ("json", "gff2", "gff3"): the run followed by `asgart-slice` with those
+    options and that format, in one go.  No filter of asgart-slice looks at `identity`, so slicing commutes with scoring:
+    rank 0 slices the result on its GPU right behind post_process (slice.apply_arrays), and only the survivors -- in
+    their original coordinates, by the slice's keys -- are broadcast, scored and extracted.  The text is then what
+    `python -m asgart_amd.slice -f FMT OPTIONS` writes for the unsliced run's file (JSON with its trailing newline) and
+    the name is out_filename with the format's extension.  With no active option and "json" nothing changes: the same
+    path through the code, the same bytes.  dist None: one process, one GPU, no collective."""
     from .postprocess import out_filename, to_json_arrays
 
-    world, rank = dist.get_world_size(), dist.get_rank()
+    world, rank = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_duplications: --trim runs on one rank only")
     reader = _choose_reader(reader, settings)
-    comm = f"cuda:{device_index}" if dist.get_backend() == "nccl" else None
+    comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
+    sliced = _check_slice(slice_options, fmt)
     index = strand = records = source = None
     chunks = [None]
     try:
         if rank == 0:
             strand, chunk_list, index, records, source = _read_input(files, settings, device_index, reader, with_sequences)
             chunks = [chunk_list]
-        dist.broadcast_object_list(chunks, src=0)
+        if dist is not None:
+            dist.broadcast_object_list(chunks, src=0)
         if world > 1:
             index = replicate_index(index, dist, device_index)
         offs, sds, keys = index.search_duplications_passes(chunks[0], [settings], shard=rank, n_shards=world,
                                                            with_keys=True)[0]
-        got = gather_families(offs, sds, dist, comm, keys=keys)
+        if dist is not None:
+            got = gather_families(offs, sds, dist, comm, keys=keys)
+        else:
+            from . import merge_shards
+
+            got = merge_shards([(offs, sds, keys)])
         post = index.post_process(*got) if rank == 0 else None
+        cut = failed = None
+        survivors = post[1] if rank == 0 else None
+        if sliced and rank == 0:
+            try:   # (a refusal must not leave the other ranks waiting in the collectives below)
+                cut, survivors = _slice_run(post, strand, settings, slice_options, device_index)
+            except ValueError as e:
+                failed, survivors = e, np.zeros((0, 4), dtype=np.uint64)
         ident = None
         if compute_score:
-            kept = _broadcast_array(post[1] if rank == 0 else None, dist, comm)
-            ident = compute_scores(index, kept, settings.reverse, settings.complement, dist, comm)
+            if dist is not None:
+                kept = _broadcast_array(survivors, dist, comm)
+                ident = compute_scores(index, kept, settings.reverse, settings.complement, dist, comm)
+            else:
+                ident = index.compute_scores(survivors, settings.reverse, settings.complement)
+        if failed is not None:
+            raise failed
         if rank != 0:
             return None
         seqs = None
         if with_sequences:
-            seqs = _sequences(source, records, device_index, post[1], settings.reverse, settings.complement)
-        return to_json_arrays(post[0], post[1], strand, settings, ident, seqs), out_filename(files, settings, prefix)
+            seqs = _sequences(source, records, device_index, survivors, settings.reverse, settings.complement)
+        name = out_filename(files, settings, prefix)
+        if not sliced:
+            return to_json_arrays(post[0], post[1], strand, settings, ident, seqs), name
+        from .slice import export_arrays
+
+        if ident is not None:
+            cut.identity = np.ascontiguousarray(ident, dtype=np.float32)
+        cut.seqs = seqs
+        return export_arrays(cut, fmt), os.path.splitext(name)[0] + "." + fmt
     finally:
         if source is not None:
             source.close()
@@ -298,7 +357,9 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     orientation], merged JSON text) and None elsewhere: each text is byte-equal to search_duplications with that
     orientation, the merged one to postprocess.merge_results over those files in that order (RunResult::from_files,
     reference src/structs.rs:114-141: strand and settings of the first, every duplication with the flags of its own
-    run).  dist None: one process, one GPU, no collective.  `--trim` needs one rank.  reader: as search_duplications."""
+    run).  dist None: one process, one GPU, no collective.  `--trim` needs one rank.  reader: as search_duplications.
+    Slicing (search_duplications' slice_options / fmt) is out of scope here: `python -m asgart_amd.slice` does it on the
+    files this writes."""
     from dataclasses import replace
 
     from . import merge_shards, orientation_flags
@@ -385,6 +446,13 @@ def _parse(argv):
     ap.add_argument("--host-reader", action="store_true",
                     help="read and prepare the FASTA files on the host (prep.read_records) instead of on rank 0's GPU; "
                          "the result is the same")
+    ap.add_argument("--format", choices=("json", "gff2", "gff3"), default="json",
+                    help="the format of the output file, as asgart-slice -f writes it")
+    from .slice import add_filter_arguments
+
+    # asgart-slice's filters under its names, but for the two this tool already uses for the search itself
+    add_filter_arguments(ap.add_argument_group("slice the result before it is scored and written (asgart-slice)"),
+                         {"min_length": ("--slice-min-length",), "collapse": ("--collapse",)}, dest_prefix="slice_")
     ap.add_argument("--prefix", default="")
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
@@ -410,6 +478,13 @@ def _parse(argv):
         ap.error("--orientations names the orientations: not together with -R / -C")
     if args.merged and not args.orientations:
         ap.error("--merged needs --orientations")
+    from .slice import options_from_args
+
+    args.slice_options = options_from_args(args, "slice_")
+    if args.slice_no_inter and args.slice_no_inter_relaxed:
+        ap.error("the argument '--no-inter-relaxed' cannot be used with '--no-inter'")
+    if args.orientations and (args.slice_options.active() or args.format != "json"):
+        ap.error("--orientations writes unsliced JSON files: slice them with python -m asgart_amd.slice")
     return args
 
 
@@ -489,7 +564,7 @@ def rank_main(argv) -> int:
             texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])
         else:
             out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix,
-                                      args.with_sequences, reader)
+                                      args.with_sequences, reader, args.slice_options, args.format)
             texts = None if out is None else [out]
         for text, name in texts or []:
             path = os.path.join(args.out_dir, name)

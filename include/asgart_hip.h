@@ -436,6 +436,70 @@ void asgart_source_destroy(asgart_source *src);
 int32_t asgart_extract_sequences(asgart_source *src, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
                                  int64_t first, uint8_t *out, uint64_t out_cap, uint64_t *seq_ends, int64_t *n_done);
 
+/* ---- the filters of asgart-slice on a result held as arrays ------------------------------------------------
+ * Replaces the per-duplication work of reference src/bin/asgart-slice.rs:126-191 for a RunResult of any size: the arm
+ * rewrite of RunResult::flatten (src/structs.rs:401-414), the retains of remove_direct .. remove_intra (:143-194), of
+ * --min-length (asgart-slice.rs:150-155), max_family_members (:196-198), keep_ / restrict_ / exclude_fragments and their
+ * _regexp forms (:232-348), every `families.retain(|f| !f.is_empty())`, and the global positions consolidate_families
+ * (:216-227) and exclude_fragments (:311-318) recompute.  It needs no index and no source: only `device`.
+ * Names never reach the device.  The host keeps a NAME TABLE (every fragment name of the map once, then every other name
+ * an arm carries, such as "unknown") and answers each question that looks at a name per entry of that table -- the
+ * reference asks them per arm, with string compares (`to_keep.iter().any(..)`, `to_flatten.iter().any(..)`):
+ *   new_id, addend   flatten: the arm's name id and what is added to its chr_*_position (:405-412); both NULL: no collapse
+ *   keep_mask        bit p set where the name passes pattern p of --keep-fragments (a literal list is ONE bit: the name
+ *                    is in it); a duplication stays iff ((mask[left] | mask[right]) & keep_all) == keep_all -- the
+ *                    patterns of -E are applied one after the other (asgart-slice.rs:159-169), so they intersect
+ *   restrict_mask    the same for --restrict-fragments: ((mask[left] & mask[right]) & restrict_all) == restrict_all
+ *   exclude          bit 0: the name is excluded by any pattern (or is in the literal list); bit 1: by the FIRST pattern
+ *                    (the list); bit 2: the name is not in the map as keep / restrict left it.  A duplication that passes
+ *                    keep, restrict and the first exclusion with bit 2 on an arm is where the reference panics
+ *                    (`find_chr(..).unwrap()`, :313-316): ASGART_E_ARG, the message names the first such input ordinal
+ *   final_pos        the position of the first fragment of that name in the final map, -1 when the map has none
+ * table_len[0..5] are the entries of the six tables in this order; each table in use must have n_names of them.
+ * options: flags_set / flags_clear are the flag bits (bit 0 reversed, bit 1 complemented) a survivor must / must not have
+ * (--no-direct: set 1, --no-reversed: clear 1, --no-uncomplemented: set 2, --no-complemented: clear 2); inter_mode 1 is
+ * --no-inter, 2 --no-inter-relaxed with collapsed_id the id of ASGART_COLLAPSED (-1: no such name); drop_empty is set when
+ * any step runs that drops the families it emptied (every one but collapse and max_family_members); relocate when the
+ * global positions are recomputed (keep, restrict or exclude ran): final_pos[id] + chr position, or 0 (`map_or(0, ..)`).
+ * Order, as the reference's: collapse; the flag, inter / intra and length filters; max_family_members on the sizes they
+ * leave (with drop_empty a family they emptied is gone before it is asked); keep, restrict, exclude.
+ * in: fam_offsets[n_families + 1], sds[n_sd] (global coordinates), flags[n_sd], chr[2 n_sd] name ids (left, right),
+ * chr_pos[2 n_sd].  out (asgart_slice_counts / _copy / _free): the surviving families and duplications IN INPUT ORDER
+ * with the rewritten chr, chr_pos and global positions, and keys[q] = the input ordinal of surviving duplication q, by
+ * which the caller gathers what the slice does not look at (identity, sequences).  Every copy target is nullable.
+ * Checked on the host before anything is launched (ASGART_E_ARG): fam_offsets not starting at 0, decreasing or not ending
+ * at n_sd; a name id outside the table; a table in use that is NULL or not n_names long. */
+typedef struct asgart_slice asgart_slice;
+typedef struct asgart_slice_options {
+    uint8_t flags_set, flags_clear;
+    uint8_t inter_mode;           /* 0 none, 1 --no-inter, 2 --no-inter-relaxed          */
+    uint8_t no_intra;
+    uint8_t drop_empty, relocate;
+    uint8_t has_min_length, has_max_family;
+    int32_t collapsed_id;
+    uint32_t keep_all, restrict_all;  /* the bits of the patterns in use; 0: option off  */
+    uint32_t exclude;                 /* 0 / 1                                           */
+    uint64_t min_length, max_family_members;
+} asgart_slice_options;
+typedef struct asgart_slice_tables {
+    int64_t n_names;
+    const int32_t *new_id;
+    const uint64_t *addend;
+    const uint32_t *keep_mask, *restrict_mask;
+    const uint8_t *exclude;
+    const int64_t *final_pos;
+    int64_t table_len[6];
+} asgart_slice_tables;
+int32_t asgart_slice_families(int32_t device, const uint64_t *fam_offsets, int64_t n_families, const asgart_proto_sd *sds,
+                              const uint8_t *flags, const int32_t *chr, const uint64_t *chr_pos, int64_t n_sd,
+                              const asgart_slice_tables *tables, const asgart_slice_options *options, asgart_slice **out);
+void asgart_slice_counts(const asgart_slice *r, uint64_t *n_families, uint64_t *n_sds);
+void asgart_slice_copy(const asgart_slice *r, uint64_t *fam_offsets, asgart_proto_sd *sds, int32_t *chr, uint64_t *chr_pos,
+                       uint8_t *flags, int64_t *keys);
+/* Milliseconds of the call behind r: [0] the whole call, [1] its kernels (HIP events), [2] of those the compaction. */
+int32_t asgart_slice_timings(const asgart_slice *r, double *ms3);
+void asgart_slice_free(asgart_slice *r);
+
 /* ---- FASTA files read on the GPU ---------------------------------------------------------------------------
  * Replace the FASTA reader in front of prepare_data and prepare_data itself (reference src/bin/asgart.rs:273-430: bio's
  * fasta::Reader and the per-record loop at :278-313, normalisation :289-301, find_chunks_to_process :317-366,
