@@ -46,6 +46,8 @@ ABI_SYMBOLS = (
     "asgart_fasta_source", "asgart_fasta_free", "asgart_fasta_timings", "asgart_fasta_geometry",
     "asgart_index_set_tail_up", "asgart_tier_segments", "asgart_tier_profile",
     "asgart_slice_families", "asgart_slice_counts", "asgart_slice_copy", "asgart_slice_timings", "asgart_slice_free",
+    "asgart_plot_filter", "asgart_plot_counts", "asgart_plot_copy", "asgart_plot_timings", "asgart_plot_free",
+    "asgart_plot_geometry",
 )
 
 
@@ -242,6 +244,20 @@ def load_library() -> C.CDLL:
         L.asgart_slice_timings.restype = C.c_int32
         L.asgart_slice_free.argtypes = [vp]
         L.asgart_slice_free.restype = None
+    if hasattr(L, "asgart_plot_filter"):
+        L.asgart_plot_filter.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_int64,
+                                         vp, C.POINTER(C.c_int64), C.POINTER(vp)]
+        L.asgart_plot_filter.restype = C.c_int32
+        L.asgart_plot_counts.argtypes = [vp, u64p, u64p, u64p]
+        L.asgart_plot_counts.restype = None
+        L.asgart_plot_copy.argtypes = [vp, vp, vp, vp]
+        L.asgart_plot_copy.restype = None
+        L.asgart_plot_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_plot_timings.restype = C.c_int32
+        L.asgart_plot_free.argtypes = [vp]
+        L.asgart_plot_free.restype = None
+        L.asgart_plot_geometry.argtypes = [u64p, u64p]
+        L.asgart_plot_geometry.restype = None
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []

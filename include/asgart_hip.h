@@ -500,6 +500,55 @@ void asgart_slice_copy(const asgart_slice *r, uint64_t *fam_offsets, asgart_prot
 int32_t asgart_slice_timings(const asgart_slice *r, double *ms3);
 void asgart_slice_free(asgart_slice *r);
 
+/* ---- the filters of asgart-plot on a result held as arrays --------------------------------------------------
+ * Replaces the per-duplication work of reference src/bin/asgart-plot.rs:463-481: the retains of --min-length (:463-465:
+ * max(left_length, right_length) >= min_length; slice's asks the shorter arm) and of --min-identity / --max-identity
+ * (:467-469: f32 compares, a NaN fails), then filter_families_in_features (:20-70), filter_duplicons_in_features (:72-119)
+ * and filter_features_in_sds (:121-163), which the reference answers by testing every duplication against every position
+ * of every feature of every track.  Here each is an interval join: two radix sorts and two bisections per arm for the
+ * intervals in which nothing wraps mod 2^64, the literal `_overlap` (:25-30) on the wrapped values for the rest.
+ * Names never reach the device.  The feature tracks come flattened in the order track, feature, position: per position
+ * pos_start (GLOBAL: `chr.position + start` of a Relative position against the map as the fragment filters left it, by
+ * the first fragment of that name), pos_length and pos_resolved (0: the map has no such fragment; start is ignored), and
+ * feat_offsets[n_features + 1], the CSR offsets of the features over the positions.  A window is
+ * (start - threshold, length + 2 * threshold), every operation wrapping as in the reference's release build.
+ * With U the first unresolved position:
+ *   filter_families   a family stays iff one of its duplications overlaps a window; with a U only positions before it are
+ *                     windows, and a non-empty family whose FIRST duplication overlaps none is the reference's panic
+ *   filter_duplicons  the same per duplication; families stay even when empty
+ *   filter_features   feature_keep[f] = 1 iff one of its positions overlaps an arm of a surviving duplication; an unresolved
+ *                     position with no overlapping position of its feature before it is the reference's panic
+ * The panic is ASGART_E_ARG with *err_position = the flat ordinal of the position to name (otherwise -1).
+ * Families emptied by the length and identity steps stay; filter_families drops the families it refuses.
+ * out (asgart_plot_counts / _copy / _free): the surviving family offsets, keys[q] = the input ordinal of survivor q in input
+ * order (the caller gathers everything else by it) and one keep byte per feature (all 1 without filter_features).
+ * force_literal sends every pair of every join through the literal kernel (a debug path: the results are the same).
+ * Checked on the host before anything is launched (ASGART_E_ARG): fam_offsets / feat_offsets not starting at 0, decreasing
+ * or not ending at n_sd / n_positions. */
+typedef struct asgart_plot asgart_plot;
+typedef struct asgart_plot_options {
+    uint8_t has_min_length, has_identity;
+    uint8_t filter_families, filter_duplicons, filter_features;   /* which of the three joins run  */
+    uint8_t force_literal;
+    float min_identity, max_identity;
+    uint64_t min_length;
+    uint64_t families_threshold, duplicons_threshold, features_threshold;
+} asgart_plot_options;
+int32_t asgart_plot_filter(int32_t device, const uint64_t *fam_offsets, int64_t n_families, const asgart_proto_sd *sds,
+                           const float *identity, int64_t n_sd, const uint64_t *feat_offsets, int64_t n_features,
+                           const uint64_t *pos_start, const uint64_t *pos_length, const uint8_t *pos_resolved,
+                           int64_t n_positions, const asgart_plot_options *options, int64_t *err_position,
+                           asgart_plot **out);
+void asgart_plot_counts(const asgart_plot *r, uint64_t *n_families, uint64_t *n_sds, uint64_t *n_features);
+void asgart_plot_copy(const asgart_plot *r, uint64_t *fam_offsets, int64_t *keys, uint8_t *feature_keep);
+/* Milliseconds of the call behind r: [0] the whole call, [1] from its first kernel to its last (HIP events; the small
+ * read-backs between the stages included), [2] of those the interval joins. */
+int32_t asgart_plot_timings(const asgart_plot *r, double *ms3);
+void asgart_plot_free(asgart_plot *r);
+/* Sizes the joins work in, for tests that place their counts on the seams: threads per workgroup, targets per LDS tile
+ * of the literal kernel. */
+void asgart_plot_geometry(uint64_t *block_threads, uint64_t *tile_windows);
+
 /* ---- FASTA files read on the GPU ---------------------------------------------------------------------------
  * Replace the FASTA reader in front of prepare_data and prepare_data itself (reference src/bin/asgart.rs:273-430: bio's
  * fasta::Reader and the per-record loop at :278-313, normalisation :289-301, find_chunks_to_process :317-366,
