@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "asgart_fasta_read", "asgart_fasta_counts", "asgart_fasta_copy", "asgart_fasta_read_text", "asgart_fasta_index",
     "asgart_fasta_source", "asgart_fasta_free", "asgart_fasta_timings", "asgart_fasta_geometry",
     "asgart_index_set_tail_up", "asgart_tier_segments", "asgart_tier_profile",
+    "asgart_fill_counts", "asgart_fill_tally", "asgart_ranked_fill_takes",
     "asgart_slice_families", "asgart_slice_counts", "asgart_slice_copy", "asgart_slice_timings", "asgart_slice_free",
     "asgart_plot_filter", "asgart_plot_counts", "asgart_plot_copy", "asgart_plot_timings", "asgart_plot_free",
     "asgart_plot_geometry",
@@ -233,6 +234,13 @@ def load_library() -> C.CDLL:
         L.asgart_tier_segments.restype = C.c_int32
         L.asgart_tier_profile.argtypes = [vp, vp]
         L.asgart_tier_profile.restype = C.c_int32
+    if hasattr(L, "asgart_fill_counts"):
+        L.asgart_fill_counts.argtypes = [vp, vp]
+        L.asgart_fill_counts.restype = C.c_int32
+        L.asgart_fill_tally.argtypes = [vp, vp]
+        L.asgart_fill_tally.restype = C.c_int32
+        L.asgart_ranked_fill_takes.argtypes = [C.c_uint64, C.c_uint64, C.c_int32]
+        L.asgart_ranked_fill_takes.restype = C.c_int32
     if hasattr(L, "asgart_slice_families"):
         L.asgart_slice_families.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp, C.POINTER(vp)]
         L.asgart_slice_families.restype = C.c_int32
@@ -430,6 +438,19 @@ class Index:
         out = np.zeros(8, dtype=np.uint64)
         _check(load_library().asgart_tier_segments(self._h, _ptr(out)))
         return out[:7].copy(), int(out[7])
+
+    def fill_counts(self) -> np.ndarray:
+        """-> uint64[6]: rows and entries read of the small, the streamed and the ranked hit-row fill of the last search call
+        (asgart_fill_counts; the ranked fill is governed by ASGART_RANKED_FILL when the index is created)."""
+        out = np.zeros(6, dtype=np.uint64)
+        _check(load_library().asgart_fill_counts(self._h, _ptr(out)))
+        return out
+
+    def fill_tally(self) -> np.ndarray:
+        """-> uint64[4, 3]: rows, interval entries and kept hits of the last search call's large hit rows, by class (asgart_fill_tally)."""
+        out = np.zeros(12, dtype=np.uint64)
+        _check(load_library().asgart_fill_tally(self._h, _ptr(out)))
+        return out.reshape(4, 3)
 
     def check_sa(self) -> int:
         """GPU verifier of the resident suffix array: number of violating slots (0 = valid)."""

@@ -446,6 +446,19 @@ constexpr uint32_t kPending = 0xFFFFFFFDu;   // large interval, counted by the w
 constexpr uint32_t kPendingRank = 0xFFFFFFFCu;  // ... by bisection of its position-sorted list (rank_count_kernel); both
                                                 // marks are gone when the probe search is over
 
+// Hit rows of frequent k-mers filled from their KEPT occurrences (fill_ranked_kernel): the hit filter keeps a tail of the
+// position-sorted list, cnt (+ 1) entries of it instead of the R entries of the suffix-array interval.
+constexpr int kRankedCap = 512;    // rows of up to this many kept hits: nine loads of 64 entries cover cnt + 1
+constexpr int kRankedMaxR = 1 << 16;  // ... out of intervals of up to this many entries: the wave's bitmap of the interval in LDS
+constexpr int kRankedSlack = 64;   // (the set-up of a row and its placement have to be paid for by the entries not streamed)
+// Does the ranked fill take a row of `cnt` kept hits out of an interval of R?  (A count of words fetched only: the clearing
+// and the scan of the row's bitmap, R / 32 words of LDS, are not in it.)  mode: 0 never, 1 when it fetches clearly
+// less than the stream (two words per kept occurrence against one per entry of the interval), 2 whenever it can (tests).
+__host__ __device__ inline bool ranked_fill_takes(uint64_t R, uint64_t cnt, int mode) {
+    if (mode <= 0 || cnt == 0 || cnt > (uint64_t)kRankedCap || R <= (uint64_t)kRankMin || R > (uint64_t)kRankedMaxR) return false;
+    return mode >= 2 || R > 2u * cnt + (uint64_t)kRankedSlack;
+}
+
 inline bool valid_text_byte(uint8_t c) {
     return c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N' || c == '$';
 }

@@ -34,6 +34,7 @@ enum Counter {
     CT_EARLY_CUR = 36,  // ... and work cursors
     CT_RANK = 38,       // entries in rank_list (large intervals counted by bisection of the position-sorted lists)
     CT_BIG0 = 39,       // entries of big_list that big_count_kernel counted (later ones were appended for the fill)
+    CT_RANKED = 40,     // entries in ranked_list (rows rank_count_kernel gives to fill_ranked_kernel instead of big_list)
     CT_ALG_BYTES = 68,  // accounting pass: bytes the probe-search kernels move by design
     CT_FLT_REJECTED,    // accounting pass: probes answered by the position bits alone
     CT_LONGSEG,         // placement: segments the lane-per-segment walk handed to the wave-per-segment kernel
@@ -55,7 +56,8 @@ enum Counter {
     CT_CLUSTER_BARREN = 168,  // segments cluster_barren_kernel proved barren
     CT_CLUSTER_CUR = 169,     // its work cursors (two launches)
     CT_TAIL_UP = 171,         // placement: segments the tail rule moved to the next tier that holds more (place_tier)
-    CT_COUNT = 176
+    CT_FILL_ACCT = 176,       // fill_account_kernel (asgart_fill_counts, asgart_fill_tally): its 18 sums
+    CT_COUNT = 196
 };
 
 __device__ inline int chunk_of(const ChunkTable &ch, uint32_t g) {

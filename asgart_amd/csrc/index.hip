@@ -221,6 +221,14 @@ int32_t option_set(Options &o, const char *name, int64_t value) {
 }
 
 // ASGART_<NAME> for every option; malformed or out-of-range values are ignored (defaults stay)
+int ranked_fill_from_env() {
+    const char *e = getenv("ASGART_RANKED_FILL");
+    if (!e || !*e) return 1;
+    char *end = nullptr;
+    const long long v = strtoll(e, &end, 10);
+    return end && *end == 0 && v >= 0 && v <= 2 ? (int)v : 1;
+}
+
 void options_from_env(Options &o) {
     auto one = [&](const char *name) {
         char env[64] = "ASGART_";
@@ -551,6 +559,8 @@ static void free_k_specific(asgart_index *idx) {
     if (idx->d_c8hi) dev_free(idx->d_c8hi);
     if (idx->d_sap) dev_free(idx->d_sap);
     idx->d_sap = nullptr;
+    if (idx->d_sar) dev_free(idx->d_sar);
+    idx->d_sar = nullptr;
     for (auto &f : idx->d_pbits) {
         if (f) dev_free(f);
         f = nullptr;
@@ -636,14 +646,31 @@ static int32_t build_sap_locked(asgart_index *idx, uint64_t k) {
         idx->d_sap = nullptr;
         return 0;
     }
+    // the slots the entries came from (fill_ranked_kernel; 32-bit positions only): without the memory for them the hit rows
+    // are filled from the suffix array alone, as they are with ASGART_RANKED_FILL=0
+    if (!idx->wide && idx->ranked_fill != 0 && dev_malloc(&idx->d_sar, (n_sa + 16) * slot) != hipSuccess) {
+        (void)hipGetLastError();
+        idx->d_sar = nullptr;
+    }
     hipStream_t s = idx->ctx[0].stream;
     // (kRankMin of pipeline_dev.hpp: rank_count_kernel only consults the list of an interval of more than 256 entries)
-    const int32_t rc_rank =
-        idx->wide ? build_rank_lists_runs<uint64_t>(idx->d_keys, (const uint64_t *)idx->d_sa, n_sa, (uint64_t *)idx->d_sap, 256u, (int)k, s)
-                  : build_rank_lists_runs<uint32_t>(idx->d_keys, (const uint32_t *)idx->d_sa, n_sa, (uint32_t *)idx->d_sap, 256u, (int)k, s);
+    auto build = [&]() {
+        return idx->wide ? build_rank_lists_runs<uint64_t>(idx->d_keys, (const uint64_t *)idx->d_sa, n_sa, (uint64_t *)idx->d_sap,
+                                                           nullptr, 256u, (int)k, s)
+                         : build_rank_lists_runs<uint32_t>(idx->d_keys, (const uint32_t *)idx->d_sa, n_sa, (uint32_t *)idx->d_sap,
+                                                           (uint32_t *)idx->d_sar, 256u, (int)k, s);
+    };
+    int32_t rc_rank = build();
+    if (rc_rank == ASGART_E_OOM && idx->d_sar) {  // (the pairs sort takes more scratch than the keys sort: the lists alone, then)
+        dev_free(idx->d_sar);
+        idx->d_sar = nullptr;
+        rc_rank = build();
+    }
     if (rc_rank != 0) {
         dev_free(idx->d_sap);
         idx->d_sap = nullptr;
+        if (idx->d_sar) dev_free(idx->d_sar);
+        idx->d_sar = nullptr;
         if (rc_rank != ASGART_E_OOM) return rc_rank;
     }
     if (idx->opt.cache_calls == 0 || idx->calls_total >= (uint64_t)idx->opt.cache_calls) BlockCache::trim();  // (the sort's scratch)
@@ -1149,7 +1176,8 @@ static int32_t index_create_impl(const uint8_t *T, int64_t n, const int64_t *SA,
     idx->trimmed = trimmed;
     idx->trim_start = trim_start;
     idx->trim_end = trim_end;
-    options_from_env(idx->opt);  // the only place the environment is read
+    options_from_env(idx->opt);  // the only place the environment is read (with the line below)
+    idx->ranked_fill = ranked_fill_from_env();
     // force_wide (tests): 64-bit slots and positions also for a small text, so that the
     // instantiations a > 4 Gb input selects can be checked against the oracle
     idx->wide = (uint64_t)n >= 0xFFFFFF00ull || idx->opt.force_wide != 0;
@@ -1280,6 +1308,7 @@ int32_t asgart_index_clone(asgart_index *src, int32_t device, asgart_index **out
     idx->trim_end = src->trim_end;
     idx->wide = src->wide;
     idx->opt = src->opt;
+    idx->ranked_fill = src->ranked_fill;
     idx->tail_up = src->tail_up;
     idx->h_tail = src->h_tail;
     for (auto &cx : idx->ctx) memset(&cx.stats, 0, sizeof(cx.stats));
@@ -1356,6 +1385,7 @@ int32_t asgart_index_create_device(const void *d_text, int64_t n, const void *d_
     idx->n = n;
     idx->n_sa = n;
     idx->opt = opt;
+    idx->ranked_fill = ranked_fill_from_env();
     idx->wide = wide;
     for (auto &cx : idx->ctx) memset(&cx.stats, 0, sizeof(cx.stats));
     int32_t rc = [&]() -> int32_t {

@@ -43,6 +43,9 @@ struct IndexView {
     // (the position bits are per orientation: RunParams::pbits)
     // occurrences of every k-mer interval sorted by position (sa_build.hip: build_rank_lists); null: none
     const SlotT *sap;
+    // ... and, parallel to it, the suffix-array slot every entry came from (meaningful inside the sorted runs only: intervals
+    // of more than kRankMin entries); null: none, hit rows are filled from the suffix array alone
+    const SlotT *sar;
     // number of suffix-array slots: n, or end - start + 1 for a --trim index (reference
     // src/bin/asgart.rs:142-148), whose array holds the suffixes of data[start..end] + '$' only
     uint64_t n_sa;
@@ -142,7 +145,7 @@ struct Workspace {
     DevBuf row_off;    // u64[P+1]
     DevBuf blk;        // scan block aggregates
     DevBuf hits;       // PosT[total hits]
-    DevBuf big_list;   // u32[P] probes with large SA intervals
+    DevBuf big_list;   // u32[P] probes with large SA intervals; from its END downwards: the rows of fill_ranked_kernel (no probe is in both)
     DevBuf rank_list;  // u32[P] ... of them, those counted by bisection (position-sorted lists)
     DevBuf seg_list;   // u32[...] segment start probes
     DevBuf counters;   // u64[32] device counters
@@ -392,10 +395,11 @@ int hw_queue_budget();
 int32_t tier_plan(int budget, const uint64_t *n_work, int64_t tier_order, const double *est_ms, double main_ms,
                   int32_t *stream_of, int32_t *launch);
 template <class SlotT>
-int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_t n, SlotT *d_sap, uint32_t min_run, int k,
-                              hipStream_t s);  // (sa_build.hip: only the runs of more than min_run equal keys; any slot width)  // the streams and events of one call context (current device)
+int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_t n, SlotT *d_sap, SlotT *d_sar, uint32_t min_run,
+                              int k, hipStream_t s);  // (sa_build.hip: only the runs of more than min_run equal keys; any slot width)  // the streams and events of one call context (current device)
 int32_t option_set(Options &o, const char *name, int64_t value);  // ASGART_E_ARG: unknown name / bad value
 void options_from_env(Options &o);
+int ranked_fill_from_env();  // ASGART_RANKED_FILL: 0, 1 (also when unset or unreadable) or 2 -- asgart_index::ranked_fill
 }  // namespace asgart
 
 namespace asgart {
@@ -466,6 +470,9 @@ struct asgart_index {
     void *d_c8lo = nullptr;
     void *d_c8hi = nullptr;
     void *d_sap = nullptr;   // position-sorted occurrence lists (IndexView::sap), or null
+    void *d_sar = nullptr;   // ... the suffix-array slot of each of their entries (IndexView::sar), or null: 32-bit slots only
+    int ranked_fill = 1;     // ASGART_RANKED_FILL when the index was created: 0 = no d_sar, 1 = ranked_fill_takes decides,
+                             // 2 = every row fill_ranked_kernel can take (tests)
     uint64_t *d_pbits[4] = {nullptr, nullptr, nullptr, nullptr};  // per orientation (reverse * 2 + complement): position bits
                                                                   // (RunParams::pbits; n bits + padding)
     bool filter_off[4] = {false, false, false, false};            // no memory for them: this orientation is searched without
@@ -567,6 +574,7 @@ struct asgart_index {
         v.n_tail8 = n_tail8;
         v.tail_bloom = tail_bloom;
         v.sap = reinterpret_cast<const SlotT *>(d_sap);
+        v.sar = reinterpret_cast<const SlotT *>(d_sar);
         v.n_sa = (uint64_t)n_sa;
         v.trim = trimmed ? 1 : 0;
         v.n_bad = n_bad;

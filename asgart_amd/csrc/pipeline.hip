@@ -618,8 +618,11 @@ struct SearchCall {
             rp, p_filt, big_list, rank_list, d_ctr);
         big_count_kernel<SlotT, false><<<2048, 256, 0, s>>>(ix, rp, p_lo, p_raw, p_filt, big_list, d_ctr);
         // (after big_count_kernel: what it appends to big_list is for the fill only)
+        // (its rows for fill_ranked_kernel: from the end of big_list's W entries downwards)
+        uint32_t *const ranked_top = big_list + W;
         if (ix.sap)
-            rank_count_kernel<SlotT, false><<<2048, 256, 0, s>>>(ix, rp, p_lo, p_raw, p_filt, rank_list, big_list, d_ctr);
+            rank_count_kernel<SlotT, false><<<2048, 256, 0, s>>>(ix, rp, p_lo, p_raw, p_filt, rank_list, big_list, ranked_top,
+                                                                 ix.sar ? idx->ranked_fill : 0, d_ctr);
         HIP_TRY(hipEventRecord(cx.ev[EV_SEARCHED], s));
         // ---- K2: scans + segmentation ----------------------------------------------
         HIP_TRY(hipMemsetAsync(scan_desc, 0, (size_t)n_blk * 16, s));
@@ -651,6 +654,11 @@ struct SearchCall {
         if (h_ctr[CT_BIG])
             fill_big_kernel<SlotT><<<2048, 256, 0, sf>>>(ix, rp, p_lo, p_raw, p_filt, row_off, hits,
                                                          big_list, d_ctr);
+        if constexpr (sizeof(SlotT) == 4) {
+            if (h_ctr[CT_RANKED])
+                fill_ranked_kernel<SlotT><<<(unsigned)std::min<uint64_t>((h_ctr[CT_RANKED] + 255) / 256, 4096), 256, 0, sf>>>(
+                    ix, rp, p_lo, p_raw, p_filt, row_off, hits, ranked_top, d_ctr);
+        }
         HIP_TRY(hipEventRecord(cx.ev[EV_HIT_ROWS], sf));
         HIP_TRY(hipGetLastError());
 
@@ -2210,6 +2218,58 @@ int32_t asgart_tier_profile(double *profile_ms, uint64_t *tail_hits) {
     return 0;
 }
 
+// the 18 sums of fill_account_kernel over what the last search call left in its context's workspace
+static int32_t fill_account(asgart_index *idx, unsigned long long *acct) {
+    for (int j = 0; j < kFillAcct; ++j) acct[j] = 0;
+    idx->acquire_all();
+    SearchCtx &cx = idx->ctx[idx->last_ctx];
+    int32_t rc = [&]() -> int32_t {
+        if (!cx.has_last || !cx.last_P) return 0;
+        REFUSE_POISONED(idx);
+        HIP_TRY(hipSetDevice(idx->device));
+        unsigned long long *d_ctr = cx.ws.counters.as<unsigned long long>();
+        hipStream_t s = cx.stream;
+        const RunParams &rp = cx.last_rp;
+        HIP_TRY(hipMemsetAsync(d_ctr + CT_FILL_ACCT, 0, kFillAcct * 8, s));
+        const unsigned grid = std::min<uint32_t>(rp.n_tiles(1024u), 1024u);
+        const uint32_t *big_list = cx.ws.big_list.as<uint32_t>();
+        const uint32_t *ranked_top = big_list + (rp.g_hi - rp.g_lo);
+        fill_account_kernel<<<grid, 256, 0, s>>>(rp, cx.ws.p_raw.as<uint32_t>() - rp.g_lo, cx.ws.p_filt.as<uint32_t>() - rp.g_lo,
+                                                 big_list, ranked_top, d_ctr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(read_back(acct, d_ctr + CT_FILL_ACCT, kFillAcct * 8, s));  // (polled drain first: common.hpp)
+        return 0;
+    }();
+    idx->release_all();
+    return rc;
+}
+
+int32_t asgart_fill_counts(asgart_index *idx, uint64_t *out) {
+    if (!idx || !out) {
+        set_error("bad argument");
+        return ASGART_E_ARG;
+    }
+    unsigned long long acct[kFillAcct];
+    RC_TRY(fill_account(idx, acct));
+    for (int j = 0; j < 6; ++j) out[j] = acct[j];
+    return 0;
+}
+
+int32_t asgart_fill_tally(asgart_index *idx, uint64_t *out) {
+    if (!idx || !out) {
+        set_error("bad argument");
+        return ASGART_E_ARG;
+    }
+    unsigned long long acct[kFillAcct];
+    RC_TRY(fill_account(idx, acct));
+    for (int j = 0; j < 12; ++j) out[j] = acct[6 + j];
+    return 0;
+}
+
+int32_t asgart_ranked_fill_takes(uint64_t interval, uint64_t kept, int32_t mode) {
+    return ranked_fill_takes(interval, kept, (int)mode) ? 1 : 0;
+}
+
 int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out) {
     if (!idx || !out) {
         set_error("bad argument");
@@ -2280,7 +2340,7 @@ int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out) {
                 if (ix.sap)
                     rank_count_kernel<SlotT, true><<<2048, 256, 0, s>>>(
                         ix, rp, cx.ws.p_lo.as<SlotT>() - rp.g_lo, cx.ws.p_raw.as<uint32_t>() - rp.g_lo, nullptr,
-                        cx.ws.rank_list.as<uint32_t>(), nullptr, d_ctr);
+                        cx.ws.rank_list.as<uint32_t>(), nullptr, nullptr, 0, d_ctr);  // (no list is written: the bytes do not depend on the ranked fill)
             };
             if (idx->wide) account(uint64_t{}); else account(uint32_t{});
             HIP_TRY(hipGetLastError());

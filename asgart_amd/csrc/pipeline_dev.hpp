@@ -341,7 +341,9 @@ __global__ __launch_bounds__(kCollectBlock) void collect_pending_kernel(RunParam
 // occurrences beyond a position threshold (src/automaton.rs:105-114), so the kept count is one bisection of
 // sap[lo..hi) -- a dozen gathers instead of the ~1000 suffix-array entries a probe of a frequent k-mer streams
 // before the early exit at max_cardinality + 1.  One thread per interval.  Probes that stay below the cardinality
-// limit are appended to big_list, from which fill_big_kernel materialises their hits (in suffix-array order).
+// limit are appended to big_list, from which fill_big_kernel materialises their hits (in suffix-array order) -- or, where
+// the kept tail of the list is much shorter than the interval (ranked_fill_takes), to the ranked list, which grows from
+// ranked_top downwards (the END of big_list's buffer: no probe is in both) and is served by fill_ranked_kernel.
 template <class SlotT, bool COUNT>
 __global__ __launch_bounds__(256) void rank_count_kernel(IndexView<SlotT> ix, RunParams rp,
                                                          const SlotT *__restrict__ p_lo,
@@ -349,6 +351,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(IndexView<SlotT> ix, Ru
                                                          uint32_t *__restrict__ p_filt,
                                                          const uint32_t *__restrict__ rank_list,
                                                          uint32_t *__restrict__ big_list,
+                                                         uint32_t *__restrict__ ranked_top, int ranked_mode,
                                                          unsigned long long *__restrict__ ctr) {
     const uint64_t n_rank = ctr[CT_RANK];
     const uint32_t lane = threadIdx.x & 63u;
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(256) void rank_count_kernel(IndexView<SlotT> ix, Ru
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t e0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~63ull; e0 < n_rank; e0 += stride) {
         const uint64_t e = e0 + lane;
-        bool refill = false;
+        bool refill = false, ranked = false;
         uint32_t g = 0;
         if (e < n_rank) {
             g = rank_list[e];
@@ -390,15 +393,24 @@ __global__ __launch_bounds__(256) void rank_count_kernel(IndexView<SlotT> ix, Ru
             const uint32_t f = cnt > (uint64_t)rp.C ? kSkipCard : (uint32_t)cnt;
             if (!COUNT) p_filt[g] = f;
             refill = f != 0u && f < kPending;
+            ranked = refill && ranked_fill_takes(R, cnt, ranked_mode);
         }
         if (!COUNT) {
-            const unsigned long long m = __ballot(refill);
+            const unsigned long long lt = (1ull << lane) - 1ull;
+            const unsigned long long m = __ballot(refill && !ranked), mr = __ballot(ranked);
             if (m) {
                 const int leader = __ffsll((long long)m) - 1;
                 unsigned long long at = 0;
                 if ((int)lane == leader) at = atomicAdd(&ctr[CT_BIG], (unsigned long long)__popcll(m));
                 at = __shfl(at, leader);
-                if (refill) big_list[at + __popcll(m & ((1ull << lane) - 1ull))] = g;
+                if (refill && !ranked) big_list[at + __popcll(m & lt)] = g;
+            }
+            if (mr) {
+                const int leader = __ffsll((long long)mr) - 1;
+                unsigned long long at = 0;
+                if ((int)lane == leader) at = atomicAdd(&ctr[CT_RANKED], (unsigned long long)__popcll(mr));
+                at = __shfl(at, leader);
+                if (ranked) *(ranked_top - 1 - (long long)(at + __popcll(mr & lt))) = g;
             }
         } else {
             bytes += refill ? 4u : 0u;
@@ -994,6 +1006,173 @@ __global__ __launch_bounds__(256) void fill_big_kernel(IndexView<SlotT> ix, RunP
                 }
             }
         }
+    }
+}
+
+// Rows of frequent k-mers, one wave per row (set-up of 64 rows side by side across the lanes, like fill_big_kernel).  The
+// hit filter keeps the occurrences beyond a position threshold -- less the probe's own offset in a reversed pass -- so the
+// cnt kept hits of a row are among the last cnt + 1 entries of the interval's POSITION-sorted list: those are read (with
+// the suffix-array slot each came from, ix.sar) instead of the R entries of the interval, and filtered like everywhere
+// else.  A row is written in suffix-array order: every kept entry sets the bit of its slot in a bitmap of the interval
+// (LDS, R bits), one pass of popcounts and a wave scan turns the bitmap into the number of kept entries below each of
+// its words, and an entry's place in the row is that number plus the set bits below its own in its word.  (A bitonic
+// sort of the kept entries in LDS -- 45 dependent compare-exchange rounds for 512 -- took 28 us per row: 26 ms per
+// GRCh38-shaped step where streaming the intervals takes 11.)  The next row's entries are in flight while a row is
+// placed.  32-bit slots only.
+constexpr int kRankedRounds = (kRankedCap + 1 + 63) / 64;  // loads of 64 entries that cover cnt + 1 <= kRankedCap + 1
+constexpr int kRankedWords = kRankedMaxR / 32;             // bitmap words per wave
+__device__ inline void wave_lds_sync() {  // LDS traffic of ONE wave: what its lanes wrote is there for its other lanes
+    __builtin_amdgcn_wave_barrier();
+    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+template <class SlotT>
+__global__ __launch_bounds__(256) void fill_ranked_kernel(IndexView<SlotT> ix, RunParams rp,
+                                                          const SlotT *__restrict__ p_lo,
+                                                          const uint32_t *__restrict__ p_raw,
+                                                          const uint32_t *__restrict__ p_filt,
+                                                          const unsigned long long *__restrict__ row_off,
+                                                          SlotT *__restrict__ hits,
+                                                          const uint32_t *__restrict__ ranked_top,
+                                                          const unsigned long long *__restrict__ ctr) {
+    static_assert(sizeof(SlotT) == 4, "32-bit slots and positions");
+    __shared__ uint32_t s_bits[4][kRankedWords];
+    __shared__ unsigned short s_below[4][kRankedWords];  // (a row keeps at most kRankedCap hits)
+    uint32_t *const bm = s_bits[threadIdx.x >> 6];
+    unsigned short *const below = s_below[threadIdx.x >> 6];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n_rk = ctr[CT_RANKED];
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t e0 = wave * 64u; e0 < n_rk; e0 += n_waves * 64u) {
+        const uint32_t np = (uint32_t)min((uint64_t)64, n_rk - e0);
+        unsigned long long s = 0, L = 0, i = 0, lo = 0, a0 = 0, w0 = 0;
+        uint32_t md = 0, cnt = 0, R = 0;
+        if (lane < np) {
+            const uint32_t g = *(ranked_top - 1 - (long long)(e0 + lane));
+            cnt = min(p_filt[g], (uint32_t)kRankedCap);              // (1..kRankedCap: ranked_fill_takes)
+            R = min(p_raw[g], (uint32_t)kRankedMaxR);                // (<= kRankedMaxR: likewise)
+            const int c = chunk_of(rp.ch, g);
+            md = rp.mode_of(c);
+            s = rp.ch.start[c];
+            L = rp.ch.len[c];
+            i = (unsigned long long)(g - rp.ch.pbase[c] + 1) * (unsigned long long)rp.step;
+            lo = p_lo[g];
+            a0 = R > cnt + 1u ? lo + R - cnt - 1u : lo;
+            w0 = row_off[g];
+        }
+        // the tail of a row's list and the slots of its entries: all rounds in flight together
+        SlotT xn[kRankedRounds], sn[kRankedRounds];
+        auto fetch = [&](uint32_t p) {
+            const unsigned long long a0_p = lane_of(a0, p), a1_p = lane_of(lo, p) + lane_of(R, p);
+#pragma unroll
+            for (int u = 0; u < kRankedRounds; ++u) {
+                const unsigned long long r = a0_p + 64u * u + lane;
+                xn[u] = r < a1_p ? ix.sap[r] : (SlotT)0;
+                sn[u] = r < a1_p ? ix.sar[r] : (SlotT)0;
+            }
+        };
+        fetch(0u);
+        for (uint32_t p = 0; p < np; ++p) {
+            const unsigned long long lo_p = lane_of(lo, p), a0_p = lane_of(a0, p), i_p = lane_of(i, p), s_p = lane_of(s, p),
+                                     L_p = lane_of(L, p), w_p = lane_of(w0, p);
+            const bool rev_p = (lane_of(md, p) & 2u) != 0u;
+            const uint32_t cnt_p = lane_of(cnt, p), R_p = lane_of(R, p);
+            const unsigned long long a1_p = lo_p + R_p;
+            SlotT x[kRankedRounds];
+            uint32_t rel[kRankedRounds];  // slot inside the interval; ~0u: not kept
+#pragma unroll
+            for (int u = 0; u < kRankedRounds; ++u) {
+                const unsigned long long r = a0_p + 64u * u + lane;
+                x[u] = xn[u];
+                const uint32_t d = (uint32_t)sn[u] - (uint32_t)lo_p;
+                rel[u] = r < a1_p && keep_hit(x[u], i_p, s_p, L_p, rev_p) && d < R_p ? d : ~0u;
+            }
+            if (p + 1 < np) fetch(p + 1u);
+            const uint32_t nw = (R_p + 31u) >> 5;
+            for (uint32_t j = lane; j < nw; j += 64u) bm[j] = 0u;
+            wave_lds_sync();
+#pragma unroll
+            for (int u = 0; u < kRankedRounds; ++u)
+                if (rel[u] != ~0u) atomicOr(&bm[rel[u] >> 5], 1u << (rel[u] & 31u));
+            wave_lds_sync();
+            uint32_t run = 0;  // kept entries below the words of this round
+            for (uint32_t base = 0; base < nw; base += 64u) {
+                const uint32_t j = base + lane;
+                const uint32_t c = j < nw ? (uint32_t)__popc(bm[j]) : 0u;
+                const uint32_t incl = wave_incl_scan(c);
+                if (j < nw) below[j] = (unsigned short)(run + incl - c);
+                run += lane_of(incl, 63u);
+            }
+            wave_lds_sync();
+#pragma unroll
+            for (int u = 0; u < kRankedRounds; ++u)
+                if (rel[u] != ~0u) {
+                    const uint32_t at = (uint32_t)below[rel[u] >> 5] + (uint32_t)__popc(bm[rel[u] >> 5] & ((1u << (rel[u] & 31u)) - 1u));
+                    if (at < cnt_p) hits[w_p + at] = x[u];  // (always: the count is the bisection of this very list)
+                }
+            wave_lds_sync();  // (the next row clears the bitmap)
+        }
+    }
+}
+
+// What the three fill kernels of the last call served, summed up afterwards from what the call left in its workspace (the
+// per-probe arrays and the two work lists) instead of costing every call counters of its own:
+//   out[0..5]   rows and entries read of fill_small_kernel, fill_big_kernel, fill_ranked_kernel (the ranked fill reads two
+//               entries -- position and slot -- per list position);
+//   out[6..17]  rows, sum of R, sum of kept hits of fill_big_kernel's rows with R <= kRankMin, with R above it but counted
+//               by streaming, counted by bisection -- and of fill_ranked_kernel's rows (all counted by bisection).
+constexpr int kFillAcct = 18;
+__global__ __launch_bounds__(256) void fill_account_kernel(RunParams rp, const uint32_t *__restrict__ p_raw,
+                                                           const uint32_t *__restrict__ p_filt,
+                                                           const uint32_t *__restrict__ big_list,
+                                                           const uint32_t *__restrict__ ranked_top,
+                                                           unsigned long long *__restrict__ ctr) {
+    unsigned long long acc[kFillAcct];
+#pragma unroll
+    for (int j = 0; j < kFillAcct; ++j) acc[j] = 0;
+    const uint32_t n_t = rp.n_tiles(1024u);
+    for (uint32_t t = blockIdx.x; t < n_t; t += gridDim.x) {
+        uint32_t g_end;
+        const uint32_t g0 = rp.tile_of(t, 1024u, g_end);
+        for (int a = 0; a < 4; ++a) {
+            const uint32_t g = g0 + (uint32_t)a * 256u + threadIdx.x;
+            if (g >= g_end) continue;
+            const uint32_t f = p_filt[g];
+            if (f == 0 || f >= kPending) continue;
+            const uint32_t raw = p_raw[g];
+            if (raw > (uint32_t)kSmallInterval) continue;
+            acc[0] += 1;
+            acc[1] += raw;
+        }
+    }
+    const uint64_t n_big = ctr[CT_BIG], n_big0 = ctr[CT_BIG0], n_rk = ctr[CT_RANKED];
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t e = tid; e < n_big; e += stride) {
+        const uint32_t g = big_list[e], f = p_filt[g];
+        if (f == 0 || f >= kPending) continue;
+        const unsigned long long R = p_raw[g];
+        acc[2] += 1;
+        acc[3] += R;
+        const int cl = e >= n_big0 ? 2 : (R > (unsigned long long)kRankMin ? 1 : 0);
+        acc[6 + 3 * cl] += 1;
+        acc[7 + 3 * cl] += R;
+        acc[8 + 3 * cl] += f;
+    }
+    for (uint64_t e = tid; e < n_rk; e += stride) {
+        const uint32_t g = *(ranked_top - 1 - (long long)e), f = p_filt[g];
+        const unsigned long long R = p_raw[g];
+        acc[4] += 1;
+        acc[5] += 2u * (R > (unsigned long long)f + 1u ? (unsigned long long)f + 1u : R);
+        acc[15] += 1;
+        acc[16] += R;
+        acc[17] += f;
+    }
+#pragma unroll
+    for (int j = 0; j < kFillAcct; ++j) {
+        unsigned long long v = acc[j];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        if ((threadIdx.x & 63u) == 0 && v) atomicAdd(&ctr[CT_FILL_ACCT + j], v);
     }
 }
 

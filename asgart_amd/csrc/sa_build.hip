@@ -670,9 +670,12 @@ __global__ __launch_bounds__(256) void big_runs_kernel(const uint64_t *__restric
 }
 }  // namespace
 
+// d_sar (or null): the slot of the suffix array every sorted entry came from -- the sort carries the slot numbers along as
+// values, read from a counting iterator (no array of them is ever held) -- for fill_ranked_kernel, which puts the kept tail
+// of a list back into suffix-array order.  Written inside the sorted runs only.
 template <class SlotT>
-int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_t n, SlotT *d_sap, uint32_t min_run, int k,
-                              hipStream_t s) {
+int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_t n, SlotT *d_sap, SlotT *d_sar, uint32_t min_run,
+                              int k, hipStream_t s) {
     if (n == 0) return 0;
     constexpr uint64_t kWindow = 1ull << 30;
     const uint64_t max_runs = kWindow / (min_run + 1u) + 2u;  // per window
@@ -702,6 +705,17 @@ int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_
             return ASGART_E_CAP;
         }
         size_t bytes = 0;
+        if (d_sar) {
+            const rocprim::counting_iterator<SlotT> slots((SlotT)w0);
+            HIP_TRY(rocprim::segmented_radix_sort_pairs(nullptr, bytes, d_sa + w0, d_sap + w0, slots, d_sar + w0, (unsigned)h[1],
+                                                        (unsigned)h[0], b_beg.as<uint32_t>(), b_end.as<uint32_t>(), 0,
+                                                        (unsigned)pos_bits, s));
+            RC_TRY(temp.reserve(bytes));
+            HIP_TRY(rocprim::segmented_radix_sort_pairs(temp.p, bytes, d_sa + w0, d_sap + w0, slots, d_sar + w0, (unsigned)h[1],
+                                                        (unsigned)h[0], b_beg.as<uint32_t>(), b_end.as<uint32_t>(), 0,
+                                                        (unsigned)pos_bits, s));
+            continue;
+        }
         HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, bytes, d_sa + w0, d_sap + w0, (unsigned)h[1], (unsigned)h[0],
                                                    b_beg.as<uint32_t>(), b_end.as<uint32_t>(), 0, (unsigned)pos_bits, s));
         RC_TRY(temp.reserve(bytes));
@@ -711,8 +725,8 @@ int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_
     HIP_TRY(stream_sync(s));
     return 0;
 }
-template int32_t build_rank_lists_runs<uint32_t>(const uint64_t *, const uint32_t *, uint64_t, uint32_t *, uint32_t, int, hipStream_t);
-template int32_t build_rank_lists_runs<uint64_t>(const uint64_t *, const uint64_t *, uint64_t, uint64_t *, uint32_t, int, hipStream_t);
+template int32_t build_rank_lists_runs<uint32_t>(const uint64_t *, const uint32_t *, uint64_t, uint32_t *, uint32_t *, uint32_t, int, hipStream_t);
+template int32_t build_rank_lists_runs<uint64_t>(const uint64_t *, const uint64_t *, uint64_t, uint64_t *, uint64_t *, uint32_t, int, hipStream_t);
 
 }  // namespace asgart
 

@@ -636,6 +636,23 @@ int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out);
  * segments, which are not run, are in none); out[7] = the segments the tail rule moved up (counted before the barren test
  * by position and option force_tier). */
 int32_t asgart_tier_segments(asgart_index *idx, uint64_t *out);
+/* The hit rows of the last search call on this index, by the kernel that filled them (summed up now, by an untimed pass
+ * over what the call left in its workspace): out[0], out[1] = rows and suffix-array entries read of the rows with intervals
+ * of up to 32 entries; out[2], out[3] = of the rows streamed from larger intervals; out[4], out[5] = rows filled from the
+ * kept tail of their k-mer's position-sorted occurrence list, and the entries read for them (two per list position: the
+ * position and the suffix-array slot it came from).
+ * The ranked fill is governed by the environment variable ASGART_RANKED_FILL, read when an index is created: 0 = off (the
+ * slots are not kept: 4 bytes per text position less), 1 or unset = rows of a whole k-mer interval of more than 256
+ * entries that keep at most 512 hits, where that reads clearly less than the interval (R > 2 * kept + 64), 2 = all such
+ * rows (tests).  Indexes with 64-bit positions always stream.  The rows are the same bytes either way. */
+int32_t asgart_fill_counts(asgart_index *idx, uint64_t *out);
+/* Diagnostic: the rows behind out[2..5] of asgart_fill_counts in four classes, for each the rows, the sum of their interval sizes and the sum of
+ * their kept hits: out[0..2] streamed, interval of 33..256 entries; out[3..5] streamed, larger, kept count found by
+ * streaming; out[6..8] streamed, kept count found by bisection; out[9..11] filled from the position-sorted list. */
+int32_t asgart_fill_tally(asgart_index *idx, uint64_t *out);
+/* Diagnostic (for tests of the rule): ASGART_RANKED_FILL = mode for a row that keeps `kept` hits of an interval of `interval` entries (host code,
+ * needs no device): 1 = filled from the position-sorted list, 0 = streamed. */
+int32_t asgart_ranked_fill_takes(uint64_t interval, uint64_t kept, int32_t mode);
 /* The tier table's figures a call starts from (host code, needs no device): profile_ms[0] = the runs over ranges,
  * profile_ms[t] = tier t's estimated duration on the GRCh38-shaped profile (what asgart_tier_plan is fed before a call
  * has measurements of its own), for a thresholded tier what is left of it where the tail rule is in force; tail_hits[t] =
