@@ -49,6 +49,8 @@ ABI_SYMBOLS = (
     "asgart_slice_families", "asgart_slice_counts", "asgart_slice_copy", "asgart_slice_timings", "asgart_slice_free",
     "asgart_plot_filter", "asgart_plot_counts", "asgart_plot_copy", "asgart_plot_timings", "asgart_plot_free",
     "asgart_plot_geometry",
+    "asgart_rosary_clusters", "asgart_rosary_counts", "asgart_rosary_copy", "asgart_rosary_timings", "asgart_rosary_free",
+    "asgart_rosary_geometry",
 )
 
 
@@ -266,6 +268,19 @@ def load_library() -> C.CDLL:
         L.asgart_plot_free.restype = None
         L.asgart_plot_geometry.argtypes = [u64p, u64p]
         L.asgart_plot_geometry.restype = None
+    if hasattr(L, "asgart_rosary_clusters"):
+        L.asgart_rosary_clusters.argtypes = [C.c_int32, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_uint64, C.POINTER(vp)]
+        L.asgart_rosary_clusters.restype = C.c_int32
+        L.asgart_rosary_counts.argtypes = [vp, u64p, u64p]
+        L.asgart_rosary_counts.restype = None
+        L.asgart_rosary_copy.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.asgart_rosary_copy.restype = None
+        L.asgart_rosary_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_rosary_timings.restype = C.c_int32
+        L.asgart_rosary_free.argtypes = [vp]
+        L.asgart_rosary_free.restype = None
+        L.asgart_rosary_geometry.argtypes = [u64p]
+        L.asgart_rosary_geometry.restype = None
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []

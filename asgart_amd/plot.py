@@ -19,8 +19,9 @@ Three layers, as in slice.py:
 
 What differs from the reference, on purpose:
   - the reference swaps two subcommands (asgart-plot.rs:507-508): `chord` draws the FLAT plot (flat_plot.rs) and `flat` the
-    chord diagram.  The swap is kept: `chord` here is FlatPlotter.  `flat` (ChordPlotter) and `rosary` are not built: the
-    chord geometry goes through cos / sin, whose vector forms need not round as libm does.  They exit with a message.
+    chord diagram.  The swap is kept: `chord` here is FlatPlotter.  `flat` (ChordPlotter) is not built: the chord geometry
+    goes through cos / sin, whose vector forms need not round as libm does.  `rosary` is not built into this tool: it is a
+    tool of its own, python -m asgart_amd.rosary (rosary.py), with the same options.  Both exit here with a message.
   - the custom feature reader collects its features in a HashMap, so the reference's feature order is arbitrary; here it
     is the order of first appearance.
   - FlatPlotter colours every feature polygon with `{:2X}` of three random i8 (flat_plot.rs:142-147); here they are drawn
@@ -52,7 +53,8 @@ COLORIZE = ("by-type", "by-position", "by-fragment", "none")
 M64 = (1 << 64) - 1                                       # usize arithmetic wraps: release build, Cargo.toml:37
 _NO_KIND = {"flat": "`flat` is the reference's ChordPlotter (asgart-plot.rs:507 swaps flat and chord); its geometry goes "
                     "through cos / sin and is not built here.  `chord` draws the flat plot.",
-            "rosary": "`rosary` (rosary_plot.rs) is not built here."}
+            "rosary": "`rosary` (rosary_plot.rs) is not built into this tool: run `python -m asgart_amd.rosary`, which takes "
+                      "the same options and `--clustering` / `--rosary`."}
 _NO_COLOR = {"by-position": "--colorize by-position needs the HSV gradient of the reference's `palette` crate, which is "
                             "not restated here",
              "by-fragment": "--colorize by-fragment shuffles its colours with thread_rng in the reference: there are no "
@@ -910,11 +912,9 @@ def export_arrays(a: ResultArrays, tracks, kind: str, options: PlotOptions, pref
 
 
 # ---- the tool -------------------------------------------------------------------------------------------------------
-def _parse(argv: List[str]):
-    import argparse
-
-    ap = argparse.ArgumentParser(prog="python -m asgart_amd.plot", description="asgart-plot: generate plots from ASGART "
-                                 "results.  The kind of plot (chord, genome, circos, flat, rosary) comes last.")
+def add_arguments(ap):
+    """The options of asgart-plot.rs:289-377 in front of the kind of plot, on an argparse parser: what this tool and
+    python -m asgart_amd.rosary share."""
     ap.add_argument("files", nargs="*", help="the input file(s); none: JSON from standard input")
     ap.add_argument("--out", help="a non-default output file name")
     ap.add_argument("--min-length", type=int, default=1000, help="filter duplicons shorter than the given value")
@@ -934,6 +934,14 @@ def _parse(argv: List[str]):
     ap.add_argument("--seed", type=int, default=0, help="seeds the colours of the feature polygons of `chord`")
     ap.add_argument("--host", action="store_true", help="run the per-object statement on the host; the bytes are the same")
     ap.add_argument("--device", type=int, default=0)
+
+
+def _parse(argv: List[str]):
+    import argparse
+
+    ap = argparse.ArgumentParser(prog="python -m asgart_amd.plot", description="asgart-plot: generate plots from ASGART "
+                                 "results.  The kind of plot (chord, genome, circos, flat, rosary) comes last.")
+    add_arguments(ap)
     at = max((k for k, tok in enumerate(argv) if tok in KINDS), default=None)
     if at is None:
         ap.error(f"the kind of plot is missing (one of {', '.join(KINDS)})")

@@ -549,6 +549,40 @@ void asgart_plot_free(asgart_plot *r);
  * of the literal kernel. */
 void asgart_plot_geometry(uint64_t *block_threads, uint64_t *tile_windows);
 
+/* ---- the duplicon clusters of the rosary plot ---------------------------------------------------------------
+ * Replaces RosaryPlotter::duplicons_for_chr, reference src/plot/rosary_plot.rs:123-192, for every fragment name in one
+ * call.  The reference, per fragment of the map, walks every duplication, compares names as strings, sorts the fragment's
+ * arms by start (stable) and folds them one by one: an arm joins the last cluster when
+ * `new.start <= last.start + last.length + margin` (:164) and then `last.length = new.start + new.length - last.start`
+ * (:165), so that `last.start + last.length` is always the end of the arm just handled.  Here: one stable radix sort of the
+ * arms by (name id, start), head[i] = i == 0 || name[i] != name[i-1] || start[i] > end[i-1] + margin (u64, every +
+ * wrapping as in the reference's release build), one scan, one segmented reduction.
+ * in: the arms in flatten order, arm 2q + side of duplication q (left 0, right 1): arm_name (ids into a table of n_names
+ * names; names never reach the device), arm_start (the position within the fragment), arm_length; flags[q] bit 0 reversed,
+ * bit 1 complemented (NULL: all 0).  Ties of (name, start) keep flatten order: the first arm of a cluster decides its colour.
+ * out (asgart_rosary_counts / _copy / _free): name_offsets[n_names + 1], the CSR rows of the clusters per name id (a name
+ * without arms has an empty row), and per cluster, in sorted order: start = its first member's, length = the end of its
+ * LAST member - start (wrapping; not the largest end: a contained short arm shortens its cluster), klass = bit 0 reversed
+ * and bit 1 complemented of the first member, bit 2 `both`: some member's two bits differ from the first's (:178), and
+ * members = the number of arms.  Every copy target is nullable.
+ * Checked on the host before anything is launched: NULL arrays with n_sds > 0, a negative count, or a name id outside
+ * [0, n_names) (the message names the first such arm): ASGART_E_ARG; 2 * n_sds >= 2^32: ASGART_E_CAP; no usable device:
+ * ASGART_E_HIP.  n_sds == 0 succeeds with n_names + 1 zero offsets.  No device memory is held once the call has returned. */
+typedef struct asgart_rosary asgart_rosary;
+int32_t asgart_rosary_clusters(int32_t device, const int32_t *arm_name, const uint64_t *arm_start,
+                               const uint64_t *arm_length, const uint8_t *flags, int64_t n_sds, int64_t n_names,
+                               uint64_t margin, asgart_rosary **out);
+void asgart_rosary_counts(const asgart_rosary *r, uint64_t *n_names, uint64_t *n_clusters);
+void asgart_rosary_copy(const asgart_rosary *r, uint64_t *name_offsets, uint64_t *start, uint64_t *length, uint8_t *klass,
+                        uint32_t *members);
+/* Milliseconds of the call behind r (rosary_plot.rs:123-192 on the device): [0] the upload, [1] the kernels from the first
+ * to the last, [2] the copy back; HIP events for the first two.  ASGART_E_ARG for a NULL argument. */
+int32_t asgart_rosary_timings(const asgart_rosary *r, double *ms3);
+void asgart_rosary_free(asgart_rosary *r);
+/* Threads per workgroup of the kernels behind asgart_rosary_clusters (rosary_plot.rs:123-192), for tests that place their
+ * arm counts on the seams. */
+void asgart_rosary_geometry(uint64_t *block_threads);
+
 /* ---- FASTA files read on the GPU ---------------------------------------------------------------------------
  * Replace the FASTA reader in front of prepare_data and prepare_data itself (reference src/bin/asgart.rs:273-430: bio's
  * fasta::Reader and the per-record loop at :278-313, normalisation :289-301, find_chunks_to_process :317-366,
