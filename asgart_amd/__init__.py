@@ -24,6 +24,7 @@ __all__ = [
     "AsgartError", "RunSettings", "ProtoSD", "Strand", "Index", "Searcher", "SearchDuplications",
     "load_library", "library_path", "ABI_SYMBOLS", "sa_build64", "search_duplications_multi", "merge_shards",
     "score_owners", "score_costs", "compute_scores_multi", "Source", "compute_scores_flags_multi", "orientation_flags",
+    "export_records", "export_geometry", "f32_shortest", "f32_pow10_table", "EXPORT_FORMATS",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -51,6 +52,8 @@ ABI_SYMBOLS = (
     "asgart_plot_geometry",
     "asgart_rosary_clusters", "asgart_rosary_counts", "asgart_rosary_copy", "asgart_rosary_timings", "asgart_rosary_free",
     "asgart_rosary_geometry",
+    "asgart_export_records", "asgart_export_size", "asgart_export_copy", "asgart_export_timings", "asgart_export_free",
+    "asgart_export_geometry", "asgart_f32_shortest", "asgart_f32_pow10_table",
 )
 
 
@@ -281,6 +284,24 @@ def load_library() -> C.CDLL:
         L.asgart_rosary_free.restype = None
         L.asgart_rosary_geometry.argtypes = [u64p]
         L.asgart_rosary_geometry.restype = None
+    if hasattr(L, "asgart_export_records"):
+        L.asgart_export_records.argtypes = [C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, vp, vp,
+                                            C.c_int64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp)]
+        L.asgart_export_records.restype = C.c_int32
+        L.asgart_export_size.argtypes = [vp]
+        L.asgart_export_size.restype = C.c_uint64
+        L.asgart_export_copy.argtypes = [vp, vp, C.c_uint64]
+        L.asgart_export_copy.restype = C.c_int32
+        L.asgart_export_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_export_timings.restype = C.c_int32
+        L.asgart_export_free.argtypes = [vp]
+        L.asgart_export_free.restype = None
+        L.asgart_export_geometry.argtypes = [u64p, u64p, u64p]
+        L.asgart_export_geometry.restype = None
+        L.asgart_f32_shortest.argtypes = [C.c_int32, vp, C.c_int64, C.c_int32, vp, vp]
+        L.asgart_f32_shortest.restype = C.c_int32
+        L.asgart_f32_pow10_table.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
+        L.asgart_f32_pow10_table.restype = C.c_int32
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []
@@ -816,6 +837,83 @@ def compute_scores_flags_multi(indices: Sequence[Index], sds: np.ndarray, flags:
     _check(load_library().asgart_compute_scores_flags_multi(arr, len(indices), _ptr(sds), _ptr(flags), len(sds),
                                                             _ptr(out)))
     return out
+
+
+EXPORT_FORMATS = {"json": 0, "gff2": 1, "gff3": 2}   # ASGART_EXPORT_JSON / _GFF2 / _GFF3
+F32_TEXT_MAX = 64                                     # ASGART_F32_TEXT_MAX
+
+
+def export_records(fmt: str, offs, sds, flags, identity, chr_, chr_pos, names: Sequence[bytes], prefix: bytes,
+                   suffix: bytes, device: int = 0, timings: Optional[list] = None) -> np.ndarray:
+    """asgart_export_records: the whole result file as uint8[size], written on the GPU.  fmt: "json", "gff2" or "gff3";
+    offs, sds, flags, chr_, chr_pos as slice.ResultArrays holds them; identity float32[n] or None (all 0); names: the name
+    table, every name as bytes in the form the format prints it (slice.export_arrays_gpu and postprocess.to_json_arrays_gpu
+    prepare it); prefix / suffix: what the file holds in front of and behind the families.  timings: a list that receives
+    the call's three millisecond figures (asgart_export_timings: upload, kernels, copy back)."""
+    if fmt not in EXPORT_FORMATS:
+        raise ValueError(f"unknown format `{fmt}` (one of {', '.join(EXPORT_FORMATS)})")
+    L = load_library()
+    offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    chr_ = np.ascontiguousarray(chr_, dtype=np.int32).reshape(-1, 2)
+    chr_pos = np.ascontiguousarray(chr_pos, dtype=np.uint64).reshape(-1, 2)
+    if identity is not None:
+        identity = np.ascontiguousarray(identity, dtype=np.float32).reshape(-1)
+    n = len(sds)
+    if len(offs) < 1 or not (len(flags) == len(chr_) == len(chr_pos) == n) or (identity is not None and len(identity) != n):
+        raise ValueError("export_records: the arrays differ in length")
+    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum([len(b) for b in names], out=name_off[1:])
+    name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+    pre, suf = (np.frombuffer(b or b"\0", dtype=np.uint8) for b in (prefix, suffix))
+    h = C.c_void_p()
+    _check(L.asgart_export_records(int(device), EXPORT_FORMATS[fmt], _ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags),
+                                   _ptr(identity), _ptr(chr_), _ptr(chr_pos), n, _ptr(name_bytes), _ptr(name_off),
+                                   len(names), _ptr(pre), len(prefix), _ptr(suf), len(suffix), C.byref(h)))
+    try:
+        out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
+        _check(L.asgart_export_copy(h, _ptr(out), len(out)))
+        if timings is not None:
+            ms = (C.c_double * 3)()
+            _check(L.asgart_export_timings(h, ms))
+            timings[:] = list(ms)
+    finally:
+        L.asgart_export_free(h)
+    return out
+
+
+def export_geometry() -> Tuple[int, int, int]:
+    """asgart_export_geometry: threads per workgroup, units per workgroup, bytes of the LDS image of the write stage."""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    load_library().asgart_export_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
+
+
+def f32_shortest(values, mode: str = "json", device: int = 0) -> List[str]:
+    """asgart_f32_shortest: every value of a float32 array as text, rendered on the GPU -- mode "json": what
+    postprocess.f32_repr gives (serde_json's form), "display": what slice.f32_display gives (Rust's `{}`)."""
+    if mode not in ("json", "display"):
+        raise ValueError("f32_shortest: mode 'json' or 'display'")
+    v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    text = np.zeros((len(v), F32_TEXT_MAX), dtype=np.uint8)
+    lens = np.zeros(len(v), dtype=np.uint8)
+    _check(load_library().asgart_f32_shortest(int(device), _ptr(v), len(v), 0 if mode == "json" else 1, _ptr(text), _ptr(lens)))
+    rows = text.view(f"S{F32_TEXT_MAX}").reshape(-1).tolist()   # (a rendered f32 holds no NUL: S stops at the padding)
+    if any(len(r) != ln for r, ln in zip(rows, lens.tolist())):
+        raise AsgartError(-2, "asgart_f32_shortest: a length does not match its text")
+    return [r.decode("ascii") for r in rows]
+
+
+def f32_pow10_table():
+    """asgart_f32_pow10_table -> (k_min, k_max, uint64[entries, 4]): hi, lo, x (as two's complement), exact per k, with
+    10^-k = (hi * 2^64 + lo) * 2^x, rounded up where exact is 0.  Needs no GPU."""
+    L = load_library()
+    lo, hi = C.c_int32(), C.c_int32()
+    n = L.asgart_f32_pow10_table(C.byref(lo), C.byref(hi), None)
+    out = np.zeros((n, 4), dtype=np.uint64)
+    L.asgart_f32_pow10_table(None, None, _ptr(out))
+    return int(lo.value), int(hi.value), out
 
 
 def trim_cache(device: int = 0) -> int:

@@ -195,6 +195,24 @@ def _choose_reader(reader: Optional[str], settings) -> str:
     return reader
 
 
+DEFAULT_WRITER = "device"   # what writer=None means for a result without sequences (profiles/export_cfg4.json)
+
+
+def _choose_writer(writer: Optional[str], with_sequences: bool) -> str:
+    """writer=None: DEFAULT_WRITER.  The device writer (csrc/export.hip) does not write sequences: a run with
+    with_sequences is written by the host exporter whatever is asked for; the bytes are the same."""
+    if writer is None:
+        writer = DEFAULT_WRITER
+    if writer not in ("device", "host"):
+        raise ValueError("writer: 'device' or 'host'")
+    return "host" if with_sequences else writer
+
+
+def _decode(file_bytes: np.ndarray) -> str:
+    """The text of a file the device writer produced (uint8, UTF-8), without a copy in between."""
+    return str(memoryview(file_bytes), "utf-8")
+
+
 def _read_input(files: Sequence[str], settings, device_index: int, reader: str, with_sequences: bool):
     """Rank 0's input step -> (strand, chunks, index, records or None, source or None).
     reader "device": one prep.read_fasta_gpu over the mapped files -- the strand stays on the GPU (strand.data is None),
@@ -258,7 +276,7 @@ def _slice_run(post, strand, settings, slice_options, device_index: int):
 
 def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
                         prefix: str = "", with_sequences: bool = False, reader: Optional[str] = None,
-                        slice_options=None, fmt: str = "json") -> Optional[Tuple[str, str]]:
+                        slice_options=None, fmt: str = "json", writer: Optional[str] = None) -> Optional[Tuple[str, str]]:
     """A whole `asgart` run (reference src/bin/asgart.rs:731-822) on the ranks of `dist`, rank r on GPU device_index:
     rank 0 prepares the input and builds the index, replicate_index copies it to every rank, each rank runs its shard of
     the search (asgart_search_duplications_passes_shard), gather_families merges the families on rank 0, rank 0 runs the
@@ -277,13 +295,18 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     their original coordinates, by the slice's keys -- are broadcast, scored and extracted.  The text is then what
     `python -m asgart_amd.slice -f FMT OPTIONS` writes for the unsliced run's file (JSON with its trailing newline) and
     the name is out_filename with the format's extension.  With no active option and "json" nothing changes: the same
-    path through the code, the same bytes.  dist None: one process, one GPU, no collective."""
-    from .postprocess import out_filename, to_json_arrays
+    path through the code, the same bytes.  dist None: one process, one GPU, no collective.
+    writer: "device" (what None means, see DEFAULT_WRITER) writes the file on rank 0's GPU (postprocess.to_json_arrays_gpu,
+    slice.export_arrays_gpu: asgart_export_records), "host" with the array exporters one format operation per duplication;
+    the text is the same either way.  Sequences are out of scope for the device writer: with_sequences takes the host
+    exporter."""
+    from .postprocess import _to_json_arrays_device, out_filename, to_json_arrays
 
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_duplications: --trim runs on one rank only")
     reader = _choose_reader(reader, settings)
+    writer = _choose_writer(writer, with_sequences)
     comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
     sliced = _check_slice(slice_options, fmt)
     index = strand = records = source = None
@@ -328,12 +351,16 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
             seqs = _sequences(source, records, device_index, survivors, settings.reverse, settings.complement)
         name = out_filename(files, settings, prefix)
         if not sliced:
+            if writer == "device":
+                return _decode(_to_json_arrays_device(post[0], post[1], strand, settings, ident, None, device_index)), name
             return to_json_arrays(post[0], post[1], strand, settings, ident, seqs), name
-        from .slice import export_arrays
+        from .slice import _export_arrays_device, export_arrays
 
         if ident is not None:
             cut.identity = np.ascontiguousarray(ident, dtype=np.float32)
         cut.seqs = seqs
+        if writer == "device":
+            return _decode(_export_arrays_device(cut, fmt, device_index)), os.path.splitext(name)[0] + "." + fmt
         return export_arrays(cut, fmt), os.path.splitext(name)[0] + "." + fmt
     finally:
         if source is not None:
@@ -344,7 +371,7 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
 
 def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool, bool]], settings, dist,
                         device_index: int, compute_score: bool = False, prefix: str = "",
-                        with_sequences: bool = False, reader: Optional[str] = None):
+                        with_sequences: bool = False, reader: Optional[str] = None, writer: Optional[str] = None):
     """One run over several orientations of one strand -- what the reference needs one `asgart` invocation per
     orientation and an `asgart-slice` merge for.  orientations: one to four distinct (reverse, complement) pairs in the
     user's order; `settings` supplies everything else (its own two flags are ignored).  Built ONCE: the records read and
@@ -359,11 +386,12 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     reference src/structs.rs:114-141: strand and settings of the first, every duplication with the flags of its own
     run).  dist None: one process, one GPU, no collective.  `--trim` needs one rank.  reader: as search_duplications.
     Slicing (search_duplications' slice_options / fmt) is out of scope here: `python -m asgart_amd.slice` does it on the
-    files this writes."""
+    files this writes.  writer: as search_duplications -- every orientation's file and the merged one are written on rank
+    0's GPU unless "host" is asked for or with_sequences is set."""
     from dataclasses import replace
 
     from . import merge_shards, orientation_flags
-    from .postprocess import out_filename, to_json_arrays
+    from .postprocess import _to_json_arrays_device, out_filename, to_json_arrays
 
     orientations = [(bool(r), bool(c)) for r, c in orientations]
     if not 1 <= len(orientations) <= 4 or len(set(orientations)) != len(orientations):
@@ -373,6 +401,7 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
     reader = _choose_reader(reader, settings)
+    writer = _choose_writer(writer, with_sequences)
     comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
     index = strand = records = source = None
     chunks = [None]
@@ -407,17 +436,22 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
         seqs = None
         if with_sequences:
             seqs = _sequences(source, records, device_index, kept, (flags & 1).astype(bool), (flags >> 1 & 1).astype(bool))
+        def text_of(offs, sds, st, ident_, seqs_, flags_):
+            if writer == "device":
+                return _decode(_to_json_arrays_device(offs, sds, strand, st, ident_, flags_, device_index))
+            return to_json_arrays(offs, sds, strand, st, ident_, seqs_, flags_)
+
         out = []
         lo = 0
         for st, (offs, sds) in zip(sts, posts):
             hi = lo + len(sds)
             part = None if seqs is None else (seqs[0][lo:hi], seqs[1][lo:hi])
-            out.append((to_json_arrays(offs, sds, strand, st, None if ident is None else ident[lo:hi], part),
+            out.append((text_of(offs, sds, st, None if ident is None else ident[lo:hi], part, None),
                         out_filename(files, st, prefix)))
             lo = hi
         sizes = np.concatenate([np.diff(p[0].astype(np.int64)) for p in posts])
         all_offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
-        return out, to_json_arrays(all_offs, kept, strand, sts[0], ident, seqs, flags)
+        return out, text_of(all_offs, kept, sts[0], ident, seqs, flags)
     finally:
         if source is not None:
             source.close()
@@ -446,6 +480,8 @@ def _parse(argv):
     ap.add_argument("--host-reader", action="store_true",
                     help="read and prepare the FASTA files on the host (prep.read_records) instead of on rank 0's GPU; "
                          "the result is the same")
+    ap.add_argument("--host-writer", action="store_true",
+                    help="write the result file with the host exporters instead of on rank 0's GPU; the bytes are the same")
     ap.add_argument("--format", choices=("json", "gff2", "gff3"), default="json",
                     help="the format of the output file, as asgart-slice -f writes it")
     from .slice import add_filter_arguments
@@ -558,13 +594,14 @@ def rank_main(argv) -> int:
                                         max_cardinality=args.max_cardinality, reverse=args.reverse,
                                         complement=args.complement, skip_masked=args.skip_masked)
         reader = "host" if args.host_reader else None
+        writer = "host" if args.host_writer else None
         if args.orientations:
             out = search_orientations(args.files, args.orientations, settings, dist, device_index, args.compute_score,
-                                      args.prefix, args.with_sequences, reader)
+                                      args.prefix, args.with_sequences, reader, writer)
             texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])
         else:
             out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix,
-                                      args.with_sequences, reader, args.slice_options, args.format)
+                                      args.with_sequences, reader, args.slice_options, args.format, writer)
             texts = None if out is None else [out]
         for text, name in texts or []:
             path = os.path.join(args.out_dir, name)

@@ -354,6 +354,47 @@ def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSetti
     return head[:-2] + ',\n  "families": ' + body + "\n}"
 
 
+def _to_json_arrays_device(offs, sds, strand, settings: RunSettings, identity=None, flags=None, device: int = 0,
+                           timings: Optional[list] = None) -> np.ndarray:
+    """to_json_arrays_gpu as the uint8 array the library filled (the drivers decode it without another copy)."""
+    from . import export_records
+
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    n, m = len(sds), len(strand.map)
+    starts = np.array([c.position for c in strand.map], dtype=np.uint64)
+    ends = starts + np.array([c.length for c in strand.map], dtype=np.uint64)
+    names = [json.dumps(c.name, ensure_ascii=False).encode("utf-8") for c in strand.map] + [b'"unknown"']
+    chr_ = np.full((n, 2), m, dtype=np.int32)   # entry len(map) is "unknown"
+    chr_pos = sds[:, :2].copy()
+    if m:
+        for side in (0, 1):   # locate of to_json_arrays: the record of a position by bisection of the map
+            pos = sds[:, side]
+            i = np.searchsorted(starts, pos, side="right").astype(np.int64) - 1
+            ok = (i >= 0) & (pos < ends[np.maximum(i, 0)])
+            chr_[:, side] = np.where(ok, i, m)
+            chr_pos[:, side] = np.where(ok, pos - starts[np.maximum(i, 0)], pos)
+    if flags is None:
+        flags = np.full(n, int(bool(settings.reverse)) | int(bool(settings.complement)) << 1, dtype=np.uint8)
+    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != n:
+        raise ValueError(f"{len(flags)} flag bytes for {n} duplications")
+    rr = run_result([], strand, settings)
+    head = to_json({"strand": rr["strand"], "settings": rr["settings"]})
+    return export_records("json", offs, sds, flags, identity, chr_, chr_pos, names,
+                          (head[:-2] + ',\n  "families": ').encode("utf-8"), b"\n}", device, timings)
+
+
+def to_json_arrays_gpu(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSettings,
+                       identity: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None, device: int = 0) -> bytes:
+    """to_json_arrays(offs, sds, strand, settings, identity, None, flags).encode("utf-8"), written on the GPU
+    (asgart_export_records, csrc/export.hip): the arms are located here by the same bisection of the strand map, the name
+    table (every map entry's name as JSON text, then "unknown") and the head of the file are prepared here once, and the
+    families -- one record per duplication, the identity's shortest digits included -- are laid out and written by the
+    library.  Sequences (to_json_arrays' seqs) are not written on the device: a result with sequences goes through
+    to_json_arrays."""
+    return _to_json_arrays_device(offs, sds, strand, settings, identity, flags, device).tobytes()
+
+
 def out_filename(files: Sequence[str], settings: RunSettings, prefix: str = "") -> str:
     """Default output name, src/bin/asgart.rs:642-714: {prefix}{stems joined '-'}[_][R][C][_a-b].json"""
     import os
@@ -410,10 +451,10 @@ def search_orientations(strands_files: Sequence[str], orientations: Sequence[Tup
     -> ([(JSON text, output file name) per orientation], merged JSON text): each text is what
     to_json(search_duplications(files, settings with that orientation, device, compute_score)) gives, the merged one
     what merge_results gives for those files in that order.  Like search_duplications below it reads the files with the
-    host reader: these two are what the drivers' texts are compared with."""
+    host reader and writes them with the host writer: these two are what the drivers' texts are compared with."""
     from .multi import search_orientations as run
 
-    return run(strands_files, orientations, settings, None, device, compute_score, reader="host")
+    return run(strands_files, orientations, settings, None, device, compute_score, reader="host", writer="host")
 
 
 def search_duplications(strands_files: Sequence[str], settings: RunSettings, device: int = 0,

@@ -11,9 +11,10 @@ Three layers, as for the step chain (postprocess.py):
   arrays       ResultArrays and apply_arrays: whatever looks at a NAME (literal sets, regular expressions, the statistics
                of flatten, the reduced map) is answered on the host once per entry of a name table; the work per
                duplication runs on the GPU (asgart_slice_families, csrc/slice.hip).  gff2_arrays, gff3_arrays and
-               json_arrays write the same bytes as the per-object exporters with one format operation per duplication.
-  the tool     the options of asgart-slice.rs:19-91 under the reference's names; the array form by default, --host for
-               the per-object statement; the bytes are the same.
+               json_arrays write the same bytes as the per-object exporters with one format operation per duplication;
+               export_arrays_gpu writes them on the GPU (asgart_export_records, csrc/export.hip).
+  the tool     the options of asgart-slice.rs:19-91 under the reference's names; the array form, written by the device
+               writer, by default, --host for the per-object statement; the bytes are the same.
 
 Regular expressions are compiled by Python's `re`, the reference's by Rust's `regex`: the common syntax (classes,
 alternation, anchors, greedy and lazy repetition) means the same; Rust's has no look-around and no back-references,
@@ -803,6 +804,48 @@ def export_arrays(a: ResultArrays, fmt: str) -> str:
     return {"json": json_arrays, "gff2": gff2_arrays, "gff3": gff3_arrays}[fmt](a)
 
 
+def _export_tables(a: ResultArrays, fmt: str) -> Tuple[List[bytes], bytes, bytes]:
+    """What the host prepares for the device writer, once per call: (the name table as `fmt` prints it, the bytes in front of
+    the families, the bytes behind them)."""
+    import json
+
+    from .postprocess import to_json
+
+    if fmt not in FORMATS:
+        raise ValueError(f"unknown format `{fmt}` (one of {', '.join(FORMATS)})")
+    if fmt == "json":
+        if a.seqs is not None:
+            raise ValueError("export_arrays_gpu: sequences are not written on the device (export_arrays writes them)")
+        names = [json.dumps(n, ensure_ascii=False) for n in a.names]
+        prefix = to_json({"strand": a._strand_dict(), "settings": a.settings})[:-2] + ',\n  "families": '
+        suffix = "\n}\n"
+    else:
+        names = [_gff_name(n) for n in a.names]
+        prefix = (f'track name=Duplications\tuseScore=1\tdescription="ASGART - {a.strand_name}"\n' if fmt == "gff2"
+                  else _gff3_head(a._strand_dict()["map"]))
+        suffix = ""
+    return [n.encode("utf-8") for n in names], prefix.encode("utf-8"), suffix.encode("utf-8")
+
+
+def _export_arrays_device(a: ResultArrays, fmt: str, device: int = 0, timings: Optional[list] = None) -> np.ndarray:
+    """export_arrays_gpu as the uint8 array the library filled; timings: receives the library's three millisecond figures
+    (upload, kernels, copy back)."""
+    from . import export_records
+
+    names, prefix, suffix = _export_tables(a, fmt)
+    return export_records(fmt, a.offs, a.sds, a.flags, a.identity, a.chr, a.chr_pos, names, prefix, suffix, device, timings)
+
+
+def export_arrays_gpu(a: ResultArrays, fmt: str, device: int = 0) -> bytes:
+    """export_arrays(a, fmt).encode("utf-8"), written on the GPU (asgart_export_records, csrc/export.hip).  The host
+    prepares what looks at a name once per entry of the name table (JSON text for "json", _gff_name for the GFF forms) and
+    the head of the file (strand and settings, the track line, the sequence-region lines); the records of all families,
+    the identities' shortest digits included, are laid out and written by the library.  Sequences (a.seqs) are out of
+    scope for the device writer: JSON with sequences raises ValueError here and is export_arrays' to write (the GFF forms
+    never print them)."""
+    return _export_arrays_device(a, fmt, device).tobytes()
+
+
 # ---- the tool -------------------------------------------------------------------------------------------------------
 def add_filter_arguments(ap, renamed: Optional[Dict[str, Sequence[str]]] = None, dest_prefix: str = ""):
     """The filter options of asgart-slice.rs:32-90 on an argparse parser.  renamed: other option strings for an option,
@@ -877,7 +920,11 @@ def main(argv=None) -> int:
         if args.host:
             text = export_text(apply(result, options), args.format)
         else:
-            text = export_arrays(apply_arrays(ResultArrays.from_result(result), options, args.device), args.format)
+            cut = apply_arrays(ResultArrays.from_result(result), options, args.device)
+            if args.format == "json" and cut.seqs is not None:   # (sequences are the host exporter's)
+                text = export_arrays(cut, args.format)
+            else:
+                text = str(memoryview(_export_arrays_device(cut, args.format, args.device)), "utf-8")
     except (ValueError, OSError, KeyError, AsgartError) as e:
         print(f"Error: {e}", file=sys.stderr)
         return 1

@@ -583,6 +583,72 @@ void asgart_rosary_free(asgart_rosary *r);
  * arm counts on the seams. */
 void asgart_rosary_geometry(uint64_t *block_threads);
 
+/* ---- result files written on the GPU ------------------------------------------------------------------------
+ * Replace the per-duplication work of the three exporters of reference src/exporters.rs for a result held as arrays: one
+ * call gives the whole file, byte for byte what the exporter writes, in one device buffer.
+ *   ASGART_EXPORT_JSON   JSONExporter::save (:12-25): serde_json::to_string_pretty of RunResult.families -- 2-space indent,
+ *                        the SD fields in struct order (src/structs.rs:472-493), left_seq / right_seq `null`, identity as
+ *                        serde_json prints an f32 (ryu: ASGART_F32_JSON below)
+ *   ASGART_EXPORT_GFF2   GFF2Exporter::save (:27-67): two lines per duplication (:38-60), coordinates as stored, the score
+ *                        `sd.identity * 100.0` (:44, one rounded f32 product, printed with `{}`: ASGART_F32_DISPLAY), an empty
+ *                        line behind every family (:62)
+ *   ASGART_EXPORT_GFF3   GFF3Exporter::save (:69-113): two lines per duplication (:86-106), 1 added to every start and end,
+ *                        the score `sd.identity` with `{}`, an empty line behind every family (:108)
+ * in: fam_offsets[n_families + 1], sds[n_sd], flags[n_sd] (bit 0 reversed, bit 1 complemented), identity[n_sd] or NULL
+ * (every identity 0: `0.0` in JSON, `0` in GFF), chr[2 n_sd] (left, right) ids into the name table, chr_pos[2 n_sd].
+ * The name table is the host's: name_bytes holds every name as the format prints it -- for JSON the quoted and escaped
+ * string (serde_json's escaping), for GFF `str::replace(name.trim(), " ", "_")` (:41, :52, :89, :100) -- and name_offsets[n_names + 1]
+ * where each starts.  prefix and suffix are opaque: for JSON everything up to and including `"families": ` and the closing
+ * `\n}`, for GFF the track line (:30-35) or the `##gff-version` / `##sequence-region` lines (:72-82) and nothing.
+ * Sums (start + length, + 1) wrap as u64.  A name of any length is legal.
+ * out: asgart_export_size bytes on `device`; asgart_export_copy moves them into a caller buffer of at least that capacity.
+ * The handle owns the device buffer until asgart_export_free; nothing else stays on the device.
+ * Checked on the host before anything is launched (ASGART_E_ARG): an unknown format, fam_offsets or name_offsets not
+ * starting at 0, decreasing or (fam_offsets) not ending at n_sd, a name id outside the table; n_sd + n_families >= 2^31 - 1:
+ * ASGART_E_CAP; no usable device: ASGART_E_HIP. */
+#define ASGART_EXPORT_JSON 0
+#define ASGART_EXPORT_GFF2 1
+#define ASGART_EXPORT_GFF3 2
+typedef struct asgart_export asgart_export;
+int32_t asgart_export_records(int32_t device, int32_t format, const uint64_t *fam_offsets, int64_t n_families,
+                              const asgart_proto_sd *sds, const uint8_t *flags, const float *identity, const int32_t *chr,
+                              const uint64_t *chr_pos, int64_t n_sd, const uint8_t *name_bytes, const uint64_t *name_offsets,
+                              int64_t n_names, const uint8_t *prefix, uint64_t prefix_len, const uint8_t *suffix,
+                              uint64_t suffix_len, asgart_export **out);
+/* Bytes of the file behind e (exporters.rs: what `out.write_all` / `writeln!` have written when save returns). */
+uint64_t asgart_export_size(const asgart_export *e);
+/* The file into dst[capacity], capacity >= asgart_export_size(e): what exporters.rs:14, :29 and :71 hand to `out`; the
+ * writer behind `out` stays the caller's. */
+int32_t asgart_export_copy(asgart_export *e, uint8_t *dst, uint64_t capacity);
+/* Milliseconds of the call behind e (exporters.rs:12-113 on the device): [0] the upload of the arrays, [1] the kernels
+ * (lengths, scan, write; HIP events for both), [2] the last asgart_export_copy (host clock; 0 before one). */
+int32_t asgart_export_timings(const asgart_export *e, double *ms3);
+/* Gives the device buffer back (the file exporters.rs:12-113 wrote is the caller's copy from then on); NULL is allowed. */
+void asgart_export_free(asgart_export *e);
+/* Sizes the write stage of asgart_export_records works in (the loops of exporters.rs:36-63 and :84-109 cut into
+ * workgroups), for tests that place their counts on the seams: threads per workgroup, units per workgroup (a unit is a
+ * record or the framing between two families: n_sd + n_families + 1 in all), bytes of the LDS image of a workgroup's range;
+ * a range larger than that is stored without the image. */
+void asgart_export_geometry(uint64_t *block_threads, uint64_t *records_per_block, uint64_t *stage_bytes);
+/* An array of f32 rendered on the device as the exporters print an identity: the shortest decimal digits that read back
+ * as the same f32, in one of two forms.
+ *   ASGART_F32_JSON      serde_json's (ryu's pretty printer; `identity` in exporters.rs:12-25): `97.3`, `100.0`, `0.0`,
+ *                        `-0.0`, `1e-7`, `3.4028235e38` (an exponent for |v| < 1e-5 and |v| >= 1e13), `null` for NaN and
+ *                        the infinities
+ *   ASGART_F32_DISPLAY   Rust's `{}` (exporters.rs:44, :55, :92, :103): always positional, `97.3`, `100`, `0`, `-0`, `0.0000001`,
+ *                        `NaN`, `inf`, `-inf`
+ * out_bytes[n * ASGART_F32_TEXT_MAX]: value i at i * ASGART_F32_TEXT_MAX, out_lens[i] bytes of it. */
+#define ASGART_F32_JSON 0
+#define ASGART_F32_DISPLAY 1
+#define ASGART_F32_TEXT_MAX 64
+int32_t asgart_f32_shortest(int32_t device, const float *values, int64_t n, int32_t mode, uint8_t *out_bytes,
+                            uint8_t *out_lens);
+/* The table of powers of ten behind the digits (serde_json's ryu carries one of the same purpose): for k = *k_min ..
+ * *k_max four words per entry -- hi, lo, x (a two's complement int64), exact -- with 10^-k = (hi * 2^64 + lo) * 2^x, exactly
+ * where exact != 0 and rounded up otherwise; computed with integer arithmetic when first used.  Needs no device.
+ * Returns the number of entries; every argument is nullable. */
+int32_t asgart_f32_pow10_table(int32_t *k_min, int32_t *k_max, uint64_t *entries);
+
 /* ---- FASTA files read on the GPU ---------------------------------------------------------------------------
  * Replace the FASTA reader in front of prepare_data and prepare_data itself (reference src/bin/asgart.rs:273-430: bio's
  * fasta::Reader and the per-record loop at :278-313, normalisation :289-301, find_chunks_to_process :317-366,
