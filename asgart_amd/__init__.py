@@ -319,6 +319,32 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _families_out(L, h, with_keys: bool = False):
+    """The arrays behind a families handle -> (fam_offsets[n_fam+1], sds[n_sd,4]), with_keys: and keys[n_fam]
+    (asgart_families_keys); the handle is freed."""
+    try:
+        nf, ns = C.c_uint64(), C.c_uint64()
+        L.asgart_families_counts(h, C.byref(nf), C.byref(ns))
+        offs = np.zeros(nf.value + 1, dtype=np.uint64)
+        sds = np.zeros((ns.value, 4), dtype=np.uint64)
+        L.asgart_families_copy(h, _ptr(offs), _ptr(sds))
+        if not with_keys:
+            return offs, sds
+        keys = np.zeros(nf.value, dtype=np.uint64)
+        L.asgart_families_keys(h, _ptr(keys))
+        return offs, sds, keys
+    finally:
+        L.asgart_families_free(h)
+
+
+def _read_timings(fn, h, timings: Optional[list]) -> None:
+    """The three millisecond figures of a result handle (fn: its asgart_*_timings) into the caller's list, if there is one."""
+    if timings is not None:
+        ms = (C.c_double * 3)()
+        _check(fn(h, ms))
+        timings[:] = list(ms)
+
+
 def _as_u8(seq) -> np.ndarray:
     if isinstance(seq, np.ndarray):
         if seq.dtype != np.uint8:
@@ -551,15 +577,7 @@ class Index:
         sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
         h = C.c_void_p()
         _check(L.asgart_post_process(self._h, _ptr(offs), len(offs) - 1, _ptr(sds), threads, C.byref(h)))
-        try:
-            nf, ns = C.c_uint64(), C.c_uint64()
-            L.asgart_families_counts(h, C.byref(nf), C.byref(ns))
-            o = np.zeros(nf.value + 1, dtype=np.uint64)
-            d = np.zeros((ns.value, 4), dtype=np.uint64)
-            L.asgart_families_copy(h, _ptr(o), _ptr(d))
-        finally:
-            L.asgart_families_free(h)
-        return o, d
+        return _families_out(L, h)
 
     def stats(self, flags: int = 2) -> Stats:
         """Statistics of the last search call.  flags: 1 = with the yardstick / accounting passes, 2 (default) = with raw_hits
@@ -589,18 +607,7 @@ class Index:
         else:
             _check(L.asgart_search_duplications_ex(self._h, _ptr(ch), len(chunks), C.byref(st), shard, n_shards,
                                                    _ptr(progress), C.byref(h)))
-        try:
-            nf, ns = C.c_uint64(), C.c_uint64()
-            L.asgart_families_counts(h, C.byref(nf), C.byref(ns))
-            offs = np.zeros(nf.value + 1, dtype=np.uint64)
-            sds = np.zeros((ns.value, 4), dtype=np.uint64)
-            L.asgart_families_copy(h, _ptr(offs), _ptr(sds))
-            keys = np.zeros(nf.value, dtype=np.uint64)
-            if with_keys:
-                L.asgart_families_keys(h, _ptr(keys))
-        finally:
-            L.asgart_families_free(h)
-        return (offs, sds, keys) if with_keys else (offs, sds)
+        return _families_out(L, h, with_keys)
 
     def search_duplications_passes(self, chunks: Sequence[Tuple[int, int]], settings: Sequence[RunSettings],
                                    shard: int = 0, n_shards: int = 1, with_keys: bool = False) -> List[tuple]:
@@ -615,22 +622,12 @@ class Index:
             _check(L.asgart_search_duplications_passes(self._h, _ptr(ch), len(chunks), sts, n, hs))
         else:
             _check(L.asgart_search_duplications_passes_shard(self._h, _ptr(ch), len(chunks), sts, n, shard, n_shards, hs))
-        out = []
+        left = list(hs)[:n]   # (a handle is freed by whoever reads it; the ones an exception leaves unread, here)
         try:
-            for j in range(n):
-                nf, ns = C.c_uint64(), C.c_uint64()
-                L.asgart_families_counts(hs[j], C.byref(nf), C.byref(ns))
-                offs = np.zeros(nf.value + 1, dtype=np.uint64)
-                sds = np.zeros((ns.value, 4), dtype=np.uint64)
-                L.asgart_families_copy(hs[j], _ptr(offs), _ptr(sds))
-                keys = np.zeros(nf.value, dtype=np.uint64)
-                if with_keys:
-                    L.asgart_families_keys(hs[j], _ptr(keys))
-                out.append((offs, sds, keys) if with_keys else (offs, sds))
+            return [_families_out(L, left.pop(0), with_keys) for _ in range(n)]
         finally:
-            for j in range(n):
-                L.asgart_families_free(hs[j])
-        return out
+            for h in left:
+                L.asgart_families_free(h)
 
     def probe_hits(self, chunks: Sequence[Tuple[int, int]], settings: RunSettings):
         """Per-probe filtered hits for all chunks: (status, row_offsets, hits)."""
@@ -747,15 +744,7 @@ def search_duplications_multi(indices: Sequence[Index], chunks: Sequence[Tuple[i
     h = C.c_void_p()
     _check(L.asgart_search_duplications_multi(arr, len(indices), _ptr(ch), len(chunks), C.byref(st), None,
                                               C.byref(h)))
-    try:
-        nf, ns = C.c_uint64(), C.c_uint64()
-        L.asgart_families_counts(h, C.byref(nf), C.byref(ns))
-        offs = np.zeros(nf.value + 1, dtype=np.uint64)
-        sds = np.zeros((ns.value, 4), dtype=np.uint64)
-        L.asgart_families_copy(h, _ptr(offs), _ptr(sds))
-    finally:
-        L.asgart_families_free(h)
-    return offs, sds
+    return _families_out(L, h)
 
 
 def score_owners(sds: np.ndarray, n_shards: int) -> np.ndarray:
@@ -874,10 +863,7 @@ def export_records(fmt: str, offs, sds, flags, identity, chr_, chr_pos, names: S
     try:
         out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
         _check(L.asgart_export_copy(h, _ptr(out), len(out)))
-        if timings is not None:
-            ms = (C.c_double * 3)()
-            _check(L.asgart_export_timings(h, ms))
-            timings[:] = list(ms)
+        _read_timings(L.asgart_export_timings, h, timings)
     finally:
         L.asgart_export_free(h)
     return out

@@ -13,12 +13,8 @@
 //             1 KiB of consecutive bytes.  Only the lines the range shares with its neighbours (its head and its tail, fewer
 //             than 16 bytes each) go out byte by byte.  A range that does not fit the image (a 5 000-byte fragment name is
 //             legal) is stored from the threads directly: slower, never refused.
-#include "common.hpp"
+#include "tool_base.hpp"
 #include "export_dev.hpp"
-
-#include <algorithm>
-
-#include <rocprim/rocprim.hpp>
 
 namespace asgart {
 namespace {
@@ -114,23 +110,6 @@ __global__ __launch_bounds__(256) void f32_shortest_kernel(const float *__restri
     out_lens[i] = (uint8_t)(s.p - text);
 }
 
-int32_t upload(DevBuf &b, const void *src, size_t bytes, hipStream_t s) {
-    RC_TRY(b.reserve(std::max<size_t>(bytes, 16)));
-    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
-    return 0;
-}
-
-int32_t use_device(const char *who, int32_t device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
-        (void)hipGetLastError();
-        set_error("%s: no usable device %d (there is no CPU fallback)", who, device);
-        return ASGART_E_HIP;
-    }
-    HIP_TRY(hipSetDevice(device));
-    return 0;
-}
-
 }  // namespace
 }  // namespace asgart
 
@@ -148,19 +127,9 @@ struct asgart_export {
 
 namespace {
 
-struct ExportWork {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    DevBuf offs, sds, flags, identity, chr, chr_pos, names, name_off, pow10, slots, lens, offsets, scan_tmp;
-    ~ExportWork() {
-        if (s) (void)hipStreamSynchronize(s);
-        for (DevBuf *b : {&offs, &sds, &flags, &identity, &chr, &chr_pos, &names, &name_off, &pow10, &slots, &lens, &offsets,
-                          &scan_tmp})
-            b->release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
+struct ExportWork : ToolWork {
+    DevBuf &offs = buf(), &sds = buf(), &flags = buf(), &identity = buf(), &chr = buf(), &chr_pos = buf(), &names = buf(),
+           &name_off = buf(), &pow10 = buf(), &slots = buf(), &lens = buf(), &offsets = buf();
 };
 
 // Every argument check of the call, before the device is looked at.
@@ -181,16 +150,7 @@ int32_t check_arguments(int32_t format, const uint64_t *fam_offsets, int64_t n_f
         set_error("asgart_export_records: 2^31 duplications and families and more are not supported");
         return ASGART_E_CAP;
     }
-    if (fam_offsets[0] != 0 || fam_offsets[n_families] != (uint64_t)n_sd) {
-        set_error("asgart_export_records: fam_offsets must start at 0 and end at n_sd = %lld (they run from %llu to %llu)",
-                  (long long)n_sd, (unsigned long long)fam_offsets[0], (unsigned long long)fam_offsets[n_families]);
-        return ASGART_E_ARG;
-    }
-    for (int64_t f = 0; f < n_families; ++f)
-        if (fam_offsets[f] > fam_offsets[f + 1]) {
-            set_error("asgart_export_records: fam_offsets decrease at family %lld", (long long)f);
-            return ASGART_E_ARG;
-        }
+    RC_TRY(check_csr("asgart_export_records", "fam_offsets", fam_offsets, n_families, n_sd, "n_sd"));
     if (name_offsets[0] != 0 || (name_offsets[n_names] && !name_bytes) || name_offsets[n_names] >= ((uint64_t)1 << 30)) {
         set_error("asgart_export_records: name_offsets must start at 0 and end below 2^30 bytes of names");
         return ASGART_E_ARG;
@@ -200,32 +160,25 @@ int32_t check_arguments(int32_t format, const uint64_t *fam_offsets, int64_t n_f
             set_error("asgart_export_records: name_offsets decrease at name %lld", (long long)k);
             return ASGART_E_ARG;
         }
-    for (int64_t q = 0; q < 2 * n_sd; ++q)
-        if (chr[q] < 0 || chr[q] >= n_names) {
-            set_error("asgart_export_records: duplication %lld has name id %d, outside the name table (%lld names)",
-                      (long long)(q / 2), chr[q], (long long)n_names);
-            return ASGART_E_ARG;
-        }
-    return 0;
+    return check_name_ids("asgart_export_records", chr, n_sd, n_names);
 }
 
 int32_t run_export(ExportWork &w, asgart_export *res, int32_t format, const uint64_t *fam_offsets, uint32_t nf,
                    const asgart_proto_sd *sds, const uint8_t *flags, const float *identity, const int32_t *chr,
                    const uint64_t *chr_pos, uint32_t n, const uint8_t *name_bytes, const uint64_t *name_offsets,
                    size_t n_names, const uint8_t *prefix, uint64_t prefix_len, const uint8_t *suffix, uint64_t suffix_len) {
-    HIP_TRY(hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking));
-    for (hipEvent_t &e : w.ev) HIP_TRY(hipEventCreate(&e));
+    RC_TRY(w.open(5));
     hipStream_t s = w.s;
     HIP_TRY(hipEventRecord(w.ev[0], s));
-    RC_TRY(upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8, s));
-    RC_TRY(upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd), s));
-    RC_TRY(upload(w.flags, flags, n, s));
-    if (identity) RC_TRY(upload(w.identity, identity, (size_t)n * 4, s));
-    RC_TRY(upload(w.chr, chr, (size_t)n * 8, s));
-    RC_TRY(upload(w.chr_pos, chr_pos, (size_t)n * 16, s));
-    RC_TRY(upload(w.names, name_bytes, (size_t)name_offsets[n_names], s));
-    RC_TRY(upload(w.name_off, name_offsets, (n_names + 1) * 8, s));
-    RC_TRY(upload(w.pow10, pow10_table(), sizeof(Pow10Entry) * kPow10Entries, s));
+    RC_TRY(w.upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8));
+    RC_TRY(w.upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd)));
+    RC_TRY(w.upload(w.flags, flags, n));
+    if (identity) RC_TRY(w.upload(w.identity, identity, (size_t)n * 4));
+    RC_TRY(w.upload(w.chr, chr, (size_t)n * 8));
+    RC_TRY(w.upload(w.chr_pos, chr_pos, (size_t)n * 16));
+    RC_TRY(w.upload(w.names, name_bytes, (size_t)name_offsets[n_names]));
+    RC_TRY(w.upload(w.name_off, name_offsets, (n_names + 1) * 8));
+    RC_TRY(w.upload(w.pow10, pow10_table(), sizeof(Pow10Entry) * kPow10Entries));
     HIP_TRY(hipEventRecord(w.ev[1], s));
     const uint32_t n_units = n + nf + 1;
     RC_TRY(w.slots.reserve((size_t)n_units * 16));
@@ -248,12 +201,7 @@ int32_t run_export(ExportWork &w, asgart_export *res, int32_t format, const uint
     export_lengths_kernel<<<(unsigned)(((uint64_t)n_units + 1 + 255) / 256), 256, 0, s>>>(in, n_units, w.slots.as<uint4>(),
                                                                                           lens);
     HIP_TRY(hipGetLastError());
-    size_t tmp = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, lens, offsets, (uint64_t)0, (size_t)n_units + 1,
-                                    rocprim::plus<uint64_t>(), s));
-    RC_TRY(w.scan_tmp.reserve(tmp + 16));
-    HIP_TRY(rocprim::exclusive_scan(w.scan_tmp.p, tmp, lens, offsets, (uint64_t)0, (size_t)n_units + 1,
-                                    rocprim::plus<uint64_t>(), s));
+    RC_TRY(w.exclusive_scan(lens, offsets, (size_t)n_units + 1));
     HIP_TRY(hipEventRecord(w.ev[2], s));
     uint64_t body = 0;
     HIP_TRY(read_back(&body, offsets + n_units, 8, s));
@@ -289,20 +237,11 @@ extern "C" int32_t asgart_export_records(int32_t device, int32_t format, const u
     RC_TRY(check_arguments(format, fam_offsets, n_families, sds, flags, chr, chr_pos, n_sd, name_bytes, name_offsets,
                            n_names, prefix, prefix_len, suffix, suffix_len, out));
     RC_TRY(use_device("asgart_export_records", device));
-    asgart_export *res = new asgart_export;
-    res->device = device;
-    int32_t rc;
-    {
-        ExportWork w;
-        rc = run_export(w, res, format, fam_offsets, (uint32_t)n_families, sds, flags, identity, chr, chr_pos,
-                        (uint32_t)n_sd, name_bytes, name_offsets, (size_t)n_names, prefix, prefix_len, suffix, suffix_len);
-    }
-    if (rc != 0) {
-        delete res;
-        return rc;
-    }
-    *out = res;
-    return 0;
+    return run_tool<ExportWork>(out, [&](ExportWork &w, asgart_export *res) {
+        res->device = device;
+        return run_export(w, res, format, fam_offsets, (uint32_t)n_families, sds, flags, identity, chr, chr_pos,
+                          (uint32_t)n_sd, name_bytes, name_offsets, (size_t)n_names, prefix, prefix_len, suffix, suffix_len);
+    });
 }
 
 extern "C" uint64_t asgart_export_size(const asgart_export *e) { return e ? e->size : 0; }
@@ -320,12 +259,7 @@ extern "C" int32_t asgart_export_copy(asgart_export *e, uint8_t *dst, uint64_t c
 }
 
 extern "C" int32_t asgart_export_timings(const asgart_export *e, double *ms3) {
-    if (!e || !ms3) {
-        set_error("asgart_export_timings: bad argument");
-        return ASGART_E_ARG;
-    }
-    for (int k = 0; k < 3; ++k) ms3[k] = e->ms[k];
-    return 0;
+    return copy_ms3("asgart_export_timings", e, ms3);
 }
 
 extern "C" void asgart_export_free(asgart_export *e) { delete e; }
@@ -351,27 +285,20 @@ extern "C" int32_t asgart_f32_shortest(int32_t device, const float *values, int6
     }
     RC_TRY(use_device("asgart_f32_shortest", device));
     if (n == 0) return 0;
-    struct Work {
-        hipStream_t s = nullptr;
-        DevBuf values, pow10, bytes, lens;
-        ~Work() {
-            if (s) (void)hipStreamSynchronize(s);
-            for (DevBuf *b : {&values, &pow10, &bytes, &lens}) b->release();
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } w;
-    HIP_TRY(hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking));
-    RC_TRY(upload(w.values, values, (size_t)n * 4, w.s));
-    RC_TRY(upload(w.pow10, pow10_table(), sizeof(Pow10Entry) * kPow10Entries, w.s));
-    RC_TRY(w.bytes.reserve((size_t)n * kF32TextMax));
-    RC_TRY(w.lens.reserve((size_t)n));
-    HIP_TRY(hipMemsetAsync(w.bytes.p, 0, (size_t)n * kF32TextMax, w.s));
+    ToolWork w;
+    DevBuf &d_values = w.buf(), &pow10 = w.buf(), &bytes = w.buf(), &lens = w.buf();
+    RC_TRY(w.open(0));
+    RC_TRY(w.upload(d_values, values, (size_t)n * 4));
+    RC_TRY(w.upload(pow10, pow10_table(), sizeof(Pow10Entry) * kPow10Entries));
+    RC_TRY(bytes.reserve((size_t)n * kF32TextMax));
+    RC_TRY(lens.reserve((size_t)n));
+    HIP_TRY(hipMemsetAsync(bytes.p, 0, (size_t)n * kF32TextMax, w.s));
     f32_shortest_kernel<<<(unsigned)(((uint64_t)n + 255) / 256), 256, 0, w.s>>>(
-        w.values.as<float>(), (uint64_t)n, mode, w.pow10.as<Pow10Entry>(), w.bytes.as<uint8_t>(), w.lens.as<uint8_t>());
+        d_values.as<float>(), (uint64_t)n, mode, pow10.as<Pow10Entry>(), bytes.as<uint8_t>(), lens.as<uint8_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(stream_sync(w.s));
-    HIP_TRY(hipMemcpyAsync(out_bytes, w.bytes.p, (size_t)n * kF32TextMax, hipMemcpyDeviceToHost, w.s));
-    HIP_TRY(hipMemcpyAsync(out_lens, w.lens.p, (size_t)n, hipMemcpyDeviceToHost, w.s));
+    HIP_TRY(hipMemcpyAsync(out_bytes, bytes.p, (size_t)n * kF32TextMax, hipMemcpyDeviceToHost, w.s));
+    HIP_TRY(hipMemcpyAsync(out_lens, lens.p, (size_t)n, hipMemcpyDeviceToHost, w.s));
     HIP_TRY(stream_sync(w.s));
     return 0;
 }

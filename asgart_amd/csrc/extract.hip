@@ -9,7 +9,7 @@
 // offsets come from a scan on the device, every lane writes one aligned 16-byte vector of the output (long arms are
 // spread over as many workgroups as their length asks for), and the copy of one piece to the host runs beside the
 // gather of the next.
-#include "common.hpp"
+#include "tool_base.hpp"
 #include "prep.hpp"
 
 #include <algorithm>
@@ -284,13 +284,7 @@ extern "C" int32_t asgart_source_create(const uint8_t *const *records, const uin
         }
         n += record_lens[r];
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
-        (void)hipGetLastError();
-        set_error("asgart_source_create: no usable device %d (there is no CPU fallback)", device);
-        return ASGART_E_HIP;
-    }
-    HIP_TRY(hipSetDevice(device));
+    RC_TRY(use_device("asgart_source_create", device));
     asgart_source *src = nullptr;
     RC_TRY(source_new(n, device, &src));
     int32_t rc = src->text.reserve((size_t)n + kPad);

@@ -26,6 +26,7 @@
 // No workgroup waits for another one: the order between tiles is the order of the launches.
 #include "index.hpp"
 #include "prep.hpp"
+#include "tool_base.hpp"
 
 #include <algorithm>
 
@@ -574,13 +575,7 @@ extern "C" int32_t asgart_fasta_read(const uint8_t *const *files, const uint64_t
         set_error("asgart_fasta_read: no record in %lld file(s) (no line starts with '>')", (long long)n_files);
         return ASGART_E_ARG;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
-        (void)hipGetLastError();
-        set_error("asgart_fasta_read: no usable device %d (there is no CPU fallback)", device);
-        return ASGART_E_HIP;
-    }
-    HIP_TRY(hipSetDevice(device));
+    RC_TRY(use_device("asgart_fasta_read", device));
     asgart_fasta *f = new asgart_fasta;
     f->device = device;
     Reader R;

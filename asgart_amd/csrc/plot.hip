@@ -23,11 +23,7 @@
 // one larger than a workgroup and one larger than 65 535 are the same case.  "First stop of a feature" is the same trick on
 // the scan of the stop flags.  Survivors keep the input order.  Lists are appended to with one atomic per wave; their order
 // differs from call to call and no result depends on it.  The error ordinals are minima (atomicMin), as slice.hip's err.
-#include "common.hpp"
-
-#include <algorithm>
-
-#include <rocprim/rocprim.hpp>
+#include "tool_base.hpp"
 
 namespace asgart {
 namespace {
@@ -58,16 +54,6 @@ __device__ inline uint32_t wave_append(bool want, uint32_t *counter) {
     if ((int)lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(mask));
     base = __shfl(base, leader);
     return base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-}
-
-// largest f in [0, n_seg) with offs[f] <= i < offs[f + 1] (empty segments are stepped over); i < offs[n_seg]
-__device__ inline uint32_t segment_of(const uint64_t *__restrict__ offs, uint32_t n_seg, uint32_t i) {
-    uint32_t lo = 0, hi = n_seg;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (offs[mid] > i) hi = mid; else lo = mid + 1;
-    }
-    return lo - 1;
 }
 
 // --min-length (the longer arm) and the identity range in f32: a NaN fails both compares
@@ -272,20 +258,6 @@ __global__ __launch_bounds__(kBlock) void plot_feature_first_kernel(const uint64
     if (!resolved[p]) atomicMin(err, p); else feat_keep[f] = 1;
 }
 
-// out_offs[k] of the k-th kept family = the rank of its first duplication; thread n_fam writes the closing entry
-__global__ __launch_bounds__(kBlock) void plot_family_offsets_kernel(const uint64_t *__restrict__ offs, uint32_t n_fam,
-                                                                    uint32_t n, const uint32_t *__restrict__ rank,
-                                                                    const uint32_t *__restrict__ fam_keep,
-                                                                    const uint32_t *__restrict__ fam_rank,
-                                                                    uint64_t *__restrict__ out_offs) {
-    const uint32_t f = blockIdx.x * kBlock + threadIdx.x;
-    if (f > n_fam) return;
-    if (f == n_fam)
-        out_offs[fam_rank[n_fam]] = rank[n];
-    else if (fam_keep[f])
-        out_offs[fam_rank[f]] = rank[offs[f]];
-}
-
 __global__ __launch_bounds__(kBlock) void plot_keys_kernel(uint32_t n, const uint32_t *__restrict__ alive,
                                                           const uint32_t *__restrict__ rank, int64_t *__restrict__ keys) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -297,8 +269,6 @@ __global__ __launch_bounds__(kBlock) void plot_fill_u32_kernel(uint32_t *__restr
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i < n) out[i] = v;
 }
-
-inline unsigned blocks_for(uint64_t items) { return (unsigned)((items + kBlock - 1) / kBlock); }
 
 }  // namespace
 }  // namespace asgart
@@ -315,7 +285,8 @@ struct asgart_plot {
 namespace {
 
 struct IntervalBuf {
-    DevBuf s, e, proper, owner;
+    DevBuf &s, &e, &proper, &owner;
+    explicit IntervalBuf(ToolWork &w) : s(w.buf()), e(w.buf()), proper(w.buf()), owner(w.buf()) {}
     int32_t reserve(size_t items) {
         items = std::max<size_t>(items, 2);
         RC_TRY(s.reserve(items * 8));
@@ -325,60 +296,21 @@ struct IntervalBuf {
         return 0;
     }
     Intervals view() const { return Intervals{s.as<uint64_t>(), e.as<uint64_t>(), proper.as<uint8_t>(), owner.as<uint32_t>()}; }
-    void release() {
-        for (DevBuf *b : {&s, &e, &proper, &owner}) b->release();
-    }
 };
 
-struct PlotWork {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    DevBuf offs, sds, identity, feat_offs, p_start, p_len, p_res;
-    DevBuf alive, rank, matched, rank_m, hit, fam_keep, fam_rank, stop, stop_rank, feat_keep, scan_tmp, sort_tmp, counters;
-    DevBuf tp_s, tp_e, ti_s, ti_e, sorted_s, sorted_e;
-    IntervalBuf arms, windows, improper;
-    DevBuf o_offs, o_keys;
+struct PlotWork : ToolWork {
+    DevBuf &offs = buf(), &sds = buf(), &identity = buf(), &feat_offs = buf(), &p_start = buf(), &p_len = buf(), &p_res = buf();
+    DevBuf &alive = buf(), &rank = buf(), &matched = buf(), &rank_m = buf(), &hit = buf(), &fam_keep = buf(), &fam_rank = buf(),
+           &stop = buf(), &stop_rank = buf(), &feat_keep = buf(), &counters = buf();
+    DevBuf &tp_s = buf(), &tp_e = buf(), &ti_s = buf(), &ti_e = buf(), &sorted_s = buf(), &sorted_e = buf();
+    IntervalBuf arms{*this}, windows{*this}, improper{*this};
+    DevBuf &o_offs = buf(), &o_keys = buf();
     double join_ms = 0;
-    ~PlotWork() {
-        if (s) (void)hipStreamSynchronize(s);
-        for (DevBuf *b : {&offs, &sds, &identity, &feat_offs, &p_start, &p_len, &p_res, &alive, &rank, &matched, &rank_m,
-                          &hit, &fam_keep, &fam_rank, &stop, &stop_rank, &feat_keep, &scan_tmp, &sort_tmp, &counters, &tp_s,
-                          &tp_e, &ti_s, &ti_e, &sorted_s, &sorted_e, &o_offs, &o_keys})
-            b->release();
-        arms.release();
-        windows.release();
-        improper.release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
 };
 
 // counters: [0] windows emitted, [1] proper targets, [2] improper targets, [3] improper queries, [4] err of the families /
 // duplicons steps, [5] err of the features step
 enum { cWindows = 0, cProper = 1, cImproper = 2, cQueries = 3, cErrU = 4, cErrFeat = 5, cCount = 8 };
-
-int32_t upload(DevBuf &b, const void *src, size_t bytes, hipStream_t s) {
-    RC_TRY(b.reserve(std::max<size_t>(bytes, 16)));
-    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
-    return 0;
-}
-
-int32_t exclusive_scan_u32(PlotWork &w, const uint32_t *in, uint32_t *out, size_t items) {
-    size_t tmp = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, items, rocprim::plus<uint32_t>(), w.s));
-    RC_TRY(w.scan_tmp.reserve(tmp + 16));
-    HIP_TRY(rocprim::exclusive_scan(w.scan_tmp.p, tmp, in, out, 0u, items, rocprim::plus<uint32_t>(), w.s));
-    return 0;
-}
-
-int32_t sort_u64(PlotWork &w, const uint64_t *in, uint64_t *out, size_t items) {
-    size_t tmp = 0;
-    HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp, in, out, items, 0, 64, w.s));
-    RC_TRY(w.sort_tmp.reserve(tmp + 16));
-    HIP_TRY(rocprim::radix_sort_keys(w.sort_tmp.p, tmp, in, out, items, 0, 64, w.s));
-    return 0;
-}
 
 // hit[owner of q] = 1 for every query that overlaps a target.  cap: the most intervals either list can hold.
 int32_t join(PlotWork &w, const Intervals &q, uint32_t nq, const Intervals &t, uint32_t nt, uint32_t force_literal,
@@ -409,8 +341,8 @@ int32_t join(PlotWork &w, const Intervals &q, uint32_t nq, const Intervals &t, u
     if (!n_proper) return 0;
     RC_TRY(w.sorted_s.reserve((size_t)n_proper * 8));
     RC_TRY(w.sorted_e.reserve((size_t)n_proper * 8));
-    RC_TRY(sort_u64(w, w.tp_s.as<uint64_t>(), w.sorted_s.as<uint64_t>(), n_proper));
-    RC_TRY(sort_u64(w, w.tp_e.as<uint64_t>(), w.sorted_e.as<uint64_t>(), n_proper));
+    RC_TRY(w.sort_keys(w.tp_s.as<uint64_t>(), w.sorted_s.as<uint64_t>(), n_proper));
+    RC_TRY(w.sort_keys(w.tp_e.as<uint64_t>(), w.sorted_e.as<uint64_t>(), n_proper));
     RC_TRY(w.improper.reserve(nq));
     const Intervals qi = w.improper.view();
     plot_bisect_kernel<<<blocks_for(nq), kBlock, 0, s>>>(q, nq, w.sorted_s.as<uint64_t>(), w.sorted_e.as<uint64_t>(), n_proper,
@@ -444,22 +376,8 @@ int32_t check_arguments(const uint64_t *fam_offsets, int64_t n_families, const a
         set_error("asgart_plot_filter: 2^30 duplications, families, features or positions and more are not supported");
         return ASGART_E_CAP;
     }
-    struct Csr { const char *name; const uint64_t *offs; int64_t n_seg, n_items; const char *items; };
-    const Csr csr[2] = {{"fam_offsets", fam_offsets, n_families, n_sd, "n_sd"},
-                        {"feat_offsets", feat_offsets, n_features, n_positions, "n_positions"}};
-    for (const Csr &c : csr) {
-        if (c.offs[0] != 0 || c.offs[c.n_seg] != (uint64_t)c.n_items) {
-            set_error("asgart_plot_filter: %s must start at 0 and end at %s = %lld (they run from %llu to %llu)", c.name,
-                      c.items, (long long)c.n_items, (unsigned long long)c.offs[0], (unsigned long long)c.offs[c.n_seg]);
-            return ASGART_E_ARG;
-        }
-        for (int64_t f = 0; f < c.n_seg; ++f)
-            if (c.offs[f] > c.offs[f + 1]) {
-                set_error("asgart_plot_filter: %s decrease at entry %lld", c.name, (long long)f);
-                return ASGART_E_ARG;
-            }
-    }
-    return 0;
+    RC_TRY(check_csr("asgart_plot_filter", "fam_offsets", fam_offsets, n_families, n_sd, "n_sd", "entry"));
+    return check_csr("asgart_plot_filter", "feat_offsets", feat_offsets, n_features, n_positions, "n_positions", "entry");
 }
 
 int32_t run_plot(PlotWork &w, asgart_plot *res, const uint64_t *fam_offsets, uint32_t nf, const asgart_proto_sd *sds,
@@ -474,16 +392,15 @@ int32_t run_plot(PlotWork &w, asgart_plot *res, const uint64_t *fam_offsets, uin
             break;
         }
     const uint32_t before_u = u == kNone ? n_pos : u;
-    HIP_TRY(hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking));
-    for (hipEvent_t &e : w.ev) HIP_TRY(hipEventCreate(&e));
+    RC_TRY(w.open(4));
     hipStream_t s = w.s;
-    RC_TRY(upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8, s));
-    RC_TRY(upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd), s));
-    RC_TRY(upload(w.identity, identity, (size_t)n * 4, s));
-    RC_TRY(upload(w.feat_offs, feat_offsets, ((size_t)n_feat + 1) * 8, s));
-    RC_TRY(upload(w.p_start, pos_start, (size_t)n_pos * 8, s));
-    RC_TRY(upload(w.p_len, pos_length, (size_t)n_pos * 8, s));
-    RC_TRY(upload(w.p_res, pos_resolved, n_pos, s));
+    RC_TRY(w.upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8));
+    RC_TRY(w.upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd)));
+    RC_TRY(w.upload(w.identity, identity, (size_t)n * 4));
+    RC_TRY(w.upload(w.feat_offs, feat_offsets, ((size_t)n_feat + 1) * 8));
+    RC_TRY(w.upload(w.p_start, pos_start, (size_t)n_pos * 8));
+    RC_TRY(w.upload(w.p_len, pos_length, (size_t)n_pos * 8));
+    RC_TRY(w.upload(w.p_res, pos_resolved, n_pos));
     // every flag array carries one closing zero, so that an exclusive scan over items + 1 ends in the total
     RC_TRY(w.alive.reserve(((size_t)n + 1) * 4));
     RC_TRY(w.rank.reserve(((size_t)n + 1) * 4));
@@ -525,7 +442,7 @@ int32_t run_plot(PlotWork &w, asgart_plot *res, const uint64_t *fam_offsets, uin
     uint32_t n_alive = 0;
     // rank of every duplication alive, and their arms as a list
     auto rescan = [&](bool with_arms) -> int32_t {
-        RC_TRY(exclusive_scan_u32(w, alive, rank, (size_t)n + 1));
+        RC_TRY(w.exclusive_scan(alive, rank, (size_t)n + 1));
         HIP_TRY(read_back(&n_alive, rank + n, 4, s));
         if (n_alive > n) {
             set_error("asgart_plot_filter: %u of %u duplications alive", n_alive, n);
@@ -583,7 +500,7 @@ int32_t run_plot(PlotWork &w, asgart_plot *res, const uint64_t *fam_offsets, uin
             plot_family_first_kernel<<<blocks_for(n), kBlock, 0, s>>>(d_offs, nf, n, alive, rank, hit, u, matched, cnt + cErrU);
             HIP_TRY(hipGetLastError());
         }
-        RC_TRY(exclusive_scan_u32(w, matched, rank_m, (size_t)n + 1));
+        RC_TRY(w.exclusive_scan(matched, rank_m, (size_t)n + 1));
         if (nf) {
             plot_family_keep_kernel<<<blocks_for(nf), kBlock, 0, s>>>(d_offs, nf, rank, rank_m, u, fam_keep);
             HIP_TRY(hipGetLastError());
@@ -613,7 +530,7 @@ int32_t run_plot(PlotWork &w, asgart_plot *res, const uint64_t *fam_offsets, uin
         RC_TRY(timed_join(windows, n_windows, arms, 2 * n_alive, hit));
         plot_stop_kernel<<<blocks_for(n_pos), kBlock, 0, s>>>(d_res, hit, n_pos, stop);
         HIP_TRY(hipGetLastError());
-        RC_TRY(exclusive_scan_u32(w, stop, stop_rank, (size_t)n_pos + 1));
+        RC_TRY(w.exclusive_scan(stop, stop_rank, (size_t)n_pos + 1));
         plot_feature_first_kernel<<<blocks_for(n_pos), kBlock, 0, s>>>(d_feat_offs, n_feat, d_res, n_pos, stop, stop_rank,
                                                                       feat_keep, cnt + cErrFeat);
         HIP_TRY(hipGetLastError());
@@ -626,7 +543,7 @@ int32_t run_plot(PlotWork &w, asgart_plot *res, const uint64_t *fam_offsets, uin
             return ASGART_E_ARG;
         }
     }
-    RC_TRY(exclusive_scan_u32(w, fam_keep, fam_rank, (size_t)nf + 1));
+    RC_TRY(w.exclusive_scan(fam_keep, fam_rank, (size_t)nf + 1));
     uint32_t nf_out = 0;
     HIP_TRY(read_back(&nf_out, fam_rank + nf, 4, s));
     if (nf_out > nf) {
@@ -635,8 +552,8 @@ int32_t run_plot(PlotWork &w, asgart_plot *res, const uint64_t *fam_offsets, uin
     }
     RC_TRY(w.o_offs.reserve(((size_t)nf_out + 1) * 8));
     RC_TRY(w.o_keys.reserve(std::max<size_t>((size_t)n_alive * 8, 16)));
-    plot_family_offsets_kernel<<<blocks_for((uint64_t)nf + 1), kBlock, 0, s>>>(d_offs, nf, n, rank, fam_keep, fam_rank,
-                                                                              w.o_offs.as<uint64_t>());
+    family_offsets_kernel<kBlock><<<blocks_for((uint64_t)nf + 1), kBlock, 0, s>>>(d_offs, nf, n, rank, fam_keep, fam_rank,
+                                                                                 w.o_offs.as<uint64_t>());
     HIP_TRY(hipGetLastError());
     if (n) {
         plot_keys_kernel<<<blocks_for(n), kBlock, 0, s>>>(n, alive, rank, w.o_keys.as<int64_t>());
@@ -670,28 +587,14 @@ extern "C" int32_t asgart_plot_filter(int32_t device, const uint64_t *fam_offset
     if (err_position) *err_position = -1;
     RC_TRY(check_arguments(fam_offsets, n_families, sds, identity, n_sd, feat_offsets, n_features, pos_start, pos_length,
                            pos_resolved, n_positions, options, out));
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
-        (void)hipGetLastError();
-        set_error("asgart_plot_filter: no usable device %d (there is no CPU fallback)", device);
-        return ASGART_E_HIP;
-    }
-    HIP_TRY(hipSetDevice(device));
-    asgart_plot *res = new asgart_plot;
+    RC_TRY(use_device("asgart_plot_filter", device));
     int64_t err_pos = -1;
-    int32_t rc;
-    {
-        PlotWork w;
-        rc = run_plot(w, res, fam_offsets, (uint32_t)n_families, sds, identity, (uint32_t)n_sd, feat_offsets,
-                      (uint32_t)n_features, pos_start, pos_length, pos_resolved, (uint32_t)n_positions, *options, &err_pos);
-    }
+    const int32_t rc = run_tool<PlotWork>(out, [&](PlotWork &w, asgart_plot *res) {
+        return run_plot(w, res, fam_offsets, (uint32_t)n_families, sds, identity, (uint32_t)n_sd, feat_offsets,
+                        (uint32_t)n_features, pos_start, pos_length, pos_resolved, (uint32_t)n_positions, *options, &err_pos);
+    });
     if (err_position) *err_position = err_pos;
-    if (rc != 0) {
-        delete res;
-        return rc;
-    }
-    *out = res;
-    return 0;
+    return rc;
 }
 
 extern "C" void asgart_plot_counts(const asgart_plot *r, uint64_t *n_families, uint64_t *n_sds, uint64_t *n_features) {
@@ -708,12 +611,7 @@ extern "C" void asgart_plot_copy(const asgart_plot *r, uint64_t *fam_offsets, in
 }
 
 extern "C" int32_t asgart_plot_timings(const asgart_plot *r, double *ms3) {
-    if (!r || !ms3) {
-        set_error("asgart_plot_timings: bad argument");
-        return ASGART_E_ARG;
-    }
-    for (int k = 0; k < 3; ++k) ms3[k] = r->ms[k];
-    return 0;
+    return copy_ms3("asgart_plot_timings", r, ms3);
 }
 
 extern "C" void asgart_plot_free(asgart_plot *r) { delete r; }

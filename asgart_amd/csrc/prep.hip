@@ -9,6 +9,7 @@
 // are found there, and the index is built from the same device buffer.
 #include "index.hpp"
 #include "prep.hpp"
+#include "tool_base.hpp"
 
 #include <algorithm>
 
@@ -196,13 +197,7 @@ extern "C" int32_t asgart_prepare_data(const uint8_t *const *records, const uint
         off[(size_t)r + 1] = off[(size_t)r] + record_lens[r];
     }
     const uint64_t n_bases = off[(size_t)n_records], n = n_bases + 1;  // + '$' (src/bin/asgart.rs:430)
-    HIP_TRY(hipSetDevice(device));
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
-        (void)hipGetLastError();
-        set_error("asgart_prepare_data: no usable device %d (there is no CPU fallback)", device);
-        return ASGART_E_HIP;
-    }
+    RC_TRY(use_device("asgart_prepare_data", device));
     DevBuf d_text, d_off;
     hipStream_t s = nullptr;
     std::vector<uint64_t> h_runs;

@@ -27,11 +27,7 @@
 //             at most one atomic per cluster per wave, none for `both` when no lane of the run differs from the head.  A
 //             cluster may span any number of workgroups.
 //   offsets   row k of the name offsets = the first cluster whose name is >= k (bisection in the clusters' names)
-#include "common.hpp"
-
-#include <algorithm>
-
-#include <rocprim/rocprim.hpp>
+#include "tool_base.hpp"
 
 namespace asgart {
 namespace {
@@ -143,8 +139,6 @@ __global__ __launch_bounds__(kBlock) void rosary_offsets_kernel(const uint32_t *
     offsets[k] = lo;
 }
 
-inline unsigned blocks_for(uint64_t items) { return (unsigned)((items + kBlock - 1) / kBlock); }
-
 }  // namespace
 }  // namespace asgart
 
@@ -159,42 +153,12 @@ struct asgart_rosary {
 
 namespace {
 
-struct RosaryWork {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    DevBuf name, start, length, flags;
-    DevBuf ord0, key1, ord1, key2, sorted_name, ord2, sort_tmp, scan_tmp;
-    DevBuf s_start, s_end, s_bits, head, rank;
-    DevBuf c_name, c_start, c_length, c_klass, c_members, offsets;
-    ~RosaryWork() {
-        if (s) (void)hipStreamSynchronize(s);
-        for (DevBuf *b : {&name, &start, &length, &flags, &ord0, &key1, &ord1, &key2, &sorted_name, &ord2, &sort_tmp,
-                          &scan_tmp, &s_start, &s_end, &s_bits, &head, &rank, &c_name, &c_start, &c_length, &c_klass,
-                          &c_members, &offsets})
-            b->release();
-        // (a released block of 256 MiB and more is kept for the next index build; without an index alive nobody wants it)
-        if (BlockCache::live_indexes() == 0) BlockCache::trim();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
+struct RosaryWork : ToolWork {
+    DevBuf &name = buf(), &start = buf(), &length = buf(), &flags = buf();
+    DevBuf &ord0 = buf(), &key1 = buf(), &ord1 = buf(), &key2 = buf(), &sorted_name = buf(), &ord2 = buf();
+    DevBuf &s_start = buf(), &s_end = buf(), &s_bits = buf(), &head = buf(), &rank = buf();
+    DevBuf &c_name = buf(), &c_start = buf(), &c_length = buf(), &c_klass = buf(), &c_members = buf(), &offsets = buf();
 };
-
-int32_t upload(DevBuf &b, const void *src, size_t bytes, hipStream_t s) {
-    RC_TRY(b.reserve(std::max<size_t>(bytes, 16)));
-    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
-    return 0;
-}
-
-template <class K>
-int32_t sort_pairs(RosaryWork &w, const K *k_in, K *k_out, const uint32_t *v_in, uint32_t *v_out, size_t items,
-                   unsigned end_bit) {
-    size_t tmp = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, k_in, k_out, v_in, v_out, items, 0, end_bit, w.s));
-    RC_TRY(w.sort_tmp.reserve(tmp + 16));
-    HIP_TRY(rocprim::radix_sort_pairs(w.sort_tmp.p, tmp, k_in, k_out, v_in, v_out, items, 0, end_bit, w.s));
-    return 0;
-}
 
 int32_t check_arguments(const int32_t *arm_name, const uint64_t *arm_start, const uint64_t *arm_length, int64_t n_sds,
                         int64_t n_names, asgart_rosary **out) {
@@ -218,14 +182,13 @@ int32_t check_arguments(const int32_t *arm_name, const uint64_t *arm_start, cons
 int32_t run_rosary(RosaryWork &w, asgart_rosary *res, const int32_t *arm_name, const uint64_t *arm_start,
                    const uint64_t *arm_length, const uint8_t *flags, uint32_t n, uint64_t n_names, uint64_t margin) {
     const uint32_t m = 2 * n;  // arms
-    HIP_TRY(hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking));
-    for (hipEvent_t &e : w.ev) HIP_TRY(hipEventCreate(&e));
+    RC_TRY(w.open(3));
     hipStream_t s = w.s;
     HIP_TRY(hipEventRecord(w.ev[0], s));
-    RC_TRY(upload(w.name, arm_name, (size_t)m * 4, s));
-    RC_TRY(upload(w.start, arm_start, (size_t)m * 8, s));
-    RC_TRY(upload(w.length, arm_length, (size_t)m * 8, s));
-    if (flags) RC_TRY(upload(w.flags, flags, n, s));
+    RC_TRY(w.upload(w.name, arm_name, (size_t)m * 4));
+    RC_TRY(w.upload(w.start, arm_start, (size_t)m * 8));
+    RC_TRY(w.upload(w.length, arm_length, (size_t)m * 8));
+    if (flags) RC_TRY(w.upload(w.flags, flags, n));
     for (DevBuf *b : {&w.ord0, &w.ord1, &w.key2, &w.sorted_name, &w.ord2, &w.c_name, &w.c_klass, &w.c_members})
         RC_TRY(b->reserve((size_t)m * 4));
     for (DevBuf *b : {&w.key1, &w.s_start, &w.s_end, &w.c_start, &w.c_length}) RC_TRY(b->reserve((size_t)m * 8));
@@ -240,23 +203,18 @@ int32_t run_rosary(RosaryWork &w, asgart_rosary *res, const int32_t *arm_name, c
     const unsigned grid = blocks_for(m);
     rosary_emit_kernel<<<grid, kBlock, 0, s>>>(w.ord0.as<uint32_t>(), m);
     HIP_TRY(hipGetLastError());
-    RC_TRY(sort_pairs(w, w.start.as<uint64_t>(), w.key1.as<uint64_t>(), w.ord0.as<uint32_t>(), w.ord1.as<uint32_t>(), m, 64));
+    RC_TRY(w.sort_pairs(w.start.as<uint64_t>(), w.key1.as<uint64_t>(), w.ord0.as<uint32_t>(), w.ord1.as<uint32_t>(), m, 64));
     rosary_name_keys_kernel<<<grid, kBlock, 0, s>>>(w.ord1.as<uint32_t>(), w.name.as<int32_t>(), m, w.key2.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     unsigned name_bits = 1;  // ceil(log2(n_names)), at least one
     while (name_bits < 32 && ((uint64_t)1 << name_bits) < n_names) ++name_bits;
-    RC_TRY(sort_pairs(w, w.key2.as<uint32_t>(), w.sorted_name.as<uint32_t>(), w.ord1.as<uint32_t>(), w.ord2.as<uint32_t>(), m,
+    RC_TRY(w.sort_pairs(w.key2.as<uint32_t>(), w.sorted_name.as<uint32_t>(), w.ord1.as<uint32_t>(), w.ord2.as<uint32_t>(), m,
                       name_bits));
     rosary_heads_kernel<<<grid, kBlock, 0, s>>>(w.ord2.as<uint32_t>(), w.sorted_name.as<uint32_t>(), w.start.as<uint64_t>(),
                                                 w.length.as<uint64_t>(), flags ? w.flags.as<uint8_t>() : nullptr, m, margin,
                                                 w.s_start.as<uint64_t>(), w.s_end.as<uint64_t>(), w.s_bits.as<uint8_t>(), head);
     HIP_TRY(hipGetLastError());
-    {
-        size_t tmp = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, head, rank, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), s));
-        RC_TRY(w.scan_tmp.reserve(tmp + 16));
-        HIP_TRY(rocprim::exclusive_scan(w.scan_tmp.p, tmp, head, rank, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), s));
-    }
+    RC_TRY(w.exclusive_scan(head, rank, (size_t)m + 1));
     rosary_open_kernel<<<grid, kBlock, 0, s>>>(head, rank, w.sorted_name.as<uint32_t>(), w.s_start.as<uint64_t>(),
                                                w.s_bits.as<uint8_t>(), m, w.c_name.as<uint32_t>(), w.c_start.as<uint64_t>(),
                                                w.c_klass.as<uint32_t>(), w.c_members.as<uint32_t>());
@@ -306,27 +264,15 @@ extern "C" int32_t asgart_rosary_clusters(int32_t device, const int32_t *arm_nam
                                           uint64_t margin, asgart_rosary **out) {
     if (out) *out = nullptr;
     RC_TRY(check_arguments(arm_name, arm_start, arm_length, n_sds, n_names, out));
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
-        (void)hipGetLastError();
-        set_error("asgart_rosary_clusters: no usable device %d (there is no CPU fallback)", device);
-        return ASGART_E_HIP;
+    RC_TRY(use_device("asgart_rosary_clusters", device));
+    if (n_sds == 0) {  // empty rows; nothing is launched
+        *out = new asgart_rosary;
+        (*out)->offsets.assign((size_t)n_names + 1, 0);
+        return 0;
     }
-    HIP_TRY(hipSetDevice(device));
-    asgart_rosary *res = new asgart_rosary;
-    int32_t rc = 0;
-    if (n_sds == 0) {
-        res->offsets.assign((size_t)n_names + 1, 0);  // empty rows; nothing is launched
-    } else {
-        RosaryWork w;
-        rc = run_rosary(w, res, arm_name, arm_start, arm_length, flags, (uint32_t)n_sds, (uint64_t)n_names, margin);
-    }
-    if (rc != 0) {
-        delete res;
-        return rc;
-    }
-    *out = res;
-    return 0;
+    return run_tool<RosaryWork>(out, [&](RosaryWork &w, asgart_rosary *res) {
+        return run_rosary(w, res, arm_name, arm_start, arm_length, flags, (uint32_t)n_sds, (uint64_t)n_names, margin);
+    });
 }
 
 extern "C" void asgart_rosary_counts(const asgart_rosary *r, uint64_t *n_names, uint64_t *n_clusters) {
@@ -346,12 +292,7 @@ extern "C" void asgart_rosary_copy(const asgart_rosary *r, uint64_t *name_offset
 }
 
 extern "C" int32_t asgart_rosary_timings(const asgart_rosary *r, double *ms3) {
-    if (!r || !ms3) {
-        set_error("asgart_rosary_timings: bad argument");
-        return ASGART_E_ARG;
-    }
-    for (int k = 0; k < 3; ++k) ms3[k] = r->ms[k];
-    return 0;
+    return copy_ms3("asgart_rosary_timings", r, ms3);
 }
 
 extern "C" void asgart_rosary_free(asgart_rosary *r) { delete r; }

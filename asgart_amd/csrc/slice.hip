@@ -13,11 +13,7 @@
 // Family sizes are differences of the scan over duplications at the family's two offsets: an empty family, one larger
 // than a workgroup and one larger than 65 535 are the same case.  Survivors keep the input order (their output slot is
 // their rank in the scan); the only atomic is the minimum that finds the first duplication exclude_fragments would panic on.
-#include "common.hpp"
-
-#include <algorithm>
-
-#include <rocprim/rocprim.hpp>
+#include "tool_base.hpp"
 
 namespace asgart {
 namespace {
@@ -51,16 +47,6 @@ __device__ inline Arms arms_of(const int2 *__restrict__ chr, const ulonglong2 *_
         a.r = t.new_id[c.y];
     }
     return a;
-}
-
-// largest f in [0, n_fam) with offs[f] <= i < offs[f + 1] (empty families are stepped over); n_fam >= 1, i < offs[n_fam]
-__device__ inline uint32_t family_of(const uint64_t *__restrict__ offs, uint32_t n_fam, uint32_t i) {
-    uint32_t lo = 0, hi = n_fam;  // first f in [0, n_fam] with offs[f] > i; offs[n_fam] = n > i
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (offs[mid] > i) hi = mid; else lo = mid + 1;
-    }
-    return lo - 1;
 }
 
 // stage A: the flag filters, inter / intra and --min-length; alive[i] = 1 where duplication i passes
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void slice_stage_b_kernel(const uint64_t *_
                                                               uint32_t *__restrict__ alive, uint32_t *__restrict__ err) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    bool ok = alive[i] != 0 && live[family_of(offs, n_fam, i)] != 0;
+    bool ok = alive[i] != 0 && live[segment_of(offs, n_fam, i)] != 0;
     if (ok && (opt.keep_all || opt.restrict_all || opt.exclude)) {
         const Arms a = arms_of(chr, chr_pos, i, t);
         if (opt.keep_all) ok = ((t.keep_mask[a.l] | t.keep_mask[a.r]) & opt.keep_all) == opt.keep_all;
@@ -132,20 +118,6 @@ __global__ __launch_bounds__(kBlock) void slice_family_keep_kernel(const uint64_
     if (f >= n_fam) return;
     const uint32_t size = rank_b[offs[f + 1]] - rank_b[offs[f]];
     kept[f] = (live[f] && !(opt.drop_empty && size == 0)) ? 1u : 0u;
-}
-
-// out_offs[k] of the k-th kept family = the rank of its first duplication; thread n_fam writes the closing entry
-__global__ __launch_bounds__(kBlock) void slice_family_offsets_kernel(const uint64_t *__restrict__ offs, uint32_t n_fam,
-                                                                     uint32_t n, const uint32_t *__restrict__ rank_b,
-                                                                     const uint32_t *__restrict__ kept,
-                                                                     const uint32_t *__restrict__ fam_rank,
-                                                                     uint64_t *__restrict__ out_offs) {
-    const uint32_t f = blockIdx.x * kBlock + threadIdx.x;
-    if (f > n_fam) return;
-    if (f == n_fam)
-        out_offs[fam_rank[n_fam]] = rank_b[n];
-    else if (kept[f])
-        out_offs[fam_rank[f]] = rank_b[offs[f]];
 }
 
 // The stable compaction.  Two lanes per duplication, each moving one aligned 16-byte half of its 32-byte asgart_proto_sd
@@ -186,8 +158,6 @@ __global__ __launch_bounds__(kBlock) void slice_compact_kernel(const uint4 *__re
     out_sds_v[2 * (size_t)j + half] = v;
 }
 
-inline unsigned blocks_for(uint64_t items) { return (unsigned)((items + kBlock - 1) / kBlock); }
-
 }  // namespace
 }  // namespace asgart
 
@@ -205,37 +175,12 @@ struct asgart_slice {
 
 namespace {
 
-struct SliceWork {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    DevBuf offs, sds, flags, chr, chr_pos, new_id, addend, keep, restr, excl, final_pos;
-    DevBuf alive, rank, live, kept, fam_rank, scan_tmp, err;
-    DevBuf o_offs, o_sds, o_flags, o_chr, o_chr_pos, o_keys;
-    ~SliceWork() {
-        if (s) (void)hipStreamSynchronize(s);
-        for (DevBuf *b : {&offs, &sds, &flags, &chr, &chr_pos, &new_id, &addend, &keep, &restr, &excl, &final_pos, &alive,
-                          &rank, &live, &kept, &fam_rank, &scan_tmp, &err, &o_offs, &o_sds, &o_flags, &o_chr, &o_chr_pos,
-                          &o_keys})
-            b->release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (s) (void)hipStreamDestroy(s);
-    }
+struct SliceWork : ToolWork {
+    DevBuf &offs = buf(), &sds = buf(), &flags = buf(), &chr = buf(), &chr_pos = buf(), &new_id = buf(), &addend = buf(),
+           &keep = buf(), &restr = buf(), &excl = buf(), &final_pos = buf();
+    DevBuf &alive = buf(), &rank = buf(), &live = buf(), &kept = buf(), &fam_rank = buf(), &err = buf();
+    DevBuf &o_offs = buf(), &o_sds = buf(), &o_flags = buf(), &o_chr = buf(), &o_chr_pos = buf(), &o_keys = buf();
 };
-
-int32_t upload(DevBuf &b, const void *src, size_t bytes, hipStream_t s) {
-    RC_TRY(b.reserve(std::max<size_t>(bytes, 16)));
-    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
-    return 0;
-}
-
-int32_t exclusive_scan_u32(SliceWork &w, const uint32_t *in, uint32_t *out, size_t items) {
-    size_t tmp = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, items, rocprim::plus<uint32_t>(), w.s));
-    RC_TRY(w.scan_tmp.reserve(tmp + 16));
-    HIP_TRY(rocprim::exclusive_scan(w.scan_tmp.p, tmp, in, out, 0u, items, rocprim::plus<uint32_t>(), w.s));
-    return 0;
-}
 
 // Every argument check of the call, before the device is looked at.
 int32_t check_arguments(const uint64_t *fam_offsets, int64_t n_families, const asgart_proto_sd *sds, const uint8_t *flags,
@@ -249,16 +194,7 @@ int32_t check_arguments(const uint64_t *fam_offsets, int64_t n_families, const a
         set_error("asgart_slice_families: 2^31 duplications or families and more are not supported");
         return ASGART_E_CAP;
     }
-    if (fam_offsets[0] != 0 || fam_offsets[n_families] != (uint64_t)n_sd) {
-        set_error("asgart_slice_families: fam_offsets must start at 0 and end at n_sd = %lld (they run from %llu to %llu)",
-                  (long long)n_sd, (unsigned long long)fam_offsets[0], (unsigned long long)fam_offsets[n_families]);
-        return ASGART_E_ARG;
-    }
-    for (int64_t f = 0; f < n_families; ++f)
-        if (fam_offsets[f] > fam_offsets[f + 1]) {
-            set_error("asgart_slice_families: fam_offsets decrease at family %lld", (long long)f);
-            return ASGART_E_ARG;
-        }
+    RC_TRY(check_csr("asgart_slice_families", "fam_offsets", fam_offsets, n_families, n_sd, "n_sd"));
     const int64_t nn = tb->n_names;
     if (nn < 0 || (n_sd && nn == 0)) {
         set_error("asgart_slice_families: empty name table");
@@ -285,12 +221,7 @@ int32_t check_arguments(const uint64_t *fam_offsets, int64_t n_families, const a
                           tb->new_id[k], (long long)nn);
                 return ASGART_E_ARG;
             }
-    for (int64_t q = 0; q < 2 * n_sd; ++q)
-        if (chr[q] < 0 || chr[q] >= nn) {
-            set_error("asgart_slice_families: duplication %lld has name id %d, outside the name table (%lld names)",
-                      (long long)(q / 2), chr[q], (long long)nn);
-            return ASGART_E_ARG;
-        }
+    RC_TRY(check_name_ids("asgart_slice_families", chr, n_sd, nn));
     if (opt->inter_mode > 2 || (opt->flags_set | opt->flags_clear) > 3 || opt->collapsed_id >= nn) {
         set_error("asgart_slice_families: bad options (inter_mode 0..2, flag bits 0..3, collapsed_id inside the name table)");
         return ASGART_E_ARG;
@@ -302,36 +233,35 @@ int32_t run_slice(SliceWork &w, asgart_slice *res, const uint64_t *fam_offsets, 
                   const uint8_t *flags, const int32_t *chr, const uint64_t *chr_pos, uint32_t n,
                   const asgart_slice_tables *tb, const asgart_slice_options &opt) {
     const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipStreamCreateWithFlags(&w.s, hipStreamNonBlocking));
-    for (hipEvent_t &e : w.ev) HIP_TRY(hipEventCreate(&e));
+    RC_TRY(w.open(4));
     hipStream_t s = w.s;
     const size_t nn = (size_t)tb->n_names;
-    RC_TRY(upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8, s));
-    RC_TRY(upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd), s));
-    RC_TRY(upload(w.flags, flags, n, s));
-    RC_TRY(upload(w.chr, chr, (size_t)n * 8, s));
-    RC_TRY(upload(w.chr_pos, chr_pos, (size_t)n * 16, s));
+    RC_TRY(w.upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8));
+    RC_TRY(w.upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd)));
+    RC_TRY(w.upload(w.flags, flags, n));
+    RC_TRY(w.upload(w.chr, chr, (size_t)n * 8));
+    RC_TRY(w.upload(w.chr_pos, chr_pos, (size_t)n * 16));
     SliceTables t{};
     if (tb->new_id) {
-        RC_TRY(upload(w.new_id, tb->new_id, nn * 4, s));
-        RC_TRY(upload(w.addend, tb->addend, nn * 8, s));
+        RC_TRY(w.upload(w.new_id, tb->new_id, nn * 4));
+        RC_TRY(w.upload(w.addend, tb->addend, nn * 8));
         t.new_id = w.new_id.as<int32_t>();
         t.addend = w.addend.as<uint64_t>();
     }
     if (opt.keep_all) {
-        RC_TRY(upload(w.keep, tb->keep_mask, nn * 4, s));
+        RC_TRY(w.upload(w.keep, tb->keep_mask, nn * 4));
         t.keep_mask = w.keep.as<uint32_t>();
     }
     if (opt.restrict_all) {
-        RC_TRY(upload(w.restr, tb->restrict_mask, nn * 4, s));
+        RC_TRY(w.upload(w.restr, tb->restrict_mask, nn * 4));
         t.restrict_mask = w.restr.as<uint32_t>();
     }
     if (opt.exclude) {
-        RC_TRY(upload(w.excl, tb->exclude, nn, s));
+        RC_TRY(w.upload(w.excl, tb->exclude, nn));
         t.exclude = w.excl.as<uint8_t>();
     }
     if (opt.relocate) {
-        RC_TRY(upload(w.final_pos, tb->final_pos, nn * 8, s));
+        RC_TRY(w.upload(w.final_pos, tb->final_pos, nn * 8));
         t.final_pos = w.final_pos.as<int64_t>();
     }
     // alive and kept carry one closing zero, so that the exclusive scans over n + 1 / nf + 1 items end in the totals
@@ -357,7 +287,7 @@ int32_t run_slice(SliceWork &w, asgart_slice *res, const uint64_t *fam_offsets, 
         slice_stage_a_kernel<<<blocks_for(n), kBlock, 0, s>>>(sds_v, d_flags, d_chr, d_chr_pos, n, t, opt, alive);
         HIP_TRY(hipGetLastError());
     }
-    RC_TRY(exclusive_scan_u32(w, alive, rank, (size_t)n + 1));
+    RC_TRY(w.exclusive_scan(alive, rank, (size_t)n + 1));
     if (nf) {
         slice_family_live_kernel<<<blocks_for(nf), kBlock, 0, s>>>(d_offs, nf, rank, opt, live);
         HIP_TRY(hipGetLastError());
@@ -366,12 +296,12 @@ int32_t run_slice(SliceWork &w, asgart_slice *res, const uint64_t *fam_offsets, 
         slice_stage_b_kernel<<<blocks_for(n), kBlock, 0, s>>>(d_offs, nf, d_chr, d_chr_pos, n, t, opt, live, alive, err);
         HIP_TRY(hipGetLastError());
     }
-    RC_TRY(exclusive_scan_u32(w, alive, rank, (size_t)n + 1));
+    RC_TRY(w.exclusive_scan(alive, rank, (size_t)n + 1));
     if (nf) {
         slice_family_keep_kernel<<<blocks_for(nf), kBlock, 0, s>>>(d_offs, nf, rank, live, opt, kept);
         HIP_TRY(hipGetLastError());
     }
-    RC_TRY(exclusive_scan_u32(w, kept, fam_rank, (size_t)nf + 1));
+    RC_TRY(w.exclusive_scan(kept, fam_rank, (size_t)nf + 1));
     HIP_TRY(hipEventRecord(w.ev[1], s));
     uint32_t h_err = 0, n_out = 0, nf_out = 0;
     HIP_TRY(read_back(&h_err, err, 4, s));
@@ -389,8 +319,8 @@ int32_t run_slice(SliceWork &w, asgart_slice *res, const uint64_t *fam_offsets, 
     RC_TRY(w.o_chr_pos.reserve(std::max<size_t>((size_t)n_out * 16, 16)));
     RC_TRY(w.o_keys.reserve(std::max<size_t>((size_t)n_out * 8, 16)));
     HIP_TRY(hipEventRecord(w.ev[2], s));
-    slice_family_offsets_kernel<<<blocks_for((uint64_t)nf + 1), kBlock, 0, s>>>(d_offs, nf, n, rank, kept, fam_rank,
-                                                                               w.o_offs.as<uint64_t>());
+    family_offsets_kernel<kBlock><<<blocks_for((uint64_t)nf + 1), kBlock, 0, s>>>(d_offs, nf, n, rank, kept, fam_rank,
+                                                                                 w.o_offs.as<uint64_t>());
     HIP_TRY(hipGetLastError());
     if (n) {
         slice_compact_kernel<<<blocks_for(2 * (uint64_t)n), kBlock, 0, s>>>(
@@ -432,25 +362,10 @@ extern "C" int32_t asgart_slice_families(int32_t device, const uint64_t *fam_off
                                          const asgart_slice_options *options, asgart_slice **out) {
     if (out) *out = nullptr;
     RC_TRY(check_arguments(fam_offsets, n_families, sds, flags, chr, chr_pos, n_sd, tables, options, out));
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
-        (void)hipGetLastError();
-        set_error("asgart_slice_families: no usable device %d (there is no CPU fallback)", device);
-        return ASGART_E_HIP;
-    }
-    HIP_TRY(hipSetDevice(device));
-    asgart_slice *res = new asgart_slice;
-    int32_t rc;
-    {
-        SliceWork w;
-        rc = run_slice(w, res, fam_offsets, (uint32_t)n_families, sds, flags, chr, chr_pos, (uint32_t)n_sd, tables, *options);
-    }
-    if (rc != 0) {
-        delete res;
-        return rc;
-    }
-    *out = res;
-    return 0;
+    RC_TRY(use_device("asgart_slice_families", device));
+    return run_tool<SliceWork>(out, [&](SliceWork &w, asgart_slice *res) {
+        return run_slice(w, res, fam_offsets, (uint32_t)n_families, sds, flags, chr, chr_pos, (uint32_t)n_sd, tables, *options);
+    });
 }
 
 extern "C" void asgart_slice_counts(const asgart_slice *r, uint64_t *n_families, uint64_t *n_sds) {
@@ -472,12 +387,7 @@ extern "C" void asgart_slice_copy(const asgart_slice *r, uint64_t *fam_offsets, 
 }
 
 extern "C" int32_t asgart_slice_timings(const asgart_slice *r, double *ms3) {
-    if (!r || !ms3) {
-        set_error("asgart_slice_timings: bad argument");
-        return ASGART_E_ARG;
-    }
-    for (int k = 0; k < 3; ++k) ms3[k] = r->ms[k];
-    return 0;
+    return copy_ms3("asgart_slice_timings", r, ms3);
 }
 
 extern "C" void asgart_slice_free(asgart_slice *r) { delete r; }

@@ -1,0 +1,175 @@
+// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, export.hip) are built on: the device check of an
+// entry point, the device work of one call (ToolWork: stream, events, every device buffer, the rocPRIM two-call wrappers),
+// the host checks of offset arrays and name ids, the bisection of an offset array on the device, and the tail of an entry
+// point.  extract.hip, fasta.hip and prep.hip take use_device from here.
+#pragma once
+
+#include "common.hpp"
+
+#include <algorithm>
+#include <deque>
+
+#include <rocprim/rocprim.hpp>
+
+namespace asgart {
+
+inline int32_t use_device(const char *who, int32_t device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
+        (void)hipGetLastError();
+        set_error("%s: no usable device %d (there is no CPU fallback)", who, device);
+        return ASGART_E_HIP;
+    }
+    HIP_TRY(hipSetDevice(device));
+    return 0;
+}
+
+inline unsigned blocks_for(uint64_t items, uint32_t block = 256) { return (unsigned)((items + block - 1) / block); }
+
+// The device work of one call: one non-blocking stream, its events and every device buffer the call uses.  A tool derives
+// from it and names each of its buffers once, as a reference that buf() hands out; the destructor is the only place where
+// they are released, so a call that returns early (a refusal after the launches, a failed allocation) leaves nothing.
+struct ToolWork {
+    hipStream_t s = nullptr;
+    std::vector<hipEvent_t> ev;
+    std::deque<DevBuf> bufs;  // (a deque: the references handed out stay valid while it grows)
+    DevBuf &scan_tmp = buf(), &sort_tmp = buf();  // rocPRIM's scratch
+
+    ToolWork() = default;
+    ToolWork(const ToolWork &) = delete;
+    ToolWork &operator=(const ToolWork &) = delete;
+    ~ToolWork() {
+        if (s) (void)hipStreamSynchronize(s);  // nothing is released under a kernel that still runs
+        for (DevBuf &b : bufs) b.release();
+        // (a released block of 256 MiB and more is kept for the next index build; without an index alive nobody wants it)
+        if (BlockCache::live_indexes() == 0) BlockCache::trim();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (s) (void)hipStreamDestroy(s);
+    }
+
+    DevBuf &buf() {
+        bufs.emplace_back();
+        return bufs.back();
+    }
+    int32_t open(size_t n_events) {
+        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        ev.assign(n_events, nullptr);
+        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+        return 0;
+    }
+    int32_t upload(DevBuf &b, const void *src, size_t bytes) {
+        RC_TRY(b.reserve(std::max<size_t>(bytes, 16)));
+        if (bytes) HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s));
+        return 0;
+    }
+    // rocPRIM's two calls each: size query, scratch reserved, run.  (Templates all three: a file gets the rocPRIM kernels
+    // of what it calls and no others.)
+    template <class T>
+    int32_t exclusive_scan(const T *in, T *out, size_t items) {
+        size_t tmp = 0;
+        HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, in, out, (T)0, items, rocprim::plus<T>(), s));
+        RC_TRY(scan_tmp.reserve(tmp + 16));
+        HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, tmp, in, out, (T)0, items, rocprim::plus<T>(), s));
+        return 0;
+    }
+    template <class K>
+    int32_t sort_keys(const K *in, K *out, size_t items) {
+        size_t tmp = 0;
+        HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp, in, out, items, 0, 8 * sizeof(K), s));
+        RC_TRY(sort_tmp.reserve(tmp + 16));
+        HIP_TRY(rocprim::radix_sort_keys(sort_tmp.p, tmp, in, out, items, 0, 8 * sizeof(K), s));
+        return 0;
+    }
+    template <class K>
+    int32_t sort_pairs(const K *k_in, K *k_out, const uint32_t *v_in, uint32_t *v_out, size_t items, unsigned end_bit) {
+        size_t tmp = 0;
+        HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, k_in, k_out, v_in, v_out, items, 0, end_bit, s));
+        RC_TRY(sort_tmp.reserve(tmp + 16));
+        HIP_TRY(rocprim::radix_sort_pairs(sort_tmp.p, tmp, k_in, k_out, v_in, v_out, items, 0, end_bit, s));
+        return 0;
+    }
+};
+
+// offs[0 .. n_seg] are the offsets of n_seg segments over n_items items: from 0 to n_items, never decreasing
+inline int32_t check_csr(const char *who, const char *name, const uint64_t *offs, int64_t n_seg, int64_t n_items,
+                         const char *items_name, const char *seg_name = "family") {
+    if (offs[0] != 0 || offs[n_seg] != (uint64_t)n_items) {
+        set_error("%s: %s must start at 0 and end at %s = %lld (they run from %llu to %llu)", who, name, items_name,
+                  (long long)n_items, (unsigned long long)offs[0], (unsigned long long)offs[n_seg]);
+        return ASGART_E_ARG;
+    }
+    for (int64_t f = 0; f < n_seg; ++f)
+        if (offs[f] > offs[f + 1]) {
+            set_error("%s: %s decrease at %s %lld", who, name, seg_name, (long long)f);
+            return ASGART_E_ARG;
+        }
+    return 0;
+}
+
+// both name ids of every duplication are rows of the name table
+inline int32_t check_name_ids(const char *who, const int32_t *chr, int64_t n_sd, int64_t n_names) {
+    for (int64_t q = 0; q < 2 * n_sd; ++q)
+        if (chr[q] < 0 || chr[q] >= n_names) {
+            set_error("%s: duplication %lld has name id %d, outside the name table (%lld names)", who, (long long)(q / 2),
+                      chr[q], (long long)n_names);
+            return ASGART_E_ARG;
+        }
+    return 0;
+}
+
+// The tail of an entry point: the result is allocated, run(work, result) fills it, the work is gone (stream drained,
+// buffers released) before the caller sees the result, and a failed call leaves no result.
+template <class Work, class Result, class Run>
+int32_t run_tool(Result **out, Run run) {
+    std::unique_ptr<Result> res(new Result);
+    {
+        Work w;
+        RC_TRY(run(w, res.get()));
+    }
+    *out = res.release();
+    return 0;
+}
+
+// the three millisecond figures of a result handle (what they mean is the tool's business)
+template <class Result>
+int32_t copy_ms3(const char *who, const Result *r, double *ms3) {
+    if (!r || !ms3) {
+        set_error("%s: bad argument", who);
+        return ASGART_E_ARG;
+    }
+    for (int k = 0; k < 3; ++k) ms3[k] = r->ms[k];
+    return 0;
+}
+
+// largest f in [0, n_seg) with offs[f] <= i < offs[f + 1] (empty segments are stepped over); n_seg >= 1, i < offs[n_seg]
+__device__ inline uint32_t segment_of(const uint64_t *__restrict__ offs, uint32_t n_seg, uint32_t i) {
+    uint32_t lo = 0, hi = n_seg;  // first f in [0, n_seg] with offs[f] > i; offs[n_seg] > i
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (offs[mid] > i) hi = mid; else lo = mid + 1;
+    }
+    return lo - 1;
+}
+
+namespace {  // (internal: slice.hip and plot.hip each get their own and link into one library)
+
+// out_offs[k] of the k-th kept family = the rank of its first duplication; thread n_fam writes the closing entry.  A template
+// of the launch's block size, so that only a file that launches it holds it.
+template <uint32_t kThreads>
+__global__ __launch_bounds__(kThreads) void family_offsets_kernel(const uint64_t *__restrict__ offs, uint32_t n_fam,
+                                                                  uint32_t n, const uint32_t *__restrict__ rank,
+                                                                  const uint32_t *__restrict__ kept,
+                                                                  const uint32_t *__restrict__ fam_rank,
+                                                                  uint64_t *__restrict__ out_offs) {
+    const uint32_t f = blockIdx.x * kThreads + threadIdx.x;
+    if (f > n_fam) return;
+    if (f == n_fam)
+        out_offs[fam_rank[n_fam]] = rank[n];
+    else if (kept[f])
+        out_offs[fam_rank[f]] = rank[offs[f]];
+}
+
+}  // namespace
+
+}  // namespace asgart

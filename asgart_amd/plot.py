@@ -761,7 +761,7 @@ def plot_filter(offs, sds, identity, ta: TrackArrays, c_options: _PlotOptions, d
     """asgart_plot_filter -> (offs int64[F' + 1], keys int64[n'], keep uint8 per feature).  The reference's panic is
     ValueError with its text; everything else the library refuses is AsgartError.  timings: receives the three
     millisecond figures of asgart_plot_timings."""
-    from . import AsgartError, _check, _ptr, load_library
+    from . import AsgartError, _check, _ptr, _read_timings, load_library
 
     L = load_library()
     offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
@@ -789,10 +789,7 @@ def plot_filter(offs, sds, identity, ta: TrackArrays, c_options: _PlotOptions, d
         keys = np.zeros(ns.value, dtype=np.int64)
         keep = np.zeros(nfeat.value, dtype=np.uint8)
         L.asgart_plot_copy(h, _ptr(o_offs), _ptr(keys), _ptr(keep))
-        if timings is not None:
-            ms = (_C.c_double * 3)()
-            _check(L.asgart_plot_timings(h, ms))
-            timings[:] = list(ms)
+        _read_timings(L.asgart_plot_timings, h, timings)
     finally:
         L.asgart_plot_free(h)
     return o_offs.astype(np.int64), keys, keep

@@ -413,7 +413,7 @@ def rosary_clusters(name_id, start, length, flags, margin: int, n_names: int, de
                     timings: Optional[list] = None):
     """asgart_rosary_clusters: clusters_numpy on the GPU, the same five arrays.  timings: receives the three millisecond
     figures of asgart_rosary_timings (upload, kernels, copy back)."""
-    from . import _check, _ptr, load_library
+    from . import _check, _ptr, _read_timings, load_library
 
     L = load_library()
     name_id = np.ascontiguousarray(name_id, dtype=np.int32).reshape(-1)
@@ -434,10 +434,7 @@ def rosary_clusters(name_id, start, length, flags, margin: int, n_names: int, de
         c_start, c_length = np.zeros(nc.value, dtype=np.uint64), np.zeros(nc.value, dtype=np.uint64)
         klass, members = np.zeros(nc.value, dtype=np.uint8), np.zeros(nc.value, dtype=np.uint32)
         L.asgart_rosary_copy(h, _ptr(offsets), _ptr(c_start), _ptr(c_length), _ptr(klass), _ptr(members))
-        if timings is not None:
-            ms = (_C.c_double * 3)()
-            _check(L.asgart_rosary_timings(h, ms))
-            timings[:] = list(ms)
+        _read_timings(L.asgart_rosary_timings, h, timings)
     finally:
         L.asgart_rosary_free(h)
     return offsets.astype(np.int64), c_start, c_length, klass, members

@@ -638,7 +638,7 @@ def slice_families(offs, sds, flags, chr_, chr_pos, sp: SlicePlan, device: int =
     three millisecond figures (asgart_slice_timings)."""
     import ctypes as C
 
-    from . import _check, _ptr, load_library
+    from . import _check, _ptr, _read_timings, load_library
 
     L = load_library()
     offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
@@ -673,10 +673,7 @@ def slice_families(offs, sds, flags, chr_, chr_pos, sp: SlicePlan, device: int =
         o_flags = np.zeros(ns.value, dtype=np.uint8)
         keys = np.zeros(ns.value, dtype=np.int64)
         L.asgart_slice_copy(h, _ptr(o_offs), _ptr(o_sds), _ptr(o_chr), _ptr(o_pos), _ptr(o_flags), _ptr(keys))
-        if timings is not None:
-            ms = (C.c_double * 3)()
-            _check(L.asgart_slice_timings(h, ms))
-            timings[:] = list(ms)
+        _read_timings(L.asgart_slice_timings, h, timings)
     finally:
         L.asgart_slice_free(h)
     return o_offs.astype(np.int64), o_sds, o_chr, o_pos, o_flags, keys
