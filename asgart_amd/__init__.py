@@ -25,6 +25,7 @@ __all__ = [
     "load_library", "library_path", "ABI_SYMBOLS", "sa_build64", "search_duplications_multi", "merge_shards",
     "score_owners", "score_costs", "compute_scores_multi", "Source", "compute_scores_flags_multi", "orientation_flags",
     "export_records", "export_geometry", "f32_shortest", "f32_pow10_table", "EXPORT_FORMATS",
+    "ResultScan", "result_geometry", "E_REFUSED",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,6 +55,8 @@ ABI_SYMBOLS = (
     "asgart_rosary_geometry",
     "asgart_export_records", "asgart_export_size", "asgart_export_copy", "asgart_export_timings", "asgart_export_free",
     "asgart_export_geometry", "asgart_f32_shortest", "asgart_f32_pow10_table",
+    "asgart_result_scan", "asgart_result_parse", "asgart_result_counts", "asgart_result_copy", "asgart_result_timings",
+    "asgart_result_free", "asgart_result_geometry",
 )
 
 
@@ -302,6 +305,21 @@ def load_library() -> C.CDLL:
         L.asgart_f32_shortest.restype = C.c_int32
         L.asgart_f32_pow10_table.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
         L.asgart_f32_pow10_table.restype = C.c_int32
+    if hasattr(L, "asgart_result_scan"):
+        L.asgart_result_scan.argtypes = [C.c_int32, vp, C.c_uint64, C.POINTER(vp), u64p, u64p]
+        L.asgart_result_scan.restype = C.c_int32
+        L.asgart_result_parse.argtypes = [vp, vp, vp, C.c_int64]
+        L.asgart_result_parse.restype = C.c_int32
+        L.asgart_result_counts.argtypes = [vp, u64p, u64p, u64p, u64p]
+        L.asgart_result_counts.restype = None
+        L.asgart_result_copy.argtypes = [vp] * 10
+        L.asgart_result_copy.restype = C.c_int32
+        L.asgart_result_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_result_timings.restype = C.c_int32
+        L.asgart_result_free.argtypes = [vp]
+        L.asgart_result_free.restype = None
+        L.asgart_result_geometry.argtypes = [u64p, u64p, u64p]
+        L.asgart_result_geometry.restype = None
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []
@@ -873,6 +891,79 @@ def export_geometry() -> Tuple[int, int, int]:
     """asgart_export_geometry: threads per workgroup, units per workgroup, bytes of the LDS image of the write stage."""
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     load_library().asgart_export_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
+
+
+E_REFUSED = -5   # ASGART_E_REFUSED: the device reader of result files leaves the input to the host reader
+
+
+class ResultScan:
+    """The two calls of the device reader of result files on one handle (asgart_result_scan, asgart_result_parse; the
+    accepted grammar is stated in include/asgart_hip.h).  ResultScan(data) uploads and classifies the bytes of a RunResult
+    JSON file (uint8 array) and holds the span [begin, end) of the value of "families"; parse(names) takes the name table
+    -- UTF-8 bytes, sorted and unique -- and returns the arrays.  A refusal is AsgartError with code E_REFUSED: the input is
+    the host reader's (slice.read_arrays does all of this)."""
+
+    def __init__(self, data: np.ndarray, device: int = 0):
+        L = load_library()
+        self._h = C.c_void_p()
+        self._data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)   # (kept alive: the scan reads its top-level keys)
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(L.asgart_result_scan(int(device), _ptr(self._data) if len(self._data) else None, len(self._data),
+                                    C.byref(self._h), C.byref(a), C.byref(b)))
+        self.begin, self.end = int(a.value), int(b.value)
+
+    def parse(self, names: Sequence[bytes]) -> dict:
+        """-> offs uint64[F + 1], sds uint64[n, 4], flags uint8[n] (bit 2: the identity is hard), identity float32[n],
+        chr int32[n, 2] (index into `names`, -1: a hard name), chr_pos uint64[n, 2], first_use uint32[len(names)],
+        name_spans uint32[n, 2, 2] and identity_spans uint32[n, 2] (start, length), n_hard_names, n_hard_identities."""
+        L = load_library()
+        name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+        np.cumsum([len(b) for b in names], out=name_off[1:])
+        name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+        _check(L.asgart_result_parse(self._h, _ptr(name_bytes), _ptr(name_off), len(names)))
+        nf, n, hn, hi = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        L.asgart_result_counts(self._h, C.byref(nf), C.byref(n), C.byref(hn), C.byref(hi))
+        n = int(n.value)
+        out = {"offs": np.zeros(int(nf.value) + 1, dtype=np.uint64), "sds": np.zeros((n, 4), dtype=np.uint64),
+               "flags": np.zeros(n, dtype=np.uint8), "identity": np.zeros(n, dtype=np.float32),
+               "chr": np.zeros((n, 2), dtype=np.int32), "chr_pos": np.zeros((n, 2), dtype=np.uint64),
+               "first_use": np.zeros(len(names), dtype=np.uint32), "name_spans": np.zeros((n, 2, 2), dtype=np.uint32),
+               "identity_spans": np.zeros((n, 2), dtype=np.uint32)}
+        _check(L.asgart_result_copy(self._h, *(_ptr(out[k]) for k in ("offs", "sds", "flags", "identity", "chr", "chr_pos",
+                                                                       "first_use", "name_spans", "identity_spans"))))
+        out["n_hard_names"], out["n_hard_identities"] = int(hn.value), int(hi.value)
+        return out
+
+    def timings(self) -> List[float]:
+        """asgart_result_timings: milliseconds of the upload, the scan kernels, the parse kernels, the copy back."""
+        ms = (C.c_double * 4)()
+        _check(load_library().asgart_result_timings(self._h, ms))
+        return list(ms)
+
+    def close(self):
+        if self._h:
+            load_library().asgart_result_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def result_geometry() -> Tuple[int, int, int]:
+    """asgart_result_geometry: bytes per tile of the scan, records per workgroup and bytes of the LDS stage of the record
+    stage."""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    load_library().asgart_result_geometry(C.byref(a), C.byref(b), C.byref(c))
     return int(a.value), int(b.value), int(c.value)
 
 

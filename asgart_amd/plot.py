@@ -43,9 +43,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import slice as _slice
-from .extract import parse_result
-from .postprocess import merge_parsed
-from .slice import COLLAPSED_NAME, ResultArrays, SliceOptions, _RUST_WHITE_SPACE, _find_chr
+from .slice import (COLLAPSED_NAME, TOOL_READER, ResultArrays, SliceOptions, _RUST_WHITE_SPACE, _find_chr, add_reader_argument,
+                    read_tool_arrays, read_tool_result)
 
 KINDS = ("chord", "genome", "circos", "flat", "rosary")   # clap's order is Flat, Chord, ...; see the swap above
 BUILT = ("chord", "genome", "circos")
@@ -930,6 +929,7 @@ def add_arguments(ap):
     ap.add_argument("--colorize", choices=COLORIZE, default="by-type")
     ap.add_argument("--seed", type=int, default=0, help="seeds the colours of the feature polygons of `chord`")
     ap.add_argument("--host", action="store_true", help="run the per-object statement on the host; the bytes are the same")
+    add_reader_argument(ap)
     ap.add_argument("--device", type=int, default=0)
 
 
@@ -954,23 +954,22 @@ def main(argv=None) -> int:
     try:
         _refuse_kind(args.kind)
         if args.files:
-            texts = []
-            for path in args.files:
-                with open(path, "r", encoding="utf-8") as fh:
-                    texts.append(fh.read())
-            result = merge_parsed([parse_result(t) for t in texts])
             prefix = out_prefix(args.out, "-".join(args.files))          # asgart-plot.rs:417-421
         else:
             print("WARN  Reading results from STDIN", file=sys.stderr)   # :423
-            result = parse_result(sys.stdin.read())
             prefix = out_prefix(args.out, "out")
+        if args.host:
+            result = read_tool_result(args.files)
+        else:   # (the feature readers look at the strand map only)
+            loaded = read_tool_arrays(args.files, "host" if args.host_reader else TOOL_READER, args.device)
+            result = {"strand": loaded._strand_dict()}
         options = PlotOptions(**{f: getattr(args, f) for f in PlotOptions.__dataclass_fields__ if hasattr(args, f)})
         options.check()
         tracks = [read_feature_file(result, path) for path in args.features]   # :430-434, against the map as loaded
         if args.host:
             files = export_text(*apply(result, tracks, options), args.kind, options, prefix)
         else:
-            arrays, kept = apply_arrays(ResultArrays.from_result(result), tracks, options, args.device)
+            arrays, kept = apply_arrays(loaded, tracks, options, args.device)
             files = export_arrays(arrays, kept, args.kind, options, prefix)
     except (ValueError, OSError, KeyError, AsgartError) as e:
         print(f"Error: {e}", file=sys.stderr)

@@ -44,10 +44,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import plot as _plot
-from .extract import parse_result
 from .plot import M64, PlotOptions, separate_with_spaces
-from .postprocess import merge_parsed
-from .slice import ResultArrays, _find_chr, f32_display
+from .slice import TOOL_READER, ResultArrays, _find_chr, f32_display, read_tool_arrays, read_tool_result
 
 F32 = np.float32
 COLORS = ("#ff5b00", "#00b2ae", "#9741ad", "#66491e")   # :249-259: direct-ish, reversed and complemented, both, feature
@@ -618,16 +616,15 @@ def main(argv=None) -> int:
     args = _parse(list(sys.argv[1:] if argv is None else argv))
     try:
         if args.files:
-            texts = []
-            for path in args.files:
-                with open(path, "r", encoding="utf-8") as fh:
-                    texts.append(fh.read())
-            result = merge_parsed([parse_result(t) for t in texts])
             prefix = _plot.out_prefix(args.out, "-".join(args.files))     # asgart-plot.rs:417-421
         else:
             print("WARN  Reading results from STDIN", file=sys.stderr)    # :423
-            result = parse_result(sys.stdin.read())
             prefix = _plot.out_prefix(args.out, "out")
+        if args.host:
+            result = read_tool_result(args.files)
+        else:   # (the feature readers look at the strand map only)
+            loaded = read_tool_arrays(args.files, "host" if args.host_reader else TOOL_READER, args.device)
+            result = {"strand": loaded._strand_dict()}
         if not 0 <= args.clustering <= M64:
             raise ValueError("--clustering is usize")
         options = PlotOptions(**{f: getattr(args, f) for f in PlotOptions.__dataclass_fields__ if hasattr(args, f)})
@@ -636,7 +633,7 @@ def main(argv=None) -> int:
         if args.host:
             text = rosary_text(*_plot.apply(result, tracks, options), args.clustering, args.rosary)
         else:
-            arrays, kept = _plot.apply_arrays(ResultArrays.from_result(result), tracks, options, args.device)
+            arrays, kept = _plot.apply_arrays(loaded, tracks, options, args.device)
             text = rosary_arrays(arrays, kept, args.clustering, args.rosary, args.device)
     except (ValueError, OSError, KeyError, AsgartError) as e:
         print(f"Error: {e}", file=sys.stderr)

@@ -1,6 +1,6 @@
 """asgart-slice (reference src/bin/asgart-slice.rs): merge, filter, collapse and convert RunResult JSON files.
 
-    python -m asgart_amd.slice [INPUT ...] [-f json|gff2|gff3] [-o OUT] [filters] [--host]
+    python -m asgart_amd.slice [INPUT ...] [-f json|gff2|gff3] [-o OUT] [filters] [--host] [--host-reader]
 
 Three layers, as for the step chain (postprocess.py):
 
@@ -13,8 +13,10 @@ Three layers, as for the step chain (postprocess.py):
                duplication runs on the GPU (asgart_slice_families, csrc/slice.hip).  gff2_arrays, gff3_arrays and
                json_arrays write the same bytes as the per-object exporters with one format operation per duplication;
                export_arrays_gpu writes them on the GPU (asgart_export_records, csrc/export.hip).
-  the tool     the options of asgart-slice.rs:19-91 under the reference's names; the array form, written by the device
-               writer, by default, --host for the per-object statement; the bytes are the same.
+  the tool     the options of asgart-slice.rs:19-91 under the reference's names; the array form, read by the device
+               reader (read_arrays: asgart_result_scan / asgart_result_parse, csrc/result_read.hip; --host-reader for
+               the host reader) and written by the device writer, by default, --host for the per-object statement; the
+               bytes are the same.
 
 Regular expressions are compiled by Python's `re`, the reference's by Rust's `regex`: the common syntax (classes,
 alternation, anchors, greedy and lazy repetition) means the same; Rust's has no look-around and no back-references,
@@ -512,6 +514,188 @@ class ResultArrays:
                 "map": [{"name": self.names[k], "position": int(p), "length": int(ln)}
                         for k, p, ln in zip(self.map_name.tolist(), self.map_pos.tolist(), self.map_len.tolist())]}
 
+    @classmethod
+    def merge(cls, parts: Sequence["ResultArrays"]) -> "ResultArrays":
+        """RunResult::from_files (src/structs.rs:114-141) on arrays: from_result(postprocess.merge_parsed(results)) for the
+        parts' results.  Strand, settings and map are the first part's; the families follow each other; the name ids of a
+        later part are remapped into the first part's table, and a name that is new to it is appended where from_result
+        meets it: in the order in which that part's arms first use it (a map name of a later part that no arm uses is not
+        carried).  Different strand names: the reference's ValueError."""
+        if not parts:
+            raise ValueError("ResultArrays.merge: no result")
+        first = parts[0]
+        for p in parts:
+            if p.strand_name != first.strand_name:
+                raise ValueError("Trying to combine ASGART files from different sources: "
+                                 f"`{p.strand_name}` and `{first.strand_name}`")
+        if len(parts) == 1:
+            return first
+        ids = {name: k for k, name in enumerate(first.names)}
+        chrs = [first.chr]
+        for p in parts[1:]:
+            remap = np.full(len(p.names), -1, dtype=np.int32)
+            used, where = np.unique(p.chr.reshape(-1), return_index=True)
+            for k in used[np.argsort(where, kind="stable")].tolist():
+                remap[k] = ids.setdefault(p.names[k], len(ids))
+            chrs.append(remap[p.chr])
+        offs, base = [first.offs], int(first.offs[-1])
+        for p in parts[1:]:
+            offs.append(p.offs[1:] + base)
+            base += int(p.offs[-1])
+        seqs = None
+        if any(p.seqs is not None for p in parts):
+            seqs = tuple([s for p in parts for s in (p.seqs[side] if p.seqs is not None else [None] * p.n)]
+                         for side in (0, 1))
+        return cls(first.strand_name, first.strand_length, first.settings, list(ids), first.map_name, first.map_pos,
+                   first.map_len, np.concatenate(offs), np.concatenate([p.sds for p in parts]),
+                   np.concatenate([p.flags for p in parts]), np.concatenate(chrs),
+                   np.concatenate([p.chr_pos for p in parts]), np.concatenate([p.identity for p in parts]), seqs)
+
+
+# ---- the reader -----------------------------------------------------------------------------------------------------
+READERS = ("auto", "device", "host")
+TABLE_EXTRAS = ("unknown", COLLAPSED_NAME)   # names outside the map that results are full of: kept off the hard path
+
+
+class Refused(ValueError):
+    """The device reader leaves this input to the host reader (read_arrays with reader="device" raises it)."""
+
+
+def name_table(map_names: Sequence[str]) -> List[str]:
+    """The name table of the device reader for a strand map: its unique names and TABLE_EXTRAS, sorted as UTF-8 bytes for
+    the bisection on the device.  A name that has no UTF-8 form (a lone surrogate from a \\u escape) stays out: a file can
+    only spell it with an escape, which is a hard name anyway."""
+    table = {}
+    for name in list(map_names) + list(TABLE_EXTRAS):
+        try:
+            table[name] = name.encode("utf-8")
+        except UnicodeEncodeError:
+            pass
+    return sorted(table, key=table.__getitem__)
+
+
+def assign_name_ids(map_names: Sequence[str], table: Sequence[str], first_use, hard: Sequence[Tuple[int, str]]):
+    """The ids ResultArrays.from_result gives (`ids.setdefault`), from what the device reader returns: the map's names come
+    first, in map order; then every other name in order of first appearance, left before right, in record order.
+    first_use[t]: the smallest 2 * record + side that uses table entry t (0xFFFFFFFF: none); hard: (2 * record + side,
+    decoded name) of every arm the device left to the host.
+    -> (names, map_name ids, the id of every table entry (-1: an entry nobody uses), the id of every hard arm)."""
+    ids: Dict[str, int] = {}
+    map_name = [ids.setdefault(name, len(ids)) for name in map_names]
+    first_use = np.asarray(first_use, dtype=np.uint32).reshape(-1)
+    events = [(int(first_use[t]), name) for t, name in enumerate(table)
+              if name not in ids and first_use[t] != 0xFFFFFFFF]
+    events += [(int(key), name) for key, name in hard if name not in ids]
+    for _, name in sorted(events, key=lambda ev: ev[0]):
+        ids.setdefault(name, len(ids))
+    table_ids = np.array([ids.get(name, -1) for name in table], dtype=np.int32).reshape(-1)
+    return list(ids), map_name, table_ids, [ids[name] for _, name in hard]
+
+
+def _input_bytes(source) -> np.ndarray:
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        return np.frombuffer(source, dtype=np.uint8)
+    with open(source, "rb") as fh:   # (open's own errors, as the host reader's open raises them)
+        return np.frombuffer(fh.read(), dtype=np.uint8)
+
+
+def _read_host(source) -> ResultArrays:
+    """The readable statement: extract.parse_result and from_result, a file opened as the tools always opened it."""
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        text = bytes(source).decode("utf-8")
+    else:
+        with open(source, "r", encoding="utf-8") as fh:
+            text = fh.read()
+    return ResultArrays.from_result(parse_result(text))
+
+
+def _read_device(data: np.ndarray, device: int = 0, stages: Optional[dict] = None) -> ResultArrays:
+    """One result file on the device (asgart_amd.ResultScan; the grammar is stated in include/asgart_hip.h); Refused where
+    the library refuses, or where the host cannot convert a value the device left to it.  stages: receives the
+    milliseconds of every stage and the hard counts."""
+    import json
+    import time
+
+    from . import AsgartError, E_REFUSED, ResultScan
+
+    clock = time.perf_counter
+    try:
+        scan = ResultScan(data, device)
+    except AsgartError as e:
+        if e.code != E_REFUSED:
+            raise
+        raise Refused(str(e)) from e
+    with scan:
+        t0 = clock()
+        a, b = scan.begin, scan.end
+        try:   # the head: strand and settings through the conversions of parse_result, the families cut out
+            head = parse_result((data[:a].tobytes() + b"[]" + data[b:].tobytes()).decode("utf-8"))
+        except Exception as e:
+            raise Refused(f"the head of the file is the host reader's to refuse: {type(e).__name__}: {e}") from e
+        map_names = [c["name"] for c in head["strand"]["map"]]
+        table = name_table(map_names)
+        t1 = clock()
+        try:
+            got = scan.parse([name.encode("utf-8") for name in table])
+        except AsgartError as e:
+            if e.code != E_REFUSED:
+                raise
+            raise Refused(str(e)) from e
+        ms = scan.timings()
+    t2 = clock()
+    chr_idx, flags, identity = got["chr"], got["flags"], got["identity"]
+    hard = []
+    try:   # the values the device left to the host: as json.loads reads them
+        for q, side in np.argwhere(chr_idx < 0).tolist():
+            start, length = got["name_spans"][q, side].tolist()
+            hard.append((2 * q + side, json.loads(data[start - 1:start + length + 1].tobytes().decode("utf-8"))))
+        for q in np.flatnonzero(flags & 4).tolist():
+            start, length = got["identity_spans"][q].tolist()
+            identity[q] = np.float32(float(json.loads(data[start:start + length].tobytes().decode("utf-8"))))
+    except Exception as e:
+        raise Refused(f"a value left to the host is the host reader's to refuse: {type(e).__name__}: {e}") from e
+    names, map_name, table_ids, hard_ids = assign_name_ids(map_names, table, got["first_use"], hard)
+    chr_ = table_ids[np.maximum(chr_idx, 0)] if len(table_ids) else np.zeros_like(chr_idx)
+    for (key, _), k in zip(hard, hard_ids):
+        chr_[key // 2, key % 2] = k
+    st = head["strand"]
+    out = ResultArrays(st["name"], st["length"], head["settings"], names, map_name, [c["position"] for c in st["map"]],
+                       [c["length"] for c in st["map"]], got["offs"].astype(np.int64), got["sds"], flags & 3, chr_,
+                       got["chr_pos"], identity, None)
+    if stages is not None:
+        stages.update(upload_ms=ms[0], scan_ms=ms[1], head_ms=(t1 - t0) * 1e3, parse_ms=ms[2], copy_ms=ms[3],
+                      fixup_ms=(clock() - t2) * 1e3, hard_names=got["n_hard_names"],
+                      hard_identities=got["n_hard_identities"])
+    return out
+
+
+def read_arrays(inputs, device: int = 0, reader: str = "auto", stages: Optional[list] = None) -> ResultArrays:
+    """RunResult JSON files as ResultArrays: what from_result(merge_parsed([parse_result(text) ...])) gives.  inputs: a
+    list of paths or bytes.  reader: "device" -- the bytes of every file are uploaded once and parsed on the GPU; the device
+    reader accepts a stated grammar and gives exactly the host's arrays for it, and everything else is Refused (a
+    ValueError with the library's message); "host" -- parse_result and from_result; "auto" -- the device, and the host
+    reader for an input it refuses, so any error is the one the host reader raises.  Several inputs are merged as
+    RunResult::from_files does (ResultArrays.merge).  stages: receives one dict per input read on the device."""
+    if reader not in READERS:
+        raise ValueError(f"unknown reader `{reader}` (one of {', '.join(READERS)})")
+    if isinstance(inputs, (str, bytes, bytearray, memoryview, os.PathLike)):
+        inputs = [inputs]
+    parts = []
+    for source in inputs:
+        if reader == "host":
+            parts.append(_read_host(source))
+            continue
+        timing = {}
+        try:
+            parts.append(_read_device(_input_bytes(source), device, timing))
+            if stages is not None:
+                stages.append(timing)
+        except Refused:
+            if reader == "device":
+                raise
+            parts.append(_read_host(source))
+    return ResultArrays.merge(parts)
+
 
 class _Options(_C.Structure):
     _fields_ = [("flags_set", _C.c_uint8), ("flags_clear", _C.c_uint8), ("inter_mode", _C.c_uint8),
@@ -875,6 +1059,35 @@ def add_filter_arguments(ap, renamed: Optional[Dict[str, Sequence[str]]] = None,
         help="use regexp matching instead of literal for keep-, restrict- and exclude-fragments")
 
 
+TOOL_READER = "auto"   # the reader behind the array form of slice, plot and rosary (README: the measurement that decides it)
+
+
+def add_reader_argument(ap):
+    ap.add_argument("--host-reader", action="store_true",
+                    help="read the input with the host reader (json.loads, one dict per duplication) instead of the "
+                         "device reader; the result is the same")
+
+
+def read_tool_result(paths: Sequence[str]) -> dict:
+    """The input of a tool for its per-object form: the files merged as RunResult::from_files does, or standard input."""
+    if not paths:
+        return parse_result(sys.stdin.read())
+    texts = []
+    for path in paths:
+        with open(path, "r", encoding="utf-8") as fh:
+            texts.append(fh.read())
+    return merge_parsed([parse_result(t) for t in texts])
+
+
+def read_tool_arrays(paths: Sequence[str], reader: str = TOOL_READER, device: int = 0) -> ResultArrays:
+    """The input of a tool for its array form (read_arrays): the files, or the bytes of standard input."""
+    if paths:
+        return read_arrays(list(paths), device, reader)
+    if reader == "host" or not hasattr(sys.stdin, "buffer"):
+        return ResultArrays.from_result(parse_result(sys.stdin.read()))
+    return read_arrays([sys.stdin.buffer.read()], device, reader)
+
+
 def options_from_args(args, dest_prefix: str = "") -> SliceOptions:
     return SliceOptions(**{f.name: getattr(args, dest_prefix + f.name) for f in fields(SliceOptions)})
 
@@ -892,6 +1105,7 @@ def _parse(argv):
     ap.add_argument("--host", action="store_true",
                     help="run the per-object statement on the host instead of the array form on the GPU; the bytes are "
                          "the same")
+    add_reader_argument(ap)
     ap.add_argument("--device", type=int, default=0, help="the GPU to slice on")
     args = ap.parse_args(argv)
     if args.no_inter and args.no_inter_relaxed:
@@ -904,20 +1118,17 @@ def main(argv=None) -> int:
 
     args = _parse(list(sys.argv[1:] if argv is None else argv))
     try:
-        if args.inputs:
-            texts = []
-            for path in args.inputs:
-                with open(path, "r", encoding="utf-8") as fh:
-                    texts.append(fh.read())
-            result = merge_parsed([parse_result(t) for t in texts])   # RunResult::from_files
-        else:
+        if not args.inputs:
             print("WARN  Reading results from STDIN", file=sys.stderr)   # asgart-slice.rs:105
-            result = parse_result(sys.stdin.read())
+        if args.host:
+            result = read_tool_result(args.inputs)
+        else:
+            arrays = read_tool_arrays(args.inputs, "host" if args.host_reader else TOOL_READER, args.device)
         options = options_from_args(args)
         if args.host:
             text = export_text(apply(result, options), args.format)
         else:
-            cut = apply_arrays(ResultArrays.from_result(result), options, args.device)
+            cut = apply_arrays(arrays, options, args.device)
             if args.format == "json" and cut.seqs is not None:   # (sequences are the host exporter's)
                 text = export_arrays(cut, args.format)
             else:

@@ -649,6 +649,69 @@ int32_t asgart_f32_shortest(int32_t device, const float *values, int64_t n, int3
  * Returns the number of entries; every argument is nullable. */
 int32_t asgart_f32_pow10_table(int32_t *k_min, int32_t *k_max, uint64_t *entries);
 
+/* ---- result files read on the GPU ---------------------------------------------------------------------------
+ * Replace, for a result wanted as arrays, RunResult::from_file of reference src/structs.rs:105-112 (serde_json::from_reader;
+ * the 13 fields of SD, :471-495): the file's bytes are uploaded once, tokenised and parsed on the device.  The rule is
+ * ACCEPT OR REFUSE, NEVER DIFFER: an accepted file gives exactly the arrays the host reader of the Python package gives; every
+ * other file is refused with ASGART_E_REFUSED and asgart_last_error names the byte offset and the rule.  No error of the host
+ * reader is ever reproduced here: the caller answers a refusal by running that reader.
+ * Two calls on one handle, because the name table comes from the head of the file:
+ *   asgart_result_scan    uploads bytes[size] (size below 2^32 - 2048) and classifies them: the quotes no odd run of
+ *                         backslashes precedes, the in-string mask (their prefix XOR), the nesting depth (a scan over the
+ *                         brackets outside strings), the tokens at depth 1 (more than 64: a refusal).  -> the byte span
+ *                         [*families_begin, *families_end) of the value of "families".  The caller parses
+ *                         bytes[:begin] + "[]" + bytes[end:] itself (strand and settings) and builds the name table.
+ *   asgart_result_parse   name_bytes / name_offsets[n_names + 1]: names as UTF-8, SORTED as bytes and unique (the device
+ *                         bisects them; ASGART_E_ARG otherwise).  Finds the families and records inside the span and parses
+ *                         every record.  Once per scan.
+ * The accepted grammar (everything else is a refusal):
+ *   whitespace   space, \t, \n, \r between any two tokens: serde's pretty form, its compact form and everything between
+ *   top level    one object; its keys hold no backslash and are exactly strand, settings, families, each once, in any
+ *                order, each value an array or object; behind the closing brace only whitespace; no byte-order mark
+ *   families     an array of arrays of objects; every byte of its span is whitespace, a structural character in its place,
+ *                a string, or a number or literal in value position (no missing, doubled or trailing comma, no missing
+ *                colon, no unbalanced bracket, no stray byte)
+ *   records      keys hold no backslash and are among the 13 field names, each at most once, in any order; the 11 other
+ *                than left_seq and right_seq are all present; left_seq and right_seq are absent or null (a string there is
+ *                refused with a reason of its own: results with sequences are the host's); no nested array or object
+ *   positions and lengths (6)   the literal 0|[1-9][0-9]* of at most 2^64 - 1
+ *   reversed, complemented      the literal true or false
+ *   identity     -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)?; converted on the device where that is exact (a significand
+ *                of at most 2^53 and a decimal exponent within +-22 once the fraction digits are folded in: one IEEE f64
+ *                multiply or divide by an exact power of ten, then one cast to f32); every other literal is HARD: flags bit
+ *                2 is set and identity_spans holds its bytes for the caller to convert
+ *   chr_left, chr_right   a string without a raw byte below 0x20.  Without a backslash and equal to a table entry: that
+ *                entry's index.  Any other string is a HARD name: chr is -1 and name_spans holds the bytes between its
+ *                quotes for the caller to decode (and to refuse, if they do not decode)
+ * out (asgart_result_copy, after a parse that succeeded; sizes from asgart_result_counts): fam_offsets[n_families + 1]
+ * (empty families stay), sds[n_sd], flags[n_sd] (bit 0 reversed, bit 1 complemented, bit 2 hard identity), identity[n_sd],
+ * chr[2 n_sd] and chr_pos[2 n_sd] (left, right), first_use[n_names] (the smallest 2 * record + side that uses the entry,
+ * 0xFFFFFFFF: none -- with it the caller numbers names in order of first appearance), name_spans[2 n_sd][2] and
+ * identity_spans[n_sd][2] (start, length; of every name and identity, hard or not).
+ * The handle owns the device memory until asgart_result_free; a refused scan leaves no handle and no device memory.
+ * No usable device: ASGART_E_HIP. */
+#define ASGART_E_REFUSED (-5) /* result reader: the input is outside the accepted grammar (the host reader's to read) */
+typedef struct asgart_result_read asgart_result_read;
+int32_t asgart_result_scan(int32_t device, const uint8_t *bytes, uint64_t size, asgart_result_read **out,
+                           uint64_t *families_begin, uint64_t *families_end);
+int32_t asgart_result_parse(asgart_result_read *r, const uint8_t *name_bytes, const uint64_t *name_offsets, int64_t n_names);
+/* Families and duplications of the parsed file (src/structs.rs:105-112: RunResult.families), and how many names and
+ * identities were left to the caller; every argument is nullable. */
+void asgart_result_counts(const asgart_result_read *r, uint64_t *n_families, uint64_t *n_sd, uint64_t *n_hard_names,
+                          uint64_t *n_hard_identities);
+int32_t asgart_result_copy(asgart_result_read *r, uint64_t *fam_offsets, asgart_proto_sd *sds, uint8_t *flags, float *identity,
+                           int32_t *chr, uint64_t *chr_pos, uint32_t *first_use, uint32_t *name_spans,
+                           uint32_t *identity_spans);
+/* Milliseconds of the calls behind r (src/structs.rs:105-112 on the device): [0] the upload of the file, [1] the scan
+ * kernels, [2] the parse kernels (HIP events for the three), [3] the last asgart_result_copy (host clock). */
+int32_t asgart_result_timings(const asgart_result_read *r, double *ms4);
+/* Gives the device memory back (what src/structs.rs:105-112 read is the caller's copy from then on); NULL is allowed. */
+void asgart_result_free(asgart_result_read *r);
+/* Sizes the reader behind asgart_result_scan works in (src/structs.rs:105-112 cut into workgroups), for tests that place
+ * their bytes on the seams: bytes per tile of the scan, records per workgroup of the record stage, bytes of its LDS stage; a
+ * range of records larger than that is walked in global memory. */
+void asgart_result_geometry(uint64_t *tile_bytes, uint64_t *records_per_block, uint64_t *stage_bytes);
+
 /* ---- FASTA files read on the GPU ---------------------------------------------------------------------------
  * Replace the FASTA reader in front of prepare_data and prepare_data itself (reference src/bin/asgart.rs:273-430: bio's
  * fasta::Reader and the per-record loop at :278-313, normalisation :289-301, find_chunks_to_process :317-366,
