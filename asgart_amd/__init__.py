@@ -25,7 +25,7 @@ __all__ = [
     "load_library", "library_path", "ABI_SYMBOLS", "sa_build64", "search_duplications_multi", "merge_shards",
     "score_owners", "score_costs", "compute_scores_multi", "Source", "compute_scores_flags_multi", "orientation_flags",
     "export_records", "export_geometry", "f32_shortest", "f32_pow10_table", "EXPORT_FORMATS",
-    "ResultScan", "result_geometry", "E_REFUSED",
+    "ResultScan", "result_geometry", "E_REFUSED", "Alignments", "align_geometry", "align_bytes",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -57,6 +57,8 @@ ABI_SYMBOLS = (
     "asgart_export_geometry", "asgart_f32_shortest", "asgart_f32_pow10_table",
     "asgart_result_scan", "asgart_result_parse", "asgart_result_counts", "asgart_result_copy", "asgart_result_timings",
     "asgart_result_free", "asgart_result_geometry",
+    "asgart_align_duplications", "asgart_alignment_counts", "asgart_alignment_copy", "asgart_alignment_timings",
+    "asgart_alignment_free", "asgart_align_geometry", "asgart_align_bytes",
 )
 
 
@@ -320,6 +322,21 @@ def load_library() -> C.CDLL:
         L.asgart_result_free.restype = None
         L.asgart_result_geometry.argtypes = [u64p, u64p, u64p]
         L.asgart_result_geometry.restype = None
+    if hasattr(L, "asgart_align_duplications"):
+        L.asgart_align_duplications.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_uint64, C.POINTER(vp)]
+        L.asgart_align_duplications.restype = C.c_int32
+        L.asgart_alignment_counts.argtypes = [vp, u64p, u64p, u64p]
+        L.asgart_alignment_counts.restype = None
+        L.asgart_alignment_copy.argtypes = [vp] * 7
+        L.asgart_alignment_copy.restype = C.c_int32
+        L.asgart_alignment_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_alignment_timings.restype = C.c_int32
+        L.asgart_alignment_free.argtypes = [vp]
+        L.asgart_alignment_free.restype = None
+        L.asgart_align_geometry.argtypes = [u64p, u64p, u64p]
+        L.asgart_align_geometry.restype = None
+        L.asgart_align_bytes.argtypes = [vp, C.c_int64, C.c_int32, vp]
+        L.asgart_align_bytes.restype = C.c_int32
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []
@@ -575,6 +592,35 @@ class Index:
         _check(load_library().asgart_compute_scores_flags(self._h, _ptr(sds), _ptr(flags), len(sds), _ptr(out)))
         return out
 
+    def align(self, sds: np.ndarray, flags: Optional[np.ndarray] = None, inclusive: bool = False, budget: int = 0,
+              timings: Optional[list] = None) -> "Alignments":
+        """One optimal unit-cost alignment of the two arms of every duplication (asgart_align_duplications): the
+        canonical path of include/asgart_hip.h as run-length-encoded operations.  flags: as compute_scores_flags.
+        inclusive: the arms are [p ..= p + length], the strings compute_scores compares, instead of [p, p + length).
+        budget: device bytes the checkpoints of one batch may take (0: half of what is free); a duplication that alone
+        needs more (align_bytes) is refused -- status 0, no runs, NaN identity -- and no result depends on it otherwise.
+        timings: a list that receives the milliseconds of upload, forward pass, traceback + compaction and copy."""
+        L = load_library()
+        sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+        flags = _score_flags(flags, len(sds))
+        h = C.c_void_p()
+        _check(L.asgart_align_duplications(self._h, _ptr(sds), _ptr(flags), len(sds), int(bool(inclusive)), int(budget),
+                                           C.byref(h)))
+        try:
+            n, nr, nref = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            L.asgart_alignment_counts(h, C.byref(n), C.byref(nr), C.byref(nref))
+            out = Alignments(np.zeros(n.value + 1, np.uint64), np.zeros(nr.value, np.uint32), np.zeros(nr.value, np.uint8),
+                             np.zeros(n.value, np.uint32), np.zeros(n.value, np.float32), np.zeros(n.value, np.uint8))
+            _check(L.asgart_alignment_copy(h, _ptr(out.run_offsets), _ptr(out.run_len), _ptr(out.run_op), _ptr(out.distance),
+                                           _ptr(out.identity), _ptr(out.status)))
+            if timings is not None:
+                ms = (C.c_double * 4)()
+                _check(L.asgart_alignment_timings(h, ms))
+                timings[:] = list(ms)
+            return out
+        finally:
+            L.asgart_alignment_free(h)
+
     def compute_scores_flags_shard(self, sds: np.ndarray, flags: Optional[np.ndarray], shard: int = 0,
                                    n_shards: int = 1) -> np.ndarray:
         """compute_scores_shard with one flag byte per duplication (asgart_compute_scores_flags_shard): the same owners,
@@ -662,6 +708,52 @@ class Index:
         _check(L.asgart_probe_hits(self._h, _ptr(ch), len(chunks), C.byref(st), _ptr(status),
                                    _ptr(offs), _ptr(hits), C.byref(nh)))
         return status, offs, hits
+
+
+@dataclass
+class Alignments:
+    """The arrays of asgart_alignment_copy: the runs of duplication q are run_offsets[q] .. run_offsets[q + 1] of run_len
+    and run_op (the bytes '=', 'X', 'I', 'D'); distance uint32, identity float32, status uint8 (0: refused)."""
+
+    run_offsets: np.ndarray
+    run_len: np.ndarray
+    run_op: np.ndarray
+    distance: np.ndarray
+    identity: np.ndarray
+    status: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.distance)
+
+    def ops(self, q: int) -> List[Tuple[int, str]]:
+        """The runs of duplication q in forward order: [(length, operation)]."""
+        a, b = int(self.run_offsets[q]), int(self.run_offsets[q + 1])
+        return list(zip(self.run_len[a:b].tolist(), self.run_op[a:b].tobytes().decode("ascii")))
+
+    def part(self, lo: int, hi: int) -> "Alignments":
+        """The duplications lo .. hi - 1 as a result of their own."""
+        a, b = int(self.run_offsets[lo]), int(self.run_offsets[hi])
+        return Alignments(self.run_offsets[lo:hi + 1] - self.run_offsets[lo], self.run_len[a:b], self.run_op[a:b],
+                          self.distance[lo:hi], self.identity[lo:hi], self.status[lo:hi])
+
+    def cigar(self, q: int) -> str:
+        """`812=1X40=3I...`; empty for a refused duplication."""
+        return "".join(f"{n}{op}" for n, op in self.ops(q))
+
+
+def align_geometry() -> Tuple[int, int, int]:
+    """(rows of one band, rows of one lane, columns of one tile W) of the alignment kernels (asgart_align_geometry)."""
+    v = [C.c_uint64() for _ in range(3)]
+    load_library().asgart_align_geometry(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
+def align_bytes(sds: np.ndarray, inclusive: bool = False) -> np.ndarray:
+    """The checkpoint bytes Index.align needs for each duplication (asgart_align_bytes; host code, no device)."""
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    out = np.zeros(len(sds), dtype=np.uint64)
+    _check(load_library().asgart_align_bytes(_ptr(sds), len(sds), int(bool(inclusive)), _ptr(out)))
+    return out
 
 
 class Source:

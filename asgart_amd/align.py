@@ -1,0 +1,192 @@
+"""The alignment of the two arms of a duplication: the readable statement, the replay check and the PAF writer.
+
+Index.align (asgart_align_duplications, csrc/align.hip) recovers one optimal unit-cost path per duplication on the GPU.
+This module states the same rule on the host, for the tests to compare byte for byte, and turns the result into text:
+
+    align_host   the full edit matrix in numpy, row by row, then the canonical trace (include/asgart_hip.h)
+    replay       does a list of runs consume exactly both arms, `=` on equal bytes and `X` on unequal ones?  -> its edits
+    paf_text     one PAF row per aligned duplication: query = left arm, target = right arm
+
+The arms: A = text[left ..] is the left arm; B is the right arm as ProtoSD::levenshtein walks it (reference
+src/structs.rs:439-452): reversed if flag bit 0 is set, complemented if bit 1 is set (ACGT and acgt swap, anything else is
+kept).  inclusive: [p ..= p + length], the strings --compute-score compares; otherwise [p, p + length).
+"""
+from __future__ import annotations
+
+import sys
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+Run = Tuple[int, str]
+
+_COMPLEMENT = np.arange(256, dtype=np.uint8)
+for _a, _b in zip(b"ACGTacgt", b"TGCAtgca"):
+    _COMPLEMENT[_a] = _b
+
+
+def arms(text, sd, flag: int, inclusive: bool) -> Tuple[np.ndarray, np.ndarray]:
+    """(A, B) of one duplication as uint8 arrays; sd = (left, right, left_length, right_length)."""
+    text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    left, right, ll, rl = (int(v) for v in sd)
+    inc = 1 if inclusive else 0
+    if left + ll + inc > len(text) or right + rl + inc > len(text):
+        raise ValueError("the duplication reaches past the end of the text")
+    a = text[left:left + ll + inc]
+    b = text[right:right + rl + inc]
+    if flag & 1:
+        b = b[::-1]
+    if flag & 2:
+        b = _COMPLEMENT[b]
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+def encode_runs(ops: str) -> List[Run]:
+    """`===X=` -> [(3, '='), (1, 'X'), (1, '=')]: maximal runs."""
+    runs: List[Run] = []
+    for op in ops:
+        if runs and runs[-1][1] == op:
+            runs[-1] = (runs[-1][0] + 1, op)
+        else:
+            runs.append((1, op))
+    return runs
+
+
+def cigar(runs: Sequence[Run]) -> str:
+    return "".join(f"{n}{op}" for n, op in runs)
+
+
+def trace(D, a, b) -> str:
+    """The canonical path through the edit matrix D of a (rows) and b (columns), as forward operations."""
+    i, j = len(a), len(b)
+    ops = []
+    while i > 0 or j > 0:
+        if i > 0 and j > 0 and D[i][j] == D[i - 1][j - 1] + (a[i - 1] != b[j - 1]):
+            ops.append("=" if a[i - 1] == b[j - 1] else "X")
+            i, j = i - 1, j - 1
+        elif i > 0 and D[i][j] == D[i - 1][j] + 1:
+            ops.append("I")   # a left-arm base without a partner
+            i -= 1
+        else:
+            ops.append("D")
+            j -= 1
+    return "".join(reversed(ops))
+
+
+def edit_matrix(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """D[i][j] = the unit-cost edit distance of a[:i] and b[:j], built row by row: the diagonal and the upper neighbour
+    give t[j]; the left neighbour is then a running minimum of t[k] + (j - k) over k <= j."""
+    n, m = len(a), len(b)
+    D = np.zeros((n + 1, m + 1), dtype=np.int64)
+    ramp = np.arange(m + 1, dtype=np.int64)
+    D[0] = ramp
+    for i in range(1, n + 1):
+        t = np.empty(m + 1, dtype=np.int64)
+        t[0] = i
+        np.minimum(D[i - 1, :-1] + (b != a[i - 1]), D[i - 1, 1:] + 1, out=t[1:])
+        D[i] = np.minimum.accumulate(t - ramp) + ramp
+    return D
+
+
+def align_host(text, sd, flag: int = 0, inclusive: bool = False) -> Tuple[List[Run], int]:
+    """(runs, distance) of one duplication: what Index.align must return for it."""
+    a, b = arms(text, sd, flag, inclusive)
+    D = edit_matrix(a, b)
+    return encode_runs(trace(D, a, b)), int(D[len(a)][len(b)])
+
+
+def replay(text, sd, flag: int, inclusive: bool, runs: Sequence[Run]) -> int:
+    """Walks the runs over both arms -> the number of edits (X, I and D bases).  ValueError when they do not consume
+    exactly both arms, when an `=` sits on unequal bytes or an `X` on equal ones, or on an unknown operation."""
+    a, b = arms(text, sd, flag, inclusive)
+    i = j = edits = 0
+    for n, op in runs:
+        n = int(n)
+        if n <= 0:
+            raise ValueError(f"a run of {n} `{op}`")
+        if op in "=X":
+            if i + n > len(a) or j + n > len(b):
+                raise ValueError(f"`{n}{op}` at ({i}, {j}) runs past an arm")
+            same = a[i:i + n] == b[j:j + n]
+            if op == "=" and not same.all():
+                raise ValueError(f"`{n}=` at ({i}, {j}) covers unequal bytes")
+            if op == "X" and same.any():
+                raise ValueError(f"`{n}X` at ({i}, {j}) covers equal bytes")
+            i, j = i + n, j + n
+        elif op == "I":
+            i += n
+        elif op == "D":
+            j += n
+        else:
+            raise ValueError(f"unknown operation `{op}`")
+        if op != "=":
+            edits += n
+    if i != len(a) or j != len(b):
+        raise ValueError(f"the runs consume {i} and {j} bases of arms of {len(a)} and {len(b)}")
+    return edits
+
+
+def align_host_all(text, sds, flags=None, inclusive: bool = False):
+    """align_host over a list, as the arrays Index.align returns (asgart_amd.Alignments)."""
+    from . import Alignments
+
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.zeros(len(sds), dtype=np.uint8) if flags is None else np.asarray(flags, dtype=np.uint8)
+    offs, lens, ops, dist = [0], [], [], []
+    for sd, f in zip(sds, flags.tolist()):
+        runs, d = align_host(text, sd, f, inclusive)
+        lens += [n for n, _ in runs]
+        ops += [ord(op) for _, op in runs]
+        offs.append(len(lens))
+        dist.append(d)
+    longest = np.maximum(sds[:, 2], sds[:, 3]).astype(np.float64)
+    ident = (100.0 * (1.0 - np.array(dist, dtype=np.float64) / longest)).astype(np.float32)
+    return Alignments(np.array(offs, np.uint64), np.array(lens, np.uint32), np.array(ops, np.uint8),
+                      np.array(dist, np.uint32), ident, np.ones(len(sds), np.uint8))
+
+
+def paf_text(offs, sds, flags, strand, aln, stderr=None) -> str:
+    """One PAF row per aligned duplication of a result: offs / sds the family arrays, flags one byte per duplication, strand
+    the run's Strand (its map names the fragments), aln the Alignments of Index.align(sds, flags, inclusive=False).
+    Query = left arm, target = right arm.  Names, fragment lengths and in-fragment positions are resolved as the JSON
+    exporter resolves them (postprocess.to_json_arrays: the fragment of a position by its start in the strand map,
+    `unknown` with the global position and the strand's length otherwise); ends are start + length.  Strand `+` for a
+    direct duplication and `-` for a reversed and complemented one; on `-` the ORDER of the runs is reversed, because
+    PAF's CIGAR runs along the target's forward strand, and the operations stay.  Column 10 is the number of `=`, column 11
+    the sum of all run lengths, column 12 is 255; tags NM:i:<distance>, fm:i:<family>, cg:Z:<cigar>.  A reversed-only or
+    complemented-only duplication has no PAF strand: ValueError.  A refused duplication gets no row and is named on stderr."""
+    offs = np.asarray(offs, dtype=np.int64)
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds):
+        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, "
+                         f"families that end at {int(offs[-1])}")
+    for q, f in enumerate(flags.tolist()):
+        if f not in (0, 3):
+            raise ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
+                             "direct (+) and reverse-complemented (-) alignments and none for this one")
+    total = sum(c.length for c in strand.map)
+
+    def locate(pos: int):
+        for c in strand.map:   # first match, as RunResult's find_chr_by_pos
+            if c.position <= pos < c.position + c.length:
+                return c.name, c.length, pos - c.position
+        return "unknown", total, pos
+
+    family = np.repeat(np.arange(len(offs) - 1), np.diff(offs))
+    rows = []
+    for q, (left, right, ll, rl) in enumerate(sds.tolist()):
+        if not aln.status[q]:
+            print(f"paf: duplication {q} (family {int(family[q])}) was refused by the alignment's memory budget: no row",
+                  file=stderr if stderr is not None else sys.stderr)
+            continue
+        runs = aln.ops(q)
+        if flags[q] == 3:
+            runs = runs[::-1]
+        qname, qlen, qpos = locate(left)
+        tname, tlen, tpos = locate(right)
+        rows.append("\t".join(str(v) for v in (
+            qname, qlen, qpos, qpos + ll, "-" if flags[q] == 3 else "+", tname, tlen, tpos, tpos + rl,
+            sum(n for n, op in runs if op == "="), sum(n for n, _ in runs), 255,
+            f"NM:i:{int(aln.distance[q])}", f"fm:i:{int(family[q])}", f"cg:Z:{cigar(runs)}")))
+    return "".join(r + "\n" for r in rows)

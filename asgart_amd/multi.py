@@ -264,6 +264,30 @@ def _check_slice(slice_options, fmt: str) -> bool:
     return slice_options.active() or fmt != "json"
 
 
+def _check_paf(paf: bool, world: int, orientations, slice_options=None) -> None:
+    """--paf, vetted before the run starts (on every rank): each refusal with its reason."""
+    if not paf:
+        return
+    if world > 1:
+        raise ValueError("--paf: the alignment has no sharded variant, it runs on one GPU (use --gpus 1)")
+    for r, c in orientations:
+        if bool(r) != bool(c):
+            raise ValueError("--paf: a PAF row has a strand for direct (+) and reverse-complemented (-) duplications; a "
+                             f"{'reversed' if r else 'complemented'}-only run has none")
+    o = slice_options
+    if o is not None and (o.collapse or o.keep_fragments is not None or o.restrict_fragments is not None
+                          or o.exclude_fragments is not None):
+        raise ValueError("--paf: --collapse and the fragment filters lay the fragments out again; the rows of a PAF file "
+                         "name positions in the fragments of the run (slice the result without them, or write no PAF)")
+
+
+def _paf_rows(index, strand, fam_offs, sds, flags) -> str:
+    """Rank 0, while the index is alive: the duplications aligned with exact ranges (Index.align) as PAF text."""
+    from .align import paf_text
+
+    return paf_text(fam_offs, sds, flags, strand, index.align(sds, flags, inclusive=False))
+
+
 def _slice_run(post, strand, settings, slice_options, device_index: int):
     """Rank 0, behind post_process: the result as arrays (what its JSON file would parse to), sliced on the GPU.
     -> (the sliced ResultArrays, the surviving duplications in the run's own coordinates: what is scored and extracted)."""
@@ -276,7 +300,8 @@ def _slice_run(post, strand, settings, slice_options, device_index: int):
 
 def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
                         prefix: str = "", with_sequences: bool = False, reader: Optional[str] = None,
-                        slice_options=None, fmt: str = "json", writer: Optional[str] = None) -> Optional[Tuple[str, str]]:
+                        slice_options=None, fmt: str = "json", writer: Optional[str] = None,
+                        paf: bool = False) -> Optional[Tuple[str, str]]:
     """A whole `asgart` run (reference src/bin/asgart.rs:731-822) on the ranks of `dist`, rank r on GPU device_index:
     rank 0 prepares the input and builds the index, replicate_index copies it to every rank, each rank runs its shard of
     the search (asgart_search_duplications_passes_shard), gather_families merges the families on rank 0, rank 0 runs the
@@ -299,7 +324,10 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     writer: "device" (what None means, see DEFAULT_WRITER) writes the file on rank 0's GPU (postprocess.to_json_arrays_gpu,
     slice.export_arrays_gpu: asgart_export_records), "host" with the array exporters one format operation per duplication;
     the text is the same either way.  Sequences are out of scope for the device writer: with_sequences takes the host
-    exporter."""
+    exporter.
+    paf: the surviving duplications -- the ones compute_score scores -- are also aligned (Index.align with exact ranges)
+    and the return value gains a third entry, the text of the PAF file (align.paf_text).  One rank only; see _check_paf."""
+    from . import orientation_flags
     from .postprocess import _to_json_arrays_device, out_filename, to_json_arrays
 
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
@@ -309,6 +337,7 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     writer = _choose_writer(writer, with_sequences)
     comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
     sliced = _check_slice(slice_options, fmt)
+    _check_paf(paf, world, [(settings.reverse, settings.complement)], slice_options)
     index = strand = records = source = None
     chunks = [None]
     try:
@@ -350,18 +379,23 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
         if with_sequences:
             seqs = _sequences(source, records, device_index, survivors, settings.reverse, settings.complement)
         name = out_filename(files, settings, prefix)
+        extra = ()
+        if paf:
+            extra = (_paf_rows(index, strand, cut.offs if sliced else post[0], survivors,
+                               orientation_flags(settings.reverse, settings.complement, len(survivors))),)
         if not sliced:
             if writer == "device":
-                return _decode(_to_json_arrays_device(post[0], post[1], strand, settings, ident, None, device_index)), name
-            return to_json_arrays(post[0], post[1], strand, settings, ident, seqs), name
+                return (_decode(_to_json_arrays_device(post[0], post[1], strand, settings, ident, None, device_index)),
+                        name) + extra
+            return (to_json_arrays(post[0], post[1], strand, settings, ident, seqs), name) + extra
         from .slice import _export_arrays_device, export_arrays
 
         if ident is not None:
             cut.identity = np.ascontiguousarray(ident, dtype=np.float32)
         cut.seqs = seqs
         if writer == "device":
-            return _decode(_export_arrays_device(cut, fmt, device_index)), os.path.splitext(name)[0] + "." + fmt
-        return export_arrays(cut, fmt), os.path.splitext(name)[0] + "." + fmt
+            return (_decode(_export_arrays_device(cut, fmt, device_index)), os.path.splitext(name)[0] + "." + fmt) + extra
+        return (export_arrays(cut, fmt), os.path.splitext(name)[0] + "." + fmt) + extra
     finally:
         if source is not None:
             source.close()
@@ -371,7 +405,8 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
 
 def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool, bool]], settings, dist,
                         device_index: int, compute_score: bool = False, prefix: str = "",
-                        with_sequences: bool = False, reader: Optional[str] = None, writer: Optional[str] = None):
+                        with_sequences: bool = False, reader: Optional[str] = None, writer: Optional[str] = None,
+                        paf: bool = False):
     """One run over several orientations of one strand -- what the reference needs one `asgart` invocation per
     orientation and an `asgart-slice` merge for.  orientations: one to four distinct (reverse, complement) pairs in the
     user's order; `settings` supplies everything else (its own two flags are ignored).  Built ONCE: the records read and
@@ -387,7 +422,9 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     run).  dist None: one process, one GPU, no collective.  `--trim` needs one rank.  reader: as search_duplications.
     Slicing (search_duplications' slice_options / fmt) is out of scope here: `python -m asgart_amd.slice` does it on the
     files this writes.  writer: as search_duplications -- every orientation's file and the merged one are written on rank
-    0's GPU unless "host" is asked for or with_sequences is set."""
+    0's GPU unless "host" is asked for or with_sequences is set.
+    paf: every orientation's entry gains a third element, the text of its PAF file (one Index.align over the survivors of
+    all orientations); the merged result gets none.  One rank, direct and RC only; see _check_paf."""
     from dataclasses import replace
 
     from . import merge_shards, orientation_flags
@@ -400,6 +437,7 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
+    _check_paf(paf, world, orientations)
     reader = _choose_reader(reader, settings)
     writer = _choose_writer(writer, with_sequences)
     comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
@@ -441,6 +479,7 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
                 return _decode(_to_json_arrays_device(offs, sds, strand, st, ident_, flags_, device_index))
             return to_json_arrays(offs, sds, strand, st, ident_, seqs_, flags_)
 
+        aln = index.align(kept, flags, inclusive=False) if paf else None
         out = []
         lo = 0
         for st, (offs, sds) in zip(sts, posts):
@@ -448,6 +487,10 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
             part = None if seqs is None else (seqs[0][lo:hi], seqs[1][lo:hi])
             out.append((text_of(offs, sds, st, None if ident is None else ident[lo:hi], part, None),
                         out_filename(files, st, prefix)))
+            if paf:
+                from .align import paf_text
+
+                out[-1] += (paf_text(offs, sds, flags[lo:hi], strand, aln.part(lo, hi)),)
             lo = hi
         sizes = np.concatenate([np.diff(p[0].astype(np.int64)) for p in posts])
         all_offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
@@ -489,6 +532,11 @@ def _parse(argv):
     # asgart-slice's filters under its names, but for the two this tool already uses for the search itself
     add_filter_arguments(ap.add_argument_group("slice the result before it is scored and written (asgart-slice)"),
                          {"min_length": ("--slice-min-length",), "collapse": ("--collapse",)}, dest_prefix="slice_")
+    ap.add_argument("--paf", action="store_true",
+                    help="also align the two arms of every surviving duplication (the ones --compute-score scores) and write "
+                         "<result stem>.paf beside every result file: one row per duplication with its CIGAR (cg:Z:).  One "
+                         "GPU; direct and RC runs only; not with --collapse or the fragment filters.  With --compute-score "
+                         "the edit matrix is walked twice: the score compares inclusive ranges, a PAF row exact ones")
     ap.add_argument("--prefix", default="")
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
@@ -521,6 +569,10 @@ def _parse(argv):
         ap.error("the argument '--no-inter-relaxed' cannot be used with '--no-inter'")
     if args.orientations and (args.slice_options.active() or args.format != "json"):
         ap.error("--orientations writes unsliced JSON files: slice them with python -m asgart_amd.slice")
+    try:
+        _check_paf(args.paf, args.gpus, args.orientations or [(args.reverse, args.complement)], args.slice_options)
+    except ValueError as e:
+        ap.error(str(e))
     return args
 
 
@@ -597,17 +649,18 @@ def rank_main(argv) -> int:
         writer = "host" if args.host_writer else None
         if args.orientations:
             out = search_orientations(args.files, args.orientations, settings, dist, device_index, args.compute_score,
-                                      args.prefix, args.with_sequences, reader, writer)
+                                      args.prefix, args.with_sequences, reader, writer, args.paf)
             texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])
         else:
             out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix,
-                                      args.with_sequences, reader, args.slice_options, args.format, writer)
+                                      args.with_sequences, reader, args.slice_options, args.format, writer, args.paf)
             texts = None if out is None else [out]
-        for text, name in texts or []:
-            path = os.path.join(args.out_dir, name)
-            with open(path, "w", encoding="utf-8") as fh:
-                fh.write(text)
-            print(f"rank 0 of {world} ({backend}): wrote {path}", flush=True)
+        for text, name, *paf in texts or []:
+            for body, path in [(text, os.path.join(args.out_dir, name))] + \
+                    [(p_, os.path.join(args.out_dir, os.path.splitext(name)[0] + ".paf")) for p_ in paf]:
+                with open(path, "w", encoding="utf-8") as fh:
+                    fh.write(body)
+                print(f"rank 0 of {world} ({backend}): wrote {path}", flush=True)
         dist.barrier()
     finally:
         dist.destroy_process_group()

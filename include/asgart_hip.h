@@ -397,6 +397,45 @@ int64_t asgart_compute_scores_flags_shard(asgart_index *idx, const asgart_proto_
 int32_t asgart_compute_scores_flags_multi(asgart_index *const *indices, int32_t n_devices, const asgart_proto_sd *sds,
                                           const uint8_t *flags, int64_t n_sd, float *identity);
 
+/* ---- the alignment of the two arms of each duplication ------------------------------------------------------
+ * ComputeScore above says how similar two arms are; this says where they differ: one optimal unit-cost path through the
+ * edit matrix of every duplication, as run-length-encoded operations.  No counterpart in the reference.
+ *   A = a_1..a_n  the left arm; B = b_1..b_m the right arm as the score walks it (reversed if flags[q] bit 0 is set,
+ *                 complemented if bit 1 is set; ACGT and acgt swap, anything else is kept; bytes compare as bytes)
+ *   inclusive     1: the arms are [p ..= p + length] (n = left_length + 1: the strings asgart_compute_scores compares);
+ *                 0: [p, p + length) (what a PAF row describes)
+ *   the path      D[i][0] = i, D[0][j] = j; traced from (n, m) while i > 0 or j > 0: if i > 0 and j > 0 and
+ *                 D[i][j] == D[i-1][j-1] + (a_i != b_j): '=' on equal bases, 'X' otherwise, i--, j--; else if i > 0 and
+ *                 D[i][j] == D[i-1][j] + 1: 'I' (a left-arm base without a partner), i--; else 'D', j--.  The operations
+ *                 are then put in forward order and run-length encoded: the result is unique.
+ *   budget_bytes  the device memory the checkpoints of one batch may take (asgart_align_bytes gives each duplication's
+ *                 share); 0: half of what is free.  The duplications are packed largest first into batches that fit.  A
+ *                 duplication that alone exceeds the budget is REFUSED: status[q] = 0, no runs, distance 0xFFFFFFFF,
+ *                 identity NaN; the others are unaffected.  NO RESULT DEPENDS ON THE BUDGET OR ON THE BATCHING.
+ *   out           asgart_alignment_counts / _copy / _free: run_offsets[n_sd + 1], the CSR rows of the runs; run_len and
+ *                 run_op ('=', 'X', 'I', 'D') per run; distance[q] = the unit-cost edit distance; identity[q] =
+ *                 100 (1 - distance / max(left_length, right_length)) as float, bit-equal to asgart_compute_scores_flags
+ *                 when inclusive = 1; status[q] = 1 aligned, 0 refused.  Any array of _copy may be NULL.
+ * Errors, those of the score: an arm past the text, two empty arms, a flag bit other than 0 and 1 (ASGART_E_ARG), arms of
+ * 2^32 bases (ASGART_E_CAP).  One wave walks each pair (a megabase pair too); there are no _shard / _multi variants. */
+typedef struct asgart_alignment asgart_alignment;
+int32_t asgart_align_duplications(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
+                                  int32_t inclusive, uint64_t budget_bytes, asgart_alignment **out);
+void asgart_alignment_counts(const asgart_alignment *a, uint64_t *n_sd, uint64_t *n_runs, uint64_t *n_refused);
+int32_t asgart_alignment_copy(const asgart_alignment *a, uint64_t *run_offsets, uint32_t *run_len, uint8_t *run_op,
+                              uint32_t *distance, float *identity, uint8_t *status);
+/* Milliseconds of the call behind a: [0] the upload, [1] the forward pass (distances and checkpoints), [2] the traceback and
+ * the compaction, [3] the copy back; summed over the batches.  ASGART_E_ARG for a NULL argument. */
+int32_t asgart_alignment_timings(const asgart_alignment *a, double *ms4);
+void asgart_alignment_free(asgart_alignment *a);
+/* Rows of one band, rows of one lane and columns of one tile (W) of the kernels behind asgart_align_duplications, for tests
+ * that place their cases on the seams. */
+void asgart_align_geometry(uint64_t *band_rows, uint64_t *lane_rows, uint64_t *tile_cols);
+/* Host code, needs no device: bytes[q] = the checkpoint bytes of duplication q,
+ * 4 (n_bands - 1)(m + 1) + 4 floor((m - 1) / W) n_bands band_rows, with n_bands = max(1, ceil(n / band_rows)) and no column
+ * checkpoint for m = 0. */
+int32_t asgart_align_bytes(const asgart_proto_sd *sds, int64_t n_sd, int32_t inclusive, uint64_t *bytes);
+
 /* ---- the steps behind the search step ------------------------------------------
  * Replaces FilterNs, ReOrder, ReduceOverlap and Sort of the reference's step chain (src/bin/asgart.rs:33-96 with
  * ProtoSD::n_content src/structs.rs:454-467, reduce_overlap :481-562; order :738-747) for the families of one run,
