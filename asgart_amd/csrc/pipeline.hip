@@ -650,7 +650,8 @@ struct SearchCall {
         hits = w.hits.as<SlotT>();
         hipStream_t sf = cx.fill_stream;
         HIP_TRY(hipEventRecord(cx.ev[EV_FILL], sf));
-        fill_small_kernel<SlotT><<<rp.n_tiles(256u), 256, 0, sf>>>(ix, rp, p_lo, p_raw, p_filt, row_off, hits);
+        fill_small_kernel<SlotT><<<(rp.n_tiles((uint32_t)kFillTile) + kFillWaves - 1u) / kFillWaves, 64 * kFillWaves, 0, sf>>>(
+            ix, rp, p_lo, p_raw, p_filt, row_off, hits);
         if (h_ctr[CT_BIG])
             fill_big_kernel<SlotT><<<2048, 256, 0, sf>>>(ix, rp, p_lo, p_raw, p_filt, row_off, hits,
                                                          big_list, d_ctr);

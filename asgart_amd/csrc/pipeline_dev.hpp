@@ -16,6 +16,63 @@
 
 namespace asgart {
 
+__device__ inline void wave_lds_sync() {  // LDS traffic of ONE wave: what its lanes wrote is there for its other lanes
+    __builtin_amdgcn_wave_barrier();
+    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---- a wave walks many small suffix-array intervals entry by entry --------------------------------------------------
+// A lane that walks its own interval sa[lo, lo + raw) holds one load in flight, the wave lasts as long as its longest
+// interval, and the lanes without an interval idle.  Here every lane of the (whole, converged) wave brings ONE item --
+// an interval of raw <= kSmallInterval entries, raw = 0: none -- and the wave processes the sum of their entries 64 at a
+// time, in suffix-array order, all loads of a round in flight together:
+//   * the exclusive prefix of raw over the lanes (wave scan) numbers the entries; entry e finds its owner -- the last
+//     lane whose prefix is <= e -- by bisection of the prefixes (six lane reads);
+//   * the owner's hit filter travels as two numbers: entry x is kept when x >= thr and x != self (HitRule);
+//   * per round, round(own, r, x, keep, km) is called by all lanes: own / r = owner lane and place inside the owner's
+//     interval of the entry this lane loaded, x its value, keep its predicate, km the ballot of `keep` over the round.
+// fill_small_kernel places the kept entries with it: an entry's rank inside its row is the popcount of km below it inside
+// its row, plus the end of the previous round's km where the row began there (a row spans at most two rounds).  No LDS,
+// no atomics.
+struct HitRule {
+    unsigned long long thr, self;
+};
+// keep_hit(x, i, s, L, reverse)  ==  x >= thr && x != self
+__device__ inline HitRule hit_rule(uint64_t i, uint64_t s, uint64_t L, bool reverse) {
+    HitRule h;
+    h.thr = reverse ? s + L - i : i + s + 1u;
+    h.self = reverse ? i : ~0ull;
+    return h;
+}
+__device__ inline uint32_t lane_get(uint32_t v, uint32_t l) {  // lane l's v, l per lane (every lane takes part)
+    return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l << 2), (int)v);
+}
+__device__ inline unsigned long long lane_get(unsigned long long v, uint32_t l) {
+    return ((unsigned long long)lane_get((uint32_t)(v >> 32), l) << 32) | lane_get((uint32_t)v, l);
+}
+template <class SlotT, class F>
+__device__ inline void walk_small_rows(const SlotT *__restrict__ sa, unsigned long long lo, uint32_t raw, HitRule hr, F &&round) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t incl = wave_incl_scan(raw), pre = incl - raw;
+    const uint32_t total = lane_of(incl, 63u);
+    for (uint32_t base = 0; base < total; base += 64u) {
+        const uint32_t e = base + lane;
+        uint32_t own = 0;
+#pragma unroll
+        for (uint32_t step = 32u; step; step >>= 1)
+            if (lane_get(pre, own + step) <= e) own += step;  // (own + step <= 63)
+        // (items without entries repeat their successor's prefix: the LAST lane with pre <= e has entries while e < total)
+        const uint32_t r = e - lane_get(pre, own);
+        const unsigned long long lo_o = lane_get(lo, own), thr_o = lane_get(hr.thr, own), self_o = lane_get(hr.self, own);
+        const bool live = e < total;
+        SlotT x = 0;
+        if (live) x = sa[lo_o + r];
+        const bool keep = live && (unsigned long long)x >= thr_o && (unsigned long long)x != self_o;
+        round(own, r, x, keep, (unsigned long long)__ballot(keep));
+    }
+}
+
 // ---------------------------------------------------------------- K1 ---------
 // Probe search: one thread per probe, one workgroup per 256 consecutive probes.
 //
@@ -33,8 +90,9 @@ namespace asgart {
 // COUNT = true is the accounting pass behind bench.py's `kernel_algorithmic_bytes`: the same
 // control flow, no stores, every load / store of the real kernel priced in bytes.
 constexpr int kProbeBlock = 256;  // probes per workgroup (one tile)
-constexpr int kProbeThreads = 64; // ... run by ONE wave: every lane stages and tests four of them, then the survivors (a fifth of
-                                  // the tile on the GRCh38-shaped input: about one per lane) are looked up.  With four waves per tile
+constexpr int kProbeThreads = 64; // ... run by ONE wave: every lane stages and tests four of them, then the survivors (a tenth of
+                                  // the tile on the GRCh38-shaped input since a position bit says "can keep a hit": about 24, on 24
+                                  // of the 64 lanes; all 256 while the bits are blank) are looked up.  With four waves per tile
                                   // three of them held their slots through the staging only to retire; a wave slot now spends most
                                   // of its life in the dependent gathers of the lookup, and no barrier involves a second wave.
 constexpr int kProbeSub = kProbeBlock / kProbeThreads;
@@ -198,10 +256,10 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
             return qt;
         };
         // ---- position bits (every probe), then the lookup of the survivors ---------------------------------
-        // About four probes in five are answered by the bits.  The lookup behind it -- prefix table, key bisection,
+        // About nine probes in ten are answered by the bits.  The lookup behind it -- prefix table, key bisection,
         // suffix-array entries -- is a chain of dependent random gathers, and a wave runs it at the speed of its
         // slowest lane however few lanes are left: the survivors of the tile are compacted (ballots) so that the
-        // lookups run with the lanes full.
+        // lookups run on the lowest lanes, 64 survivors at a time.
         uint32_t n_surv = 0;
 #pragma unroll
         for (int u = 0; u < kProbeSub; ++u) {
@@ -916,32 +974,78 @@ __global__ __launch_bounds__(256) void raw_hits_kernel(IndexView<SlotT> ix, RunP
 }
 
 // ---------------------------------------------------------------- K3 ---------
+// Rows of small intervals.  One probe in twenty has such a row on the GRCh38-shaped input: with a thread per probe those
+// few lanes gathered their three per-probe values and then walked their interval one dependent load at a time.  A wave
+// now takes a tile of kFillTile probes: their p_filt words are read coalesced, all in flight; the probes with a row (f != 0
+// && f < kPending) are compacted by ballots into a list in LDS; p_raw, p_lo and row_off are gathered for those only, 64 at
+// a time, and the entries of their intervals are spread over the lanes (walk_small_rows), each kept entry placed by its
+// rank inside its row.
+constexpr int kFillTile = 1024, kFillWaves = 4;  // probes per wave; waves per workgroup
 template <class SlotT>
-__global__ __launch_bounds__(256) void fill_small_kernel(IndexView<SlotT> ix, RunParams rp,
-                                                         const SlotT *__restrict__ p_lo,
-                                                         const uint32_t *__restrict__ p_raw,
-                                                         const uint32_t *__restrict__ p_filt,
-                                                         const unsigned long long *__restrict__ row_off,
-                                                         SlotT *__restrict__ hits) {
+__global__ __launch_bounds__(64 * kFillWaves) void fill_small_kernel(IndexView<SlotT> ix, RunParams rp,
+                                                                     const SlotT *__restrict__ p_lo,
+                                                                     const uint32_t *__restrict__ p_raw,
+                                                                     const uint32_t *__restrict__ p_filt,
+                                                                     const unsigned long long *__restrict__ row_off,
+                                                                     SlotT *__restrict__ hits) {
+    __shared__ unsigned short s_rows[kFillWaves][kFillTile];  // per wave: the tile's probes with a row (offsets from its first)
+    unsigned short *const rows = s_rows[threadIdx.x >> 6];
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const uint32_t tile = uni(blockIdx.x * (uint32_t)kFillWaves + (threadIdx.x >> 6));
+    if (tile >= rp.n_tiles((uint32_t)kFillTile)) return;  // (the whole wave; no workgroup barrier below)
     uint32_t g_end;
-    const uint32_t gb = rp.tile_of(blockIdx.x, 256u, g_end);
-    const uint32_t g = gb + threadIdx.x;
-    // (the chunk of the workgroup's first probe, once, in scalar registers; a thread whose probe lies behind a chunk boundary
-    // steps on from there -- 256 consecutive probes rarely span two chunks -- instead of bisecting the table per thread)
-    int c = chunk_of_uniform(rp.ch, gb);
-    if (g >= g_end) return;
-    const uint32_t f = p_filt[g];
-    if (f == 0 || f >= kPending) return;
-    const uint32_t raw = p_raw[g];
-    if (raw > (uint32_t)kSmallInterval) return;
-    while (c + 1 < rp.ch.n_chunks && g >= rp.ch.pbase[c + 1]) ++c;
-    const uint64_t s = rp.ch.start[c], L = rp.ch.len[c];
-    const uint64_t i = (uint64_t)(g - rp.ch.pbase[c] + 1) * (uint64_t)rp.step;
-    const uint64_t lo = p_lo[g];
-    unsigned long long w = row_off[g];
-    for (uint32_t r = 0; r < raw; ++r) {
-        const SlotT x = ix.sa[lo + r];
-        if (keep_hit(x, i, s, L, (rp.mode_of(c) & 2u) != 0u)) hits[w++] = x;
+    const uint32_t gb = rp.tile_of(tile, (uint32_t)kFillTile, g_end);
+    // (the chunk of the tile's first probe, once, in scalar registers; a lane whose probe lies behind a chunk boundary
+    // steps on from there -- a tile rarely spans two chunks -- instead of bisecting the table per lane)
+    const int c0 = chunk_of_uniform(rp.ch, gb);
+    constexpr int kSub = kFillTile / 64;
+    uint32_t f[kSub];
+#pragma unroll
+    for (int u = 0; u < kSub; ++u) {
+        const uint32_t g = gb + (uint32_t)u * 64u + lane;
+        f[u] = g < g_end ? p_filt[g] : 0u;
+    }
+    uint32_t n_rows = 0;
+#pragma unroll
+    for (int u = 0; u < kSub; ++u) {
+        const bool has = f[u] != 0u && f[u] < kPending;
+        const unsigned long long m = __ballot(has);
+        if (has) rows[n_rows + (uint32_t)__popcll(m & lt_mask)] = (unsigned short)((uint32_t)u * 64u + lane);
+        n_rows += (uint32_t)__popcll(m);
+    }
+    n_rows = uni(n_rows);
+    wave_lds_sync();
+    for (uint32_t j0 = 0; j0 < n_rows; j0 += 64u) {
+        const uint32_t j = j0 + lane;
+        uint32_t raw = 0;
+        unsigned long long lo = 0, w = 0;
+        HitRule hr = {0ull, 0ull};
+        if (j < n_rows) {
+            const uint32_t g = gb + rows[j];
+            raw = p_raw[g];
+            if (raw > (uint32_t)kSmallInterval) raw = 0;  // (fill_big_kernel's, fill_ranked_kernel's)
+            lo = p_lo[g];
+            w = row_off[g];
+            int c = c0;
+            while (c + 1 < rp.ch.n_chunks && g >= rp.ch.pbase[c + 1]) ++c;
+            hr = hit_rule((uint64_t)(g - rp.ch.pbase[c] + 1) * (uint64_t)rp.step, rp.ch.start[c], rp.ch.len[c],
+                          (rp.mode_of(c) & 2u) != 0u);
+        }
+        unsigned long long km_prev = 0;  // the round before (wave-uniform)
+        walk_small_rows(ix.sa, lo, raw, hr,
+                        [&](uint32_t own, uint32_t r, SlotT x, bool keep, unsigned long long km) {
+                            // the kept entries of the row in front of this one: r entries, the last min(r, lane) of them in
+                            // the lanes below, the others at the end of the round before
+                            const unsigned long long w_o = lane_get(w, own);
+                            if (keep) {
+                                const uint32_t here = min(r, lane);
+                                uint32_t rank = (uint32_t)__popcll(km & lt_mask & ~((1ull << (lane - here)) - 1ull));
+                                if (r > here) rank += (uint32_t)__popcll(km_prev >> (64u - (r - here)));  // (1 <= r - here < 32)
+                                hits[w_o + rank] = x;
+                            }
+                            km_prev = km;
+                        });
     }
 }
 
@@ -1021,11 +1125,6 @@ __global__ __launch_bounds__(256) void fill_big_kernel(IndexView<SlotT> ix, RunP
 // placed.  32-bit slots only.
 constexpr int kRankedRounds = (kRankedCap + 1 + 63) / 64;  // loads of 64 entries that cover cnt + 1 <= kRankedCap + 1
 constexpr int kRankedWords = kRankedMaxR / 32;             // bitmap words per wave
-__device__ inline void wave_lds_sync() {  // LDS traffic of ONE wave: what its lanes wrote is there for its other lanes
-    __builtin_amdgcn_wave_barrier();
-    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
 template <class SlotT>
 __global__ __launch_bounds__(256) void fill_ranked_kernel(IndexView<SlotT> ix, RunParams rp,
                                                           const SlotT *__restrict__ p_lo,

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 __device__ __host__ inline uint64_t mix(uint64_t x) {
     x ^= x >> 33;
@@ -68,7 +69,110 @@ static void run(const void *table, size_t bytes, const char *name) {
     hipFree(d_out);
 }
 
+// The shape of the probe search's lookup: one wave per workgroup, `a` of its 64 lanes active, every active lane walks
+// chains of `c` dependent 8-byte gathers (a new chain starts at a fresh index) with ONE load in flight.  The grid is
+// 256 CUs x 4 SIMDs x w workgroups, all resident from launch to exit (w <= 8), so w is the occupancy.
+__global__ __launch_bounds__(64) void gather_lanes(const uint64_t *__restrict__ table, uint64_t mask, int a, int c, int chains,
+                                                   unsigned long long *out) {
+    if ((int)threadIdx.x >= a) return;
+    uint64_t seed = mix(((uint64_t)blockIdx.x * 64u + threadIdx.x) * 0x9E3779B97F4A7C15ull + 1);
+    uint64_t acc = 0;
+#pragma unroll 1
+    for (int it = 0; it < chains; ++it) {
+        uint64_t idx = mix(seed + (uint64_t)it);
+#pragma unroll 1
+        for (int j = 0; j < c; ++j) {
+            const uint64_t v = table[idx & mask];
+            acc += v;
+            idx = mix(idx ^ v);
+        }
+    }
+    if (acc == 0x123456789abcdefull) out[0] = acc;
+}
+
+#define HIP_OK(call)                                                                              \
+    do {                                                                                          \
+        const hipError_t e_ = (call);                                                             \
+        if (e_ != hipSuccess) {                                                                   \
+            fprintf(stderr, "%s: %s\n", #call, hipGetErrorString(e_));                            \
+            return false;                                                                         \
+        }                                                                                         \
+    } while (0)
+
+static bool run_lanes(const uint64_t *table, size_t bytes, int a, int w, int c) {
+    const uint64_t mask = bytes / 8 - 1;
+    const int blocks = 256 * 4 * w, chains = 3072 / c;
+    unsigned long long *d_out;
+    HIP_OK(hipMalloc(&d_out, 8));
+    hipEvent_t e0, e1;
+    HIP_OK(hipEventCreate(&e0));
+    HIP_OK(hipEventCreate(&e1));
+    gather_lanes<<<blocks, 64>>>(table, mask, a, c, chains, d_out);  // warm-up
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(e0));
+    const int reps = 3;
+    for (int r = 0; r < reps; ++r) gather_lanes<<<blocks, 64>>>(table, mask, a, c, chains, d_out);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(e1));
+    HIP_OK(hipEventSynchronize(e1));
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    if (!(ms > 0.f)) {
+        fprintf(stderr, "lanes: no time measured\n");
+        return false;
+    }
+    const double gathers = (double)reps * blocks * a * chains * c;
+    printf("lanes a=%d of 64, w=%d waves per SIMD, chain c=%d: %7.2f G gathers/s, %d loads in flight per CU, %.3f ms per launch\n",
+           a, w, c, gathers / ms / 1e6, 4 * w * a, ms / reps);
+    HIP_OK(hipEventDestroy(e0));
+    HIP_OK(hipEventDestroy(e1));
+    HIP_OK(hipFree(d_out));
+    return true;
+}
+
+static bool fill_table(uint64_t *table, size_t bytes) {
+    fill<<<4096, 256>>>(table, bytes / 8);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    return true;
+}
+
+// usage:
+//   ubench_gather [GIB]                         the rounds of U independent / dependent gathers, table of GIB (16) GiB
+//   ubench_gather lanes    A W C [A W C ...]     lane fill A of 64, W waves per SIMD, chains of C: table of 16 GiB
+//   ubench_gather lanes<G> A W C [A W C ...]     ... on a table of G GiB, a power of two (lanes64 ALLOCATES 64 GiB of device
+//                                               memory: the index of a GRCh38-sized text spreads its gathers over 41 GB)
 int main(int argc, char **argv) {
+    if (argc > 1 && !strncmp(argv[1], "lanes", 5)) {
+        char *end = argv[1] + 5;
+        const long g = *end ? strtol(argv[1] + 5, &end, 10) : 16;
+        if (*end || g < 1 || g > 128 || (g & (g - 1)) || argc < 5 || (argc - 2) % 3) {
+            fprintf(stderr, "usage: %s lanes[GiB: a power of two up to 128, default 16] A W C [A W C ...]\n", argv[0]);
+            return 1;
+        }
+        const size_t gib = (size_t)g, bytes = gib << 30;
+        uint64_t *table;
+        if (hipMalloc(&table, bytes) != hipSuccess) {
+            fprintf(stderr, "hipMalloc(%zu GiB) failed\n", gib);
+            return 1;
+        }
+        if (!fill_table(table, bytes)) return 1;
+        printf("table %zu GiB\n", gib);
+        for (int i = 2; i + 2 < argc; i += 3) {
+            const int a = atoi(argv[i]), w = atoi(argv[i + 1]), c = atoi(argv[i + 2]);
+            if (a < 1 || a > 64 || w < 1 || w > 8 || c < 1 || c > 3072) {
+                fprintf(stderr, "lanes: 1 <= a <= 64, 1 <= w <= 8, 1 <= c <= 3072\n");
+                return 1;
+            }
+            if (!run_lanes(table, bytes, a, w, c)) return 1;
+        }
+        hipFree(table);
+        return 0;
+    }
+    if (argc > 1 && (argv[1][0] < '0' || argv[1][0] > '9')) {
+        fprintf(stderr, "usage: %s [GiB] | lanes[GiB] A W C [A W C ...]\n", argv[0]);
+        return 1;
+    }
     const size_t gib = argc > 1 ? (size_t)atoi(argv[1]) : 16;  // power of two
     const size_t bytes = gib << 30;
     uint64_t *table;
