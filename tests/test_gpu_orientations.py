@@ -37,7 +37,8 @@ def _check_flags(idx, text, sds, seed, cell_budget):
     want = np.array([uniform[f][q] for q, f in enumerate(flags.tolist())], dtype=np.float32)
     whole = idx.compute_scores_flags(sds, flags)
     assert np.array_equal(_bits(whole), _bits(want))
-    # the small duplications against the oracle, each with its own flags
+    # the small duplications against the oracle, each with its own flags (the large ones are compared between entry
+    # points only; tests/test_gpu_score_reach.py scores long arms with mixed flags against the oracle and a banded reference)
     cells = (sds[:, 2] + 1).astype(np.float64) * (sds[:, 3] + 1)
     order = np.argsort(cells, kind="stable")
     pick = order[:max(1, int((np.cumsum(cells[order]) <= cell_budget).sum()))]

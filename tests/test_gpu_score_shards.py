@@ -40,6 +40,8 @@ def _with_long_rows(text, sds, seed):
 
 def _oracle(text, sds, rc, cell_budget=None):
     """Oracle identities, all of them or (cell_budget) the smallest duplications up to that many DP cells in all."""
+    # (with a budget the large duplications are compared between entry points only; tests/test_gpu_score_reach.py has
+    # arms of up to 66 000 bases, and more pairs than waves and workgroups, against the oracle and a banded reference)
     cells = (sds[:, 2] + 1).astype(np.float64) * (sds[:, 3] + 1)
     pick = np.arange(len(sds))
     if cell_budget is not None:
