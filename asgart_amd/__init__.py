@@ -26,6 +26,7 @@ __all__ = [
     "score_owners", "score_costs", "compute_scores_multi", "Source", "compute_scores_flags_multi", "orientation_flags",
     "export_records", "export_geometry", "f32_shortest", "f32_pow10_table", "EXPORT_FORMATS",
     "ResultScan", "result_geometry", "E_REFUSED", "Alignments", "align_geometry", "align_bytes",
+    "paf_records", "paf_geometry",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -59,6 +60,7 @@ ABI_SYMBOLS = (
     "asgart_result_free", "asgart_result_geometry",
     "asgart_align_duplications", "asgart_alignment_counts", "asgart_alignment_copy", "asgart_alignment_timings",
     "asgart_alignment_free", "asgart_align_geometry", "asgart_align_bytes",
+    "asgart_paf_records", "asgart_paf_geometry",
 )
 
 
@@ -337,6 +339,12 @@ def load_library() -> C.CDLL:
         L.asgart_align_geometry.restype = None
         L.asgart_align_bytes.argtypes = [vp, C.c_int64, C.c_int32, vp]
         L.asgart_align_bytes.restype = C.c_int32
+    if hasattr(L, "asgart_paf_records"):
+        L.asgart_paf_records.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp,
+                                         C.c_int64, C.POINTER(vp)]
+        L.asgart_paf_records.restype = C.c_int32
+        L.asgart_paf_geometry.argtypes = [u64p, u64p, u64p]
+        L.asgart_paf_geometry.restype = None
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []
@@ -983,6 +991,59 @@ def export_geometry() -> Tuple[int, int, int]:
     """asgart_export_geometry: threads per workgroup, units per workgroup, bytes of the LDS image of the write stage."""
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     load_library().asgart_export_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
+
+
+def paf_records(offs, sds, flags, status, distance, chr_, chr_pos, run_offsets, run_len, run_op, names: Sequence[bytes],
+                name_length, device: int = 0, timings: Optional[list] = None) -> np.ndarray:
+    """asgart_paf_records: the whole PAF file as uint8[size], written on the GPU (csrc/paf.hip).  offs, sds, flags, chr_,
+    chr_pos as export_records takes them; status, distance, run_offsets, run_len, run_op as Alignments holds them; names: the
+    name table, every name as the bytes to write; name_length: the length of the fragment behind each name.  timings: a list
+    that receives the call's three millisecond figures (asgart_export_timings: upload, kernels, copy back)."""
+    L = load_library()
+    if not hasattr(L, "asgart_paf_records"):
+        raise AsgartError(-3, f"{library_path()} has no asgart_paf_records: rebuild it; there is no host fallback behind "
+                              "this call (align.paf_text is the host writer)")
+    offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    status = np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
+    distance = np.ascontiguousarray(distance, dtype=np.uint32).reshape(-1)
+    chr_ = np.ascontiguousarray(chr_, dtype=np.int32).reshape(-1, 2)
+    chr_pos = np.ascontiguousarray(chr_pos, dtype=np.uint64).reshape(-1, 2)
+    run_offsets = np.ascontiguousarray(run_offsets, dtype=np.uint64).reshape(-1)
+    run_len = np.ascontiguousarray(run_len, dtype=np.uint32).reshape(-1)
+    run_op = np.ascontiguousarray(run_op, dtype=np.uint8).reshape(-1)
+    name_length = np.ascontiguousarray(name_length, dtype=np.uint64).reshape(-1)
+    n = len(sds)
+    if len(offs) < 1 or not (len(flags) == len(status) == len(distance) == len(chr_) == len(chr_pos) == n) or \
+            len(run_offsets) != n + 1 or len(run_len) != len(run_op) or len(name_length) != len(names):
+        raise ValueError("paf_records: the arrays differ in length")
+    if len(run_len) < int(run_offsets[-1]) < 1 << 32:   # (2^32 runs and more are the library's to refuse, unread)
+        raise ValueError(f"paf_records: run_offsets end at {int(run_offsets[-1])}, there are {len(run_len)} runs")
+    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum([len(b) for b in names], out=name_off[1:])
+    name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+    if len(run_len) == 0:
+        run_len, run_op = np.zeros(1, np.uint32), np.zeros(1, np.uint8)
+    h = C.c_void_p()
+    _check(L.asgart_paf_records(int(device), _ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags), _ptr(status),
+                                _ptr(distance), _ptr(chr_), _ptr(chr_pos), n, _ptr(run_offsets), _ptr(run_len),
+                                _ptr(run_op), _ptr(name_bytes), _ptr(name_off), _ptr(name_length), len(names), C.byref(h)))
+    try:
+        out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
+        _check(L.asgart_export_copy(h, _ptr(out), len(out)))
+        _read_timings(L.asgart_export_timings, h, timings)
+    finally:
+        L.asgart_export_free(h)
+    return out
+
+
+def paf_geometry() -> Tuple[int, int, int]:
+    """asgart_paf_geometry: threads per workgroup of the write stage, the most runs one workgroup's range can hold, bytes of
+    the file a workgroup owns (its LDS image)."""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    load_library().asgart_paf_geometry(C.byref(a), C.byref(b), C.byref(c))
     return int(a.value), int(b.value), int(c.value)
 
 

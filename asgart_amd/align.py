@@ -6,6 +6,7 @@ This module states the same rule on the host, for the tests to compare byte for 
     align_host   the full edit matrix in numpy, row by row, then the canonical trace (include/asgart_hip.h)
     replay       does a list of runs consume exactly both arms, `=` on equal bytes and `X` on unequal ones?  -> its edits
     paf_text     one PAF row per aligned duplication: query = left arm, target = right arm
+    paf_text_gpu the same bytes, written on the GPU (asgart_paf_records, csrc/paf.hip)
 
 The arms: A = text[left ..] is the left arm; B is the right arm as ProtoSD::levenshtein walks it (reference
 src/structs.rs:439-452): reversed if flag bit 0 is set, complemented if bit 1 is set (ACGT and acgt swap, anything else is
@@ -190,3 +191,53 @@ def paf_text(offs, sds, flags, strand, aln, stderr=None) -> str:
             sum(n for n, op in runs if op == "="), sum(n for n, _ in runs), 255,
             f"NM:i:{int(aln.distance[q])}", f"fm:i:{int(family[q])}", f"cg:Z:{cigar(runs)}")))
     return "".join(r + "\n" for r in rows)
+
+
+def _paf_text_device(offs, sds, flags, strand, aln, device: int = 0, stderr=None,
+                     timings: Optional[dict] = None) -> np.ndarray:
+    """paf_text_gpu as the uint8 array the library filled (the drivers decode it without another copy)."""
+    import time
+
+    from . import paf_records
+    from .postprocess import locate_arms
+
+    offs = np.asarray(offs, dtype=np.int64)
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds):
+        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, "
+                         f"families that end at {int(offs[-1])}")
+    odd = np.flatnonzero((flags != 0) & (flags != 3))
+    if len(odd):
+        q, f = int(odd[0]), int(flags[odd[0]])
+        raise ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
+                         "direct (+) and reverse-complemented (-) alignments and none for this one")
+    t0 = time.perf_counter()
+    total = sum(c.length for c in strand.map)
+    names = [c.name.encode("utf-8") for c in strand.map] + [b"unknown"]
+    name_length = np.array([c.length for c in strand.map] + [total], dtype=np.uint64)
+    chr_, chr_pos = locate_arms(sds, strand)
+    status = np.asarray(aln.status, dtype=np.uint8).reshape(-1)
+    refused = np.flatnonzero(status == 0)
+    if len(refused):
+        family = np.searchsorted(offs, refused, side="right") - 1
+        for q, f in zip(refused.tolist(), family.tolist()):
+            print(f"paf: duplication {q} (family {f}) was refused by the alignment's memory budget: no row",
+                  file=stderr if stderr is not None else sys.stderr)
+    t1 = time.perf_counter()
+    ms: list = []
+    out = paf_records(offs, sds, flags, status, aln.distance, chr_, chr_pos, aln.run_offsets, aln.run_len, aln.run_op,
+                      names, name_length, device, ms)
+    if timings is not None:
+        timings.update(names=(t1 - t0) * 1e3, upload=ms[0], kernels=ms[1], copy=ms[2])
+    return out
+
+
+def paf_text_gpu(offs, sds, flags, strand, aln, device: int = 0, stderr=None, timings: Optional[dict] = None) -> bytes:
+    """paf_text(offs, sds, flags, strand, aln, stderr).encode("utf-8"), written on the GPU (asgart_paf_records,
+    csrc/paf.hip): the arms are located here by postprocess.locate_arms (the bisection the device writer of the JSON file
+    uses), the name table -- every map entry's name, then `unknown` with the strand's length -- is prepared here once, and
+    the rows, one thread per CIGAR run, are laid out and written by the library.  The same ValueError texts as paf_text and
+    the same stderr line per refused duplication, in the same order.  timings: a dict that receives the call's stages in
+    milliseconds: names (locate and name table), upload, kernels, copy."""
+    return _paf_text_device(offs, sds, flags, strand, aln, device, stderr, timings).tobytes()

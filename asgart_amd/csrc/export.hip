@@ -115,16 +115,6 @@ __global__ __launch_bounds__(256) void f32_shortest_kernel(const float *__restri
 
 using namespace asgart;
 
-struct asgart_export {
-    int32_t device = 0;
-    DevBuf file;          // the whole file, on the device
-    uint64_t size = 0;
-    double ms[3] = {0, 0, 0};
-    ~asgart_export() {
-        if (file.p && hipSetDevice(device) == hipSuccess) file.release();
-    }
-};
-
 namespace {
 
 struct ExportWork : ToolWork {

@@ -1,0 +1,251 @@
+// paf.hip -- PAF files written on the GPU: asgart_paf_records, the counterpart of align.paf_text for a caller of the C ABI.
+//
+// What a row consists of is stated once, in paf_dev.hpp.  A row's CIGAR is as long as its two arms have edits, so nothing
+// here works row by row except the head:
+//   runs      one thread per run: the bytes of its text (the digits of its length and the operation), its `=` bases, its bases;
+//   scans     three 64-bit exclusive scans over the runs (rocPRIM): P, M and B.  A row's CIGAR bytes, its column 10 and its
+//             column 11 are differences of them at the row's first run and behind its last;
+//   rows      one thread per row (a duplication with status != 0; the host numbers them while it checks the flags): its
+//             family by bisection, the length of its head by running the head through a sink that counts, its length;
+//   scan      a 64-bit exclusive scan of the row lengths: every row's place in the file, and the file's size;
+//   write     a workgroup owns kStage consecutive BYTES of the file -- not rows, not runs -- so that its range starts on a
+//             16-byte line whatever the rows hold.  It finds the rows of its first and last byte by bisection of the row
+//             starts and the runs of those two rows that reach into its range by bisection of P; the heads in the range are
+//             dealt out a row per thread, the runs a run per thread, each storing the bytes that fall inside the range into
+//             an LDS image of it.  Then all threads move the image out with one aligned 16-byte store per lane.  A head
+//             longer than the image (a 20 000-byte name) is composed by the workgroups it spans, each its own part; there is
+//             no second path.
+#include "tool_base.hpp"
+#include "paf_dev.hpp"
+
+namespace asgart {
+namespace {
+
+constexpr uint32_t kThreads = 256;          // per workgroup of the write stage
+constexpr uint32_t kStage = 16384;          // bytes of the file per workgroup, and of its LDS image: nine fit a CU's 160 KiB
+constexpr uint32_t kRunsMax = kStage / 2;   // a run is two bytes at least: the runs one image can hold
+constexpr uint32_t kLine = 16;              // bytes per store of the copy out
+
+__global__ __launch_bounds__(256) void paf_runs_kernel(const uint32_t *__restrict__ run_len,
+                                                       const uint8_t *__restrict__ run_op, uint64_t n_runs,
+                                                       uint64_t *__restrict__ text, uint64_t *__restrict__ match,
+                                                       uint64_t *__restrict__ bases) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t > n_runs) return;
+    if (t == n_runs) {   // the closing entry: the scans end in the totals
+        text[t] = match[t] = bases[t] = 0;
+        return;
+    }
+    const uint32_t len = run_len[t];
+    text[t] = decimal_digits(len) + 1;
+    match[t] = run_op[t] == '=' ? len : 0;
+    bases[t] = len;
+}
+
+__global__ __launch_bounds__(256) void paf_rows_kernel(PafIn in, uint32_t *__restrict__ head_len, uint32_t *__restrict__ fam,
+                                                       uint64_t *__restrict__ lens) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k > in.n_rows) return;
+    if (k == in.n_rows) {
+        lens[k] = 0;
+        return;
+    }
+    const uint32_t q = in.kept[k];
+    const uint32_t f = segment_of(in.offs, in.n_fam, q);
+    CountSink c;
+    emit_paf_head(c, in, q, f);
+    head_len[k] = (uint32_t)c.n;
+    fam[k] = f;
+    lens[k] = c.n + (in.P[in.run_off[q + 1]] - in.P[in.run_off[q]]) + 1;
+}
+
+__global__ __launch_bounds__(kThreads) void paf_write_kernel(PafIn in, uint64_t size, uint8_t *__restrict__ out) {
+    __shared__ __align__(16) uint8_t stage[kStage];
+    const uint64_t g0 = (uint64_t)blockIdx.x * kStage;
+    if (g0 >= size) return;
+    const uint64_t g1 = min(g0 + kStage, size);
+    paf_compose(in, g0, g1, threadIdx.x, kThreads, stage);
+    __syncthreads();
+    const uint32_t bytes = (uint32_t)(g1 - g0), lines = (bytes + kLine - 1) / kLine;
+    for (uint32_t l = threadIdx.x; l < lines; l += kThreads) {
+        if ((l + 1) * kLine <= bytes) {
+            *reinterpret_cast<uint4 *>(out + g0 + (uint64_t)l * kLine) = *reinterpret_cast<const uint4 *>(stage + l * kLine);
+        } else {   // the last line of the file
+            for (uint32_t b = l * kLine; b < bytes; ++b) out[g0 + b] = stage[b];
+        }
+    }
+}
+
+struct PafWork : ToolWork {
+    DevBuf &offs = buf(), &sds = buf(), &flags = buf(), &distance = buf(), &chr = buf(), &chr_pos = buf(), &run_off = buf(),
+           &run_len = buf(), &run_op = buf(), &names = buf(), &name_off = buf(), &name_len = buf(), &kept = buf(),
+           &text = buf(), &match = buf(), &bases = buf(), &P = buf(), &M = buf(), &B = buf(), &head_len = buf(), &fam = buf(),
+           &lens = buf(), &row_start = buf();
+};
+
+const char kWho[] = "asgart_paf_records";
+
+// Every argument check of the call, before the device is looked at; kept: the duplications with a row.
+int32_t check_arguments(const uint64_t *fam_offsets, int64_t n_families, const asgart_proto_sd *sds, const uint8_t *flags,
+                        const uint8_t *status, const uint32_t *distance, const int32_t *chr, const uint64_t *chr_pos,
+                        int64_t n_sd, const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
+                        const uint8_t *name_bytes, const uint64_t *name_offsets, const uint64_t *name_length, int64_t n_names,
+                        asgart_export **out, std::vector<uint32_t> &kept) {
+    if (!out || !fam_offsets || n_families < 0 || n_sd < 0 || n_names < 0 || !name_offsets || (n_names && !name_length) ||
+        (n_sd && (!sds || !flags || !status || !distance || !chr || !chr_pos || !run_offsets))) {
+        set_error("%s: bad argument", kWho);
+        return ASGART_E_ARG;
+    }
+    if (n_sd >= (int64_t)1 << 31 || n_families >= (int64_t)1 << 31) {
+        set_error("%s: 2^31 rows (or families) and more are not supported", kWho);
+        return ASGART_E_CAP;
+    }
+    RC_TRY(check_csr(kWho, "fam_offsets", fam_offsets, n_families, n_sd, "n_sd"));
+    const uint64_t n_runs = n_sd ? run_offsets[n_sd] : 0;
+    if (n_runs >= (uint64_t)1 << 32) {
+        set_error("%s: run_offsets end at %llu; 2^32 runs and more are not supported", kWho, (unsigned long long)n_runs);
+        return ASGART_E_CAP;
+    }
+    if (n_sd) RC_TRY(check_csr(kWho, "run_offsets", run_offsets, n_sd, (int64_t)n_runs, "the run count", "duplication"));
+    if (n_runs && (!run_len || !run_op)) {
+        set_error("%s: bad argument (%llu runs and no run_len or run_op)", kWho, (unsigned long long)n_runs);
+        return ASGART_E_ARG;
+    }
+    if (name_offsets[0] != 0 || (name_offsets[n_names] && !name_bytes) || name_offsets[n_names] >= ((uint64_t)1 << 30)) {
+        set_error("%s: name_offsets must start at 0 and end below 2^30 bytes of names", kWho);
+        return ASGART_E_ARG;
+    }
+    for (int64_t k = 0; k < n_names; ++k)
+        if (name_offsets[k] > name_offsets[k + 1]) {
+            set_error("%s: name_offsets decrease at name %lld", kWho, (long long)k);
+            return ASGART_E_ARG;
+        }
+    RC_TRY(check_name_ids(kWho, chr, n_sd, n_names));
+    for (int64_t q = 0; q < n_sd; ++q) {
+        if (!status[q]) continue;
+        if (flags[q] != 0 && flags[q] != 3) {
+            set_error("%s: duplication %lld has flag byte %u: a PAF row has a strand for 0 (direct, +) and 3 (reversed and "
+                      "complemented, -) only", kWho, (long long)q, (unsigned)flags[q]);
+            return ASGART_E_ARG;
+        }
+        for (int arm = 0; arm < 2; ++arm) {
+            const uint64_t pos = chr_pos[2 * q + arm], len = arm ? sds[q].right_length : sds[q].left_length;
+            if (pos + len < pos) {
+                set_error("%s: duplication %lld: position %llu + length %llu wraps past 2^64", kWho, (long long)q,
+                          (unsigned long long)pos, (unsigned long long)len);
+                return ASGART_E_ARG;
+            }
+        }
+        kept.push_back((uint32_t)q);
+    }
+    return 0;
+}
+
+int32_t run_paf(PafWork &w, asgart_export *res, const uint64_t *fam_offsets, uint32_t nf, const asgart_proto_sd *sds,
+                const uint8_t *flags, const uint32_t *distance, const int32_t *chr, const uint64_t *chr_pos, uint32_t n,
+                const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op, const uint8_t *name_bytes,
+                const uint64_t *name_offsets, const uint64_t *name_length, size_t n_names,
+                const std::vector<uint32_t> &kept) {
+    const uint32_t n_rows = (uint32_t)kept.size();
+    if (n_rows == 0) return 0;   // an empty file: nothing to launch
+    const uint64_t n_runs = run_offsets[n];
+    RC_TRY(w.open(5));
+    hipStream_t s = w.s;
+    HIP_TRY(hipEventRecord(w.ev[0], s));
+    RC_TRY(w.upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8));
+    RC_TRY(w.upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd)));
+    RC_TRY(w.upload(w.flags, flags, n));
+    RC_TRY(w.upload(w.distance, distance, (size_t)n * 4));
+    RC_TRY(w.upload(w.chr, chr, (size_t)n * 8));
+    RC_TRY(w.upload(w.chr_pos, chr_pos, (size_t)n * 16));
+    RC_TRY(w.upload(w.run_off, run_offsets, ((size_t)n + 1) * 8));
+    RC_TRY(w.upload(w.run_len, run_len, (size_t)n_runs * 4));
+    RC_TRY(w.upload(w.run_op, run_op, (size_t)n_runs));
+    RC_TRY(w.upload(w.names, name_bytes, (size_t)name_offsets[n_names]));
+    RC_TRY(w.upload(w.name_off, name_offsets, (n_names + 1) * 8));
+    RC_TRY(w.upload(w.name_len, name_length, n_names * 8));
+    RC_TRY(w.upload(w.kept, kept.data(), (size_t)n_rows * 4));
+    HIP_TRY(hipEventRecord(w.ev[1], s));
+    for (DevBuf *b : {&w.text, &w.match, &w.bases, &w.P, &w.M, &w.B}) RC_TRY(b->reserve(((size_t)n_runs + 1) * 8));
+    RC_TRY(w.head_len.reserve((size_t)n_rows * 4));
+    RC_TRY(w.fam.reserve((size_t)n_rows * 4));
+    RC_TRY(w.lens.reserve(((size_t)n_rows + 1) * 8));
+    RC_TRY(w.row_start.reserve(((size_t)n_rows + 1) * 8));
+    paf_runs_kernel<<<blocks_for(n_runs + 1), 256, 0, s>>>(w.run_len.as<uint32_t>(), w.run_op.as<uint8_t>(), n_runs,
+                                                          w.text.as<uint64_t>(), w.match.as<uint64_t>(),
+                                                          w.bases.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    RC_TRY(w.exclusive_scan(w.text.as<uint64_t>(), w.P.as<uint64_t>(), (size_t)n_runs + 1));
+    RC_TRY(w.exclusive_scan(w.match.as<uint64_t>(), w.M.as<uint64_t>(), (size_t)n_runs + 1));
+    RC_TRY(w.exclusive_scan(w.bases.as<uint64_t>(), w.B.as<uint64_t>(), (size_t)n_runs + 1));
+    PafIn in{};
+    in.offs = w.offs.as<uint64_t>();
+    in.sds = w.sds.as<uint64_t>();
+    in.flags = w.flags.as<uint8_t>();
+    in.distance = w.distance.as<uint32_t>();
+    in.chr = w.chr.as<int32_t>();
+    in.chr_pos = w.chr_pos.as<uint64_t>();
+    in.run_off = w.run_off.as<uint64_t>();
+    in.run_len = w.run_len.as<uint32_t>();
+    in.run_op = w.run_op.as<uint8_t>();
+    in.names = w.names.as<uint8_t>();
+    in.name_off = w.name_off.as<uint64_t>();
+    in.name_len = w.name_len.as<uint64_t>();
+    in.kept = w.kept.as<uint32_t>();
+    in.P = w.P.as<uint64_t>();
+    in.M = w.M.as<uint64_t>();
+    in.B = w.B.as<uint64_t>();
+    in.head_len = w.head_len.as<uint32_t>();
+    in.fam = w.fam.as<uint32_t>();
+    in.row_start = w.row_start.as<uint64_t>();
+    in.n_fam = nf;
+    in.n_rows = n_rows;
+    paf_rows_kernel<<<blocks_for((uint64_t)n_rows + 1), 256, 0, s>>>(in, w.head_len.as<uint32_t>(), w.fam.as<uint32_t>(),
+                                                                     w.lens.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    RC_TRY(w.exclusive_scan(w.lens.as<uint64_t>(), w.row_start.as<uint64_t>(), (size_t)n_rows + 1));
+    HIP_TRY(hipEventRecord(w.ev[2], s));
+    HIP_TRY(read_back(&res->size, in.row_start + n_rows, 8, s));
+    RC_TRY(res->file.reserve(std::max<size_t>(res->size, 16)));
+    HIP_TRY(hipEventRecord(w.ev[3], s));
+    paf_write_kernel<<<blocks_for(res->size, kStage), kThreads, 0, s>>>(in, res->size, res->file.as<uint8_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(w.ev[4], s));
+    HIP_TRY(stream_sync(s));
+    float up = 0, a = 0, b = 0;
+    HIP_TRY(hipEventElapsedTime(&up, w.ev[0], w.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&a, w.ev[1], w.ev[2]));
+    HIP_TRY(hipEventElapsedTime(&b, w.ev[3], w.ev[4]));
+    res->ms[0] = up;
+    res->ms[1] = (double)a + (double)b;
+    return 0;
+}
+
+}  // namespace
+}  // namespace asgart
+
+using namespace asgart;
+
+extern "C" int32_t asgart_paf_records(int32_t device, const uint64_t *fam_offsets, int64_t n_families,
+                                      const asgart_proto_sd *sds, const uint8_t *flags, const uint8_t *status,
+                                      const uint32_t *distance, const int32_t *chr, const uint64_t *chr_pos, int64_t n_sd,
+                                      const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
+                                      const uint8_t *name_bytes, const uint64_t *name_offsets, const uint64_t *name_length,
+                                      int64_t n_names, asgart_export **out) {
+    if (out) *out = nullptr;
+    std::vector<uint32_t> kept;
+    RC_TRY(check_arguments(fam_offsets, n_families, sds, flags, status, distance, chr, chr_pos, n_sd, run_offsets, run_len,
+                           run_op, name_bytes, name_offsets, name_length, n_names, out, kept));
+    RC_TRY(use_device(kWho, device));
+    return run_tool<PafWork>(out, [&](PafWork &w, asgart_export *res) {
+        res->device = device;
+        return run_paf(w, res, fam_offsets, (uint32_t)n_families, sds, flags, distance, chr, chr_pos, (uint32_t)n_sd,
+                       run_offsets, run_len, run_op, name_bytes, name_offsets, name_length, (size_t)n_names, kept);
+    });
+}
+
+extern "C" void asgart_paf_geometry(uint64_t *block_threads, uint64_t *runs_per_block, uint64_t *stage_bytes) {
+    if (block_threads) *block_threads = kThreads;
+    if (runs_per_block) *runs_per_block = kRunsMax;
+    if (stage_bytes) *stage_bytes = kStage;
+}

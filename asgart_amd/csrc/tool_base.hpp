@@ -1,4 +1,4 @@
-// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, export.hip) are built on: the device check of an
+// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, export.hip, paf.hip) are built on: the device check of an
 // entry point, the device work of one call (ToolWork: stream, events, every device buffer, the rocPRIM two-call wrappers),
 // the host checks of offset arrays and name ids, the bisection of an offset array on the device, and the tail of an entry
 // point.  extract.hip, fasta.hip and prep.hip take use_device from here.
@@ -173,3 +173,15 @@ __global__ __launch_bounds__(kThreads) void family_offsets_kernel(const uint64_t
 }  // namespace
 
 }  // namespace asgart
+
+// The handle of a file written on the device (export.hip: asgart_export_records; paf.hip: asgart_paf_records);
+// asgart_export_size, _copy, _timings and _free (export.hip) work on it whichever call made it.
+struct asgart_export {
+    int32_t device = 0;
+    asgart::DevBuf file;  // the whole file, on the device
+    uint64_t size = 0;
+    double ms[3] = {0, 0, 0};
+    ~asgart_export() {
+        if (file.p && hipSetDevice(device) == hipSuccess) file.release();
+    }
+};

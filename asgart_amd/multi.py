@@ -208,6 +208,24 @@ def _choose_writer(writer: Optional[str], with_sequences: bool) -> str:
     return "host" if with_sequences else writer
 
 
+# writer=None for a PAF file: the device writer from this many CIGAR runs on, the host writer below.  A call of the device
+# writer costs 6 to 8 ms whatever it writes, with a spread of 5 to 6 ms; align.paf_text costs 0.13 ms per thousand runs.
+# profiles/paf_synth.json: at 80 536 runs the two medians are closer than the device's spread, at 2^20 runs and at 21
+# million the device's is below the host's by more than both spreads.
+PAF_DEVICE_MIN_RUNS = 1 << 20
+
+
+def _choose_paf_writer(writer: Optional[str], n_runs: int) -> str:
+    """The writer of a PAF file of n_runs CIGAR runs: "device" (align.paf_text_gpu) or "host" (align.paf_text, what
+    --host-writer asks for) as asked; writer=None: by size, see PAF_DEVICE_MIN_RUNS.  A PAF row holds no sequence, so
+    with_sequences -- which sends the RESULT file to the host exporter -- does not matter here."""
+    if writer is None:
+        return "device" if n_runs >= PAF_DEVICE_MIN_RUNS else "host"
+    if writer not in ("device", "host"):
+        raise ValueError("writer: 'device' or 'host'")
+    return writer
+
+
 def _decode(file_bytes: np.ndarray) -> str:
     """The text of a file the device writer produced (uint8, UTF-8), without a copy in between."""
     return str(memoryview(file_bytes), "utf-8")
@@ -281,11 +299,19 @@ def _check_paf(paf: bool, world: int, orientations, slice_options=None) -> None:
                          "name positions in the fragments of the run (slice the result without them, or write no PAF)")
 
 
-def _paf_rows(index, strand, fam_offs, sds, flags) -> str:
-    """Rank 0, while the index is alive: the duplications aligned with exact ranges (Index.align) as PAF text."""
-    from .align import paf_text
+def _paf_text(fam_offs, sds, flags, strand, aln, writer: Optional[str], device_index: int) -> str:
+    """The PAF text of aligned duplications by the writer the run asked for (_choose_paf_writer): "device"
+    asgart_paf_records (align._paf_text_device), "host" align.paf_text; the text is the same either way."""
+    from .align import _paf_text_device, paf_text
 
-    return paf_text(fam_offs, sds, flags, strand, index.align(sds, flags, inclusive=False))
+    if _choose_paf_writer(writer, len(aln.run_len)) == "device":
+        return _decode(_paf_text_device(fam_offs, sds, flags, strand, aln, device_index))
+    return paf_text(fam_offs, sds, flags, strand, aln)
+
+
+def _paf_rows(index, strand, fam_offs, sds, flags, writer: Optional[str], device_index: int) -> str:
+    """Rank 0, while the index is alive: the duplications aligned with exact ranges (Index.align) as PAF text."""
+    return _paf_text(fam_offs, sds, flags, strand, index.align(sds, flags, inclusive=False), writer, device_index)
 
 
 def _slice_run(post, strand, settings, slice_options, device_index: int):
@@ -326,7 +352,9 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     the text is the same either way.  Sequences are out of scope for the device writer: with_sequences takes the host
     exporter.
     paf: the surviving duplications -- the ones compute_score scores -- are also aligned (Index.align with exact ranges)
-    and the return value gains a third entry, the text of the PAF file (align.paf_text).  One rank only; see _check_paf."""
+    and the return value gains a third entry, the text of the PAF file, written as `writer` asks (align.paf_text_gpu or
+    align.paf_text; None: by the number of runs, PAF_DEVICE_MIN_RUNS; with_sequences does not send it to the host, a PAF
+    row holds no sequence).  One rank only; see _check_paf."""
     from . import orientation_flags
     from .postprocess import _to_json_arrays_device, out_filename, to_json_arrays
 
@@ -334,6 +362,7 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_duplications: --trim runs on one rank only")
     reader = _choose_reader(reader, settings)
+    paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
     sliced = _check_slice(slice_options, fmt)
@@ -382,7 +411,8 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
         extra = ()
         if paf:
             extra = (_paf_rows(index, strand, cut.offs if sliced else post[0], survivors,
-                               orientation_flags(settings.reverse, settings.complement, len(survivors))),)
+                               orientation_flags(settings.reverse, settings.complement, len(survivors)), paf_writer,
+                               device_index),)
         if not sliced:
             if writer == "device":
                 return (_decode(_to_json_arrays_device(post[0], post[1], strand, settings, ident, None, device_index)),
@@ -424,7 +454,8 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     files this writes.  writer: as search_duplications -- every orientation's file and the merged one are written on rank
     0's GPU unless "host" is asked for or with_sequences is set.
     paf: every orientation's entry gains a third element, the text of its PAF file (one Index.align over the survivors of
-    all orientations); the merged result gets none.  One rank, direct and RC only; see _check_paf."""
+    all orientations, written as in search_duplications); the merged result gets none.  One rank, direct and RC only; see
+    _check_paf."""
     from dataclasses import replace
 
     from . import merge_shards, orientation_flags
@@ -439,6 +470,7 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
     _check_paf(paf, world, orientations)
     reader = _choose_reader(reader, settings)
+    paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
     index = strand = records = source = None
@@ -488,9 +520,7 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
             out.append((text_of(offs, sds, st, None if ident is None else ident[lo:hi], part, None),
                         out_filename(files, st, prefix)))
             if paf:
-                from .align import paf_text
-
-                out[-1] += (paf_text(offs, sds, flags[lo:hi], strand, aln.part(lo, hi)),)
+                out[-1] += (_paf_text(offs, sds, flags[lo:hi], strand, aln.part(lo, hi), paf_writer, device_index),)
             lo = hi
         sizes = np.concatenate([np.diff(p[0].astype(np.int64)) for p in posts])
         all_offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
@@ -524,7 +554,8 @@ def _parse(argv):
                     help="read and prepare the FASTA files on the host (prep.read_records) instead of on rank 0's GPU; "
                          "the result is the same")
     ap.add_argument("--host-writer", action="store_true",
-                    help="write the result file with the host exporters instead of on rank 0's GPU; the bytes are the same")
+                    help="write the result file with the host exporters, and the PAF file of --paf with the host writer, instead "
+                         "of on rank 0's GPU; the bytes are the same")
     ap.add_argument("--format", choices=("json", "gff2", "gff3"), default="json",
                     help="the format of the output file, as asgart-slice -f writes it")
     from .slice import add_filter_arguments

@@ -354,25 +354,37 @@ def to_json_arrays(offs: np.ndarray, sds: np.ndarray, strand, settings: RunSetti
     return head[:-2] + ',\n  "families": ' + body + "\n}"
 
 
+def locate_arms(sds, strand) -> Tuple[np.ndarray, np.ndarray]:
+    """Both arms of every duplication in the strand map, for the device writers (JSON: _to_json_arrays_device; PAF:
+    align.paf_text_gpu) -> (chr int32[n, 2], chr_pos uint64[n, 2]).  chr is the ordinal of the map entry that holds the
+    arm's global position -- by bisection of the map, whose records follow one another: the first-match scan of
+    RunResult's find_chr_by_pos finds the same record -- and chr_pos the position inside it; a position in no record gets
+    len(strand.map), the row of `unknown` in the writers' name tables, and keeps its global position."""
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    n, m = len(sds), len(strand.map)
+    starts = np.array([c.position for c in strand.map], dtype=np.uint64)
+    ends = starts + np.array([c.length for c in strand.map], dtype=np.uint64)
+    chr_ = np.full((n, 2), m, dtype=np.int32)   # entry len(map) is "unknown"
+    chr_pos = sds[:, :2].copy()
+    if m:
+        for side in (0, 1):   # locate of to_json_arrays
+            pos = sds[:, side]
+            i = np.searchsorted(starts, pos, side="right").astype(np.int64) - 1
+            ok = (i >= 0) & (pos < ends[np.maximum(i, 0)])
+            chr_[:, side] = np.where(ok, i, m)
+            chr_pos[:, side] = np.where(ok, pos - starts[np.maximum(i, 0)], pos)
+    return chr_, chr_pos
+
+
 def _to_json_arrays_device(offs, sds, strand, settings: RunSettings, identity=None, flags=None, device: int = 0,
                            timings: Optional[list] = None) -> np.ndarray:
     """to_json_arrays_gpu as the uint8 array the library filled (the drivers decode it without another copy)."""
     from . import export_records
 
     sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
-    n, m = len(sds), len(strand.map)
-    starts = np.array([c.position for c in strand.map], dtype=np.uint64)
-    ends = starts + np.array([c.length for c in strand.map], dtype=np.uint64)
+    n = len(sds)
     names = [json.dumps(c.name, ensure_ascii=False).encode("utf-8") for c in strand.map] + [b'"unknown"']
-    chr_ = np.full((n, 2), m, dtype=np.int32)   # entry len(map) is "unknown"
-    chr_pos = sds[:, :2].copy()
-    if m:
-        for side in (0, 1):   # locate of to_json_arrays: the record of a position by bisection of the map
-            pos = sds[:, side]
-            i = np.searchsorted(starts, pos, side="right").astype(np.int64) - 1
-            ok = (i >= 0) & (pos < ends[np.maximum(i, 0)])
-            chr_[:, side] = np.where(ok, i, m)
-            chr_pos[:, side] = np.where(ok, pos - starts[np.maximum(i, 0)], pos)
+    chr_, chr_pos = locate_arms(sds, strand)
     if flags is None:
         flags = np.full(n, int(bool(settings.reverse)) | int(bool(settings.complement)) << 1, dtype=np.uint8)
     flags = np.asarray(flags, dtype=np.uint8).reshape(-1)

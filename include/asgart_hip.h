@@ -669,6 +669,38 @@ void asgart_export_free(asgart_export *e);
  * record or the framing between two families: n_sd + n_families + 1 in all), bytes of the LDS image of a workgroup's range;
  * a range larger than that is stored without the image. */
 void asgart_export_geometry(uint64_t *block_threads, uint64_t *records_per_block, uint64_t *stage_bytes);
+
+/* ---- PAF files written on the GPU -----------------------------------------------------------------------------
+ * The alignments of asgart_align_duplications (inclusive = 0) as a PAF file: one call gives the whole file in one device
+ * buffer, an asgart_export like the result files above (asgart_export_size, _copy, _timings and _free work on it).  No
+ * counterpart in the reference.  For every duplication q with status[q] != 0, in order, one line of fifteen columns separated
+ * by tabs and ended by `\n`; query = left arm, target = right arm:
+ *    1  the name chr[2q]          2  name_length of it     3  chr_pos[2q]        4  column 3 + left_length
+ *    5  `+` for flags[q] == 0, `-` for flags[q] == 3
+ *    6  the name chr[2q + 1]      7  name_length of it     8  chr_pos[2q + 1]    9  column 8 + right_length
+ *   10  the sum of the row's `=` run lengths    11  the sum of all its run lengths    12  `255`
+ *   13  `NM:i:<distance[q]>`    14  `fm:i:<f>`, fam_offsets[f] <= q < fam_offsets[f + 1]    15  `cg:Z:<CIGAR>`
+ * The CIGAR is `<run_len><run_op>` for the runs run_offsets[q] .. run_offsets[q + 1]; on a `-` row the runs are written in
+ * reverse order, the operations unchanged (PAF's CIGAR runs along the target's forward strand).  A row without runs ends in
+ * `cg:Z:`.  status[q] == 0 (a refused alignment): no row, whatever else is given for q.  The name table is the host's: the
+ * bytes of every name as they are to be written (name_bytes, name_offsets[n_names + 1]) and the length of the fragment it
+ * names (name_length[n_names]); a name of any length is legal.  The run count is run_offsets[n_sd]; columns 10 and 11 are
+ * u64 sums.
+ * Checked on the host before anything is launched or read further: NULL arrays with a positive count, fam_offsets /
+ * run_offsets / name_offsets not starting at 0, decreasing or (fam_offsets) not ending at n_sd, a name id outside the table,
+ * a flag other than 0 or 3 on a duplication with a row (the message names the first), a position + length that wraps past
+ * 2^64 on one: ASGART_E_ARG; 2^31 duplications or 2^32 runs and more: ASGART_E_CAP; no usable device: ASGART_E_HIP.
+ * n_sd == 0, or every status 0, succeeds with an empty file.  The handle owns the file until asgart_export_free; nothing
+ * else stays on the device. */
+int32_t asgart_paf_records(int32_t device, const uint64_t *fam_offsets, int64_t n_families, const asgart_proto_sd *sds,
+                           const uint8_t *flags, const uint8_t *status, const uint32_t *distance, const int32_t *chr,
+                           const uint64_t *chr_pos, int64_t n_sd, const uint64_t *run_offsets, const uint32_t *run_len,
+                           const uint8_t *run_op, const uint8_t *name_bytes, const uint64_t *name_offsets,
+                           const uint64_t *name_length, int64_t n_names, asgart_export **out);
+/* Sizes the write stage of asgart_paf_records works in, for tests that place their counts on the seams: threads per
+ * workgroup, the most runs one workgroup's range can hold (a run is two bytes at least), bytes of the file a workgroup owns
+ * (its LDS image; workgroup i writes the bytes [i * stage_bytes, (i + 1) * stage_bytes) of the file). */
+void asgart_paf_geometry(uint64_t *block_threads, uint64_t *runs_per_block, uint64_t *stage_bytes);
 /* An array of f32 rendered on the device as the exporters print an identity: the shortest decimal digits that read back
  * as the same f32, in one of two forms.
  *   ASGART_F32_JSON      serde_json's (ryu's pretty printer; `identity` in exporters.rs:12-25): `97.3`, `100.0`, `0.0`,
