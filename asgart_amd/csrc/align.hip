@@ -19,6 +19,8 @@
 // The host packs the duplications, largest first, into batches whose checkpoints fit the caller's budget; a duplication that
 // alone exceeds it is refused, the others are unaffected, and no result depends on the budget or on the batching.
 // Integer work throughout; plain vector loads and stores and LDS.
+// The systolic step of both kernels, with and without the direction bits, is lev_dev.hpp's (lev_inputs, lev_column,
+// lev_store_bottom); the right arm, the identity and the checks of the list are there too, shared with score.hip.
 #include "index.hpp"
 #include "tool_base.hpp"
 #include "align_dev.hpp"
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_
                                                                     unsigned long long *__restrict__ cursor,
                                                                     uint32_t *__restrict__ distance,
                                                                     float *__restrict__ identity) {
-    constexpr int R = kAlignRows;
+    constexpr int R = kLevRows;
     constexpr uint32_t W = kAlignTile;
     const int lane = threadIdx.x & 63;
     for (;;) {
@@ -66,29 +68,20 @@ __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_
         const AlignShape g = align_shape(sd, bt.inclusive);
         const uint32_t la = (uint32_t)g.n, lb = (uint32_t)g.m;
         const uint8_t *A = text + sd.left;
-        const uint8_t *B = text + sd.right;
-        const uint32_t orient = (uint32_t)__builtin_amdgcn_readfirstlane(bt.flags ? (int)bt.flags[item] : 0);
-        const bool reversed = orient & 1u, complemented = orient & 2u;
-        auto b_at = [&](uint32_t j) -> uint32_t {  // j-th base of the right arm after reverse/complement
-            const uint32_t c = B[reversed ? lb - 1u - j : j];
-            return complemented ? align_complement(c) : c;
-        };
+        const RightArm rb = right_arm(text + sd.right, lb, orientation_of(bt.flags, item, 0, 0));
         uint32_t *colck = ck + bt.ck_off[k];
         uint32_t *rowck = colck + g.col_words();
         const uint64_t row_stride = g.m + 1u;
         uint32_t result = 0;
         uint32_t bi = 0;
-        for (uint32_t band = 0; band < la && lb > 0; band += 64u * R, ++bi) {
+        for (uint32_t band = 0; band < la && lb > 0; band += kLevBand, ++bi) {
             const uint32_t i0 = band + (uint32_t)lane * R;  // rows i0+1 .. i0+R (1-based) are this lane's
-            const bool more_bands = band + 64u * R < la;
+            const bool more_bands = band + kLevBand < la;
             const uint32_t *top_row = bi ? rowck + (uint64_t)(bi - 1u) * row_stride : rowck;  // (read for bi > 0 only)
             uint32_t *bottom_row = rowck + (uint64_t)bi * row_stride;                         // (written if more_bands)
             uint32_t a[R], col[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                a[r] = i0 + r < la ? (uint32_t)A[i0 + r] : 0x100u;  // padding rows match nothing
-                col[r] = i0 + r + 1u;                               // D[i][0] = i
-            }
+            lev_rows(a, i0, la, A);
+            lev_first_column(col, i0);
             uint32_t diag_in = i0;       // D[i0][j-1] for the lane's next column
             uint32_t last_out = 0;       // D[i0+R][j] of the column just done
             uint32_t b_pipe = 0;         // base of the lane's current column (travels down the lanes)
@@ -99,38 +92,14 @@ __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_
                     const uint32_t j1 = s + 1u + (uint32_t)lane;  // column of lane 0 at step s + lane
                     // (written by this wave one band ago: read past the vector L1)
                     top_chunk = band == 0 ? j1 : (j1 <= lb ? __atomic_load_n(&top_row[j1], __ATOMIC_RELAXED) : 0u);
-                    b_chunk = s + (uint32_t)lane < lb ? b_at(s + (uint32_t)lane) : 0u;
+                    b_chunk = s + (uint32_t)lane < lb ? rb.at(s + (uint32_t)lane) : 0u;
                 }
-                // the value above the lane's first row, D[i0][j]: lane l-1 finished column j one step ago
-                uint32_t up_in = __shfl_up(last_out, 1);
-                const uint32_t top0 = __shfl(top_chunk, (int)(s & 63u));
-                uint32_t b_in = __shfl_up(b_pipe, 1);
-                const uint32_t b0 = __shfl(b_chunk, (int)(s & 63u));
-                if (lane == 0) {
-                    up_in = top0;
-                    b_in = b0;
-                }
-                b_pipe = b_in;
+                const LevIn in = lev_inputs(last_out, top_chunk, b_pipe, b_chunk, s, lane);
                 const int64_t j = (int64_t)s - lane + 1;
                 if (j >= 1 && j <= (int64_t)lb) {
-                    uint32_t up = up_in, diag = diag_in;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const uint32_t left = col[r];
-                        const uint32_t v = min(diag + (a[r] != b_in ? 1u : 0u), min(up, left) + 1u);
-                        diag = left;
-                        up = v;
-                        col[r] = v;
-                    }
-                    diag_in = up_in;
+                    lev_column<false>(a, col, diag_in, in);
                     last_out = col[R - 1];
-                    if ((uint32_t)j == lb && la > i0 && la <= i0 + R) {
-                        uint32_t v = 0;
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-                            if (i0 + r + 1u == la) v = col[r];
-                        result = v;
-                    }
+                    if ((uint32_t)j == lb && la > i0 && la <= i0 + R) result = lev_row_value(col, i0, la);
                     // a column checkpoint: the lane's 16 values of column j, 64 contiguous bytes
                     if (((uint32_t)j & (W - 1u)) == 0u && (uint32_t)j < lb) {
                         uint4 *dst = reinterpret_cast<uint4 *>(colck + (uint64_t)((uint32_t)j / W - 1u) * g.rows_padded + i0);
@@ -139,19 +108,7 @@ __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_
                             dst[v4] = make_uint4(col[4 * v4], col[4 * v4 + 1], col[4 * v4 + 2], col[4 * v4 + 3]);
                     }
                 }
-                if (more_bands) {
-                    // lane 63 finishes column jo = s - 62; collect 64 of them, store them together
-                    const uint32_t v63 = __shfl(last_out, 63);
-                    const int64_t jo = (int64_t)s - 62;
-                    if (jo >= 1 && jo <= (int64_t)lb) {
-                        if ((uint32_t)lane == ((uint32_t)jo & 63u)) out_chunk = v63;
-                        if (((uint32_t)jo & 63u) == 63u || (uint32_t)jo == lb) {
-                            const uint32_t jbase = (uint32_t)jo & ~63u;
-                            const uint32_t jw = jbase + (uint32_t)lane;
-                            if (jw >= 1u && jw <= (uint32_t)jo) bottom_row[jw] = out_chunk;
-                        }
-                    }
-                }
+                if (more_bands) lev_store_bottom(last_out, s, lane, lb, out_chunk, bottom_row);
             }
             // the next band reads what this one wrote (same wave: program order; make it visible)
             __threadfence_block();
@@ -160,13 +117,12 @@ __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_
         if (la == 0 || lb == 0) {
             dist = la + lb;  // one arm is empty: the other one, base by base
         } else {
-            const uint32_t owner = ((la - 1u) % (64u * R)) / R;  // lane of row la in the last band
+            const uint32_t owner = ((la - 1u) % kLevBand) / R;  // lane of row la in the last band
             dist = __shfl(result, (int)owner);
         }
         if (lane == 0) {
-            const uint64_t longest = sd.left_length > sd.right_length ? sd.left_length : sd.right_length;
             distance[item] = dist;
-            identity[item] = (float)(100.0 * (1.0 - (double)dist / (double)longest));  // identity_of of score.hip
+            identity[item] = identity_of(sd, dist);
         }
     }
 }
@@ -189,7 +145,7 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
                                                              uint64_t *__restrict__ n_runs,
                                                              unsigned long long *__restrict__ cursor,
                                                              uint32_t *__restrict__ overflow) {
-    constexpr int R = kAlignRows;
+    constexpr int R = kLevRows;
     constexpr uint32_t W = kAlignTile;
     __shared__ uint32_t dirs[kAlignDirWords];  // dirs[c * 64 + lane]: the directions of the lane's 16 rows in column c of the tile
     const int lane = threadIdx.x;
@@ -204,13 +160,7 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
         const AlignShape g = align_shape(sd, bt.inclusive);
         const uint32_t la = (uint32_t)g.n, lb = (uint32_t)g.m;
         const uint8_t *A = text + sd.left;
-        const uint8_t *B = text + sd.right;
-        const uint32_t orient = (uint32_t)__builtin_amdgcn_readfirstlane(bt.flags ? (int)bt.flags[item] : 0);
-        const bool reversed = orient & 1u, complemented = orient & 2u;
-        auto b_at = [&](uint32_t j) -> uint32_t {
-            const uint32_t c = B[reversed ? lb - 1u - j : j];
-            return complemented ? align_complement(c) : c;
-        };
+        const RightArm rb = right_arm(text + sd.right, lb, orientation_of(bt.flags, item, 0, 0));
         const uint32_t *colck = ck + bt.ck_off[k];
         const uint32_t *rowck = colck + g.col_words();
         const uint64_t row_stride = g.m + 1u;
@@ -238,8 +188,8 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
         };
         uint32_t i = la, j = lb;  // the cell the path stands on
         while (i > 0 && j > 0) {
-            const uint32_t b = (i - 1u) / kAlignBand, cb = (j - 1u) / W;
-            const uint32_t band = b * kAlignBand, j0 = cb * W;
+            const uint32_t b = (i - 1u) / kLevBand, cb = (j - 1u) / W;
+            const uint32_t band = b * kLevBand, j0 = cb * W;
             const uint32_t wt = min(W, lb - j0);  // columns j0+1 .. j0+wt
             const uint32_t *top_row = b ? rowck + (uint64_t)(b - 1u) * row_stride : rowck;  // D[band][..] (read for b > 0 only)
             {
@@ -247,8 +197,7 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
                 const uint32_t i0 = band + (uint32_t)lane * R;
                 uint32_t a[R], col[R];
                 if (cb == 0) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r) col[r] = i0 + r + 1u;
+                    lev_first_column(col, i0);
                 } else {
                     const uint4 *src = reinterpret_cast<const uint4 *>(colck + (uint64_t)(cb - 1u) * g.rows_padded + i0);
 #pragma unroll
@@ -260,8 +209,7 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
                         col[4 * v4 + 3] = v.w;
                     }
                 }
-#pragma unroll
-                for (int r = 0; r < R; ++r) a[r] = i0 + r < la ? (uint32_t)A[i0 + r] : 0x100u;
+                lev_rows(a, i0, la, A);
                 // D[i0][j0]: the last seed value of the lane above; for lane 0 the boundary itself
                 uint32_t diag_in = __shfl_up(col[R - 1], 1);
                 if (lane == 0) diag_in = b == 0 ? j0 : (j0 == 0 ? band : top_row[j0]);
@@ -271,35 +219,13 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
                     if ((s & 63u) == 0u) {
                         const uint32_t j1 = j0 + s + 1u + (uint32_t)lane;
                         top_chunk = b == 0 ? j1 : (j1 <= lb ? top_row[j1] : 0u);
-                        b_chunk = j1 <= lb ? b_at(j1 - 1u) : 0u;
+                        b_chunk = j1 <= lb ? rb.at(j1 - 1u) : 0u;
                     }
-                    uint32_t up_in = __shfl_up(last_out, 1);
-                    const uint32_t top0 = __shfl(top_chunk, (int)(s & 63u));
-                    uint32_t b_in = __shfl_up(b_pipe, 1);
-                    const uint32_t b0 = __shfl(b_chunk, (int)(s & 63u));
-                    if (lane == 0) {
-                        up_in = top0;
-                        b_in = b0;
-                    }
-                    b_pipe = b_in;
+                    const LevIn in = lev_inputs(last_out, top_chunk, b_pipe, b_chunk, s, lane);
                     const int32_t c = (int32_t)s - lane;  // column of the tile, 0-based
                     if (c >= 0 && c < (int32_t)wt) {
-                        uint32_t up = up_in, diag = diag_in, bits = 0;
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const uint32_t left = col[r];
-                            const uint32_t cost = a[r] != b_in ? 1u : 0u;
-                            const uint32_t dg = diag + cost;
-                            const uint32_t v = min(dg, min(up, left) + 1u);
-                            const uint32_t d = v == dg ? cost : (v == up + 1u ? (uint32_t)kOpInsert : (uint32_t)kOpDelete);
-                            bits |= d << (2 * r);
-                            diag = left;
-                            up = v;
-                            col[r] = v;
-                        }
-                        diag_in = up_in;
+                        dirs[(uint32_t)c * 64u + (uint32_t)lane] = lev_column<true>(a, col, diag_in, in);
                         last_out = col[R - 1];
-                        dirs[(uint32_t)c * 64u + (uint32_t)lane] = bits;
                     }
                 }
             }
@@ -338,48 +264,6 @@ __global__ __launch_bounds__(kBlock) void align_compact_kernel(const uint64_t *_
     const uint32_t op = slot_op[src];
     out_len[t] = slot_len[src];
     out_op[t] = op == kOpMatch ? '=' : op == kOpMismatch ? 'X' : op == kOpInsert ? 'I' : 'D';
-}
-
-// the checks of check_scores_input and check_flags of score.hip, in the mode's own lengths
-int32_t check_align_input(const char *fn, uint64_t n_text, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
-                          int inclusive) {
-    for (int64_t q = 0; flags && q < n_sd; ++q)
-        if (flags[q] & ~3u) {
-            set_error("%s: duplication %lld has flag byte %u (bit 0 reversed, bit 1 complemented)", fn, (long long)q,
-                      (unsigned)flags[q]);
-            return ASGART_E_ARG;
-        }
-    for (int64_t q = 0; q < n_sd; ++q) {
-        const asgart_proto_sd &sd = sds[q];
-        const uint64_t inc = inclusive ? 1u : 0u;
-        if (sd.left > n_text || sd.right > n_text || sd.left_length + inc < inc || sd.right_length + inc < inc ||
-            sd.left_length + inc > n_text - sd.left || sd.right_length + inc > n_text - sd.right) {
-            set_error("%s: duplication %lld reaches past the end of the text", fn, (long long)q);
-            return ASGART_E_ARG;
-        }
-        if (sd.left_length == 0 && sd.right_length == 0) {
-            set_error("%s: duplication %lld has two empty arms", fn, (long long)q);
-            return ASGART_E_ARG;
-        }
-        if (sd.left_length >= 0xFFFFFFFFull || sd.right_length >= 0xFFFFFFFFull ||
-            sd.left_length + sd.right_length + 2u >= 0xFFFFFFFFull) {
-            set_error("%s: arms of 2^32 bases are not supported", fn);
-            return ASGART_E_CAP;
-        }
-    }
-    return 0;
-}
-
-int32_t check_list_args(const char *fn, const asgart_proto_sd *sds, int64_t n_sd, const void *out) {
-    if (n_sd < 0 || !out || (n_sd > 0 && !sds)) {
-        set_error("%s: bad argument", fn);
-        return ASGART_E_ARG;
-    }
-    if ((uint64_t)n_sd >= 0xFFFFFFFFull) {  // (ordinals are 32-bit)
-        set_error("%s: 2^32 duplications in one call are not supported", fn);
-        return ASGART_E_CAP;
-    }
-    return 0;
 }
 
 }  // namespace
@@ -605,12 +489,13 @@ extern "C" int32_t asgart_align_duplications(asgart_index *idx, const asgart_pro
                                              asgart_alignment **out) {
     const char *fn = "asgart_align_duplications";
     if (out) *out = nullptr;
-    if (!idx) {
+    if (!idx || !out) {  // (the result is made for an empty list too)
         set_error("%s: bad argument", fn);
         return ASGART_E_ARG;
     }
     RC_TRY(check_list_args(fn, sds, n_sd, out));
-    RC_TRY(check_align_input(fn, (uint64_t)idx->n, sds, flags, n_sd, inclusive != 0));
+    RC_TRY(check_flags(fn, flags, n_sd));
+    RC_TRY(check_arms(fn, (uint64_t)idx->n, sds, n_sd, inclusive != 0));
     REFUSE_POISONED(idx);
     HIP_TRY(hipSetDevice(idx->device));
     try {
@@ -662,12 +547,16 @@ extern "C" int32_t asgart_alignment_timings(const asgart_alignment *a, double *m
 extern "C" void asgart_alignment_free(asgart_alignment *a) { delete a; }
 
 extern "C" void asgart_align_geometry(uint64_t *band_rows, uint64_t *lane_rows, uint64_t *tile_cols) {
-    if (band_rows) *band_rows = kAlignBand;
-    if (lane_rows) *lane_rows = kAlignRows;
+    if (band_rows) *band_rows = kLevBand;
+    if (lane_rows) *lane_rows = kLevRows;
     if (tile_cols) *tile_cols = kAlignTile;
 }
 
 extern "C" int32_t asgart_align_bytes(const asgart_proto_sd *sds, int64_t n_sd, int32_t inclusive, uint64_t *bytes) {
+    if (!bytes) {
+        set_error("asgart_align_bytes: bad argument");
+        return ASGART_E_ARG;
+    }
     RC_TRY(check_list_args("asgart_align_bytes", sds, n_sd, bytes));
     for (int64_t q = 0; q < n_sd; ++q) bytes[q] = align_shape(sds[q], inclusive != 0).bytes();
     return 0;

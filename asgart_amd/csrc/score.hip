@@ -10,9 +10,15 @@
 // goes through an HBM scratch row, read and written 64 columns at a time.  Long duplications get a
 // workgroup of 16 waves that walk 16 consecutive bands as a pipeline (see levenshtein_long_kernel).  Integer work, bit-exact by
 // construction; the identity is formed in f64 like the reference and narrowed to f32.
+// The right arm, its orientation, the identity and the host's checks of a list are in lev_dev.hpp, shared with align.hip.
+// That header also states the step below once, for align.hip's two kernels.  The two score kernels keep their own text of
+// it: built on the header's helpers the score call measured 1.0 - 1.5 % slower, outside the parent's spread, although
+// band_steps' loop came out instruction for instruction as before (levenshtein_kernel's, at 95 VGPRs for 93, was not
+// compared; DESIGN_HISTORY.md).
 // The orientation of the right arm is per duplication (asgart_compute_scores_flags*: one flag byte each) or per call
 // (asgart_compute_scores*: the same kernels without a flag array).
 #include "index.hpp"
+#include "lev_dev.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -29,6 +35,8 @@ namespace {
 constexpr int kScoreThreads = 256;  // four duplications per workgroup
 constexpr int kScoreRows = 16;      // rows per lane
 constexpr uint32_t kBand = 64u * kScoreRows;  // rows of one band (a wave's 64 lanes)
+// (lev_dev.hpp states the same geometry for align.hip)
+static_assert(kScoreRows == kLevRows && kBand == kLevBand, "score.hip and lev_dev.hpp disagree on the band");
 constexpr int kLongWaves = 16;                // waves of levenshtein_long_kernel's workgroup ...
 constexpr int kLongRows = kLongWaves + 2;     // ... and the boundary rows it has in flight
 // A duplication whose left arm has at least half a workgroup's bands goes to levenshtein_long_kernel, the rest to
@@ -43,40 +51,6 @@ __host__ __device__ inline uint32_t long_chunk_steps(uint64_t n_steps) {
     uint32_t C = (uint32_t)((n_steps + 2u * kLongWaves - 1u) / (2u * kLongWaves));
     C = (C + 63u) & ~63u;
     return C > 128u ? C : 128u;
-}
-
-// utils::complement_nucleotide / structs::TR on the normalised alphabet; anything else is kept
-__device__ inline uint32_t complement_base(uint32_t c) {
-    switch (c) {
-    case 'A': return 'T';
-    case 'T': return 'A';
-    case 'G': return 'C';
-    case 'C': return 'G';
-    case 'a': return 't';
-    case 't': return 'a';
-    case 'g': return 'c';
-    case 'c': return 'g';
-    default: return c;
-    }
-}
-
-// the right arm as the DP walks it: reversed / complemented first (src/structs.rs:443-448)
-struct RightArm {
-    const uint8_t *B;
-    uint32_t lb;
-    int reversed, complemented;
-    __device__ uint32_t at(uint32_t j) const {
-        const uint32_t c = B[reversed ? lb - 1u - j : j];
-        return complemented ? complement_base(c) : c;
-    }
-};
-
-// The orientation of duplication `item`: its flag byte (bit 0 reversed, bit 1 complemented, the encoding of
-// asgart_extract_sequences) or, without a flag array, the call's two constants.  `item` is the same in every lane of
-// the wave that picked the duplication up, so the byte is read once and kept in a scalar register.
-__device__ inline uint32_t orientation_of(const uint8_t *flags, uint32_t item, int reversed, int complemented) {
-    const uint32_t f = flags ? (uint32_t)flags[item] : (reversed ? 1u : 0u) | (complemented ? 2u : 0u);
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)f);
 }
 
 // one lane's share of a band of 64 x R rows
@@ -159,11 +133,6 @@ __device__ inline void band_steps(BandState &st, uint32_t s_lo, uint32_t s_hi, u
             }
         }
     }
-}
-
-__device__ inline float identity_of(const asgart_proto_sd &sd, uint32_t dist) {
-    const uint64_t longest = sd.left_length > sd.right_length ? sd.left_length : sd.right_length;
-    return (float)(100.0 * (1.0 - (double)dist / (double)longest));  // src/structs.rs:451, then `as f32`
 }
 
 // ---- one wave per duplication: the bulk (the band loop written out: the shared band_steps form of
@@ -348,12 +317,6 @@ __global__ __launch_bounds__(256) void gather_owned_kernel(const asgart_proto_sd
     }
 }
 
-// the kernels count rows, columns and distances in 32 bits
-bool arms_too_long(const asgart_proto_sd &sd) {
-    return sd.left_length >= 0xFFFFFFFFull || sd.right_length >= 0xFFFFFFFFull ||
-           sd.left_length + sd.right_length + 2u >= 0xFFFFFFFFull;
-}
-
 // What one duplication costs the device, in wave-steps (a step: one column of a band, 64 lanes x kScoreRows cells), the
 // way the kernels dispatch it.  Short: one wave walks ceil(la / kBand) bands of lb + 63 steps.  Long: kLongWaves waves
 // are held for the 2 (n_bands - 1) + n_chunks chunks of C steps of the band pipeline, its fill and drain included.
@@ -390,41 +353,17 @@ void score_owners(const asgart_proto_sd *sds, int64_t n_sd, int32_t n_shards, in
     }
 }
 
-// the reference slices [p ..= p + len] and panics past the end of the strand
-int32_t check_scores_input(const char *fn, const asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd) {
-    const uint64_t n = (uint64_t)idx->n;
-    for (int64_t q = 0; q < n_sd; ++q) {
-        const asgart_proto_sd &sd = sds[q];
-        if (sd.left > n || sd.left_length >= n - sd.left || sd.right > n || sd.right_length >= n - sd.right) {
-            set_error("%s: duplication %lld reaches past the end of the text", fn, (long long)q);
-            return ASGART_E_ARG;
-        }
-        if (sd.left_length == 0 && sd.right_length == 0) {
-            set_error("%s: duplication %lld has two empty arms", fn, (long long)q);
-            return ASGART_E_ARG;
-        }
-        if (arms_too_long(sd)) {
-            set_error("%s: arms of 2^32 bases are not supported", fn);
-            return ASGART_E_CAP;
-        }
-    }
-    return 0;
-}
-
 // The orientations of one call: a flag byte per duplication (bit 0 reversed, bit 1 complemented), or one pair for all.
 struct Orientations {
     const uint8_t *flags;  // host, one per duplication of the call's list; NULL: the two constants below
     int32_t reversed, complemented;
 };
 
-int32_t check_flags(const char *fn, const uint8_t *flags, int64_t n_sd) {
-    for (int64_t q = 0; flags && q < n_sd; ++q)
-        if (flags[q] & ~3u) {
-            set_error("%s: duplication %lld has flag byte %u (bit 0 reversed, bit 1 complemented)", fn, (long long)q,
-                      (unsigned)flags[q]);
-            return ASGART_E_ARG;
-        }
-    return 0;
+// what every entry point checks of a non-empty list, the flag bytes first (the score's ranges are inclusive)
+int32_t check_scores_input(const char *fn, const asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
+                           const Orientations &o) {
+    RC_TRY(check_flags(fn, o.flags, n_sd));
+    return check_arms(fn, (uint64_t)idx->n, sds, n_sd, 1);
 }
 
 // Long duplications (many bands) get a whole workgroup each, the rest one wave each; both lists are served largest first.
@@ -484,14 +423,19 @@ int32_t score_launch(const asgart_index *idx, Workspace &w, hipStream_t s, const
     return 0;
 }
 
-// Scores the duplications q with owner[q] == shard (owner NULL: all of them) on one of idx's call contexts; writes
-// identity[q] for those only.  Returns how many, < 0 on error.  The full list goes to the device once and the owned
-// ones are gathered there.
-int64_t score_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd, const int32_t *owner, int32_t shard,
-                    const Orientations &o, float *identity) {
+// the ordinals q with owner[q] == shard, ascending
+std::vector<uint32_t> owned_by(const int32_t *owner, int64_t n_sd, int32_t shard) {
     std::vector<uint32_t> mine;
     for (int64_t q = 0; q < n_sd; ++q)
         if (owner[q] == shard) mine.push_back((uint32_t)q);
+    return mine;
+}
+
+// Scores the duplications `mine` (distinct ordinals into sds) on one of idx's call contexts; writes identity[q] for those
+// only.  Returns how many, < 0 on error.  The full list goes to the device once.  A part of it is gathered there; the whole
+// list needs no gather: the kernels walk it where it lies and the identities are read back straight into the caller's array.
+int64_t score_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd, std::vector<uint32_t> mine,
+                    const Orientations &o, float *identity) {
     if (mine.empty()) return 0;
     REFUSE_POISONED(idx);
     HIP_TRY(hipSetDevice(idx->device));
@@ -504,13 +448,14 @@ int64_t score_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
     } unlock{idx, which};
     Workspace &w = cx.ws;
     hipStream_t s = cx.stream;
-    const ScorePlan p = score_plan(sds, mine);
+    const ScorePlan p = score_plan(sds, std::move(mine));
     std::vector<uint32_t> owned(p.long_list);  // the schedule, as ordinals into the full list
     owned.insert(owned.end(), p.wave_list.begin(), p.wave_list.end());
     const size_t m = owned.size();
-    // the buffers score_all uses: out_a = full list, then the gathered one; seg_vals = list, then ordinals, then the
-    // flag bytes of the full list and of the gathered one
-    RC_TRY(w.out_a.reserve(((size_t)n_sd + m) * sizeof(asgart_proto_sd)));
+    const bool whole = m == (size_t)n_sd;
+    // out_a = full list, then the gathered one; seg_vals = the kernels' list, then the ordinals to gather, then the flag
+    // bytes of the full list and of the gathered one
+    RC_TRY(w.out_a.reserve(((size_t)n_sd + (whole ? 0 : m)) * sizeof(asgart_proto_sd)));
     RC_TRY(w.seg_vals.reserve(m * 8 + (size_t)n_sd + m + 64));
     RC_TRY(w.out_b.reserve(m * sizeof(float) + 64));
     RC_TRY(score_reserve(w, p));
@@ -520,7 +465,13 @@ int64_t score_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
     uint8_t *d_flags = o.flags ? (uint8_t *)(d_owned + m) : nullptr, *d_sub_flags = o.flags ? d_flags + n_sd : nullptr;
     HIP_TRY(hipMemcpyAsync(w.out_a.p, sds, (size_t)n_sd * sizeof(asgart_proto_sd), hipMemcpyHostToDevice, s));
     if (o.flags) HIP_TRY(hipMemcpyAsync(d_flags, o.flags, (size_t)n_sd, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_owned, owned.data(), m * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(whole ? d_list : d_owned, owned.data(), m * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(stream_sync(s));  // (pageable host sources, `owned` among them: no copy is in flight at a return below)
+    if (whole) {  // the schedule is the kernels' list, and identity[q] is entry q of what they write
+        RC_TRY(score_launch(idx, w, s, p, d_sds, d_list, d_flags, o, w.out_b.as<float>()));
+        HIP_TRY(read_back(identity, w.out_b.p, m * sizeof(float), s));
+        return (int64_t)m;
+    }
     const unsigned grid_g = (unsigned)std::min<size_t>((m + 255) / 256, 1024);
     gather_owned_kernel<<<grid_g, 256, 0, s>>>(d_sds, d_flags, d_owned, (uint64_t)m, d_sub, d_sub_flags, d_list);
     HIP_TRY(hipGetLastError());
@@ -532,19 +483,13 @@ int64_t score_shard(asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd,
 }
 
 int32_t check_shard_args(const char *fn, const asgart_proto_sd *sds, int64_t n_sd, int32_t n_shards, const void *out) {
-    if (n_sd < 0 || (n_sd > 0 && (!sds || !out))) {
-        set_error("%s: bad argument", fn);
-        return ASGART_E_ARG;
-    }
+    RC_TRY(check_list_pointers(fn, sds, n_sd, out));
     if (n_shards < 1) {
         set_error("%s: %d shards (at least 1)", fn, n_shards);
         return ASGART_E_ARG;
     }
-    if ((uint64_t)n_sd >= 0xFFFFFFFFull) {  // (ordinals are 32-bit)
-        set_error("%s: 2^32 duplications in one call are not supported", fn);
-        return ASGART_E_CAP;
-    }
-    for (int64_t q = 0; q < n_sd; ++q)
+    RC_TRY(check_list_count(fn, n_sd));
+    for (int64_t q = 0; q < n_sd; ++q)  // (before the bounds of any duplication: the cost model needs no text)
         if (arms_too_long(sds[q])) {
             set_error("%s: arms of 2^32 bases are not supported", fn);
             return ASGART_E_CAP;
@@ -555,44 +500,22 @@ int32_t check_shard_args(const char *fn, const asgart_proto_sd *sds, int64_t n_s
 // asgart_compute_scores[_flags]: the whole list on one call context
 int32_t score_all(const char *fn, asgart_index *idx, const asgart_proto_sd *sds, int64_t n_sd, const Orientations &o,
                   float *identity) {
-    if (!idx || n_sd < 0 || (n_sd > 0 && (!sds || !identity))) {
+    if (!idx) {
         set_error("%s: bad argument", fn);
         return ASGART_E_ARG;
     }
+    RC_TRY(check_list_pointers(fn, sds, n_sd, identity));
     if (n_sd == 0) return 0;
-    RC_TRY(check_flags(fn, o.flags, n_sd));
-    RC_TRY(check_scores_input(fn, idx, sds, n_sd));
-    REFUSE_POISONED(idx);
-    HIP_TRY(hipSetDevice(idx->device));
-    int which = 0;
-    SearchCtx &cx = idx->acquire_one(&which);
-    struct Unlock {
-        asgart_index *i;
-        int w;
-        ~Unlock() { i->release_one(w); }
-    } unlock{idx, which};
-    Workspace &w = cx.ws;
-    hipStream_t s = cx.stream;
-    std::vector<uint32_t> all((size_t)n_sd);
-    for (int64_t q = 0; q < n_sd; ++q) all[(size_t)q] = (uint32_t)q;
-    const ScorePlan p = score_plan(sds, std::move(all));
-    RC_TRY(w.out_a.reserve((size_t)n_sd * sizeof(asgart_proto_sd)));
-    RC_TRY(w.out_b.reserve((size_t)n_sd * sizeof(float) + 64));
-    RC_TRY(w.seg_vals.reserve((size_t)n_sd * 5 + 64));  // the list, then the flag bytes
-    RC_TRY(score_reserve(w, p));
-    uint32_t *d_list = w.seg_vals.as<uint32_t>();
-    uint8_t *d_flags = o.flags ? (uint8_t *)(d_list + n_sd) : nullptr;
-    HIP_TRY(hipMemcpyAsync(w.out_a.p, sds, (size_t)n_sd * sizeof(asgart_proto_sd), hipMemcpyHostToDevice, s));
-    if (o.flags) HIP_TRY(hipMemcpyAsync(d_flags, o.flags, (size_t)n_sd, hipMemcpyHostToDevice, s));
-    if (!p.long_list.empty())
-        HIP_TRY(hipMemcpyAsync(d_list, p.long_list.data(), p.long_list.size() * 4, hipMemcpyHostToDevice, s));
-    if (!p.wave_list.empty())
-        HIP_TRY(hipMemcpyAsync(d_list + p.long_list.size(), p.wave_list.data(), p.wave_list.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(stream_sync(s));  // (pageable host sources)
-    RC_TRY(score_launch(idx, w, s, p, w.out_a.as<asgart_proto_sd>(), d_list, d_flags, o, w.out_b.as<float>()));
-    HIP_TRY(read_back(identity, w.out_b.p, (size_t)n_sd * sizeof(float), s));
-    HIP_TRY(stream_sync(s));
-    return 0;
+    RC_TRY(check_scores_input(fn, idx, sds, n_sd, o));
+    try {
+        std::vector<uint32_t> all((size_t)n_sd);
+        for (int64_t q = 0; q < n_sd; ++q) all[(size_t)q] = (uint32_t)q;
+        const int64_t rc = score_shard(idx, sds, n_sd, std::move(all), o, identity);
+        return rc < 0 ? (int32_t)rc : 0;
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", fn);
+        return ASGART_E_OOM;
+    }
 }
 
 }  // namespace
@@ -641,12 +564,11 @@ static int64_t score_one_shard(const char *fn, asgart_index *idx, const asgart_p
         return ASGART_E_ARG;
     }
     if (n_sd == 0) return 0;
-    RC_TRY(check_flags(fn, o.flags, n_sd));          // the whole list: every rank fails alike
-    RC_TRY(check_scores_input(fn, idx, sds, n_sd));
+    RC_TRY(check_scores_input(fn, idx, sds, n_sd, o));  // the whole list: every rank fails alike
     try {
         std::vector<int32_t> owner((size_t)n_sd);
         score_owners(sds, n_sd, n_shards, owner.data());
-        return score_shard(idx, sds, n_sd, owner.data(), shard, o, identity);
+        return score_shard(idx, sds, n_sd, owned_by(owner.data(), n_sd, shard), o, identity);
     } catch (const std::bad_alloc &) {
         set_error("%s: out of host memory", fn);
         return ASGART_E_OOM;
@@ -680,8 +602,7 @@ static int32_t score_devices(const char *fn, asgart_index *const *indices, int32
         }
     RC_TRY(check_shard_args(fn, sds, n_sd, n_devices, identity));
     if (n_sd == 0) return 0;
-    RC_TRY(check_flags(fn, o.flags, n_sd));
-    RC_TRY(check_scores_input(fn, indices[0], sds, n_sd));
+    RC_TRY(check_scores_input(fn, indices[0], sds, n_sd, o));
     try {
         std::vector<int32_t> owner((size_t)n_sd);
         score_owners(sds, n_sd, n_devices, owner.data());
@@ -692,7 +613,7 @@ static int32_t score_devices(const char *fn, asgart_index *const *indices, int32
         for (int32_t r = 0; r < n_devices; ++r)
             workers.emplace_back([&, r]() {
                 try {
-                    rcs[r] = score_shard(indices[r], sds, n_sd, owner.data(), r, o, identity);
+                    rcs[r] = score_shard(indices[r], sds, n_sd, owned_by(owner.data(), n_sd, r), o, identity);
                     if (rcs[r] < 0) errs[r] = asgart_last_error();  // the message is thread-local
                 } catch (const std::bad_alloc &) {
                     rcs[r] = ASGART_E_OOM;
