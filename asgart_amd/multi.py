@@ -10,15 +10,18 @@ in the CPU tests and on one-GPU boxes):
   gather_families   the small per-shard lists to one rank, merged there (section 8e (2)).
 `--compute-score` splits the same way, by duplication (asgart_score_owners: cost-balanced, the same on every rank):
 compute_scores gathers the (input ordinal, identity) pairs of every rank and puts them back in input order.
-search_duplications is a whole run on N ranks, FASTA files to the RunResult JSON text; `python -m asgart_amd.multi
---gpus N files...` starts the ranks and writes the reference's output file.  search_orientations is a run over a list
-of orientations with everything built once (`--orientations direct,RC [--merged NAME]`): one file per orientation, each
-the bytes of its own run, and the merged result asgart-slice makes of them.
+A whole run on N ranks, FASTA files to result texts, is ONE driver (_run) over a list of orientations; the two entry
+points vet their arguments, call it and write what rank 0 gets back.  search_duplications is the run with one
+orientation, to the RunResult JSON text (or a sliced one, or GFF); `python -m asgart_amd.multi --gpus N files...` starts
+the ranks and writes the reference's output file.  search_orientations is the run with up to four
+(`--orientations direct,RC [--merged NAME]`): one file per orientation, each the bytes of its own run, and the merged
+result asgart-slice makes of them.
 """
 from __future__ import annotations
 
 import os
 import sys
+from collections import namedtuple
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -309,11 +312,6 @@ def _paf_text(fam_offs, sds, flags, strand, aln, writer: Optional[str], device_i
     return paf_text(fam_offs, sds, flags, strand, aln)
 
 
-def _paf_rows(index, strand, fam_offs, sds, flags, writer: Optional[str], device_index: int) -> str:
-    """Rank 0, while the index is alive: the duplications aligned with exact ranges (Index.align) as PAF text."""
-    return _paf_text(fam_offs, sds, flags, strand, index.align(sds, flags, inclusive=False), writer, device_index)
-
-
 def _slice_run(post, strand, settings, slice_options, device_index: int):
     """Rank 0, behind post_process: the result as arrays (what its JSON file would parse to), sliced on the GPU.
     -> (the sliced ResultArrays, the surviving duplications in the run's own coordinates: what is scored and extracted)."""
@@ -324,113 +322,165 @@ def _slice_run(post, strand, settings, slice_options, device_index: int):
     return cut, np.ascontiguousarray(arrays.sds[keys])
 
 
-def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
-                        prefix: str = "", with_sequences: bool = False, reader: Optional[str] = None,
-                        slice_options=None, fmt: str = "json", writer: Optional[str] = None,
-                        paf: bool = False) -> Optional[Tuple[str, str]]:
-    """A whole `asgart` run (reference src/bin/asgart.rs:731-822) on the ranks of `dist`, rank r on GPU device_index:
-    rank 0 prepares the input and builds the index, replicate_index copies it to every rank, each rank runs its shard of
-    the search (asgart_search_duplications_passes_shard), gather_families merges the families on rank 0, rank 0 runs the
-    steps behind the search (Index.post_process), the surviving duplications go to every rank, which score their share
-    (compute_scores) with compute_score.  Returns, on rank 0, (JSON text, output file name) -- the text is byte-equal to
-    postprocess.to_json(postprocess.search_duplications(files, settings, device, compute_score)) on one GPU, the name
-    postprocess.out_filename(files, settings, prefix) -- and None on the other ranks.  With world size 1 this is the
-    single-GPU driver.  `--trim` needs world size 1 (a trimmed index is not replicated).  with_sequences: rank 0 also
-    fills left_seq / right_seq from the raw records it read (asgart_amd.Source on its GPU): the text `asgart` followed by
-    `asgart-extract -I` gives (extract.result_text), without its trailing newline.  reader: "device" (the default
-    without --trim) reads the files on rank 0's GPU (prep.read_fasta_gpu: index and Source from one upload), "host" with
-    prep.read_records as before; the text is the same either way.
-    slice_options (slice.SliceOptions) / fmt ("json", "gff2", "gff3"): the run followed by `asgart-slice` with those
-    options and that format, in one go.  No filter of asgart-slice looks at `identity`, so slicing commutes with scoring:
-    rank 0 slices the result on its GPU right behind post_process (slice.apply_arrays), and only the survivors -- in
-    their original coordinates, by the slice's keys -- are broadcast, scored and extracted.  The text is then what
-    `python -m asgart_amd.slice -f FMT OPTIONS` writes for the unsliced run's file (JSON with its trailing newline) and
-    the name is out_filename with the format's extension.  With no active option and "json" nothing changes: the same
-    path through the code, the same bytes.  dist None: one process, one GPU, no collective.
-    writer: "device" (what None means, see DEFAULT_WRITER) writes the file on rank 0's GPU (postprocess.to_json_arrays_gpu,
-    slice.export_arrays_gpu: asgart_export_records), "host" with the array exporters one format operation per duplication;
-    the text is the same either way.  Sequences are out of scope for the device writer: with_sequences takes the host
-    exporter.
-    paf: the surviving duplications -- the ones compute_score scores -- are also aligned (Index.align with exact ranges)
-    and the return value gains a third entry, the text of the PAF file, written as `writer` asks (align.paf_text_gpu or
-    align.paf_text; None: by the number of runs, PAF_DEVICE_MIN_RUNS; with_sequences does not send it to the host, a PAF
-    row holds no sequence).  One rank only; see _check_paf."""
-    from . import orientation_flags
-    from .postprocess import _to_json_arrays_device, out_filename, to_json_arrays
+# What _run leaves on rank 0, all of it on the host.  A _Part is one orientation: its RunSettings, the family offsets of its
+# file (behind post_process, or those of `cut`), the sliced slice.ResultArrays (None: not sliced) and the range of its
+# duplications, survivors[lo:hi].  survivors (n, 4) uint64 and flags uint8[n] hold the parts' duplications one behind the
+# other; ident float32[n], seqs (left, right) and aln (Alignments) are None unless the run was asked for them.
+_Part = namedtuple("_Part", "settings offs cut lo hi")
+_Run = namedtuple("_Run", "files device_index strand parts survivors flags ident seqs aln")
+
+
+def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool, with_sequences: bool, reader: str,
+         paf: bool, sliced: bool = False, slice_options=None) -> Optional[_Run]:
+    """The run protocol, once: a whole `asgart` run (reference src/bin/asgart.rs:731-822) for each of the one to four
+    RunSettings `sts`, which differ in orientation only, on the ranks of `dist` (None: one process, no collective), rank r
+    on GPU device_index.  The entry points have vetted the arguments.  Built ONCE: rank 0 reads the input and builds the
+    index, every other rank gets a replica; ONE fused search over all settings, each rank its shard.  Then per orientation
+    in the given order, as the reference runs them per invocation (families of different orientations are never reduced
+    against each other): the families are merged on rank 0, which runs the steps behind the search and, `sliced` (only the
+    single-run entry passes it and slice_options), slices the result on its GPU right there: no filter of asgart-slice looks
+    at `identity`, so slicing commutes with scoring.  What is left of all orientations -- the survivors, a sliced run's in
+    its original coordinates -- is one list with a flag byte each: with compute_score it is broadcast once and every rank
+    scores its share; with_sequences is one extraction from the Source of the read (device reader) or the raw records
+    (host reader); paf one alignment with exact ranges.  A slice that is refused (ValueError) is raised behind the
+    collectives, which then run without survivors: the other ranks must not wait in them.
+    -> the _Run on rank 0, None elsewhere; the Source and the index are closed either way."""
+    from . import merge_shards, orientation_flags
 
     world, rank = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
-    if settings.trim is not None and world > 1:
-        raise ValueError("multi.search_duplications: --trim runs on one rank only")
-    reader = _choose_reader(reader, settings)
-    paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
-    writer = _choose_writer(writer, with_sequences)
     comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
-    sliced = _check_slice(slice_options, fmt)
-    _check_paf(paf, world, [(settings.reverse, settings.complement)], slice_options)
     index = strand = records = source = None
     chunks = [None]
     try:
         if rank == 0:
-            strand, chunk_list, index, records, source = _read_input(files, settings, device_index, reader, with_sequences)
+            strand, chunk_list, index, records, source = _read_input(files, sts[0], device_index, reader, with_sequences)
             chunks = [chunk_list]
         if dist is not None:
             dist.broadcast_object_list(chunks, src=0)
         if world > 1:
             index = replicate_index(index, dist, device_index)
-        offs, sds, keys = index.search_duplications_passes(chunks[0], [settings], shard=rank, n_shards=world,
-                                                           with_keys=True)[0]
-        if dist is not None:
-            got = gather_families(offs, sds, dist, comm, keys=keys)
-        else:
-            from . import merge_shards
-
-            got = merge_shards([(offs, sds, keys)])
-        post = index.post_process(*got) if rank == 0 else None
-        cut = failed = None
-        survivors = post[1] if rank == 0 else None
-        if sliced and rank == 0:
-            try:   # (a refusal must not leave the other ranks waiting in the collectives below)
-                cut, survivors = _slice_run(post, strand, settings, slice_options, device_index)
-            except ValueError as e:
-                failed, survivors = e, np.zeros((0, 4), dtype=np.uint64)
+        raw = index.search_duplications_passes(chunks[0], sts, shard=rank, n_shards=world, with_keys=True)
+        parts, kept, failed, n = [], [], None, 0
+        for st, (offs, sds, keys) in zip(sts, raw):
+            got = gather_families(offs, sds, dist, comm, keys=keys) if dist is not None else \
+                merge_shards([(offs, sds, keys)])
+            if rank != 0:
+                continue
+            offs, sds = index.post_process(*got)
+            cut = None
+            if sliced:
+                try:
+                    cut, sds = _slice_run((offs, sds), strand, st, slice_options, device_index)
+                    offs = cut.offs
+                except ValueError as e:
+                    failed, sds = e, sds[:0]
+            parts.append(_Part(st, offs, cut, n, n + len(sds)))
+            kept.append(sds)
+            n += len(sds)
+        survivors = flags = None
+        if rank == 0:
+            survivors = np.concatenate(kept).reshape(-1, 4)
+            flags = np.concatenate([orientation_flags(st.reverse, st.complement, len(k)) for st, k in zip(sts, kept)])
         ident = None
         if compute_score:
-            if dist is not None:
-                kept = _broadcast_array(survivors, dist, comm)
-                ident = compute_scores(index, kept, settings.reverse, settings.complement, dist, comm)
-            else:
-                ident = index.compute_scores(survivors, settings.reverse, settings.complement)
+            # One orientation is scored with its two constants, several with a flag byte per duplication: two device calls
+            # (the second uploads the flags and gathers by them), so a single run does not take the second.
+            one = len(sts) == 1
+            if dist is None:
+                ident = index.compute_scores(survivors, sts[0].reverse, sts[0].complement) if one else \
+                    index.compute_scores_flags_shard(survivors, flags, shard=0, n_shards=1)
+            else:   # the duplications travel as one (n, 4) array, with their flag bytes as one (n, 5) array
+                both = None
+                if rank == 0:
+                    both = survivors if one else np.column_stack([survivors, flags.astype(np.uint64)])
+                both = _broadcast_array(both, dist, comm, cols=4 if one else 5)
+                ident = compute_scores(index, both[:, :4], sts[0].reverse, sts[0].complement, dist, comm,
+                                       flags=None if one else both[:, 4].astype(np.uint8))
         if failed is not None:
             raise failed
         if rank != 0:
             return None
-        seqs = None
-        if with_sequences:
-            seqs = _sequences(source, records, device_index, survivors, settings.reverse, settings.complement)
-        name = out_filename(files, settings, prefix)
-        extra = ()
-        if paf:
-            extra = (_paf_rows(index, strand, cut.offs if sliced else post[0], survivors,
-                               orientation_flags(settings.reverse, settings.complement, len(survivors)), paf_writer,
-                               device_index),)
-        if not sliced:
-            if writer == "device":
-                return (_decode(_to_json_arrays_device(post[0], post[1], strand, settings, ident, None, device_index)),
-                        name) + extra
-            return (to_json_arrays(post[0], post[1], strand, settings, ident, seqs), name) + extra
-        from .slice import _export_arrays_device, export_arrays
-
-        if ident is not None:
-            cut.identity = np.ascontiguousarray(ident, dtype=np.float32)
-        cut.seqs = seqs
-        if writer == "device":
-            return (_decode(_export_arrays_device(cut, fmt, device_index)), os.path.splitext(name)[0] + "." + fmt) + extra
-        return (export_arrays(cut, fmt), os.path.splitext(name)[0] + "." + fmt) + extra
+        seqs = _sequences(source, records, device_index, survivors, (flags & 1).astype(bool),
+                          (flags >> 1 & 1).astype(bool)) if with_sequences else None
+        aln = index.align(survivors, flags, inclusive=False) if paf else None
+        return _Run(files, device_index, strand, parts, survivors, flags, ident, seqs, aln)
     finally:
         if source is not None:
             source.close()
         if index is not None:
             index.close()
+
+
+def _json_text(run: _Run, offs, lo: int, hi: int, settings, writer: str, flags=None) -> str:
+    """The unsliced JSON file of survivors[lo:hi] of a run as the families `offs`, written on rank 0's GPU
+    (asgart_export_records) or, "host", one format operation per duplication.  flags: for a file of several orientations."""
+    from .postprocess import _to_json_arrays_device, to_json_arrays
+
+    sds = run.survivors[lo:hi]
+    ident = None if run.ident is None else run.ident[lo:hi]
+    if writer == "device":
+        return _decode(_to_json_arrays_device(offs, sds, run.strand, settings, ident, flags, run.device_index))
+    seqs = None if run.seqs is None else (run.seqs[0][lo:hi], run.seqs[1][lo:hi])
+    return to_json_arrays(offs, sds, run.strand, settings, ident, seqs, flags)
+
+
+def _texts(run: _Run, part: _Part, prefix: str, writer: str, paf_writer: Optional[str], fmt: str = "json") -> tuple:
+    """One orientation's entry of what the entry points return: (the text of its result file, the file's name[, the text of
+    its PAF file]).  writer: what _choose_writer gave; paf_writer: the `writer` argument as it was asked for, None decides
+    by the run count of this orientation's own alignments.  fmt: of a sliced part, whose file is named after it."""
+    from .postprocess import out_filename
+
+    st, offs, cut, lo, hi = part
+    name = out_filename(run.files, st, prefix)
+    if cut is None:
+        text = _json_text(run, offs, lo, hi, st, writer)
+    else:
+        from .slice import _export_arrays_device, export_arrays
+
+        if run.ident is not None:
+            cut.identity = np.ascontiguousarray(run.ident[lo:hi], dtype=np.float32)
+        if run.seqs is not None:
+            cut.seqs = (run.seqs[0][lo:hi], run.seqs[1][lo:hi])
+        name = os.path.splitext(name)[0] + "." + fmt
+        text = _decode(_export_arrays_device(cut, fmt, run.device_index)) if writer == "device" else export_arrays(cut, fmt)
+    if run.aln is None:
+        return text, name
+    return text, name, _paf_text(offs, run.survivors[lo:hi], run.flags[lo:hi], run.strand, run.aln.part(lo, hi), paf_writer,
+                                 run.device_index)
+
+
+def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
+                        prefix: str = "", with_sequences: bool = False, reader: Optional[str] = None,
+                        slice_options=None, fmt: str = "json", writer: Optional[str] = None,
+                        paf: bool = False) -> Optional[Tuple[str, str]]:
+    """A whole `asgart` run on the ranks of `dist`, rank r on GPU device_index: _run with this one orientation (dist None:
+    one process, one GPU; with world size 1 this is the single-GPU driver).  Returns, on rank 0, (JSON text, output file
+    name) -- the text is byte-equal to postprocess.to_json(postprocess.search_duplications(files, settings, device,
+    compute_score)) on one GPU, the name postprocess.out_filename(files, settings, prefix) -- and None on the other ranks.
+    `--trim` needs world size 1 (a trimmed index is not replicated).  with_sequences: left_seq / right_seq are filled,
+    the text `asgart` followed by `asgart-extract -I` gives (extract.result_text), without its trailing newline.
+    reader: "device" (the default without --trim) reads the files on rank 0's GPU (prep.read_fasta_gpu: index and Source
+    from one upload), "host" with prep.read_records; the text is the same either way.
+    slice_options (slice.SliceOptions) / fmt ("json", "gff2", "gff3"): the run followed by `asgart-slice` with those
+    options and that format, in one go.  The text is then what `python -m asgart_amd.slice -f FMT OPTIONS` writes for the
+    unsliced run's file (JSON with its trailing newline) and the name is out_filename with the format's extension.  With no
+    active option and "json" nothing changes: the same path through the code, the same bytes.
+    writer: "device" (what None means, see DEFAULT_WRITER) writes the file on rank 0's GPU, "host" with the array
+    exporters; the text is the same either way.  with_sequences takes the host exporter: the device writer writes none.
+    paf: the surviving duplications -- the ones compute_score scores -- are also aligned and the return value gains a
+    third entry, the text of the PAF file, written as `writer` asks (align.paf_text_gpu or align.paf_text; None: by the
+    number of runs, PAF_DEVICE_MIN_RUNS; with_sequences does not matter, a PAF row holds no sequence).  One rank only; see
+    _check_paf."""
+    world = dist.get_world_size() if dist is not None else 1
+    if settings.trim is not None and world > 1:
+        raise ValueError("multi.search_duplications: --trim runs on one rank only")
+    reader = _choose_reader(reader, settings)
+    paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
+    writer = _choose_writer(writer, with_sequences)
+    sliced = _check_slice(slice_options, fmt)
+    _check_paf(paf, world, [(settings.reverse, settings.complement)], slice_options)
+    run = _run(files, [settings], dist, device_index, compute_score, with_sequences, reader, paf, sliced, slice_options)
+    return None if run is None else _texts(run, run.parts[0], prefix, writer, paf_writer, fmt)
 
 
 def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool, bool]], settings, dist,
@@ -438,98 +488,34 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
                         with_sequences: bool = False, reader: Optional[str] = None, writer: Optional[str] = None,
                         paf: bool = False):
     """One run over several orientations of one strand -- what the reference needs one `asgart` invocation per
-    orientation and an `asgart-slice` merge for.  orientations: one to four distinct (reverse, complement) pairs in the
-    user's order; `settings` supplies everything else (its own two flags are ignored).  Built ONCE: the records read and
-    prepared, the index, its replicas; ONE fused search over the settings of every orientation
-    (asgart_search_duplications_passes[_shard]); then per orientation, as the reference runs them per invocation (families
-    of different orientations are never reduced against each other), gather_families and, on rank 0, post_process.  With
-    compute_score the survivors of all orientations, concatenated in the given order with their flag bytes, are
-    broadcast once and scored by ONE Index.compute_scores_flags_shard per rank; with_sequences is one Source and one
-    extraction over the same list.  Returns, on rank 0, ([(JSON text, out_filename(files, its settings, prefix)) per
-    orientation], merged JSON text) and None elsewhere: each text is byte-equal to search_duplications with that
-    orientation, the merged one to postprocess.merge_results over those files in that order (RunResult::from_files,
-    reference src/structs.rs:114-141: strand and settings of the first, every duplication with the flags of its own
-    run).  dist None: one process, one GPU, no collective.  `--trim` needs one rank.  reader: as search_duplications.
-    Slicing (search_duplications' slice_options / fmt) is out of scope here: `python -m asgart_amd.slice` does it on the
-    files this writes.  writer: as search_duplications -- every orientation's file and the merged one are written on rank
-    0's GPU unless "host" is asked for or with_sequences is set.
-    paf: every orientation's entry gains a third element, the text of its PAF file (one Index.align over the survivors of
-    all orientations, written as in search_duplications); the merged result gets none.  One rank, direct and RC only; see
-    _check_paf."""
+    orientation and an `asgart-slice` merge for: _run with one RunSettings per orientation.  orientations: one to four
+    distinct (reverse, complement) pairs in the user's order; `settings` supplies everything else (its own two flags are
+    ignored).  Returns, on rank 0, ([search_duplications' return value for each orientation, byte for byte], merged JSON
+    text) and None elsewhere; the merged text is what postprocess.merge_results gives over those files in that order
+    (RunResult::from_files, reference src/structs.rs:114-141: strand and settings of the first, every duplication with the
+    flags of its own run) and is written like the others.  `--trim`, reader, writer, with_sequences, paf (the merged
+    result gets no PAF text; direct and RC only, see _check_paf): as search_duplications.  Slicing is out of scope here:
+    `python -m asgart_amd.slice` does it on the files this writes."""
     from dataclasses import replace
-
-    from . import merge_shards, orientation_flags
-    from .postprocess import _to_json_arrays_device, out_filename, to_json_arrays
 
     orientations = [(bool(r), bool(c)) for r, c in orientations]
     if not 1 <= len(orientations) <= 4 or len(set(orientations)) != len(orientations):
         raise ValueError("multi.search_orientations: one to four distinct (reverse, complement) pairs")
-    sts = [replace(settings, reverse=r, complement=c) for r, c in orientations]
-    world, rank = (dist.get_world_size(), dist.get_rank()) if dist is not None else (1, 0)
+    world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
     _check_paf(paf, world, orientations)
     reader = _choose_reader(reader, settings)
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
-    comm = f"cuda:{device_index}" if dist is not None and dist.get_backend() == "nccl" else None
-    index = strand = records = source = None
-    chunks = [None]
-    try:
-        if rank == 0:
-            strand, chunk_list, index, records, source = _read_input(files, settings, device_index, reader, with_sequences)
-            chunks = [chunk_list]
-        if dist is not None:
-            dist.broadcast_object_list(chunks, src=0)
-        if world > 1:
-            index = replicate_index(index, dist, device_index)
-        raw = index.search_duplications_passes(chunks[0], sts, shard=rank, n_shards=world, with_keys=True)
-        posts = []
-        for offs, sds, keys in raw:
-            got = gather_families(offs, sds, dist, comm, keys=keys) if dist is not None else \
-                merge_shards([(offs, sds, keys)])
-            posts.append(index.post_process(*got) if rank == 0 else None)
-        kept = flags = None
-        if rank == 0:
-            kept = np.concatenate([p[1] for p in posts]).reshape(-1, 4)
-            flags = np.concatenate([orientation_flags(r, c, len(p[1])) for (r, c), p in zip(orientations, posts)])
-        ident = None
-        if compute_score:
-            if dist is not None:   # the duplications and their flag bytes travel as one (n, 5) array
-                both = _broadcast_array(np.column_stack([kept, flags.astype(np.uint64)]) if rank == 0 else None, dist,
-                                        comm, cols=5)
-                ident = compute_scores(index, both[:, :4], False, False, dist, comm, flags=both[:, 4].astype(np.uint8))
-            else:
-                ident = index.compute_scores_flags_shard(kept, flags, shard=0, n_shards=1)
-        if rank != 0:
-            return None
-        seqs = None
-        if with_sequences:
-            seqs = _sequences(source, records, device_index, kept, (flags & 1).astype(bool), (flags >> 1 & 1).astype(bool))
-        def text_of(offs, sds, st, ident_, seqs_, flags_):
-            if writer == "device":
-                return _decode(_to_json_arrays_device(offs, sds, strand, st, ident_, flags_, device_index))
-            return to_json_arrays(offs, sds, strand, st, ident_, seqs_, flags_)
-
-        aln = index.align(kept, flags, inclusive=False) if paf else None
-        out = []
-        lo = 0
-        for st, (offs, sds) in zip(sts, posts):
-            hi = lo + len(sds)
-            part = None if seqs is None else (seqs[0][lo:hi], seqs[1][lo:hi])
-            out.append((text_of(offs, sds, st, None if ident is None else ident[lo:hi], part, None),
-                        out_filename(files, st, prefix)))
-            if paf:
-                out[-1] += (_paf_text(offs, sds, flags[lo:hi], strand, aln.part(lo, hi), paf_writer, device_index),)
-            lo = hi
-        sizes = np.concatenate([np.diff(p[0].astype(np.int64)) for p in posts])
-        all_offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
-        return out, text_of(all_offs, kept, sts[0], ident, seqs, flags)
-    finally:
-        if source is not None:
-            source.close()
-        if index is not None:
-            index.close()
+    sts = [replace(settings, reverse=r, complement=c) for r, c in orientations]
+    run = _run(files, sts, dist, device_index, compute_score, with_sequences, reader, paf)
+    if run is None:
+        return None
+    sizes = np.concatenate([np.diff(p.offs.astype(np.int64)) for p in run.parts])
+    all_offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    return ([_texts(run, p, prefix, writer, paf_writer) for p in run.parts],
+            _json_text(run, all_offs, 0, len(run.survivors), sts[0], writer, run.flags))
 
 
 def _parse(argv):
@@ -676,15 +662,14 @@ def rank_main(argv) -> int:
         settings = RunSettings.from_cli(k=args.probe_size, gap=args.max_gap, min_length=args.min_length,
                                         max_cardinality=args.max_cardinality, reverse=args.reverse,
                                         complement=args.complement, skip_masked=args.skip_masked)
-        reader = "host" if args.host_reader else None
-        writer = "host" if args.host_writer else None
+        asked = dict(compute_score=args.compute_score, prefix=args.prefix, with_sequences=args.with_sequences,
+                     reader="host" if args.host_reader else None, writer="host" if args.host_writer else None, paf=args.paf)
         if args.orientations:
-            out = search_orientations(args.files, args.orientations, settings, dist, device_index, args.compute_score,
-                                      args.prefix, args.with_sequences, reader, writer, args.paf)
+            out = search_orientations(args.files, args.orientations, settings, dist, device_index, **asked)
             texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])
         else:
-            out = search_duplications(args.files, settings, dist, device_index, args.compute_score, args.prefix,
-                                      args.with_sequences, reader, args.slice_options, args.format, writer, args.paf)
+            out = search_duplications(args.files, settings, dist, device_index, slice_options=args.slice_options,
+                                      fmt=args.format, **asked)
             texts = None if out is None else [out]
         for text, name, *paf in texts or []:
             for body, path in [(text, os.path.join(args.out_dir, name))] + \

@@ -209,3 +209,29 @@ def test_sequences_of_a_run_over_orientations(hiplib, tmp_path, monkeypatch):
     singles = [sd for text, _ in per for fam in extract.parse_result(text)["families"] for sd in fam]
     assert [(sd["left_seq"], sd["right_seq"], sd["reversed"]) for sd in both] == \
         [(sd["left_seq"], sd["right_seq"], sd["reversed"]) for sd in singles]
+
+
+@pytest.mark.gpu
+def test_a_list_of_one_orientation_is_the_single_run(hiplib, tmp_path):
+    """The seam between the two entry points of the one driver: search_orientations with a single orientation returns what
+    search_duplications returns for it -- result text, name and PAF text -- and its merge of one file is that file.  In
+    process, with scores and PAF rows, with the default writers and with the host's (the genome of
+    test_gpu_align.test_multi_writes_a_paf_file_per_orientation, which has duplications of both orientations)."""
+    recs = synth.make_genome([90_000, 60_000], seed=41, sd_per_mb=60, sd_len=(1000, 5000), alu_frac=0.03, l1_frac=0.0,
+                             sat_per_record=0, short_n_per_mb=10)
+    files = [str(tmp_path / "g.fa")]
+    _write_fasta(files[0], recs)
+    base = asgart_amd.RunSettings.from_cli(complement=True)          # its own two flags are ignored
+    for tok in ("direct", "RC"):
+        r, c = ORIENTATIONS[tok]
+        st = asgart_amd.RunSettings.from_cli(reverse=r, complement=c)
+        for writer in (None, "host"):
+            per, merged = multi.search_orientations(files, [(r, c)], base, None, 0, compute_score=True, writer=writer,
+                                                    paf=True)
+            want = multi.search_duplications(files, st, None, 0, compute_score=True, writer=writer, paf=True)
+            assert len(want) == 3 and per == [want], (tok, writer)
+            assert want[1] == postprocess.out_filename(files, st) and '"identity": ' in want[0]
+            assert len(want[2].splitlines()) >= 1, tok
+            path = tmp_path / f"{tok}_{writer}.json"
+            path.write_text(per[0][0], encoding="utf-8")
+            assert merged == postprocess.merge_results([str(path)]) == per[0][0], (tok, writer)

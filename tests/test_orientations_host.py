@@ -161,6 +161,51 @@ def test_orientations_on_the_command_line():
             multi._parse(argv)
 
 
+def test_the_two_entry_points_keep_their_signatures_and_vet_before_they_read(tmp_path):
+    """Both are thin functions over one driver: what callers see of them stays, and every refusal comes before a file is
+    opened (the path below does not exist) or a GPU is touched."""
+    import inspect
+
+    def params(fn):
+        return [(p.name, p.default) for p in inspect.signature(fn).parameters.values()]
+
+    none = inspect.Parameter.empty
+    assert params(multi.search_duplications) == [
+        ("files", none), ("settings", none), ("dist", none), ("device_index", none), ("compute_score", False),
+        ("prefix", ""), ("with_sequences", False), ("reader", None), ("slice_options", None), ("fmt", "json"),
+        ("writer", None), ("paf", False)]
+    assert params(multi.search_orientations) == [
+        ("files", none), ("orientations", none), ("settings", none), ("dist", none), ("device_index", none),
+        ("compute_score", False), ("prefix", ""), ("with_sequences", False), ("reader", None), ("writer", None),
+        ("paf", False)]
+
+    class TwoRanks:
+        def get_world_size(self):
+            return 2
+
+        def get_rank(self):
+            return 0
+
+        def get_backend(self):
+            return "gloo"
+
+    files = [str(tmp_path / "absent.fa")]
+    plain, trimmed = RunSettings.from_cli(), RunSettings(trim=(10, 500))
+    direct, rc = (False, False), (True, True)
+    for orientations, settings, dist, paf, text in (
+            ([], plain, None, False, "multi.search_orientations: one to four distinct"),
+            ([direct, rc, (True, False), (False, True), direct], plain, None, False, "one to four distinct"),
+            ([direct, rc, direct], plain, None, False, "one to four distinct"),
+            ([direct], trimmed, TwoRanks(), False, "multi.search_orientations: --trim runs on one rank only"),
+            ([(True, False)], plain, None, True, "--paf: a PAF row has a strand")):
+        with pytest.raises(ValueError, match=text):
+            multi.search_orientations(files, orientations, settings, dist, 0, paf=paf)
+    with pytest.raises(ValueError, match="multi.search_duplications: --trim runs on one rank only"):
+        multi.search_duplications(files, trimmed, TwoRanks(), 0)
+    with pytest.raises(ValueError, match="--paf: a PAF row has a strand"):
+        multi.search_duplications(files, RunSettings.from_cli(reverse=True), None, 0, paf=True)
+
+
 def test_flag_entry_points_are_exported(hiplib):
     names = ("asgart_compute_scores_flags", "asgart_compute_scores_flags_shard", "asgart_compute_scores_flags_multi")
     for name in names:
