@@ -48,7 +48,7 @@ ABI_SYMBOLS = (
     "asgart_fasta_read", "asgart_fasta_counts", "asgart_fasta_copy", "asgart_fasta_read_text", "asgart_fasta_index",
     "asgart_fasta_source", "asgart_fasta_free", "asgart_fasta_timings", "asgart_fasta_geometry",
     "asgart_index_set_tail_up", "asgart_tier_segments", "asgart_tier_profile",
-    "asgart_fill_counts", "asgart_fill_tally", "asgart_ranked_fill_takes",
+    "asgart_fill_counts", "asgart_fill_tally", "asgart_ranked_fill_takes", "asgart_hit_rule",
     "asgart_slice_families", "asgart_slice_counts", "asgart_slice_copy", "asgart_slice_timings", "asgart_slice_free",
     "asgart_plot_filter", "asgart_plot_counts", "asgart_plot_copy", "asgart_plot_timings", "asgart_plot_free",
     "asgart_plot_geometry",
@@ -253,6 +253,9 @@ def load_library() -> C.CDLL:
         L.asgart_fill_tally.restype = C.c_int32
         L.asgart_ranked_fill_takes.argtypes = [C.c_uint64, C.c_uint64, C.c_int32]
         L.asgart_ranked_fill_takes.restype = C.c_int32
+    if hasattr(L, "asgart_hit_rule"):
+        L.asgart_hit_rule.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]
+        L.asgart_hit_rule.restype = None
     if hasattr(L, "asgart_slice_families"):
         L.asgart_slice_families.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp, C.POINTER(vp)]
         L.asgart_slice_families.restype = C.c_int32

@@ -1,5 +1,6 @@
 // device_base.hpp -- what every device header of the pipeline starts from: the tier count, the device counters, the chunk
-// lookup, the LDS barrier, and the wave-level primitives (uniform values, lane reads, DPP scans).
+// lookup, a probe's place (ProbeAt) and the hit filter (HitRule), the LDS barriers, and the wave-level primitives (uniform
+// values, lane reads, DPP scans).
 #pragma once
 
 #include "search_dev.hpp"
@@ -81,11 +82,47 @@ __device__ inline int chunk_of_uniform(const ChunkTable &ch, uint32_t g) {
     return __builtin_amdgcn_readfirstlane(lo);
 }
 
-// hit filter of src/automaton.rs:105-114
-__device__ inline bool keep_hit(uint64_t x, uint64_t i, uint64_t s, uint64_t L, bool reverse) {
-    if (!reverse) return x > i + s;  // implies x != i
-    return x != i && x >= s + L - i;
+// Where a probe lies: probe g of chunk c is the needle offset i = (g - pbase[c] + 1) * step into the chunk text[s, s + L),
+// the needle prepared the way of the chunk's pass (md: bit 1 = reversed, bit 0 = complemented).  The + 1, the stride and
+// the pass's mode are part of the parity argument of DESIGN.md 5.4: every kernel that needs a probe's place takes it from
+// here.  (load_segment, extend_common_dev.hpp, reads the same table for a segment.)
+struct ProbeAt {
+    uint64_t i, s, L;
+    uint32_t md;
+};
+__device__ inline ProbeAt probe_at(const RunParams &rp, int c, uint32_t g) {  // c = chunk_of(rp.ch, g), known to the caller
+    ProbeAt pa;
+    pa.i = (uint64_t)(g - rp.ch.pbase[c] + 1) * (uint64_t)rp.step;
+    pa.s = rp.ch.start[c];
+    pa.L = rp.ch.len[c];
+    pa.md = rp.mode_of(c);
+    return pa;
 }
+__device__ inline ProbeAt probe_at(const RunParams &rp, uint32_t g) { return probe_at(rp, chunk_of(rp.ch, g), g); }
+
+// The text position whose position bit (RunParams::pbits) belongs to the probe: the first base its k-mer covers in the
+// text.  Signed: the idle lanes of a staged tile may ask in front of the text.
+__device__ inline long long probe_bit_pos(const ProbeAt &pa, int k) {
+    return (pa.md & 2u) ? (long long)(pa.s + pa.L - pa.i) - k : (long long)(pa.s + pa.i);
+}
+
+// The hit filter of src/automaton.rs:105-114 -- which occurrences x of a probe's k-mer are kept -- as two numbers:
+//     x is kept  <=>  x >= thr && x != self
+// THIS is the definition every kernel filters by: two numbers travel from a row's owner lane to its wave in four lane
+// reads, and a position-sorted list is bisected at thr.  A direct pass keeps x > i + s, which implies x != i: self = 0
+// lies below every thr there (thr >= 1) and is never met.  A reversed pass keeps x >= s + L - i less the needle offset
+// itself (`m.start != i`: a chunk offset compared with a text position, as the reference does).
+struct HitRule {
+    unsigned long long thr, self;
+    __host__ __device__ inline bool keeps(unsigned long long x) const { return x >= thr && x != self; }
+};
+__host__ __device__ inline HitRule hit_rule(uint64_t i, uint64_t s, uint64_t L, bool reverse) {
+    HitRule h;
+    h.thr = reverse ? s + L - i : i + s + 1u;
+    h.self = reverse ? i : 0ull;
+    return h;
+}
+__device__ inline HitRule hit_rule(const ProbeAt &pa) { return hit_rule(pa.i, pa.s, pa.L, (pa.md & 2u) != 0u); }
 
 // Workgroup barrier for data exchanged through LDS only.  __syncthreads() also waits for the
 // wave's outstanding GLOBAL stores (vmcnt(0)): one record written to HBM would stall every wave
@@ -105,6 +142,20 @@ __device__ inline uint32_t lane_of(uint32_t v, uint32_t l) {
 }
 __device__ inline unsigned long long lane_of(unsigned long long v, uint32_t l) {
     return ((unsigned long long)lane_of((uint32_t)(v >> 32), l) << 32) | lane_of((uint32_t)v, l);
+}
+__device__ inline uint32_t lane_get(uint32_t v, uint32_t l) {  // lane l's v, l per lane (every lane takes part)
+    return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l << 2), (int)v);
+}
+__device__ inline unsigned long long lane_get(unsigned long long v, uint32_t l) {
+    return ((unsigned long long)lane_get((uint32_t)(v >> 32), l) << 32) | lane_get((uint32_t)v, l);
+}
+// a row's hit filter, from its owner lane to the wave
+__device__ inline HitRule lane_of(const HitRule &h, uint32_t l) { return HitRule{lane_of(h.thr, l), lane_of(h.self, l)}; }
+__device__ inline HitRule lane_get(const HitRule &h, uint32_t l) { return HitRule{lane_get(h.thr, l), lane_get(h.self, l)}; }
+__device__ inline void wave_lds_sync() {  // LDS traffic of ONE wave: what its lanes wrote is there for its other lanes
+    __builtin_amdgcn_wave_barrier();
+    __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
 }
 
 // inclusive prefix sum across the 64 lanes of a wave (gfx9 DPP: row shifts + row broadcasts)

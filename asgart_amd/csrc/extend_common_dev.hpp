@@ -2,7 +2,7 @@
 // extend_fast_dev.hpp, extend_k8_dev.hpp): the launch parameters, the record list, the statistics of the persistent
 // workgroups, the arm predicate, and the walk over the probes of a segment -- where a segment ends, the batch of up to
 // 64 probes under the cursor, the next hit-probe of a batch, the record of a retired arm.  The representation of the
-// automaton is described in extend_wave_dev.hpp; plan_ranges_kernel and validate_cuts_kernel (pipeline_dev.hpp) read
+// automaton is described in extend_wave_dev.hpp; plan_ranges_kernel and validate_cuts_kernel (ranges_dev.hpp) read
 // what the runs over ranges leave behind (RangeRun, SplitSeg, kDumpWords).
 #pragma once
 

@@ -653,7 +653,7 @@ static int32_t build_sap_locked(asgart_index *idx, uint64_t k) {
         idx->d_sar = nullptr;
     }
     hipStream_t s = idx->ctx[0].stream;
-    // (kRankMin of pipeline_dev.hpp: rank_count_kernel only consults the list of an interval of more than 256 entries)
+    // (kRankMin of common.hpp: rank_count_kernel, probe_dev.hpp, only consults the list of an interval of more than 256 entries)
     auto build = [&]() {
         return idx->wide ? build_rank_lists_runs<uint64_t>(idx->d_keys, (const uint64_t *)idx->d_sa, n_sa, (uint64_t *)idx->d_sap,
                                                            nullptr, 256u, (int)k, s)

@@ -126,6 +126,8 @@ struct RunParams {
         return lo + (t - w * tw) * tile;
     }
 };
+// the mode of the pass these settings ask for, as RunParams::modes and mode_of_pass hold it
+inline uint32_t mode_of_settings(const asgart_settings &st) { return (st.reverse ? 2u : 0u) | (st.complement ? 1u : 0u); }
 
 // One emitted duplication arm, keyed for the reference's output order (chunk order, discovery order
 // inside the chunk, arm order inside the family).
@@ -326,7 +328,7 @@ struct Options {
                                     // every probe up, the later ones skip the probes that cannot keep a hit; 0: none, every probe is looked
                                     // up (bits already learned are kept, not freed, and serve again when the option returns to 1)
     int64_t barren = 2;             // segments that provably emit nothing are not run at all: 1 = those with too few hit-probes for any arm to
-                                    // reach min_duplication_length (pipeline_dev.hpp: segment_is_barren); 2 = also those whose hits leave
+                                    // reach min_duplication_length (place_dev.hpp: segment_is_barren); 2 = also those whose hits leave
                                     // no run of consecutive occupied position buckets long enough (cluster_barren_kernel: the bursts of
                                     // interspersed repeats); 0 = every segment runs
     int64_t fuse_passes = 1;        // asgart_search_duplications_passes, passes that differ in orientation only: 2 = always as ONE job (one
@@ -347,7 +349,7 @@ struct Options {
     int64_t dense6 = 32;            // segments of ANY length whose arm bound sends them to tier 6 go to tier 3 instead with at least this
                                     // many hits per processed probe on average (0: off)
     int64_t split = 1;              // 1: the long segments of the long-shape tiers run as RANGES side by side (plan_ranges_kernel,
-                                    // pipeline_dev.hpp): every range starts from an empty arm list split_warm probes in front of its cut,
+                                    // ranges_dev.hpp): every range starts from an empty arm list split_warm probes in front of its cut,
                                     // and what it holds AT the cut is compared with what the range before holds there; a segment with a cut
                                     // that differs keeps the ranges up to it and runs the rest as ONE more run (the whole segment again when
                                     // its first cut fails); the index remembers what the segment needs (split_warm_max).  With 32-bit
@@ -379,7 +381,7 @@ struct Options {
     int64_t watchdog_s = 120;       // a search call whose device work makes no progress for this many seconds returns ASGART_E_HIP with the
                                     // last heartbeats of its kernels instead of waiting forever; 0: wait forever
 };
-// The tail rule of the placement (place_tier, pipeline_dev.hpp; the thresholds are TierTable's, pipeline.hip), set with
+// The tail rule of the placement (place_tier, place_dev.hpp; the thresholds are TierTable's, pipeline.hip), set with
 // asgart_index_set_tail_up.  (Not an entry of the option table above.)
 struct TailUp {
     int32_t mode = 1;  // 0: off; 1: on in calls with fewer tier streams than arm-resident tiers that can hold work; 2: always on (tests)

@@ -578,7 +578,7 @@ struct SearchCall {
         for (int p = 0; p < 4; ++p) {
             rp.pbits[p] = nullptr;
             if (p >= n_passes) continue;
-            const int mode = (sts[p].reverse ? 2 : 0) | (sts[p].complement ? 1 : 0);
+            const uint32_t mode = mode_of_settings(sts[p]);
             rp.modes |= (uint32_t)mode << (8 * p);
             rp.pbits[p] = opt.posbits ? idx->d_pbits[mode] : nullptr;
             if (rp.pbits[p] && idx->pbits_uses[mode] == 0) rp.blank |= 1u << p;  // (this call finds them all ones)
@@ -717,7 +717,7 @@ struct SearchCall {
         pp.barren = opt.barren ? 1u : 0u;
         pp.seg_info = nullptr;
         const bool cluster_barren = opt.barren >= 2 && rp.M > (uint64_t)k;
-        // long segments as ranges side by side (option split; plan_ranges_kernel in pipeline_dev.hpp): the long shape of the
+        // long segments as ranges side by side (option split; plan_ranges_kernel in ranges_dev.hpp): the long shape of the
         // one-barrier kernel; also in a sharded call (the segments its window cuts short are left alone: only
         // a segment whose end the placement walk has seen is cut)
         split_on = opt.split >= (sizeof(SlotT) == 4 ? 1 : 2) && arms_kernel && (opt.split_len == 0 || opt.split_len >= 64);
@@ -1763,7 +1763,7 @@ int32_t run_search_passes(asgart_index *idx, const uint64_t *chunks, int64_t n_c
             ready = idx->k == st->probe_size;
             const bool filterable = !(idx->opt.posbits == 0 || idx->trimmed || st->probe_size > (uint64_t)kMaxKey);
             for (int32_t p = 0; p < n_passes && need_blank < 0; ++p) {
-                const int mode = (sts[p].reverse ? 2 : 0) | (sts[p].complement ? 1 : 0);
+                const uint32_t mode = mode_of_settings(sts[p]);
                 if (filterable && ready && !idx->filter_off[mode] && !idx->d_pbits[mode]) need_blank = mode;
             }
             want_sap = !(idx->opt.lazy_aux && (!ready || idx->calls_total == 0)) && !idx->sap_tried;
@@ -1790,7 +1790,7 @@ int32_t run_search_passes(asgart_index *idx, const uint64_t *chunks, int64_t n_c
         std::lock_guard<std::mutex> lk(idx->mu);
         const uint64_t before = idx->calls_total;
         idx->calls_total += (uint64_t)n_passes;
-        for (int32_t p = 0; p < n_passes; ++p) ++idx->pbits_uses[(sts[p].reverse ? 2 : 0) | (sts[p].complement ? 1 : 0)];
+        for (int32_t p = 0; p < n_passes; ++p) ++idx->pbits_uses[mode_of_settings(sts[p])];
         trim_now = idx->opt.cache_calls > 0 && before < (uint64_t)idx->opt.cache_calls && idx->calls_total >= (uint64_t)idx->opt.cache_calls;
     }
     if (trim_now) {  // (option cache_calls: what the index build released goes back to the device now -- behind the caller's back:
@@ -1806,7 +1806,7 @@ int32_t run_search_passes(asgart_index *idx, const uint64_t *chunks, int64_t n_c
         // for the orientation (a call that shared the chip with another one measures longer, and the order must not flip
         // because of that)
         std::lock_guard<std::mutex> lk(idx->mu);
-        double &t = idx->tail_ms[(st->reverse ? 2 : 0) | (st->complement ? 1 : 0)];
+        double &t = idx->tail_ms[mode_of_settings(*st)];
         t = t < 0.0 ? cx.stats.ms_extend : std::min(t, cx.stats.ms_extend);
     }
     idx->release_one(which);
@@ -1989,7 +1989,7 @@ int32_t asgart_search_duplications_passes_shard(asgart_index *idx, const uint64_
         }
         uint64_t modes_sig = 0;
         for (int32_t j = 0; fusable && j < n_passes; ++j)
-            modes_sig = modes_sig * 4u + ((settings[j].reverse ? 2u : 0u) | (settings[j].complement ? 1u : 0u));
+            modes_sig = modes_sig * 4u + mode_of_settings(settings[j]);
         auto same_as_verdict = [&]() {
             const asgart_index::FuseVerdict &v = idx->fuse_verdict;
             return v.n_passes == n_passes && v.k == settings[0].probe_size && v.G == settings[0].max_gap_size &&
@@ -2100,7 +2100,7 @@ int32_t asgart_search_duplications_passes_shard(asgart_index *idx, const uint64_
         for (int m = 0; m < 4; ++m) tail_ms[m] = idx->tail_ms[m];
     }
     auto weight = [&](int32_t j) {
-        const int mode = (settings[j].reverse ? 2 : 0) | (settings[j].complement ? 1 : 0);
+        const uint32_t mode = mode_of_settings(settings[j]);
         const double t = tail_ms[mode];
         return t >= 0.0 ? t : 1e30 + (settings[j].reverse ? 1e29 : 0.0);
     };
@@ -2269,6 +2269,12 @@ int32_t asgart_fill_tally(asgart_index *idx, uint64_t *out) {
 
 int32_t asgart_ranked_fill_takes(uint64_t interval, uint64_t kept, int32_t mode) {
     return ranked_fill_takes(interval, kept, (int)mode) ? 1 : 0;
+}
+
+void asgart_hit_rule(uint64_t i, uint64_t s, uint64_t L, int32_t reverse, uint64_t *out) {
+    const HitRule hr = hit_rule(i, s, L, reverse != 0);
+    out[0] = hr.thr;
+    out[1] = hr.self;
 }
 
 int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out) {

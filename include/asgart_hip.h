@@ -887,6 +887,10 @@ int32_t asgart_fill_tally(asgart_index *idx, uint64_t *out);
 /* Diagnostic (for tests of the rule): ASGART_RANKED_FILL = mode for a row that keeps `kept` hits of an interval of `interval` entries (host code,
  * needs no device): 1 = filled from the position-sorted list, 0 = streamed. */
 int32_t asgart_ranked_fill_takes(uint64_t interval, uint64_t kept, int32_t mode);
+/* Diagnostic (for tests of the rule): the hit filter of the probe at needle offset i of the chunk text[s, s + L), in a
+ * reversed pass or a direct one, as the kernels state it (host code, needs no device): occurrence x is kept when
+ * x >= out[0] && x != out[1]  (src/automaton.rs:105-114). */
+void asgart_hit_rule(uint64_t i, uint64_t s, uint64_t L, int32_t reverse, uint64_t *out);
 /* The tier table's figures a call starts from (host code, needs no device): profile_ms[0] = the runs over ranges,
  * profile_ms[t] = tier t's estimated duration on the GRCh38-shaped profile (what asgart_tier_plan is fed before a call
  * has measurements of its own), for a thresholded tier what is left of it where the tail rule is in force; tail_hits[t] =

@@ -208,6 +208,23 @@ def test_reversed_pass_drops_the_probes_own_offset(mirror, switch, monkeypatch):
             assert int(idx.fill_counts()[4]) > 0
 
 
+def test_large_rows_with_64_bit_slots(planted, mirror, monkeypatch):
+    """ASGART_FORCE_WIDE=1: the ranked fill is 32-bit only, so the large rows are counted by rank_count_kernel<uint64_t>
+    (threshold and own offset compared with 64-bit list entries) and streamed by fill_big_kernel<uint64_t>.  The mirror
+    text reversed -- the probe's own offset is in its list --, the planted one direct and reverse + complement; both chunk
+    lists, max_cardinality 500 and 8; against the oracle's rows."""
+    monkeypatch.setenv("ASGART_FORCE_WIDE", "1")
+    for case, modes in ((mirror, (REV,)), (planted, (DIRECT, RC))):
+        with asgart_amd.Index(case.text, case.oidx.sa) as idx:
+            for card in (500, 8):
+                for mode in modes:
+                    for name, chunks in case.chunks.items():
+                        got = idx.probe_hits(chunks, _settings(mode, card))
+                        _assert_rows(got, case.oracle_rows(name, mode, card), (card, mode, name))
+                        if card == 500:   # (rows counted by bisection were streamed, none came from the ranked fill)
+                            assert int(idx.fill_tally()[2, 0]) > 0 and int(idx.fill_counts()[4]) == 0
+
+
 @pytest.mark.parametrize("switch", SWITCH)
 def test_an_interval_at_and_above_what_the_bitmap_holds(tract, switch, monkeypatch):
     """R = 65 536 fills the wave's bitmap to its last bit and is taken (under 1 as well: at most 500 are kept); R = 65 537

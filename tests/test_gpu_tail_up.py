@@ -1,4 +1,4 @@
-"""The tail rule of the placement (asgart_index_set_tail_up; place_tier in asgart_amd/csrc/pipeline_dev.hpp): a segment that
+"""The tail rule of the placement (asgart_index_set_tail_up; place_tier in asgart_amd/csrc/place_dev.hpp): a segment that
 its arm bound sends to tier 2, 4 or 5 and that has at least the tier's threshold of hits runs in the next arm-resident
 workgroup tier that holds more.  Placement never changes results: every battery case and two flat tandem arrays (one whose
 arm bound fits tier 4, one tier 5) give the oracle's families, ProtoSDs and the same keys with the rule off and on, as single
