@@ -26,7 +26,7 @@ __all__ = [
     "score_owners", "score_costs", "compute_scores_multi", "Source", "compute_scores_flags_multi", "orientation_flags",
     "export_records", "export_geometry", "f32_shortest", "f32_pow10_table", "EXPORT_FORMATS",
     "ResultScan", "result_geometry", "E_REFUSED", "Alignments", "align_geometry", "align_bytes",
-    "paf_records", "paf_geometry",
+    "paf_records", "paf_geometry", "paf_records_cs", "paf_cs_geometry", "CS_MODES",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -60,7 +60,8 @@ ABI_SYMBOLS = (
     "asgart_result_free", "asgart_result_geometry",
     "asgart_align_duplications", "asgart_alignment_counts", "asgart_alignment_copy", "asgart_alignment_timings",
     "asgart_alignment_free", "asgart_align_geometry", "asgart_align_bytes",
-    "asgart_paf_records", "asgart_paf_geometry",
+    "asgart_paf_records", "asgart_paf_geometry", "asgart_paf_records_cs", "asgart_paf_cs_geometry",
+    "asgart_index_read_text",
 )
 
 
@@ -348,6 +349,14 @@ def load_library() -> C.CDLL:
         L.asgart_paf_records.restype = C.c_int32
         L.asgart_paf_geometry.argtypes = [u64p, u64p, u64p]
         L.asgart_paf_geometry.restype = None
+    if hasattr(L, "asgart_paf_records_cs"):
+        L.asgart_paf_records_cs.argtypes = [vp, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp,
+                                            vp, C.c_int64, C.POINTER(vp)]
+        L.asgart_paf_records_cs.restype = C.c_int32
+        L.asgart_paf_cs_geometry.argtypes = [u64p, u64p, u64p, u64p]
+        L.asgart_paf_cs_geometry.restype = None
+        L.asgart_index_read_text.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
+        L.asgart_index_read_text.restype = C.c_int32
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []
@@ -572,6 +581,13 @@ class Index:
     def sa_read(self, lo: int, hi: int) -> np.ndarray:
         out = np.empty(max(0, hi - lo), dtype=np.int64)
         _check(load_library().asgart_sa_read(self._h, lo, hi, _ptr(out)))
+        return out
+
+    def read_text(self, lo: int, hi: int) -> np.ndarray:
+        """The bytes [lo, hi) of the index's normalised text as uint8 (asgart_index_read_text): with the device FASTA
+        reader the index holds the only copy of it."""
+        out = np.empty(max(0, hi - lo), dtype=np.uint8)
+        _check(load_library().asgart_index_read_text(self._h, lo, hi, _ptr(out)))
         return out
 
     def compute_scores(self, sds: np.ndarray, reversed_: bool = False, complemented: bool = False) -> np.ndarray:
@@ -997,15 +1013,13 @@ def export_geometry() -> Tuple[int, int, int]:
     return int(a.value), int(b.value), int(c.value)
 
 
-def paf_records(offs, sds, flags, status, distance, chr_, chr_pos, run_offsets, run_len, run_op, names: Sequence[bytes],
-                name_length, device: int = 0, timings: Optional[list] = None) -> np.ndarray:
-    """asgart_paf_records: the whole PAF file as uint8[size], written on the GPU (csrc/paf.hip).  offs, sds, flags, chr_,
-    chr_pos as export_records takes them; status, distance, run_offsets, run_len, run_op as Alignments holds them; names: the
-    name table, every name as the bytes to write; name_length: the length of the fragment behind each name.  timings: a list
-    that receives the call's three millisecond figures (asgart_export_timings: upload, kernels, copy back)."""
+def _paf_records(call, who: str, offs, sds, flags, status, distance, chr_, chr_pos, run_offsets, run_len, run_op,
+                 names: Sequence[bytes], name_length, timings: Optional[list]) -> np.ndarray:
+    """What paf_records and paf_records_cs share: the arrays as the library takes them, call(the arguments behind the
+    first one or two, the handle) and the copy of the file."""
     L = load_library()
-    if not hasattr(L, "asgart_paf_records"):
-        raise AsgartError(-3, f"{library_path()} has no asgart_paf_records: rebuild it; there is no host fallback behind "
+    if not hasattr(L, "asgart_" + who):
+        raise AsgartError(-3, f"{library_path()} has no asgart_{who}: rebuild it; there is no host fallback behind "
                               "this call (align.paf_text is the host writer)")
     offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
     sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
@@ -1021,18 +1035,18 @@ def paf_records(offs, sds, flags, status, distance, chr_, chr_pos, run_offsets, 
     n = len(sds)
     if len(offs) < 1 or not (len(flags) == len(status) == len(distance) == len(chr_) == len(chr_pos) == n) or \
             len(run_offsets) != n + 1 or len(run_len) != len(run_op) or len(name_length) != len(names):
-        raise ValueError("paf_records: the arrays differ in length")
+        raise ValueError(f"{who}: the arrays differ in length")
     if len(run_len) < int(run_offsets[-1]) < 1 << 32:   # (2^32 runs and more are the library's to refuse, unread)
-        raise ValueError(f"paf_records: run_offsets end at {int(run_offsets[-1])}, there are {len(run_len)} runs")
+        raise ValueError(f"{who}: run_offsets end at {int(run_offsets[-1])}, there are {len(run_len)} runs")
     name_off = np.zeros(len(names) + 1, dtype=np.uint64)
     np.cumsum([len(b) for b in names], out=name_off[1:])
     name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
     if len(run_len) == 0:
         run_len, run_op = np.zeros(1, np.uint32), np.zeros(1, np.uint8)
     h = C.c_void_p()
-    _check(L.asgart_paf_records(int(device), _ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags), _ptr(status),
-                                _ptr(distance), _ptr(chr_), _ptr(chr_pos), n, _ptr(run_offsets), _ptr(run_len),
-                                _ptr(run_op), _ptr(name_bytes), _ptr(name_off), _ptr(name_length), len(names), C.byref(h)))
+    _check(call(_ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags), _ptr(status), _ptr(distance), _ptr(chr_), _ptr(chr_pos), n,
+                _ptr(run_offsets), _ptr(run_len), _ptr(run_op), _ptr(name_bytes), _ptr(name_off), _ptr(name_length),
+                len(names), C.byref(h)))
     try:
         out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
         _check(L.asgart_export_copy(h, _ptr(out), len(out)))
@@ -1042,12 +1056,46 @@ def paf_records(offs, sds, flags, status, distance, chr_, chr_pos, run_offsets, 
     return out
 
 
+def paf_records(offs, sds, flags, status, distance, chr_, chr_pos, run_offsets, run_len, run_op, names: Sequence[bytes],
+                name_length, device: int = 0, timings: Optional[list] = None) -> np.ndarray:
+    """asgart_paf_records: the whole PAF file as uint8[size], written on the GPU (csrc/paf.hip).  offs, sds, flags, chr_,
+    chr_pos as export_records takes them; status, distance, run_offsets, run_len, run_op as Alignments holds them; names: the
+    name table, every name as the bytes to write; name_length: the length of the fragment behind each name.  timings: a list
+    that receives the call's three millisecond figures (asgart_export_timings: upload, kernels, copy back)."""
+    return _paf_records(lambda *a: load_library().asgart_paf_records(int(device), *a), "paf_records", offs, sds, flags, status,
+                        distance, chr_, chr_pos, run_offsets, run_len, run_op, names, name_length, timings)
+
+
+CS_MODES = {"short": 1, "long": 2}   # cs_mode of asgart_paf_records_cs
+
+
+def paf_records_cs(index: "Index", cs: str, offs, sds, flags, status, distance, chr_, chr_pos, run_offsets, run_len, run_op,
+                   names: Sequence[bytes], name_length, timings: Optional[list] = None) -> np.ndarray:
+    """asgart_paf_records_cs: the file of paf_records with the cs:Z: column, "short" or "long" (include/asgart_hip.h states
+    the rule, align.cs_text is its readable form).  The device and the bases are the index's; everything else as
+    paf_records."""
+    if cs not in CS_MODES:
+        raise ValueError("cs: 'short' or 'long'")
+    if index is None:
+        raise ValueError("paf_records_cs: the cs:Z: column needs the index whose text the duplications lie in")
+    return _paf_records(lambda *a: load_library().asgart_paf_records_cs(index._h, CS_MODES[cs], *a), "paf_records_cs", offs,
+                        sds, flags, status, distance, chr_, chr_pos, run_offsets, run_len, run_op, names, name_length, timings)
+
+
 def paf_geometry() -> Tuple[int, int, int]:
     """asgart_paf_geometry: threads per workgroup of the write stage, the most runs one workgroup's range can hold, bytes of
     the file a workgroup owns (its LDS image)."""
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     load_library().asgart_paf_geometry(C.byref(a), C.byref(b), C.byref(c))
     return int(a.value), int(b.value), int(c.value)
+
+
+def paf_cs_geometry() -> Tuple[int, int, int, int]:
+    """asgart_paf_cs_geometry: paf_geometry's three sizes and solo_bytes, the most bytes of one run's cs text inside a
+    workgroup's range that one thread composes alone."""
+    a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    load_library().asgart_paf_cs_geometry(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return int(a.value), int(b.value), int(c.value), int(d.value)
 
 
 E_REFUSED = -5   # ASGART_E_REFUSED: the device reader of result files leaves the input to the host reader

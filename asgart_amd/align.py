@@ -7,6 +7,8 @@ This module states the same rule on the host, for the tests to compare byte for 
     replay       does a list of runs consume exactly both arms, `=` on equal bytes and `X` on unequal ones?  -> its edits
     paf_text     one PAF row per aligned duplication: query = left arm, target = right arm
     paf_text_gpu the same bytes, written on the GPU (asgart_paf_records, csrc/paf.hip)
+    cs_text      minimap2's difference string (cs:Z:) of one row: the bases behind its CIGAR; both writers add it as a
+                 sixteenth column when asked (cs="short" or "long"; asgart_paf_records_cs on the GPU)
 
 The arms: A = text[left ..] is the left arm; B is the right arm as ProtoSD::levenshtein walks it (reference
 src/structs.rs:439-452): reversed if flag bit 0 is set, complemented if bit 1 is set (ACGT and acgt swap, anything else is
@@ -146,7 +148,73 @@ def align_host_all(text, sds, flags=None, inclusive: bool = False):
                       np.array(dist, np.uint32), ident, np.ones(len(sds), np.uint8))
 
 
-def paf_text(offs, sds, flags, strand, aln, stderr=None) -> str:
+def _lower(b: np.ndarray) -> bytes:
+    """A..Z -> a..z, every other byte kept"""
+    return np.where((b >= 65) & (b <= 90), b + 32, b).astype(np.uint8).tobytes()
+
+
+def cs_text(text, sd, flag: int, runs: Sequence[Run], long: bool = False) -> str:
+    """The cs:Z: difference string of one PAF row: sd = (left, right, left_length, right_length) in `text`, flag 0 (`+`) or
+    3 (`-`), runs as Index.align gives them -- in the order given, NOT reversed for a `-` row; the reversal is done here.
+    Run t of n bases starts at the arm offsets i (the bases of the earlier runs with `=`, `X` or `I`) and j (`=`, `X` or
+    `D`) and stands for the query bytes Q and the target bytes T,
+        `+`   Q = text[left + i : left + i + n]                           T = text[right + j : right + j + n]
+        `-`   Q = complement of text[left + i : left + i + n], reversed   T = text[right + rl - j - n : right + rl - j]
+    (on a `-` row the string runs along the target's forward strand, the query reverse-complemented, as minimap2 writes
+    it).  Its text: `=` is `:n`, or long `=` and T as stored; `X` is `*`, low(T[v]), low(Q[v]) for every base; `I` -- a
+    left-arm base without a partner -- `+` and low(Q); `D` `-` and low(T); low maps A..Z to a..z.  The texts are joined in
+    the order of the CIGAR: as given for `+`, reversed for `-`.  Nothing is compared: an `X` over equal bytes prints two
+    equal letters.  ValueError: a flag other than 0 and 3, an unknown operation, a run of no base, runs that do not consume
+    exactly both arms, arms that reach past the text."""
+    if flag not in (0, 3):
+        raise ValueError(f"flag {flag}: a PAF row has a strand for 0 (direct, +) and 3 (reversed and complemented, -) only")
+    text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    left, right, ll, rl = (int(v) for v in sd)
+    if left + ll > len(text) or right + rl > len(text):
+        raise ValueError("the duplication reaches past the end of the text")
+    parts = []
+    i = j = 0
+    for n, op in runs:
+        n = int(n)
+        if op not in ("=", "X", "I", "D"):
+            raise ValueError(f"unknown operation `{op}`")
+        if n <= 0:
+            raise ValueError(f"a run of {n} `{op}`")
+        if i + (n if op != "D" else 0) > ll or j + (n if op != "I" else 0) > rl:
+            raise ValueError(f"`{n}{op}` at ({i}, {j}) runs past an arm: the runs do not consume arms of {ll} and {rl}")
+        if flag == 0:
+            q = text[left + i:left + i + n]
+            t = text[right + j:right + j + n]
+        else:
+            q = _COMPLEMENT[text[left + i:left + i + n]][::-1]
+            t = text[right + rl - j - n:right + rl - j]
+        if op == "=":
+            parts.append("=" + t.tobytes().decode("latin-1") if long else f":{n}")
+        elif op == "X":
+            both = np.empty(3 * n, dtype=np.uint8)
+            both[0::3] = ord("*")
+            both[1::3] = np.frombuffer(_lower(t), dtype=np.uint8)
+            both[2::3] = np.frombuffer(_lower(q), dtype=np.uint8)
+            parts.append(both.tobytes().decode("latin-1"))
+        elif op == "I":
+            parts.append("+" + _lower(q).decode("latin-1"))
+        else:
+            parts.append("-" + _lower(t).decode("latin-1"))
+        if op != "D":
+            i += n
+        if op != "I":
+            j += n
+    if i != ll or j != rl:
+        raise ValueError(f"the runs consume {i} and {j} bases of arms of {ll} and {rl}")
+    return "".join(parts if flag == 0 else parts[::-1])
+
+
+def _check_cs(cs: Optional[str]) -> None:
+    if cs not in (None, "short", "long"):
+        raise ValueError("cs: None, 'short' or 'long'")
+
+
+def paf_text(offs, sds, flags, strand, aln, stderr=None, cs: Optional[str] = None, text=None) -> str:
     """One PAF row per aligned duplication of a result: offs / sds the family arrays, flags one byte per duplication, strand
     the run's Strand (its map names the fragments), aln the Alignments of Index.align(sds, flags, inclusive=False).
     Query = left arm, target = right arm.  Names, fragment lengths and in-fragment positions are resolved as the JSON
@@ -155,7 +223,14 @@ def paf_text(offs, sds, flags, strand, aln, stderr=None) -> str:
     direct duplication and `-` for a reversed and complemented one; on `-` the ORDER of the runs is reversed, because
     PAF's CIGAR runs along the target's forward strand, and the operations stay.  Column 10 is the number of `=`, column 11
     the sum of all run lengths, column 12 is 255; tags NM:i:<distance>, fm:i:<family>, cg:Z:<cigar>.  A reversed-only or
-    complemented-only duplication has no PAF strand: ValueError.  A refused duplication gets no row and is named on stderr."""
+    complemented-only duplication has no PAF strand: ValueError.  A refused duplication gets no row and is named on stderr.
+    cs: "short" or "long" appends the column `cs:Z:` + cs_text(text, ...) to every row; `text` is then the text the
+    duplications lie in (ValueError without it)."""
+    _check_cs(cs)
+    if cs is not None:
+        if text is None:
+            raise ValueError("paf_text: cs needs the text the duplications lie in (text=)")
+        text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else text
     offs = np.asarray(offs, dtype=np.int64)
     sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
     flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
@@ -182,6 +257,7 @@ def paf_text(offs, sds, flags, strand, aln, stderr=None) -> str:
                   file=stderr if stderr is not None else sys.stderr)
             continue
         runs = aln.ops(q)
+        tag = [] if cs is None else ["cs:Z:" + cs_text(text, (left, right, ll, rl), int(flags[q]), runs, cs == "long")]
         if flags[q] == 3:
             runs = runs[::-1]
         qname, qlen, qpos = locate(left)
@@ -189,16 +265,19 @@ def paf_text(offs, sds, flags, strand, aln, stderr=None) -> str:
         rows.append("\t".join(str(v) for v in (
             qname, qlen, qpos, qpos + ll, "-" if flags[q] == 3 else "+", tname, tlen, tpos, tpos + rl,
             sum(n for n, op in runs if op == "="), sum(n for n, _ in runs), 255,
-            f"NM:i:{int(aln.distance[q])}", f"fm:i:{int(family[q])}", f"cg:Z:{cigar(runs)}")))
+            f"NM:i:{int(aln.distance[q])}", f"fm:i:{int(family[q])}", f"cg:Z:{cigar(runs)}", *tag)))
     return "".join(r + "\n" for r in rows)
 
 
 def _paf_text_device(offs, sds, flags, strand, aln, device: int = 0, stderr=None,
-                     timings: Optional[dict] = None) -> np.ndarray:
+                     timings: Optional[dict] = None, cs: Optional[str] = None, index=None) -> np.ndarray:
     """paf_text_gpu as the uint8 array the library filled (the drivers decode it without another copy)."""
     import time
 
-    from . import paf_records
+    from . import paf_records, paf_records_cs
+    _check_cs(cs)
+    if cs is not None and index is None:
+        raise ValueError("paf_text_gpu: cs needs the index whose text the duplications lie in (index=)")
     from .postprocess import locate_arms
 
     offs = np.asarray(offs, dtype=np.int64)
@@ -226,18 +305,27 @@ def _paf_text_device(offs, sds, flags, strand, aln, device: int = 0, stderr=None
                   file=stderr if stderr is not None else sys.stderr)
     t1 = time.perf_counter()
     ms: list = []
-    out = paf_records(offs, sds, flags, status, aln.distance, chr_, chr_pos, aln.run_offsets, aln.run_len, aln.run_op,
-                      names, name_length, device, ms)
+    if cs is None:
+        out = paf_records(offs, sds, flags, status, aln.distance, chr_, chr_pos, aln.run_offsets, aln.run_len, aln.run_op,
+                          names, name_length, device, ms)
+    else:
+        out = paf_records_cs(index, cs, offs, sds, flags, status, aln.distance, chr_, chr_pos, aln.run_offsets, aln.run_len,
+                             aln.run_op, names, name_length, ms)
     if timings is not None:
         timings.update(names=(t1 - t0) * 1e3, upload=ms[0], kernels=ms[1], copy=ms[2])
     return out
 
 
-def paf_text_gpu(offs, sds, flags, strand, aln, device: int = 0, stderr=None, timings: Optional[dict] = None) -> bytes:
+def paf_text_gpu(offs, sds, flags, strand, aln, device: int = 0, stderr=None, timings: Optional[dict] = None,
+                 cs: Optional[str] = None, index=None) -> bytes:
     """paf_text(offs, sds, flags, strand, aln, stderr).encode("utf-8"), written on the GPU (asgart_paf_records,
     csrc/paf.hip): the arms are located here by postprocess.locate_arms (the bisection the device writer of the JSON file
     uses), the name table -- every map entry's name, then `unknown` with the strand's length -- is prepared here once, and
     the rows, one thread per CIGAR run, are laid out and written by the library.  The same ValueError texts as paf_text and
     the same stderr line per refused duplication, in the same order.  timings: a dict that receives the call's stages in
-    milliseconds: names (locate and name table), upload, kernels, copy."""
-    return _paf_text_device(offs, sds, flags, strand, aln, device, stderr, timings).tobytes()
+    milliseconds: names (locate and name table), upload, kernels, copy.
+    cs: "short" or "long" adds the cs:Z: column (asgart_paf_records_cs); index is then the Index whose text the
+    duplications lie in, and the file is written on ITS device (`device` is not looked at)."""
+    if cs is None:
+        return _paf_text_device(offs, sds, flags, strand, aln, device, stderr, timings).tobytes()
+    return _paf_text_device(offs, sds, flags, strand, aln, device, stderr, timings, cs=cs, index=index).tobytes()

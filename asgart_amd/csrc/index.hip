@@ -1614,6 +1614,24 @@ int32_t asgart_sa_read(asgart_index *idx, uint64_t lo, uint64_t hi, int64_t *out
     return 0;
 }
 
+int32_t asgart_index_read_text(asgart_index *idx, uint64_t lo, uint64_t hi, uint8_t *out) {
+    if (!idx || hi < lo || hi > (uint64_t)idx->n || (hi > lo && !out)) {
+        set_error("asgart_index_read_text: bad range");
+        return ASGART_E_ARG;
+    }
+    if (hi == lo) return 0;
+    REFUSE_POISONED(idx);
+    HIP_TRY(hipSetDevice(idx->device));
+    idx->acquire_all();
+    struct Unlock {
+        asgart_index *i;
+        ~Unlock() { i->release_all(); }
+    } unlock{idx};
+    HIP_TRY(read_back(out, idx->d_text + lo, hi - lo, idx->ctx[0].stream));
+    HIP_TRY(stream_sync(idx->ctx[0].stream));
+    return 0;
+}
+
 int32_t asgart_tier_plan(int32_t budget, const uint64_t *n_work, int64_t tier_order, const double *est_ms, double main_ms,
                          int32_t *stream_of, int32_t *launch) {
     return asgart::tier_plan(budget, n_work, tier_order, est_ms, main_ms, stream_of, launch);

@@ -216,14 +216,20 @@ def _choose_writer(writer: Optional[str], with_sequences: bool) -> str:
 # profiles/paf_synth.json: at 80 536 runs the two medians are closer than the device's spread, at 2^20 runs and at 21
 # million the device's is below the host's by more than both spreads.
 PAF_DEVICE_MIN_RUNS = 1 << 20
+# The same for a PAF file with the cs:Z: column (--cs).  The host writer slices the text for every run and costs 2.5 ms per
+# thousand runs, the device call its 7 to 9 ms (spread 3 to 5 ms) up to 2^20 runs.  profiles/paf_cs_synth.json (short) and
+# profiles/paf_cs_long_synth.json: at 80 536 runs, the smallest size measured, at 2^20 and at 21 million the device's median is
+# below the host's by more than both spreads, in both forms.  Nothing smaller was measured, so that size is the threshold.
+PAF_CS_DEVICE_MIN_RUNS = 80_536
 
 
-def _choose_paf_writer(writer: Optional[str], n_runs: int) -> str:
+def _choose_paf_writer(writer: Optional[str], n_runs: int, cs: Optional[str] = None) -> str:
     """The writer of a PAF file of n_runs CIGAR runs: "device" (align.paf_text_gpu) or "host" (align.paf_text, what
-    --host-writer asks for) as asked; writer=None: by size, see PAF_DEVICE_MIN_RUNS.  A PAF row holds no sequence, so
-    with_sequences -- which sends the RESULT file to the host exporter -- does not matter here."""
+    --host-writer asks for) as asked; writer=None: by size, see PAF_DEVICE_MIN_RUNS (with the cs:Z: column:
+    PAF_CS_DEVICE_MIN_RUNS).  A PAF row holds no sequence, so with_sequences -- which sends the RESULT file to the host
+    exporter -- does not matter here."""
     if writer is None:
-        return "device" if n_runs >= PAF_DEVICE_MIN_RUNS else "host"
+        return "device" if n_runs >= (PAF_DEVICE_MIN_RUNS if cs is None else PAF_CS_DEVICE_MIN_RUNS) else "host"
     if writer not in ("device", "host"):
         raise ValueError("writer: 'device' or 'host'")
     return writer
@@ -285,8 +291,12 @@ def _check_slice(slice_options, fmt: str) -> bool:
     return slice_options.active() or fmt != "json"
 
 
-def _check_paf(paf: bool, world: int, orientations, slice_options=None) -> None:
-    """--paf, vetted before the run starts (on every rank): each refusal with its reason."""
+def _check_paf(paf: bool, world: int, orientations, slice_options=None, cs: Optional[str] = None) -> None:
+    """--paf and --cs, vetted before the run starts (on every rank): each refusal with its reason."""
+    if cs not in (None, "short", "long"):
+        raise ValueError("--cs: short or long")
+    if cs is not None and not paf:
+        raise ValueError("--cs: the cs:Z: tag is a column of the PAF file; it needs --paf")
     if not paf:
         return
     if world > 1:
@@ -302,14 +312,33 @@ def _check_paf(paf: bool, world: int, orientations, slice_options=None) -> None:
                          "name positions in the fragments of the run (slice the result without them, or write no PAF)")
 
 
-def _paf_text(fam_offs, sds, flags, strand, aln, writer: Optional[str], device_index: int) -> str:
+def _paf_and_cs(paf):
+    """The `paf` argument of the entry points -> (paf, cs): False and True as they are, "short" and "long" are True with
+    the cs:Z: column in that form.  (The column came after the entry points' signatures were fixed; it rides on `paf`.)"""
+    if isinstance(paf, str):
+        if paf not in ("short", "long"):
+            raise ValueError("paf: False, True, or 'short' / 'long' for rows with the cs:Z: column")
+        return True, paf
+    return bool(paf), None
+
+
+def _paf_text(fam_offs, sds, flags, strand, aln, writer: Optional[str], device_index: int, cs: Optional[str] = None,
+              index=None) -> str:
     """The PAF text of aligned duplications by the writer the run asked for (_choose_paf_writer): "device"
-    asgart_paf_records (align._paf_text_device), "host" align.paf_text; the text is the same either way."""
+    asgart_paf_records (align._paf_text_device), "host" align.paf_text; the text is the same either way.  cs: with the
+    cs:Z: column, "short" or "long"; index is then the run's index, still open: the device writer (asgart_paf_records_cs)
+    reads the bases from it, the host writer from strand.data or, where the device reader left no copy on the host, from
+    Index.read_text."""
     from .align import _paf_text_device, paf_text
 
-    if _choose_paf_writer(writer, len(aln.run_len)) == "device":
-        return _decode(_paf_text_device(fam_offs, sds, flags, strand, aln, device_index))
-    return paf_text(fam_offs, sds, flags, strand, aln)
+    if cs is None:
+        if _choose_paf_writer(writer, len(aln.run_len)) == "device":
+            return _decode(_paf_text_device(fam_offs, sds, flags, strand, aln, device_index))
+        return paf_text(fam_offs, sds, flags, strand, aln)
+    if _choose_paf_writer(writer, len(aln.run_len), cs) == "device":
+        return _decode(_paf_text_device(fam_offs, sds, flags, strand, aln, device_index, cs=cs, index=index))
+    text = strand.data if strand.data is not None else index.read_text(0, index.n)
+    return paf_text(fam_offs, sds, flags, strand, aln, cs=cs, text=text)
 
 
 def _slice_run(post, strand, settings, slice_options, device_index: int):
@@ -325,13 +354,15 @@ def _slice_run(post, strand, settings, slice_options, device_index: int):
 # What _run leaves on rank 0, all of it on the host.  A _Part is one orientation: its RunSettings, the family offsets of its
 # file (behind post_process, or those of `cut`), the sliced slice.ResultArrays (None: not sliced) and the range of its
 # duplications, survivors[lo:hi].  survivors (n, 4) uint64 and flags uint8[n] hold the parts' duplications one behind the
-# other; ident float32[n], seqs (left, right) and aln (Alignments) are None unless the run was asked for them.
-_Part = namedtuple("_Part", "settings offs cut lo hi")
+# other; ident float32[n], seqs (left, right) and aln (Alignments) are None unless the run was asked for them.  paf: the text of
+# the part's PAF file where it had to be written while the index was open (--cs: the bases are the index's), None otherwise.
+_Part = namedtuple("_Part", "settings offs cut lo hi paf", defaults=(None,))
 _Run = namedtuple("_Run", "files device_index strand parts survivors flags ident seqs aln")
 
 
 def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool, with_sequences: bool, reader: str,
-         paf: bool, sliced: bool = False, slice_options=None) -> Optional[_Run]:
+         paf: bool, sliced: bool = False, slice_options=None, cs: Optional[str] = None,
+         paf_writer: Optional[str] = None) -> Optional[_Run]:
     """The run protocol, once: a whole `asgart` run (reference src/bin/asgart.rs:731-822) for each of the one to four
     RunSettings `sts`, which differ in orientation only, on the ranks of `dist` (None: one process, no collective), rank r
     on GPU device_index.  The entry points have vetted the arguments.  Built ONCE: rank 0 reads the input and builds the
@@ -342,8 +373,9 @@ def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool
     at `identity`, so slicing commutes with scoring.  What is left of all orientations -- the survivors, a sliced run's in
     its original coordinates -- is one list with a flag byte each: with compute_score it is broadcast once and every rank
     scores its share; with_sequences is one extraction from the Source of the read (device reader) or the raw records
-    (host reader); paf one alignment with exact ranges.  A slice that is refused (ValueError) is raised behind the
-    collectives, which then run without survivors: the other ranks must not wait in them.
+    (host reader); paf one alignment with exact ranges; with cs (the cs:Z: column) every part's PAF text is written right
+    there, by the writer paf_writer asks for, because the index is closed when this returns.  A slice that is refused
+    (ValueError) is raised behind the collectives, which then run without survivors: the other ranks must not wait in them.
     -> the _Run on rank 0, None elsewhere; the Source and the index are closed either way."""
     from . import merge_shards, orientation_flags
 
@@ -403,6 +435,9 @@ def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool
         seqs = _sequences(source, records, device_index, survivors, (flags & 1).astype(bool),
                           (flags >> 1 & 1).astype(bool)) if with_sequences else None
         aln = index.align(survivors, flags, inclusive=False) if paf else None
+        if paf and cs is not None:
+            parts = [p._replace(paf=_paf_text(p.offs, survivors[p.lo:p.hi], flags[p.lo:p.hi], strand, aln.part(p.lo, p.hi),
+                                              paf_writer, device_index, cs, index)) for p in parts]
         return _Run(files, device_index, strand, parts, survivors, flags, ident, seqs, aln)
     finally:
         if source is not None:
@@ -430,7 +465,7 @@ def _texts(run: _Run, part: _Part, prefix: str, writer: str, paf_writer: Optiona
     by the run count of this orientation's own alignments.  fmt: of a sliced part, whose file is named after it."""
     from .postprocess import out_filename
 
-    st, offs, cut, lo, hi = part
+    st, offs, cut, lo, hi, paf_text = part
     name = out_filename(run.files, st, prefix)
     if cut is None:
         text = _json_text(run, offs, lo, hi, st, writer)
@@ -445,6 +480,8 @@ def _texts(run: _Run, part: _Part, prefix: str, writer: str, paf_writer: Optiona
         text = _decode(_export_arrays_device(cut, fmt, run.device_index)) if writer == "device" else export_arrays(cut, fmt)
     if run.aln is None:
         return text, name
+    if paf_text is not None:
+        return text, name, paf_text
     return text, name, _paf_text(offs, run.survivors[lo:hi], run.flags[lo:hi], run.strand, run.aln.part(lo, hi), paf_writer,
                                  run.device_index)
 
@@ -470,7 +507,9 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     paf: the surviving duplications -- the ones compute_score scores -- are also aligned and the return value gains a
     third entry, the text of the PAF file, written as `writer` asks (align.paf_text_gpu or align.paf_text; None: by the
     number of runs, PAF_DEVICE_MIN_RUNS; with_sequences does not matter, a PAF row holds no sequence).  One rank only; see
-    _check_paf."""
+    _check_paf.  paf="short" or paf="long" (what --paf --cs [short|long] passes) is paf=True with the cs:Z: column in every
+    row of the PAF text (align.cs_text), in that form; writer=None then decides by PAF_CS_DEVICE_MIN_RUNS."""
+    paf, cs = _paf_and_cs(paf)
     world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_duplications: --trim runs on one rank only")
@@ -478,8 +517,9 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     sliced = _check_slice(slice_options, fmt)
-    _check_paf(paf, world, [(settings.reverse, settings.complement)], slice_options)
-    run = _run(files, [settings], dist, device_index, compute_score, with_sequences, reader, paf, sliced, slice_options)
+    _check_paf(paf, world, [(settings.reverse, settings.complement)], slice_options, cs)
+    run = _run(files, [settings], dist, device_index, compute_score, with_sequences, reader, paf, sliced, slice_options, cs,
+               paf_writer)
     return None if run is None else _texts(run, run.parts[0], prefix, writer, paf_writer, fmt)
 
 
@@ -494,22 +534,23 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     text) and None elsewhere; the merged text is what postprocess.merge_results gives over those files in that order
     (RunResult::from_files, reference src/structs.rs:114-141: strand and settings of the first, every duplication with the
     flags of its own run) and is written like the others.  `--trim`, reader, writer, with_sequences, paf (the merged
-    result gets no PAF text; direct and RC only, see _check_paf): as search_duplications.  Slicing is out of scope here:
-    `python -m asgart_amd.slice` does it on the files this writes."""
+    result gets no PAF text; direct and RC only, see _check_paf; "short" / "long": with the cs:Z: column): as
+    search_duplications.  Slicing is out of scope here: `python -m asgart_amd.slice` does it on the files this writes."""
     from dataclasses import replace
 
+    paf, cs = _paf_and_cs(paf)
     orientations = [(bool(r), bool(c)) for r, c in orientations]
     if not 1 <= len(orientations) <= 4 or len(set(orientations)) != len(orientations):
         raise ValueError("multi.search_orientations: one to four distinct (reverse, complement) pairs")
     world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
-    _check_paf(paf, world, orientations)
+    _check_paf(paf, world, orientations, None, cs)
     reader = _choose_reader(reader, settings)
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     sts = [replace(settings, reverse=r, complement=c) for r, c in orientations]
-    run = _run(files, sts, dist, device_index, compute_score, with_sequences, reader, paf)
+    run = _run(files, sts, dist, device_index, compute_score, with_sequences, reader, paf, cs=cs, paf_writer=paf_writer)
     if run is None:
         return None
     sizes = np.concatenate([np.diff(p.offs.astype(np.int64)) for p in run.parts])
@@ -554,6 +595,9 @@ def _parse(argv):
                          "<result stem>.paf beside every result file: one row per duplication with its CIGAR (cg:Z:).  One "
                          "GPU; direct and RC runs only; not with --collapse or the fragment filters.  With --compute-score "
                          "the edit matrix is walked twice: the score compares inclusive ranges, a PAF row exact ones")
+    ap.add_argument("--cs", nargs="?", const="short", choices=("short", "long"), default=None,
+                    help="with --paf: give every row minimap2's difference string as a sixteenth column (cs:Z:), the bases "
+                         "behind the CIGAR; short (what a bare --cs means) writes `:<n>` for matching bases, long writes them out")
     ap.add_argument("--prefix", default="")
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
@@ -587,7 +631,7 @@ def _parse(argv):
     if args.orientations and (args.slice_options.active() or args.format != "json"):
         ap.error("--orientations writes unsliced JSON files: slice them with python -m asgart_amd.slice")
     try:
-        _check_paf(args.paf, args.gpus, args.orientations or [(args.reverse, args.complement)], args.slice_options)
+        _check_paf(args.paf, args.gpus, args.orientations or [(args.reverse, args.complement)], args.slice_options, args.cs)
     except ValueError as e:
         ap.error(str(e))
     return args
@@ -663,7 +707,8 @@ def rank_main(argv) -> int:
                                         max_cardinality=args.max_cardinality, reverse=args.reverse,
                                         complement=args.complement, skip_masked=args.skip_masked)
         asked = dict(compute_score=args.compute_score, prefix=args.prefix, with_sequences=args.with_sequences,
-                     reader="host" if args.host_reader else None, writer="host" if args.host_writer else None, paf=args.paf)
+                     reader="host" if args.host_reader else None, writer="host" if args.host_writer else None,
+                     paf=args.cs or args.paf)
         if args.orientations:
             out = search_orientations(args.files, args.orientations, settings, dist, device_index, **asked)
             texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])

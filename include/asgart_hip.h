@@ -701,6 +701,42 @@ int32_t asgart_paf_records(int32_t device, const uint64_t *fam_offsets, int64_t 
  * workgroup, the most runs one workgroup's range can hold (a run is two bytes at least), bytes of the file a workgroup owns
  * (its LDS image; workgroup i writes the bytes [i * stage_bytes, (i + 1) * stage_bytes) of the file). */
 void asgart_paf_geometry(uint64_t *block_threads, uint64_t *runs_per_block, uint64_t *stage_bytes);
+/* The same file with minimap2's difference string: a row of asgart_paf_records, byte for byte, with one more column before
+ * the `\n`, `\tcs:Z:<CS>`: not only where the two arms differ, as the CIGAR says, but how.  The device and the text are the
+ * index's; cs_mode 1 is the short form, 2 the long one.  Every other argument is asgart_paf_records', and so is the result.
+ * CS is the concatenation of the texts of the row's runs, in the order of the CIGAR: as given for a `+` row, reversed for a
+ * `-` row.  Run t of duplication q = (left, right, left_length ll, right_length rl), n = run_len[t] bases long, starts at the
+ * arm offsets
+ *    i_t = the sum of run_len over the row's runs BEFORE t (in the order given) with run_op `=`, `X` or `I`,
+ *    j_t = the same sum for `=`, `X` or `D`,
+ * and stands for the base positions v = 0 .. n-1 with
+ *    row              query byte Q(v)                          target byte T(v)
+ *    `+` (flag 0)     text[left + i_t + v]                     text[right + j_t + v]
+ *    `-` (flag 3)     comp(text[left + i_t + n - 1 - v])       text[right + rl - j_t - n + v]
+ * comp swaps ACGT and acgt and keeps every other byte (the complement of asgart_compute_scores); low maps `A`..`Z` to
+ * `a`..`z` and keeps every other byte.  On a `-` row the string runs along the target's forward strand and the query is shown
+ * reverse-complemented, as minimap2 does.  The text of a run:
+ *    `=`   short: `:` and the decimal n.  Long: `=` and T(0 .. n-1) as stored
+ *    `X`   for each v: `*`, low(T(v)), low(Q(v))
+ *    `I`   `+` and low(Q(0 .. n-1))        (a left-arm base without a partner)
+ *    `D`   `-` and low(T(0 .. n-1))
+ * The writer prints what the runs say and compares no bases: an `X` over equal bytes prints two equal letters.  Example: the
+ * text `ACGTTAGC` `GG` `ACCTAGCA`, the duplication (0, 10, 8, 8), flag 0, runs `2=1I1X4=1D`: `:2+g*ct:4-a`, long
+ * `=AC+g*ct=TAGC-a`; with `TGCTAGGT` as the right arm and flag 3 the row's CIGAR is `1D4=1X1I2=` and its cs `-t:4*ga+c:2`,
+ * long `-t=GCTA*ga+c=GT`.
+ * Checked beyond the checks of asgart_paf_records, for the duplications with a row only (ASGART_E_ARG, the message names
+ * the first such duplication): cs_mode other than 1 or 2 and idx NULL (before anything else); an arm that reaches past the
+ * text; and, on the device, behind the layout and before a byte is written, a run_op outside `=XID`, a run_len of 0, runs
+ * that do not consume exactly left_length and right_length bases.  A refused call leaves nothing on the device. */
+int32_t asgart_paf_records_cs(asgart_index *idx, int32_t cs_mode, const uint64_t *fam_offsets, int64_t n_families,
+                              const asgart_proto_sd *sds, const uint8_t *flags, const uint8_t *status,
+                              const uint32_t *distance, const int32_t *chr, const uint64_t *chr_pos, int64_t n_sd,
+                              const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
+                              const uint8_t *name_bytes, const uint64_t *name_offsets, const uint64_t *name_length,
+                              int64_t n_names, asgart_export **out);
+/* asgart_paf_geometry's three sizes, which hold for asgart_paf_records_cs too, and solo_bytes: the most bytes of one run's
+ * cs text inside a workgroup's range that one thread composes alone; a run with more is composed by the whole workgroup. */
+void asgart_paf_cs_geometry(uint64_t *block_threads, uint64_t *runs_per_block, uint64_t *stage_bytes, uint64_t *solo_bytes);
 /* An array of f32 rendered on the device as the exporters print an identity: the shortest decimal digits that read back
  * as the same f32, in one of two forms.
  *   ASGART_F32_JSON      serde_json's (ryu's pretty printer; `identity` in exporters.rs:12-25): `97.3`, `100.0`, `0.0`,
@@ -844,6 +880,9 @@ int32_t asgart_searcher_cache_get(asgart_index *idx, const uint8_t *patterns8, i
 int32_t asgart_searcher_search(asgart_index *idx, const uint8_t *patterns, int64_t n_pat,
                                uint64_t k, uint64_t *lo, uint64_t *hi);
 int32_t asgart_sa_read(asgart_index *idx, uint64_t lo, uint64_t hi, int64_t *out);
+/* The bytes [lo, hi) of the index's normalised text into out[hi - lo] (an index built by the device FASTA reader is the only
+ * copy of it: a host writer of cs:Z: tags reads the arms back with this).  lo > hi or hi past the text: ASGART_E_ARG. */
+int32_t asgart_index_read_text(asgart_index *idx, uint64_t lo, uint64_t hi, uint8_t *out);
 
 /* Per-probe filtered hit lists exactly as the automaton consumes them
  * (reference src/automaton.rs:96-117), for all chunks concatenated: probe j of

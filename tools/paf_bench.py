@@ -1,7 +1,7 @@
 """The PAF file of a list of alignments written two ways: align.paf_text (the host: one format operation per run) and
 align.paf_text_gpu (asgart_paf_records, csrc/paf.hip).
 
-    python tools/paf_bench.py [out.json] [--quick]
+    python tools/paf_bench.py [out.json] [--quick] [--cs short|long]
 
 Synthetic Alignments, no index: rows whose runs alternate between `=` (geometric lengths, mean 60) and an edit (`X`, `I` or
 `D`, geometric, mean 1.4), a third of them `-` rows, on a strand of 24 fragments.  Three sizes: 512 rows with 80 536 runs (the
@@ -16,6 +16,10 @@ Per size, both writers in this process on this box, medians of 5 with the spread
              -> str, what the drivers return); device_s = call + decode, what a driver pays instead of host_s
   identical  the two texts are equal
   device_wins  the reader's rule for a default: the device median is below the host's by more than both spreads
+--cs short|long: both writers add the cs:Z: column (align.paf_text(cs=, text=) against asgart_paf_records_cs).  The bases
+come from a random text of TEXT_BYTES (ACGT, 2 % N) that is indexed once; the arms lie anywhere in it, on a strand of 24
+fragments of that text, and the runs of a row consume its arms exactly, as the writer demands.  The same three sizes, the
+same figures; the index build is not part of any of them.
 Prints one JSON line with the commit; --quick: two small sizes (a rehearsal)."""
 import io
 import json
@@ -35,10 +39,19 @@ from asgart_amd import align  # noqa: E402
 from asgart_amd.prep import Start  # noqa: E402
 
 FRAGMENT = 100_000_000
+TEXT_BYTES = 1 << 23                                               # of the random text behind --cs, its `$` included
 
 
-def make_alignments(rows: int, runs: int, seed: int):
-    """-> (offs, sds, flags, strand, aln): `rows` duplications in families of about 2, `runs` runs in all"""
+def make_text(seed: int = 20) -> np.ndarray:
+    rng = np.random.default_rng(seed)
+    text = np.frombuffer(b"ACGTN", np.uint8)[rng.choice(5, TEXT_BYTES, p=[0.245, 0.245, 0.245, 0.245, 0.02])].copy()
+    text[-1] = ord("$")
+    return text
+
+
+def make_alignments(rows: int, runs: int, seed: int, n_text: int = 0):
+    """-> (offs, sds, flags, strand, aln): `rows` duplications in families of about 2, `runs` runs in all.  n_text: the arms
+    lie in a text of that many bytes (before its last one) and the strand's 24 fragments cover it"""
     rng = np.random.default_rng(seed)
     counts = rng.multinomial(runs, np.full(rows, 1.0 / rows))
     run_offsets = np.zeros(rows + 1, np.uint64)
@@ -52,11 +65,16 @@ def make_alignments(rows: int, runs: int, seed: int):
     edits = np.where(match, 0, run_len).astype(np.uint64)
     sums = [np.add.reduceat(np.append(v, 0), np.minimum(run_offsets[:-1], runs).astype(np.int64)) * (counts > 0)
             for v in (on_left, on_right, edits)]
-    strand = asgart_amd.Strand("synthetic", None, [Start(f"chr{i + 1}", i * FRAGMENT, FRAGMENT) for i in range(24)])
+    fragment = n_text // 24 if n_text else FRAGMENT
+    strand = asgart_amd.Strand("synthetic", None, [Start(f"chr{i + 1}", i * fragment, fragment) for i in range(24)])
     sds = np.zeros((rows, 4), np.uint64)
-    sds[:, 0] = rng.integers(0, 24 * FRAGMENT - 100_000, rows)
-    sds[:, 1] = rng.integers(0, 24 * FRAGMENT - 100_000, rows)
     sds[:, 2], sds[:, 3] = sums[0], sums[1]
+    if n_text:
+        sds[:, 0] = rng.integers(0, n_text - sds[:, 2].astype(np.int64))
+        sds[:, 1] = rng.integers(0, n_text - sds[:, 3].astype(np.int64))
+    else:
+        sds[:, 0] = rng.integers(0, 24 * FRAGMENT - 100_000, rows)
+        sds[:, 1] = rng.integers(0, 24 * FRAGMENT - 100_000, rows)
     flags = np.where(rng.random(rows) < 1 / 3, 3, 0).astype(np.uint8)
     cuts = np.sort(rng.choice(np.arange(1, rows), max(rows // 2 - 1, 0), replace=False)) if rows > 2 else np.zeros(0, np.int64)
     offs = np.concatenate([[0], cuts, [rows]]).astype(np.uint64)
@@ -69,8 +87,10 @@ def spread(xs, digits=4):
     return {"median": round(statistics.median(xs), digits), "spread": round(max(xs) - min(xs), digits)}
 
 
-def bench_case(rows: int, runs: int, seed: int, sample_rows: int, reps: int = 5) -> dict:
-    offs, sds, flags, strand, aln = make_alignments(rows, runs, seed)
+def bench_case(rows: int, runs: int, seed: int, sample_rows: int, reps: int = 5, cs=None, text=None, index=None) -> dict:
+    offs, sds, flags, strand, aln = make_alignments(rows, runs, seed, len(text) if cs else 0)
+    host_kw = dict(cs=cs, text=text) if cs else {}
+    dev_kw = dict(cs=cs, index=index) if cs else {}
     # the host: the whole list, or its first sample_rows rows scaled by runs
     scaled = sample_rows < rows
     k = min(sample_rows, rows)
@@ -78,22 +98,22 @@ def bench_case(rows: int, runs: int, seed: int, sample_rows: int, reps: int = 5)
     host = []
     for _ in range(reps):
         t0 = time.perf_counter()
-        want = align.paf_text([0, k], sds[:k], flags[:k], strand, part)
+        want = align.paf_text([0, k], sds[:k], flags[:k], strand, part, **host_kw)
         host.append((time.perf_counter() - t0) * runs / part_runs)
     whole_once = None
     if scaled:
         t0 = time.perf_counter()
-        want = align.paf_text(offs, sds, flags, strand, aln)
+        want = align.paf_text(offs, sds, flags, strand, aln, **host_kw)
         whole_once = round(time.perf_counter() - t0, 4)
     else:
-        want = align.paf_text(offs, sds, flags, strand, aln)          # (with the families of the whole list)
-    align._paf_text_device(offs, sds, flags, strand, aln)            # (the first call loads the code object)
+        want = align.paf_text(offs, sds, flags, strand, aln, **host_kw)   # (with the families of the whole list)
+    align._paf_text_device(offs, sds, flags, strand, aln, **dev_kw)  # (the first call loads the code object)
     stages = {s: [] for s in ("names", "upload", "kernels", "copy_back", "call", "decode")}
     device = []
     for _ in range(reps):
         ms = {}
         t0 = time.perf_counter()
-        data = align._paf_text_device(offs, sds, flags, strand, aln, 0, io.StringIO(), ms)
+        data = align._paf_text_device(offs, sds, flags, strand, aln, 0, io.StringIO(), ms, **dev_kw)
         t1 = time.perf_counter()
         got = str(memoryview(data), "utf-8")
         t2 = time.perf_counter()
@@ -111,6 +131,9 @@ def bench_case(rows: int, runs: int, seed: int, sample_rows: int, reps: int = 5)
 
 def main():
     args = sys.argv[1:]
+    cs = args[args.index("--cs") + 1] if "--cs" in args else None
+    if cs not in (None, "short", "long"):
+        sys.exit("--cs short|long")
     out_path = next((a for a in args if a.endswith(".json")), None)
     sizes = [(64, 5_000, 64), (3_000, 90_000, 500)] if "--quick" in args else \
         [(512, 80_536, 512), (8_192, 1 << 20, 8_192), (140_113, 140_113 * 150, 2_000)]
@@ -118,10 +141,19 @@ def main():
     threads, per_block, stage = asgart_amd.paf_geometry()
     res = {"commit": commit or None, "reps": 5,
            "geometry": {"block_threads": threads, "runs_per_block": per_block, "stage_bytes": stage}, "cases": []}
+    text = index = None
+    if cs:
+        res["cs"] = cs
+        res["geometry"]["solo_bytes"] = asgart_amd.paf_cs_geometry()[3]
+        res["text_bytes"] = TEXT_BYTES
+        text = make_text()
+        index = asgart_amd.Index(text, None)
     for i, (rows, runs, sample) in enumerate(sizes):
-        case = bench_case(rows, runs, 21 + i, sample)
+        case = bench_case(rows, runs, 21 + i, sample, cs=cs, text=text, index=index)
         res["cases"].append(case)
         print(json.dumps(case), file=sys.stderr, flush=True)
+    if index is not None:
+        index.close()
     line = json.dumps(res)
     print(line, flush=True)
     if out_path:
