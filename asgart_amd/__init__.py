@@ -25,7 +25,7 @@ __all__ = [
     "load_library", "library_path", "ABI_SYMBOLS", "sa_build64", "search_duplications_multi", "merge_shards",
     "score_owners", "score_costs", "compute_scores_multi", "Source", "compute_scores_flags_multi", "orientation_flags",
     "export_records", "export_geometry", "f32_shortest", "f32_pow10_table", "EXPORT_FORMATS",
-    "ResultScan", "result_geometry", "E_REFUSED", "Alignments", "align_geometry", "align_bytes",
+    "ResultScan", "result_geometry", "E_REFUSED", "Alignments", "align_geometry", "align_bytes", "align_bytes_banded",
     "paf_records", "paf_geometry", "paf_records_cs", "paf_cs_geometry", "CS_MODES",
 ]
 
@@ -60,6 +60,7 @@ ABI_SYMBOLS = (
     "asgart_result_free", "asgart_result_geometry",
     "asgart_align_duplications", "asgart_alignment_counts", "asgart_alignment_copy", "asgart_alignment_timings",
     "asgart_alignment_free", "asgart_align_geometry", "asgart_align_bytes",
+    "asgart_align_duplications_banded", "asgart_alignment_rounds", "asgart_align_bytes_banded",
     "asgart_paf_records", "asgart_paf_geometry", "asgart_paf_records_cs", "asgart_paf_cs_geometry",
     "asgart_index_read_text",
 )
@@ -343,6 +344,13 @@ def load_library() -> C.CDLL:
         L.asgart_align_geometry.restype = None
         L.asgart_align_bytes.argtypes = [vp, C.c_int64, C.c_int32, vp]
         L.asgart_align_bytes.restype = C.c_int32
+    if hasattr(L, "asgart_align_duplications_banded"):
+        L.asgart_align_duplications_banded.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, vp, C.c_uint64, C.POINTER(vp)]
+        L.asgart_align_duplications_banded.restype = C.c_int32
+        L.asgart_alignment_rounds.argtypes = [vp, C.POINTER(C.c_uint32), u64p]
+        L.asgart_alignment_rounds.restype = C.c_int32
+        L.asgart_align_bytes_banded.argtypes = [vp, C.c_int64, C.c_int32, vp, vp]
+        L.asgart_align_bytes_banded.restype = C.c_int32
     if hasattr(L, "asgart_paf_records"):
         L.asgart_paf_records.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp,
                                          C.c_int64, C.POINTER(vp)]
@@ -620,19 +628,30 @@ class Index:
         return out
 
     def align(self, sds: np.ndarray, flags: Optional[np.ndarray] = None, inclusive: bool = False, budget: int = 0,
-              timings: Optional[list] = None) -> "Alignments":
+              timings: Optional[list] = None, max_distance=None, rounds: Optional[list] = None) -> "Alignments":
         """One optimal unit-cost alignment of the two arms of every duplication (asgart_align_duplications): the
         canonical path of include/asgart_hip.h as run-length-encoded operations.  flags: as compute_scores_flags.
         inclusive: the arms are [p ..= p + length], the strings compute_scores compares, instead of [p, p + length).
         budget: device bytes the checkpoints of one batch may take (0: half of what is free); a duplication that alone
         needs more (align_bytes) is refused -- status 0, no runs, NaN identity -- and no result depends on it otherwise.
-        timings: a list that receives the milliseconds of upload, forward pass, traceback + compaction and copy."""
+        timings: a list that receives the milliseconds of upload, forward pass, traceback + compaction and copy.
+        max_distance: None walks the whole edit matrix of every duplication.  Anything else walks a diagonal corridor of it
+        (asgart_align_duplications_banded; the budget is then in align_bytes_banded's bytes): an integer or a uint32 array
+        bounds the edits of every duplication or of each -- one with more gets status 2, no runs, NaN identity -- and
+        "auto" lets the library choose and widen the bounds until none is beyond its own.  Every status-1 entry is
+        bit-equal to the entry without max_distance.
+        rounds: a list that receives [passes over the list, cells of the forward passes] (asgart_alignment_rounds)."""
         L = load_library()
         sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
         flags = _score_flags(flags, len(sds))
         h = C.c_void_p()
-        _check(L.asgart_align_duplications(self._h, _ptr(sds), _ptr(flags), len(sds), int(bool(inclusive)), int(budget),
-                                           C.byref(h)))
+        if max_distance is None:
+            _check(L.asgart_align_duplications(self._h, _ptr(sds), _ptr(flags), len(sds), int(bool(inclusive)), int(budget),
+                                               C.byref(h)))
+        else:
+            bounds = None if isinstance(max_distance, str) and max_distance == "auto" else _bounds(max_distance, len(sds))
+            _check(L.asgart_align_duplications_banded(self._h, _ptr(sds), _ptr(flags), len(sds), int(bool(inclusive)),
+                                                      None if bounds is None else _ptr(bounds), int(budget), C.byref(h)))
         try:
             n, nr, nref = C.c_uint64(), C.c_uint64(), C.c_uint64()
             L.asgart_alignment_counts(h, C.byref(n), C.byref(nr), C.byref(nref))
@@ -644,6 +663,10 @@ class Index:
                 ms = (C.c_double * 4)()
                 _check(L.asgart_alignment_timings(h, ms))
                 timings[:] = list(ms)
+            if rounds is not None:
+                nr_, nc_ = C.c_uint32(), C.c_uint64()
+                _check(L.asgart_alignment_rounds(h, C.byref(nr_), C.byref(nc_)))
+                rounds[:] = [int(nr_.value), int(nc_.value)]
             return out
         finally:
             L.asgart_alignment_free(h)
@@ -740,7 +763,8 @@ class Index:
 @dataclass
 class Alignments:
     """The arrays of asgart_alignment_copy: the runs of duplication q are run_offsets[q] .. run_offsets[q + 1] of run_len
-    and run_op (the bytes '=', 'X', 'I', 'D'); distance uint32, identity float32, status uint8 (0: refused)."""
+    and run_op (the bytes '=', 'X', 'I', 'D'); distance uint32, identity float32, status uint8 (1: aligned; 0: refused by
+    the budget; 2: more edits than max_distance -- both without runs, distance 0xFFFFFFFF, identity NaN)."""
 
     run_offsets: np.ndarray
     run_len: np.ndarray
@@ -764,7 +788,7 @@ class Alignments:
                           self.distance[lo:hi], self.identity[lo:hi], self.status[lo:hi])
 
     def cigar(self, q: int) -> str:
-        """`812=1X40=3I...`; empty for a refused duplication."""
+        """`812=1X40=3I...`; empty for a refused duplication and for one beyond its max_distance."""
         return "".join(f"{n}{op}" for n, op in self.ops(q))
 
 
@@ -780,6 +804,28 @@ def align_bytes(sds: np.ndarray, inclusive: bool = False) -> np.ndarray:
     sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
     out = np.zeros(len(sds), dtype=np.uint64)
     _check(load_library().asgart_align_bytes(_ptr(sds), len(sds), int(bool(inclusive)), _ptr(out)))
+    return out
+
+
+def _bounds(max_distance, n: int) -> np.ndarray:
+    """max_distance of Index.align as one uint32 per duplication: an integer for all, or an array of n."""
+    if isinstance(max_distance, str):
+        raise ValueError('max_distance: None, "auto", an integer or one uint32 per duplication')
+    v = np.asarray(max_distance)
+    if v.ndim == 0:
+        v = np.full(n, v)
+    if v.shape != (n,) or not np.issubdtype(v.dtype, np.integer) or (len(v) and (v.min() < 0 or v.max() > 0xFFFFFFFF)):
+        raise ValueError(f"max_distance: {n} duplications need one bound, or {n}, each an integer in [0, 2^32)")
+    return np.ascontiguousarray(v, dtype=np.uint32)
+
+
+def align_bytes_banded(sds: np.ndarray, max_distance, inclusive: bool = False) -> np.ndarray:
+    """The checkpoint bytes Index.align(max_distance=) needs for each duplication within its bound
+    (asgart_align_bytes_banded; host code, no device)."""
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    bounds = _bounds(max_distance, len(sds))
+    out = np.zeros(len(sds), dtype=np.uint64)
+    _check(load_library().asgart_align_bytes_banded(_ptr(sds), len(sds), int(bool(inclusive)), _ptr(bounds), _ptr(out)))
     return out
 
 

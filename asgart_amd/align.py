@@ -3,7 +3,10 @@
 Index.align (asgart_align_duplications, csrc/align.hip) recovers one optimal unit-cost path per duplication on the GPU.
 This module states the same rule on the host, for the tests to compare byte for byte, and turns the result into text:
 
-    align_host   the full edit matrix in numpy, row by row, then the canonical trace (include/asgart_hip.h)
+    align_host   the full edit matrix in numpy, row by row, then the canonical trace (include/asgart_hip.h); with
+                 max_distance the matrix of the corridor, everything outside it a large constant, or EXCEEDS
+    corridor     the columns every band computes for a bound on the distance, and the checkpoint bytes (the host
+                 statement of csrc/align_dev.hpp: BandedShape); auto_bounds: the bounds the automatic mode goes through
     replay       does a list of runs consume exactly both arms, `=` on equal bytes and `X` on unequal ones?  -> its edits
     paf_text     one PAF row per aligned duplication: query = left arm, target = right arm
     paf_text_gpu the same bytes, written on the GPU (asgart_paf_records, csrc/paf.hip)
@@ -91,10 +94,82 @@ def edit_matrix(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     return D
 
 
-def align_host(text, sd, flag: int = 0, inclusive: bool = False) -> Tuple[List[Run], int]:
-    """(runs, distance) of one duplication: what Index.align must return for it."""
+BIG = 1 << 30        # what a cell outside the corridor counts as (include/asgart_hip.h)
+EXCEEDS = "exceeds"  # align_host's answer for a duplication with more edits than max_distance
+# the automatic bounds (csrc/align_dev.hpp: kAlignAutoFloor, kAlignAutoShare, kAlignAutoFactor; reasoned, not swept)
+AUTO_FLOOR, AUTO_SHARE, AUTO_FACTOR = 64, 64, 4
+
+
+def _geometry(band: Optional[int], tile: Optional[int]) -> Tuple[int, int]:
+    if band is None or tile is None:
+        from . import align_geometry
+        rows, _, cols = align_geometry()
+        band, tile = band or rows, tile or cols
+    return int(band), int(tile)
+
+
+def corridor(n: int, m: int, T: int, band: Optional[int] = None, tile: Optional[int] = None):
+    """The corridor of arms of n and m bases for the bound T -> (ranges, bytes): ranges[b] = (lo, hi), the columns band b
+    computes (its rows are b band + 1 .. min((b + 1) band, n)), and the checkpoint bytes asgart_align_bytes_banded gives.
+    ranges is None when T < |m - n| (more than T edits without any work) and empty for an empty arm; bytes are 0 then.
+    band, tile: the rows of a band and the columns W between two column checkpoints (None: asgart_align_geometry's)."""
+    band, tile = _geometry(band, tile)
+    n, m, T = int(n), int(m), int(T)
+    if T < abs(m - n):
+        return None, 0
+    if n == 0 or m == 0:
+        return [], 0
+    e = (T - abs(m - n)) // 2
+    kmin, kmax = min(0, m - n) - e, max(0, m - n) + e
+    n_bands = -(-n // band)
+    ranges = [(max(1, b * band + 1 + kmin), min(m, min((b + 1) * band, n) + kmax)) for b in range(n_bands)]
+    wmax = min(m, band + kmax - kmin)
+    return ranges, 4 * n_bands * band * (-(-(wmax - 1) // tile)) + 4 * (n_bands - 1) * (wmax + 1)
+
+
+def auto_bounds(n: int, m: int) -> List[int]:
+    """The bounds the automatic mode tries for arms of n and m bases, in order; the last one, n + m, is the whole matrix."""
+    bounds = [min(abs(m - n) + max(AUTO_FLOOR, max(n, m) // AUTO_SHARE), n + m)]
+    while bounds[-1] < n + m:
+        bounds.append(min(AUTO_FACTOR * bounds[-1], n + m))
+    return bounds
+
+
+def corridor_matrix(a: np.ndarray, b: np.ndarray, T: int, band: Optional[int] = None) -> np.ndarray:
+    """edit_matrix with every cell outside the corridor of T at BIG or more (row 0 is kept; column 0 where a band starts at
+    column 1).  T >= |m - n|."""
+    n, m = len(a), len(b)
+    ranges, _ = corridor(n, m, T, band)
+    D = np.full((n + 1, m + 1), BIG, dtype=np.int64)
+    ramp = np.arange(m + 1, dtype=np.int64)
+    D[0] = ramp
+    band, _ = _geometry(band, None)
+    for i in range(1, n + 1):
+        lo, hi = ranges[(i - 1) // band]
+        t = np.full(m + 1, BIG, dtype=np.int64)
+        t[0] = i if lo == 1 else BIG
+        t[lo:hi + 1] = np.minimum(D[i - 1, lo - 1:hi] + (b[lo - 1:hi] != a[i - 1]), D[i - 1, lo:hi + 1] + 1)
+        row = np.minimum.accumulate(t - ramp) + ramp
+        D[i, 0] = t[0]
+        D[i, lo:hi + 1] = row[lo:hi + 1]
+    return D
+
+
+def align_host(text, sd, flag: int = 0, inclusive: bool = False, max_distance: Optional[int] = None):
+    """(runs, distance) of one duplication: what Index.align must return for it.  max_distance: the same from the matrix of
+    the corridor (corridor_matrix), or EXCEEDS when the distance is more than max_distance: what
+    Index.align(max_distance=) must say (status 2)."""
     a, b = arms(text, sd, flag, inclusive)
-    D = edit_matrix(a, b)
+    if max_distance is None:
+        D = edit_matrix(a, b)
+    elif int(max_distance) < abs(len(b) - len(a)):
+        return EXCEEDS
+    elif len(a) == 0 or len(b) == 0:
+        D = edit_matrix(a, b)   # one arm is empty: the other one, base by base, within any bound of its length
+    else:
+        D = corridor_matrix(a, b, int(max_distance))
+        if D[len(a)][len(b)] > int(max_distance):
+            return EXCEEDS
     return encode_runs(trace(D, a, b)), int(D[len(a)][len(b)])
 
 
@@ -214,6 +289,10 @@ def _check_cs(cs: Optional[str]) -> None:
         raise ValueError("cs: None, 'short' or 'long'")
 
 
+# why a duplication has no alignment, by its status
+_REFUSAL = {0: "memory budget", 2: "bound on the edits"}
+
+
 def paf_text(offs, sds, flags, strand, aln, stderr=None, cs: Optional[str] = None, text=None) -> str:
     """One PAF row per aligned duplication of a result: offs / sds the family arrays, flags one byte per duplication, strand
     the run's Strand (its map names the fragments), aln the Alignments of Index.align(sds, flags, inclusive=False).
@@ -223,7 +302,8 @@ def paf_text(offs, sds, flags, strand, aln, stderr=None, cs: Optional[str] = Non
     direct duplication and `-` for a reversed and complemented one; on `-` the ORDER of the runs is reversed, because
     PAF's CIGAR runs along the target's forward strand, and the operations stay.  Column 10 is the number of `=`, column 11
     the sum of all run lengths, column 12 is 255; tags NM:i:<distance>, fm:i:<family>, cg:Z:<cigar>.  A reversed-only or
-    complemented-only duplication has no PAF strand: ValueError.  A refused duplication gets no row and is named on stderr.
+    complemented-only duplication has no PAF strand: ValueError.  A refused duplication (status 0, or 2: beyond the bound
+    its alignment was given) gets no row and is named on stderr.
     cs: "short" or "long" appends the column `cs:Z:` + cs_text(text, ...) to every row; `text` is then the text the
     duplications lie in (ValueError without it)."""
     _check_cs(cs)
@@ -252,9 +332,9 @@ def paf_text(offs, sds, flags, strand, aln, stderr=None, cs: Optional[str] = Non
     family = np.repeat(np.arange(len(offs) - 1), np.diff(offs))
     rows = []
     for q, (left, right, ll, rl) in enumerate(sds.tolist()):
-        if not aln.status[q]:
-            print(f"paf: duplication {q} (family {int(family[q])}) was refused by the alignment's memory budget: no row",
-                  file=stderr if stderr is not None else sys.stderr)
+        if aln.status[q] != 1:
+            print(f"paf: duplication {q} (family {int(family[q])}) was refused by the alignment's "
+                  f"{_REFUSAL[int(aln.status[q])]}: no row", file=stderr if stderr is not None else sys.stderr)
             continue
         runs = aln.ops(q)
         tag = [] if cs is None else ["cs:Z:" + cs_text(text, (left, right, ll, rl), int(flags[q]), runs, cs == "long")]
@@ -296,12 +376,13 @@ def _paf_text_device(offs, sds, flags, strand, aln, device: int = 0, stderr=None
     names = [c.name.encode("utf-8") for c in strand.map] + [b"unknown"]
     name_length = np.array([c.length for c in strand.map] + [total], dtype=np.uint64)
     chr_, chr_pos = locate_arms(sds, strand)
-    status = np.asarray(aln.status, dtype=np.uint8).reshape(-1)
+    why = np.asarray(aln.status, dtype=np.uint8).reshape(-1)
+    status = (why == 1).astype(np.uint8)   # (the library writes no row for status 0: beyond its bound is no row either)
     refused = np.flatnonzero(status == 0)
     if len(refused):
         family = np.searchsorted(offs, refused, side="right") - 1
         for q, f in zip(refused.tolist(), family.tolist()):
-            print(f"paf: duplication {q} (family {f}) was refused by the alignment's memory budget: no row",
+            print(f"paf: duplication {q} (family {f}) was refused by the alignment's {_REFUSAL[int(why[q])]}: no row",
                   file=stderr if stderr is not None else sys.stderr)
     t1 = time.perf_counter()
     ms: list = []

@@ -18,6 +18,14 @@
 //   compact   reverses the slots into CSR order.
 // The host packs the duplications, largest first, into batches whose checkpoints fit the caller's budget; a duplication that
 // alone exceeds it is refused, the others are unaffected, and no result depends on the budget or on the batching.
+//
+// asgart_align_duplications_banded is the same three stages inside a diagonal corridor: for a bound on the distance every
+// band walks the column rectangle around the diagonals a path within the bound can reach, and keeps checkpoints of that
+// width (align_dev.hpp: BandedShape; include/asgart_hip.h has the rule and the proofs that the runs are the same runs).
+// The forward and the traceback kernel are templates of one flag: <false> is the code above, on the path and in the
+// registers it had before the corridor (profiles/align_banded_resources.txt), <true> moves the walk's columns to the rectangle.  A duplication beyond its bound leaves
+// between the two kernels (the host reads the distances), so slot counts and compaction see aligned ones only.  Without
+// bounds from the caller the host runs rounds: the library's first bound, then four times as much for those beyond it.
 // Integer work throughout; plain vector loads and stores and LDS.
 // The systolic step of both kernels, with and without the direction bits, is lev_dev.hpp's (lev_inputs, lev_column,
 // lev_store_bottom); the right arm, the identity and the checks of the list are there too, shared with score.hip.
@@ -46,9 +54,29 @@ struct Batch {
     const uint64_t *ck_off;
     uint64_t n;
     int inclusive;
+    const uint32_t *bound;    // max_distance of every duplication of the list (the corridor kernels only)
 };
 
+// D[band][j] for a band of the corridor: the bottom row of the band above where that band has column j (its columns
+// plo .. phi), kAlignBig elsewhere.  kFresh: written by this wave one band ago, read past the vector L1.
+template <bool kFresh>
+__device__ __forceinline__ uint32_t corridor_top(const uint32_t *top_row, uint32_t plo, uint32_t phi, uint32_t j) {
+    if (j < plo || j > phi) return kAlignBig;
+    if constexpr (kFresh) return __atomic_load_n(&top_row[j - plo + 1u], __ATOMIC_RELAXED);
+    return top_row[j - plo + 1u];
+}
+
+// the column left of a corridor band's rectangle
+__device__ __forceinline__ void corridor_first_column(uint32_t (&col)[kLevRows]) {
+#pragma unroll
+    for (int r = 0; r < kLevRows; ++r) col[r] = kAlignBig;
+}
+
 // ---- forward: distances and checkpoints (the band loop written out, as in levenshtein_kernel) -----------------------
+// kBanded: every band walks the columns lo .. hi of its corridor rectangle (align_dev.hpp: BandedShape) instead of 1 .. m;
+// a step's column is then counted from lo, and what lies outside the rectangles is kAlignBig.  A distance beyond the bound
+// is stored as 0xFFFFFFFF.
+template <bool kBanded>
 __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_t *__restrict__ text, Batch bt,
                                                                     uint32_t *__restrict__ ck,
                                                                     unsigned long long *__restrict__ cursor,
@@ -70,8 +98,14 @@ __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_
         const uint8_t *A = text + sd.left;
         const RightArm rb = right_arm(text + sd.right, lb, orientation_of(bt.flags, item, 0, 0));
         uint32_t *colck = ck + bt.ck_off[k];
-        uint32_t *rowck = colck + g.col_words();
-        const uint64_t row_stride = g.m + 1u;
+        BandedShape c{};
+        uint32_t bound = 0;
+        if constexpr (kBanded) {
+            bound = bt.bound[item];
+            c = banded_shape(sd, bt.inclusive, bound);
+        }
+        uint32_t *rowck = colck + (kBanded ? c.col_words() : g.col_words());
+        const uint64_t row_stride = kBanded ? c.row_stride : g.m + 1u;
         uint32_t result = 0;
         uint32_t bi = 0;
         for (uint32_t band = 0; band < la && lb > 0; band += kLevBand, ++bi) {
@@ -81,34 +115,56 @@ __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_
             uint32_t *bottom_row = rowck + (uint64_t)bi * row_stride;                         // (written if more_bands)
             uint32_t a[R], col[R];
             lev_rows(a, i0, la, A);
-            lev_first_column(col, i0);
             uint32_t diag_in = i0;       // D[i0][j-1] for the lane's next column
+            uint32_t lo = 1, hi = lb, plo = 1, phi = 0, ck0 = 0;  // the band's columns, those of the band above, the first checkpoint
+            if constexpr (kBanded) {
+                lo = c.lo(bi), hi = c.hi(bi), ck0 = c.first_ck(bi);
+                if (bi) plo = c.lo(bi - 1u), phi = c.hi(bi - 1u);
+                if (lo == 1u) {
+                    lev_first_column(col, i0);
+                } else {  // D[..][lo - 1] is outside, but for D[band][lo - 1], which the band above may have
+                    corridor_first_column(col);
+                    diag_in = lane ? kAlignBig : (band == 0 ? lo - 1u : corridor_top<true>(top_row, plo, phi, lo - 1u));
+                }
+            } else {
+                lev_first_column(col, i0);
+            }
+            const uint32_t wb = hi - lo + 1u;  // (lb without a corridor)
             uint32_t last_out = 0;       // D[i0+R][j] of the column just done
             uint32_t b_pipe = 0;         // base of the lane's current column (travels down the lanes)
             uint32_t top_chunk = 0, b_chunk = 0, out_chunk = 0;
-            const uint32_t n_steps = lb + 63u;
+            const uint32_t n_steps = (kBanded ? wb : lb) + 63u;
             for (uint32_t s = 0; s < n_steps; ++s) {
                 if ((s & 63u) == 0u) {  // 64 columns of the top boundary and of the right arm at a time
-                    const uint32_t j1 = s + 1u + (uint32_t)lane;  // column of lane 0 at step s + lane
-                    // (written by this wave one band ago: read past the vector L1)
-                    top_chunk = band == 0 ? j1 : (j1 <= lb ? __atomic_load_n(&top_row[j1], __ATOMIC_RELAXED) : 0u);
-                    b_chunk = s + (uint32_t)lane < lb ? rb.at(s + (uint32_t)lane) : 0u;
+                    if constexpr (kBanded) {
+                        const uint32_t j1 = lo + s + (uint32_t)lane;  // the chunks start at the rectangle's first column
+                        top_chunk = band == 0 ? j1 : corridor_top<true>(top_row, plo, phi, j1);
+                        b_chunk = j1 <= lb ? rb.at(j1 - 1u) : 0u;
+                    } else {
+                        const uint32_t j1 = s + 1u + (uint32_t)lane;  // column of lane 0 at step s + lane
+                        // (written by this wave one band ago: read past the vector L1)
+                        top_chunk = band == 0 ? j1 : (j1 <= lb ? __atomic_load_n(&top_row[j1], __ATOMIC_RELAXED) : 0u);
+                        b_chunk = s + (uint32_t)lane < lb ? rb.at(s + (uint32_t)lane) : 0u;
+                    }
                 }
                 const LevIn in = lev_inputs(last_out, top_chunk, b_pipe, b_chunk, s, lane);
-                const int64_t j = (int64_t)s - lane + 1;
-                if (j >= 1 && j <= (int64_t)lb) {
+                const int64_t j = (int64_t)s - lane + 1;  // (kBanded: counted from lo)
+                if (j >= 1 && j <= (int64_t)(kBanded ? wb : lb)) {
                     lev_column<false>(a, col, diag_in, in);
                     last_out = col[R - 1];
-                    if ((uint32_t)j == lb && la > i0 && la <= i0 + R) result = lev_row_value(col, i0, la);
+                    const uint32_t ja = kBanded ? lo - 1u + (uint32_t)j : (uint32_t)j;
+                    if (ja == lb && la > i0 && la <= i0 + R) result = lev_row_value(col, i0, la);
                     // a column checkpoint: the lane's 16 values of column j, 64 contiguous bytes
-                    if (((uint32_t)j & (W - 1u)) == 0u && (uint32_t)j < lb) {
-                        uint4 *dst = reinterpret_cast<uint4 *>(colck + (uint64_t)((uint32_t)j / W - 1u) * g.rows_padded + i0);
+                    if ((ja & (W - 1u)) == 0u && ja < (kBanded ? hi : lb)) {
+                        uint4 *dst = reinterpret_cast<uint4 *>(
+                            kBanded ? colck + ((uint64_t)bi * c.ck_per_band + (ja / W - ck0)) * kLevBand + (uint32_t)lane * R
+                                    : colck + (uint64_t)(ja / W - 1u) * g.rows_padded + i0);
 #pragma unroll
                         for (int v4 = 0; v4 < R / 4; ++v4)
                             dst[v4] = make_uint4(col[4 * v4], col[4 * v4 + 1], col[4 * v4 + 2], col[4 * v4 + 3]);
                     }
                 }
-                if (more_bands) lev_store_bottom(last_out, s, lane, lb, out_chunk, bottom_row);
+                if (more_bands) lev_store_bottom(last_out, s, lane, kBanded ? wb : lb, out_chunk, bottom_row);
             }
             // the next band reads what this one wrote (same wave: program order; make it visible)
             __threadfence_block();
@@ -120,6 +176,8 @@ __global__ __launch_bounds__(kFwdThreads) void align_forward_kernel(const uint8_
             const uint32_t owner = ((la - 1u) % kLevBand) / R;  // lane of row la in the last band
             dist = __shfl(result, (int)owner);
         }
+        if constexpr (kBanded)
+            if (dist > bound) dist = 0xFFFFFFFFu;  // more than the bound, and nothing else is known
         if (lane == 0) {
             distance[item] = dist;
             identity[item] = identity_of(sd, dist);
@@ -137,6 +195,9 @@ __global__ __launch_bounds__(kBlock) void align_slot_counts_kernel(const uint32_
 }
 
 // ---- traceback: one wave per duplication, a tile at a time --------------------------------------------------------
+// kBanded: over the forward pass's corridor checkpoints.  A tile is rebuilt where its band's rectangle is: the columns
+// jt0 + 1 .. jt0 + wt, seeded like the forward pass.  (Only duplications within their bound are handed over.)
+template <bool kBanded>
 __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__restrict__ text, Batch bt,
                                                              const uint32_t *__restrict__ ck,
                                                              const uint32_t *__restrict__ distance,
@@ -162,8 +223,10 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
         const uint8_t *A = text + sd.left;
         const RightArm rb = right_arm(text + sd.right, lb, orientation_of(bt.flags, item, 0, 0));
         const uint32_t *colck = ck + bt.ck_off[k];
-        const uint32_t *rowck = colck + g.col_words();
-        const uint64_t row_stride = g.m + 1u;
+        BandedShape c{};
+        if constexpr (kBanded) c = banded_shape(sd, bt.inclusive, bt.bound[item]);
+        const uint32_t *rowck = colck + (kBanded ? c.col_words() : g.col_words());
+        const uint64_t row_stride = kBanded ? c.row_stride : g.m + 1u;
         const uint64_t slot = slot_off[k];
         const uint64_t slot_cap = 2ull * distance[item] + 1ull;
         // the run being collected (every lane keeps the same copy; lane 0 writes) and how many were written
@@ -190,16 +253,33 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
         while (i > 0 && j > 0) {
             const uint32_t b = (i - 1u) / kLevBand, cb = (j - 1u) / W;
             const uint32_t band = b * kLevBand, j0 = cb * W;
-            const uint32_t wt = min(W, lb - j0);  // columns j0+1 .. j0+wt
             const uint32_t *top_row = b ? rowck + (uint64_t)(b - 1u) * row_stride : rowck;  // D[band][..] (read for b > 0 only)
+            uint32_t jt0 = j0, wt = min(W, lb - j0);  // columns jt0+1 .. jt0+wt
+            uint32_t lo = 1, plo = 1, phi = 0;
+            if constexpr (kBanded) {
+                lo = c.lo(b);
+                if (b) plo = c.lo(b - 1u), phi = c.hi(b - 1u);
+                if (j < lo || j > c.hi(b)) {  // (no optimal path leaves the corridor: never, and never a tile without columns)
+                    if (lane == 0) atomicOr(overflow, 1u);
+                    i = j = 0;
+                    run_op = kOpNone;
+                    break;
+                }
+                jt0 = max(j0, lo - 1u);
+                wt = min(j0 + W, c.hi(b)) - jt0;
+            }
             {
                 // rebuild the tile: the forward step, seeded with the column left of the tile and the cell above it
                 const uint32_t i0 = band + (uint32_t)lane * R;
                 uint32_t a[R], col[R];
-                if (cb == 0) {
+                if (jt0 == 0) {
                     lev_first_column(col, i0);
+                } else if (kBanded && j0 < lo) {  // the tile starts at the rectangle's first column
+                    corridor_first_column(col);
                 } else {
-                    const uint4 *src = reinterpret_cast<const uint4 *>(colck + (uint64_t)(cb - 1u) * g.rows_padded + i0);
+                    const uint4 *src = reinterpret_cast<const uint4 *>(
+                        kBanded ? colck + ((uint64_t)b * c.ck_per_band + (cb - c.first_ck(b))) * kLevBand + (uint32_t)lane * R
+                                : colck + (uint64_t)(cb - 1u) * g.rows_padded + i0);
 #pragma unroll
                     for (int v4 = 0; v4 < R / 4; ++v4) {
                         const uint4 v = src[v4];
@@ -212,13 +292,18 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
                 lev_rows(a, i0, la, A);
                 // D[i0][j0]: the last seed value of the lane above; for lane 0 the boundary itself
                 uint32_t diag_in = __shfl_up(col[R - 1], 1);
-                if (lane == 0) diag_in = b == 0 ? j0 : (j0 == 0 ? band : top_row[j0]);
+                if constexpr (kBanded) {
+                    if (lane == 0) diag_in = b == 0 ? jt0 : (jt0 == 0 ? band : corridor_top<false>(top_row, plo, phi, jt0));
+                } else {
+                    if (lane == 0) diag_in = b == 0 ? j0 : (j0 == 0 ? band : top_row[j0]);
+                }
                 uint32_t last_out = 0, b_pipe = 0, top_chunk = 0, b_chunk = 0;
                 const uint32_t n_steps = wt + 63u;
                 for (uint32_t s = 0; s < n_steps; ++s) {
                     if ((s & 63u) == 0u) {
-                        const uint32_t j1 = j0 + s + 1u + (uint32_t)lane;
-                        top_chunk = b == 0 ? j1 : (j1 <= lb ? top_row[j1] : 0u);
+                        const uint32_t j1 = jt0 + s + 1u + (uint32_t)lane;
+                        if constexpr (kBanded) top_chunk = b == 0 ? j1 : corridor_top<false>(top_row, plo, phi, j1);
+                        else top_chunk = b == 0 ? j1 : (j1 <= lb ? top_row[j1] : 0u);
                         b_chunk = j1 <= lb ? rb.at(j1 - 1u) : 0u;
                     }
                     const LevIn in = lev_inputs(last_out, top_chunk, b_pipe, b_chunk, s, lane);
@@ -231,9 +316,9 @@ __global__ __launch_bounds__(64) void align_traceback_kernel(const uint8_t *__re
             }
             __syncthreads();
             // walk the path through the tile (the same walk in every lane: uniform LDS reads)
-            while (i > band && j > j0) {
+            while (i > band && j > jt0) {
                 const uint32_t row = i - 1u - band;
-                const uint32_t d = (dirs[(j - 1u - j0) * 64u + row / R] >> (2u * (row % R))) & 3u;
+                const uint32_t d = (dirs[(j - 1u - jt0) * 64u + row / R] >> (2u * (row % R))) & 3u;
                 emit(d, 1u);
                 if (d != kOpDelete) --i;
                 if (d != kOpInsert) --j;
@@ -278,12 +363,14 @@ struct asgart_alignment {
     std::vector<float> identity;
     uint64_t n_refused = 0;
     double ms[4] = {0, 0, 0, 0};
+    uint32_t rounds = 0;  // passes over the list (one, unless the bounds are the library's)
+    uint64_t cells = 0;   // cells of the forward passes of all rounds
 };
 
 namespace {
 
 struct AlignWork : ToolWork {
-    DevBuf &sds = buf(), &flags = buf(), &distance = buf(), &identity = buf(), &counters = buf();
+    DevBuf &sds = buf(), &flags = buf(), &distance = buf(), &identity = buf(), &counters = buf(), &bound = buf();
     DevBuf &members = buf(), &order = buf(), &ck_off = buf(), &ck = buf();
     DevBuf &cnt = buf(), &slot_off = buf(), &slot_len = buf(), &slot_op = buf(), &n_runs = buf(), &out_off = buf();
     DevBuf &out_len = buf(), &out_op = buf();
@@ -297,24 +384,36 @@ struct BatchRuns {
     std::vector<uint8_t> op;
 };
 
+// the checkpoint bytes and the forward pass's cells of one duplication: of the whole matrix, or of the corridor of its bound
+uint64_t checkpoint_bytes(const asgart_proto_sd &sd, int inclusive, const uint32_t *bound, size_t q) {
+    return bound ? banded_shape(sd, inclusive, bound[q]).bytes() : align_shape(sd, inclusive).bytes();
+}
+
+uint64_t forward_cells(const asgart_proto_sd &sd, int inclusive, const uint32_t *bound, size_t q) {
+    if (bound) return banded_shape(sd, inclusive, bound[q]).cells();
+    const AlignShape g = align_shape(sd, inclusive);
+    return g.n * g.m;
+}
+
+// One batch.  bound: NULL, or max_distance of every duplication of the list (it is in w.bound then): the corridor kernels
+// run, the members found beyond their bound go to `beyond` and leave br.members, and the traceback sees the others only.
 int32_t run_batch(AlignWork &w, asgart_alignment *res, const asgart_index *idx, const asgart_proto_sd *sds, bool has_flags,
-                  int inclusive, BatchRuns &br) {
+                  int64_t n_sd, int inclusive, BatchRuns &br, const uint32_t *bound, std::vector<uint32_t> &beyond) {
     hipStream_t s = w.s;
-    const uint64_t nk = br.members.size();
+    uint64_t nk = br.members.size();
     // served largest first; the checkpoints of member k start at ck_off[k] (slots of whole 16-byte vectors)
     std::vector<uint32_t> order((size_t)nk);
-    std::vector<uint64_t> ck_off((size_t)nk);
+    std::vector<uint64_t> ck_off((size_t)nk), cells((size_t)nk);
     uint64_t words = 0;
     for (uint64_t k = 0; k < nk; ++k) {
+        const uint32_t q = br.members[(size_t)k];
         order[(size_t)k] = (uint32_t)k;
         ck_off[(size_t)k] = words;
-        words += (align_shape(sds[br.members[(size_t)k]], inclusive).bytes() / 4u + 3u) & ~(uint64_t)3;
+        words += (checkpoint_bytes(sds[q], inclusive, bound, q) / 4u + 3u) & ~(uint64_t)3;
+        cells[(size_t)k] = forward_cells(sds[q], inclusive, bound, q);
+        res->cells += cells[(size_t)k];
     }
-    auto cells = [&](uint32_t k) {
-        const AlignShape g = align_shape(sds[br.members[k]], inclusive);
-        return (double)g.n * (double)g.m;
-    };
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells(x) > cells(y); });
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells[x] > cells[y]; });
 
     HIP_TRY(hipEventRecord(w.ev[0], s));
     RC_TRY(w.upload(w.members, br.members.data(), (size_t)nk * 4));
@@ -328,15 +427,61 @@ int32_t run_batch(AlignWork &w, asgart_alignment *res, const asgart_index *idx, 
     HIP_TRY(stream_sync(s));  // (pageable host sources)
     HIP_TRY(hipEventRecord(w.ev[1], s));
 
-    const Batch bt{w.sds.as<asgart_proto_sd>(), has_flags ? w.flags.as<uint8_t>() : nullptr, w.members.as<uint32_t>(),
-                   w.order.as<uint32_t>(), w.ck_off.as<uint64_t>(), nk, inclusive};
+    Batch bt{w.sds.as<asgart_proto_sd>(), has_flags ? w.flags.as<uint8_t>() : nullptr, w.members.as<uint32_t>(),
+             w.order.as<uint32_t>(), w.ck_off.as<uint64_t>(), nk, inclusive, bound ? w.bound.as<uint32_t>() : nullptr};
     uint32_t *d_dist = w.distance.as<uint32_t>();
     const unsigned waves_per_wg = kFwdThreads / 64;
     const unsigned grid_f = (unsigned)std::min<uint64_t>((nk + waves_per_wg - 1) / waves_per_wg, 1024);
-    align_forward_kernel<<<grid_f, kFwdThreads, 0, s>>>(idx->d_text, bt, w.ck.as<uint32_t>(), cursors, d_dist,
-                                                         w.identity.as<float>());
+    if (bound)
+        align_forward_kernel<true><<<grid_f, kFwdThreads, 0, s>>>(idx->d_text, bt, w.ck.as<uint32_t>(), cursors, d_dist,
+                                                                   w.identity.as<float>());
+    else
+        align_forward_kernel<false><<<grid_f, kFwdThreads, 0, s>>>(idx->d_text, bt, w.ck.as<uint32_t>(), cursors, d_dist,
+                                                                    w.identity.as<float>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(w.ev[2], s));
+
+    if (bound) {  // who is within the bound?  The others have no path to trace.
+        std::vector<uint32_t> dist((size_t)n_sd);
+        HIP_TRY(read_back(dist.data(), d_dist, (size_t)n_sd * 4, s));
+        std::vector<uint32_t> kept;
+        std::vector<uint64_t> kept_off, kept_cells;
+        for (uint64_t k = 0; k < nk; ++k) {
+            const uint32_t q = br.members[(size_t)k];
+            if (dist[q] == 0xFFFFFFFFu) {
+                beyond.push_back(q);
+            } else {
+                kept.push_back(q);
+                kept_off.push_back(ck_off[(size_t)k]);
+                kept_cells.push_back(cells[(size_t)k]);
+            }
+        }
+        if (kept.size() != nk) {
+            br.members.swap(kept);
+            ck_off.swap(kept_off);
+            cells.swap(kept_cells);
+            nk = br.members.size();
+            order.resize((size_t)nk);
+            for (uint64_t k = 0; k < nk; ++k) order[(size_t)k] = (uint32_t)k;
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells[x] > cells[y]; });
+            RC_TRY(w.upload(w.members, br.members.data(), (size_t)nk * 4));
+            RC_TRY(w.upload(w.order, order.data(), (size_t)nk * 4));
+            RC_TRY(w.upload(w.ck_off, ck_off.data(), (size_t)nk * 8));
+            HIP_TRY(stream_sync(s));  // (pageable host sources)
+            bt.n = nk;
+        }
+    }
+    if (nk == 0) {  // nobody is left: no runs
+        HIP_TRY(hipEventRecord(w.ev[3], s));
+        HIP_TRY(stream_sync(s));
+        br.off.assign(1, 0);
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, w.ev[k], w.ev[k + 1]));
+            res->ms[k] += (double)ms;
+        }
+        return 0;
+    }
 
     uint64_t *cnt = w.cnt.as<uint64_t>(), *slot_off = w.slot_off.as<uint64_t>();
     uint64_t *n_runs = w.n_runs.as<uint64_t>(), *out_off = w.out_off.as<uint64_t>();
@@ -349,9 +494,14 @@ int32_t run_batch(AlignWork &w, asgart_alignment *res, const asgart_index *idx, 
     RC_TRY(w.slot_op.reserve((size_t)n_slots + 16));
     HIP_TRY(hipMemsetAsync(n_runs + nk, 0, 8, s));
     const unsigned grid_t = (unsigned)std::min<uint64_t>(nk, 2048);
-    align_traceback_kernel<<<grid_t, 64, 0, s>>>(idx->d_text, bt, w.ck.as<uint32_t>(), d_dist, slot_off,
-                                                 w.slot_len.as<uint32_t>(), w.slot_op.as<uint8_t>(), n_runs, cursors + 1,
-                                                 overflow);
+    if (bound)
+        align_traceback_kernel<true><<<grid_t, 64, 0, s>>>(idx->d_text, bt, w.ck.as<uint32_t>(), d_dist, slot_off,
+                                                           w.slot_len.as<uint32_t>(), w.slot_op.as<uint8_t>(), n_runs,
+                                                           cursors + 1, overflow);
+    else
+        align_traceback_kernel<false><<<grid_t, 64, 0, s>>>(idx->d_text, bt, w.ck.as<uint32_t>(), d_dist, slot_off,
+                                                            w.slot_len.as<uint32_t>(), w.slot_op.as<uint8_t>(), n_runs,
+                                                            cursors + 1, overflow);
     HIP_TRY(hipGetLastError());
     RC_TRY(w.exclusive_scan(n_runs, out_off, (size_t)nk + 1));
     uint64_t n_total = 0;
@@ -396,8 +546,77 @@ int32_t run_batch(AlignWork &w, asgart_alignment *res, const asgart_index *idx, 
     return 0;
 }
 
+// what the corridor kernels count in 32 bits: kAlignBig + n + m, and a bound below kAlignBig (max_distance NULL: the library's)
+int32_t check_banded(const char *fn, const asgart_proto_sd *sds, int64_t n_sd, int inclusive, const uint32_t *max_distance) {
+    for (int64_t q = 0; q < n_sd; ++q) {
+        const AlignShape g = align_shape(sds[q], inclusive);
+        if (g.n + g.m >= kAlignBandedCap) {
+            set_error("%s: duplication %lld has arms of 2^30 bases together; a corridor is not supported for them", fn,
+                      (long long)q);
+            return ASGART_E_CAP;
+        }
+        if (max_distance && max_distance[q] >= kAlignBandedCap) {
+            set_error("%s: max_distance[%lld] = %u; it must be below 2^30", fn, (long long)q, (unsigned)max_distance[q]);
+            return ASGART_E_ARG;
+        }
+    }
+    return 0;
+}
+
+// One pass over the duplications `items` (ascending), each within bound[q] where there is a bound: batches by checkpoint
+// bytes, largest first, a new one whenever the next duplication no longer fits.  Sets status[q] to 0 (alone over the
+// budget) or 2 (beyond its bound) and says where the runs of the others are.
+int32_t run_round(AlignWork &w, asgart_alignment *res, const asgart_index *idx, const asgart_proto_sd *sds, bool has_flags,
+                  int64_t n_sd, int inclusive, uint64_t budget, const std::vector<uint32_t> &items, const uint32_t *bound,
+                  std::vector<BatchRuns> &batches, std::vector<uint32_t> &batch_of, std::vector<uint32_t> &slot_of) {
+    ++res->rounds;
+    if (bound) {
+        RC_TRY(w.upload(w.bound, bound, (size_t)n_sd * 4));
+        HIP_TRY(stream_sync(w.s));  // (a pageable host source)
+    }
+    std::vector<uint64_t> bytes((size_t)n_sd, 0);
+    std::vector<uint32_t> by_size;
+    for (uint32_t q : items) {
+        if (bound && banded_shape(sds[q], inclusive, bound[q]).beyond) {  // T < |m - n|: no work
+            res->status[q] = 2;
+            continue;
+        }
+        bytes[q] = checkpoint_bytes(sds[q], inclusive, bound, q);
+        if (bytes[q] > budget)
+            res->status[q] = 0;
+        else
+            by_size.push_back(q);
+    }
+    std::stable_sort(by_size.begin(), by_size.end(), [&](uint32_t x, uint32_t y) { return bytes[x] > bytes[y]; });
+    const size_t first = batches.size();
+    uint64_t held = 0;
+    for (uint32_t q : by_size) {
+        if (batches.size() == first || held + bytes[q] > budget) {
+            batches.emplace_back();
+            held = 0;
+        }
+        batches.back().members.push_back(q);
+        held += bytes[q];
+    }
+    std::vector<uint32_t> beyond;
+    for (size_t b = first; b < batches.size(); ++b) {
+        BatchRuns &br = batches[b];
+        std::sort(br.members.begin(), br.members.end());
+        RC_TRY(run_batch(w, res, idx, sds, has_flags, n_sd, inclusive, br, bound, beyond));
+        for (size_t k = 0; k < br.members.size(); ++k) {
+            batch_of[br.members[k]] = (uint32_t)b;
+            slot_of[br.members[k]] = (uint32_t)k;
+        }
+    }
+    for (uint32_t q : beyond) res->status[q] = 2;
+    return 0;
+}
+
+// max_distance: the caller's bounds; automatic: the library's (align_dev.hpp: align_auto_first, align_auto_next), round
+// after round for those that were beyond theirs; neither: the whole matrix of every duplication.
 int32_t run_align(AlignWork &w, asgart_alignment *res, const asgart_index *idx, const asgart_proto_sd *sds,
-                  const uint8_t *flags, int64_t n_sd, int inclusive, uint64_t budget) {
+                  const uint8_t *flags, int64_t n_sd, int inclusive, uint64_t budget, const uint32_t *max_distance,
+                  bool automatic) {
     RC_TRY(w.open(4));
     hipStream_t s = w.s;
     if (budget == 0) {  // half of what is free
@@ -416,40 +635,35 @@ int32_t run_align(AlignWork &w, asgart_alignment *res, const asgart_index *idx, 
     HIP_TRY(stream_sync(s));
     res->ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up).count();
 
-    // batches: largest first, a new one whenever the next duplication no longer fits
     res->status.assign((size_t)n_sd, 1);
-    std::vector<uint64_t> bytes((size_t)n_sd);
-    std::vector<uint32_t> by_size;
-    for (int64_t q = 0; q < n_sd; ++q) {
-        bytes[(size_t)q] = align_shape(sds[q], inclusive).bytes();
-        if (bytes[(size_t)q] > budget) {
-            res->status[(size_t)q] = 0;
-            ++res->n_refused;
-        } else {
-            by_size.push_back((uint32_t)q);
-        }
-    }
-    std::stable_sort(by_size.begin(), by_size.end(), [&](uint32_t x, uint32_t y) { return bytes[x] > bytes[y]; });
     std::vector<BatchRuns> batches;
-    uint64_t held = 0;
-    for (uint32_t q : by_size) {
-        if (batches.empty() || held + bytes[q] > budget) {
-            batches.emplace_back();
-            held = 0;
+    std::vector<uint32_t> batch_of((size_t)n_sd, 0), slot_of((size_t)n_sd, 0), items((size_t)n_sd), auto_bound;
+    for (int64_t q = 0; q < n_sd; ++q) items[(size_t)q] = (uint32_t)q;
+    if (automatic) {
+        auto_bound.resize((size_t)n_sd);
+        for (int64_t q = 0; q < n_sd; ++q) {
+            const AlignShape g = align_shape(sds[q], inclusive);
+            auto_bound[(size_t)q] = align_auto_first(g.n, g.m);
         }
-        batches.back().members.push_back(q);
-        held += bytes[q];
+        max_distance = auto_bound.data();
     }
-    std::vector<uint32_t> batch_of((size_t)n_sd, 0), slot_of((size_t)n_sd, 0);
-    for (size_t b = 0; b < batches.size(); ++b) {
-        BatchRuns &br = batches[b];
-        std::sort(br.members.begin(), br.members.end());
-        for (size_t k = 0; k < br.members.size(); ++k) {
-            batch_of[br.members[k]] = (uint32_t)b;
-            slot_of[br.members[k]] = (uint32_t)k;
+    for (;;) {
+        RC_TRY(run_round(w, res, idx, sds, flags != nullptr, n_sd, inclusive, budget, items, max_distance, batches, batch_of,
+                         slot_of));
+        if (!automatic) break;
+        // again, with a larger bound, for those beyond theirs; at n + m the corridor is the matrix and nobody is beyond it
+        std::vector<uint32_t> again;
+        for (uint32_t q : items) {
+            const AlignShape g = align_shape(sds[q], inclusive);
+            if (res->status[q] != 2 || auto_bound[q] >= g.n + g.m) continue;
+            auto_bound[q] = align_auto_next(auto_bound[q], g.n, g.m);
+            res->status[q] = 1;
+            again.push_back(q);
         }
-        RC_TRY(run_batch(w, res, idx, sds, flags != nullptr, inclusive, br));
+        if (again.empty()) break;
+        items.swap(again);
     }
+    for (int64_t q = 0; q < n_sd; ++q) res->n_refused += res->status[(size_t)q] == 0;
 
     const auto t0 = std::chrono::steady_clock::now();
     res->distance.resize((size_t)n_sd);
@@ -459,7 +673,7 @@ int32_t run_align(AlignWork &w, asgart_alignment *res, const asgart_index *idx, 
     res->run_offsets.assign((size_t)n_sd + 1, 0);
     for (int64_t q = 0; q < n_sd; ++q) {
         uint64_t runs = 0;
-        if (res->status[(size_t)q]) {
+        if (res->status[(size_t)q] == 1) {
             const BatchRuns &br = batches[batch_of[(size_t)q]];
             runs = br.off[slot_of[(size_t)q] + 1u] - br.off[slot_of[(size_t)q]];
         } else {
@@ -471,7 +685,7 @@ int32_t run_align(AlignWork &w, asgart_alignment *res, const asgart_index *idx, 
     res->run_len.resize((size_t)n_runs);
     res->run_op.resize((size_t)n_runs);
     for (int64_t q = 0; q < n_sd; ++q) {
-        if (!res->status[(size_t)q]) continue;
+        if (res->status[(size_t)q] != 1) continue;
         const BatchRuns &br = batches[batch_of[(size_t)q]];
         const uint64_t from = br.off[slot_of[(size_t)q]], runs = br.off[slot_of[(size_t)q] + 1u] - from;
         if (!runs) continue;
@@ -484,10 +698,12 @@ int32_t run_align(AlignWork &w, asgart_alignment *res, const asgart_index *idx, 
 
 }  // namespace
 
-extern "C" int32_t asgart_align_duplications(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags,
-                                             int64_t n_sd, int32_t inclusive, uint64_t budget_bytes,
-                                             asgart_alignment **out) {
-    const char *fn = "asgart_align_duplications";
+namespace {
+
+// the two entry points: the whole matrix (banded = false), or corridors for the caller's bounds or, without any, the library's
+int32_t align_entry(const char *fn, asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
+                    int32_t inclusive, bool banded, const uint32_t *max_distance, uint64_t budget_bytes,
+                    asgart_alignment **out) {
     if (out) *out = nullptr;
     if (!idx || !out) {  // (the result is made for an empty list too)
         set_error("%s: bad argument", fn);
@@ -496,6 +712,7 @@ extern "C" int32_t asgart_align_duplications(asgart_index *idx, const asgart_pro
     RC_TRY(check_list_args(fn, sds, n_sd, out));
     RC_TRY(check_flags(fn, flags, n_sd));
     RC_TRY(check_arms(fn, (uint64_t)idx->n, sds, n_sd, inclusive != 0));
+    if (banded) RC_TRY(check_banded(fn, sds, n_sd, inclusive != 0, max_distance));
     REFUSE_POISONED(idx);
     HIP_TRY(hipSetDevice(idx->device));
     try {
@@ -505,12 +722,38 @@ extern "C" int32_t asgart_align_duplications(asgart_index *idx, const asgart_pro
             return 0;
         }
         return run_tool<AlignWork>(out, [&](AlignWork &w, asgart_alignment *res) {
-            return run_align(w, res, idx, sds, flags, n_sd, inclusive != 0, budget_bytes);
+            return run_align(w, res, idx, sds, flags, n_sd, inclusive != 0, budget_bytes, max_distance,
+                             banded && !max_distance);
         });
     } catch (const std::bad_alloc &) {
         set_error("%s: out of host memory", fn);
         return ASGART_E_OOM;
     }
+}
+
+}  // namespace
+
+extern "C" int32_t asgart_align_duplications(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags,
+                                             int64_t n_sd, int32_t inclusive, uint64_t budget_bytes,
+                                             asgart_alignment **out) {
+    return align_entry("asgart_align_duplications", idx, sds, flags, n_sd, inclusive, false, nullptr, budget_bytes, out);
+}
+
+extern "C" int32_t asgart_align_duplications_banded(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags,
+                                                    int64_t n_sd, int32_t inclusive, const uint32_t *max_distance,
+                                                    uint64_t budget_bytes, asgart_alignment **out) {
+    return align_entry("asgart_align_duplications_banded", idx, sds, flags, n_sd, inclusive, true, max_distance,
+                       budget_bytes, out);
+}
+
+extern "C" int32_t asgart_alignment_rounds(const asgart_alignment *a, uint32_t *rounds, uint64_t *cells) {
+    if (!a) {
+        set_error("asgart_alignment_rounds: bad argument");
+        return ASGART_E_ARG;
+    }
+    if (rounds) *rounds = a->rounds;
+    if (cells) *cells = a->cells;
+    return 0;
 }
 
 extern "C" void asgart_alignment_counts(const asgart_alignment *a, uint64_t *n_sd, uint64_t *n_runs, uint64_t *n_refused) {
@@ -550,6 +793,19 @@ extern "C" void asgart_align_geometry(uint64_t *band_rows, uint64_t *lane_rows, 
     if (band_rows) *band_rows = kLevBand;
     if (lane_rows) *lane_rows = kLevRows;
     if (tile_cols) *tile_cols = kAlignTile;
+}
+
+extern "C" int32_t asgart_align_bytes_banded(const asgart_proto_sd *sds, int64_t n_sd, int32_t inclusive,
+                                             const uint32_t *max_distance, uint64_t *bytes) {
+    const char *fn = "asgart_align_bytes_banded";
+    if (!bytes || !max_distance) {
+        set_error("%s: bad argument", fn);
+        return ASGART_E_ARG;
+    }
+    RC_TRY(check_list_args(fn, sds, n_sd, bytes));
+    RC_TRY(check_banded(fn, sds, n_sd, inclusive != 0, max_distance));
+    for (int64_t q = 0; q < n_sd; ++q) bytes[q] = banded_shape(sds[q], inclusive != 0, max_distance[q]).bytes();
+    return 0;
 }
 
 extern "C" int32_t asgart_align_bytes(const asgart_proto_sd *sds, int64_t n_sd, int32_t inclusive, uint64_t *bytes) {

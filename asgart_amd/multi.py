@@ -291,12 +291,45 @@ def _check_slice(slice_options, fmt: str) -> bool:
     return slice_options.active() or fmt != "json"
 
 
-def _check_paf(paf: bool, world: int, orientations, slice_options=None, cs: Optional[str] = None) -> None:
-    """--paf and --cs, vetted before the run starts (on every rank): each refusal with its reason."""
+def _paf_band(value):
+    """--paf-band -> "full" (the whole edit matrix of every duplication, Index.align as it was), "auto" (a diagonal corridor
+    with the library's bounds: the same rows) or a Fraction P in (0, 100]: a corridor for at most floor(P max(n, m) / 100)
+    edits, and no row for a duplication with more.  ValueError for anything else."""
+    from fractions import Fraction
+
+    if value in (None, "full", "auto"):
+        return value or "full"
+    try:
+        p = Fraction(str(value))
+    except (ValueError, ZeroDivisionError):
+        p = None
+    if p is None or not 0 < p <= 100:
+        raise ValueError(f"--paf-band: auto, full or a percentage of the longer arm in (0, 100], not `{value}`")
+    return p
+
+
+def _align_for_paf(index, sds, flags, paf_band):
+    """The alignment behind the PAF rows, as --paf-band asks for it (_paf_band has vetted it)."""
+    band = _paf_band(paf_band)
+    if band == "full":
+        return index.align(sds, flags, inclusive=False)
+    if band == "auto":
+        return index.align(sds, flags, inclusive=False, max_distance="auto")
+    longest = [max(int(ll), int(rl)) for ll, rl in sds[:, 2:].tolist()]
+    bounds = np.array([band.numerator * n // (band.denominator * 100) for n in longest], dtype=np.uint32)
+    return index.align(sds, flags, inclusive=False, max_distance=bounds)
+
+
+def _check_paf(paf: bool, world: int, orientations, slice_options=None, cs: Optional[str] = None,
+               paf_band: Optional[str] = None) -> None:
+    """--paf, --cs and --paf-band, vetted before the run starts (on every rank): each refusal with its reason."""
     if cs not in (None, "short", "long"):
         raise ValueError("--cs: short or long")
     if cs is not None and not paf:
         raise ValueError("--cs: the cs:Z: tag is a column of the PAF file; it needs --paf")
+    band = _paf_band(paf_band)
+    if band != "full" and not paf:
+        raise ValueError("--paf-band: the corridor is that of the alignment behind the PAF file; it needs --paf")
     if not paf:
         return
     if world > 1:
@@ -312,14 +345,24 @@ def _check_paf(paf: bool, world: int, orientations, slice_options=None, cs: Opti
                          "name positions in the fragments of the run (slice the result without them, or write no PAF)")
 
 
+# `paf` of the entry points when the alignment is to stay inside a corridor: the cs:Z: form (None: no such column) and
+# --paf-band's value (_paf_band)
+Paf = namedtuple("Paf", "cs band", defaults=(None, "full"))
+
+
 def _paf_and_cs(paf):
-    """The `paf` argument of the entry points -> (paf, cs): False and True as they are, "short" and "long" are True with
-    the cs:Z: column in that form.  (The column came after the entry points' signatures were fixed; it rides on `paf`.)"""
+    """The `paf` argument of the entry points -> (paf, cs, band): False and True as they are, "short" and "long" are True
+    with the cs:Z: column in that form, a Paf is True with its column and its --paf-band value.  (The column and the corridor
+    came after the entry points' signatures were fixed; they ride on `paf`.)"""
+    if isinstance(paf, Paf):
+        if paf.cs not in (None, "short", "long"):
+            raise ValueError("paf: Paf.cs is None, 'short' or 'long'")
+        return True, paf.cs, paf.band
     if isinstance(paf, str):
         if paf not in ("short", "long"):
-            raise ValueError("paf: False, True, or 'short' / 'long' for rows with the cs:Z: column")
-        return True, paf
-    return bool(paf), None
+            raise ValueError("paf: False, True, 'short' / 'long' for rows with the cs:Z: column, or a Paf")
+        return True, paf, None
+    return bool(paf), None, None
 
 
 def _paf_text(fam_offs, sds, flags, strand, aln, writer: Optional[str], device_index: int, cs: Optional[str] = None,
@@ -362,7 +405,7 @@ _Run = namedtuple("_Run", "files device_index strand parts survivors flags ident
 
 def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool, with_sequences: bool, reader: str,
          paf: bool, sliced: bool = False, slice_options=None, cs: Optional[str] = None,
-         paf_writer: Optional[str] = None) -> Optional[_Run]:
+         paf_writer: Optional[str] = None, paf_band: Optional[str] = None) -> Optional[_Run]:
     """The run protocol, once: a whole `asgart` run (reference src/bin/asgart.rs:731-822) for each of the one to four
     RunSettings `sts`, which differ in orientation only, on the ranks of `dist` (None: one process, no collective), rank r
     on GPU device_index.  The entry points have vetted the arguments.  Built ONCE: rank 0 reads the input and builds the
@@ -373,7 +416,7 @@ def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool
     at `identity`, so slicing commutes with scoring.  What is left of all orientations -- the survivors, a sliced run's in
     its original coordinates -- is one list with a flag byte each: with compute_score it is broadcast once and every rank
     scores its share; with_sequences is one extraction from the Source of the read (device reader) or the raw records
-    (host reader); paf one alignment with exact ranges; with cs (the cs:Z: column) every part's PAF text is written right
+    (host reader); paf one alignment with exact ranges, inside the corridor paf_band asks for (_align_for_paf); with cs (the cs:Z: column) every part's PAF text is written right
     there, by the writer paf_writer asks for, because the index is closed when this returns.  A slice that is refused
     (ValueError) is raised behind the collectives, which then run without survivors: the other ranks must not wait in them.
     -> the _Run on rank 0, None elsewhere; the Source and the index are closed either way."""
@@ -434,7 +477,7 @@ def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool
             return None
         seqs = _sequences(source, records, device_index, survivors, (flags & 1).astype(bool),
                           (flags >> 1 & 1).astype(bool)) if with_sequences else None
-        aln = index.align(survivors, flags, inclusive=False) if paf else None
+        aln = _align_for_paf(index, survivors, flags, paf_band) if paf else None
         if paf and cs is not None:
             parts = [p._replace(paf=_paf_text(p.offs, survivors[p.lo:p.hi], flags[p.lo:p.hi], strand, aln.part(p.lo, p.hi),
                                               paf_writer, device_index, cs, index)) for p in parts]
@@ -508,8 +551,12 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     third entry, the text of the PAF file, written as `writer` asks (align.paf_text_gpu or align.paf_text; None: by the
     number of runs, PAF_DEVICE_MIN_RUNS; with_sequences does not matter, a PAF row holds no sequence).  One rank only; see
     _check_paf.  paf="short" or paf="long" (what --paf --cs [short|long] passes) is paf=True with the cs:Z: column in every
-    row of the PAF text (align.cs_text), in that form; writer=None then decides by PAF_CS_DEVICE_MIN_RUNS."""
-    paf, cs = _paf_and_cs(paf)
+    row of the PAF text (align.cs_text), in that form; writer=None then decides by PAF_CS_DEVICE_MIN_RUNS.
+    paf=Paf(cs, band) (what --paf-band passes) is paf=True, with the column if cs is "short" or "long", aligned as band
+    says: "full" over the whole edit matrix; "auto" inside a diagonal corridor that the library widens until every
+    duplication is within it: the same text; a percentage P (a number or its text) bounds the edits of a duplication by
+    floor(P max(n, m) / 100): one with more gets no row and a line on stderr (_paf_band)."""
+    paf, cs, paf_band = _paf_and_cs(paf)
     world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_duplications: --trim runs on one rank only")
@@ -517,9 +564,9 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     sliced = _check_slice(slice_options, fmt)
-    _check_paf(paf, world, [(settings.reverse, settings.complement)], slice_options, cs)
+    _check_paf(paf, world, [(settings.reverse, settings.complement)], slice_options, cs, paf_band)
     run = _run(files, [settings], dist, device_index, compute_score, with_sequences, reader, paf, sliced, slice_options, cs,
-               paf_writer)
+               paf_writer, paf_band)
     return None if run is None else _texts(run, run.parts[0], prefix, writer, paf_writer, fmt)
 
 
@@ -534,23 +581,24 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     text) and None elsewhere; the merged text is what postprocess.merge_results gives over those files in that order
     (RunResult::from_files, reference src/structs.rs:114-141: strand and settings of the first, every duplication with the
     flags of its own run) and is written like the others.  `--trim`, reader, writer, with_sequences, paf (the merged
-    result gets no PAF text; direct and RC only, see _check_paf; "short" / "long": with the cs:Z: column): as
+    result gets no PAF text; direct and RC only, see _check_paf; "short" / "long": with the cs:Z: column; a Paf: inside a corridor): as
     search_duplications.  Slicing is out of scope here: `python -m asgart_amd.slice` does it on the files this writes."""
     from dataclasses import replace
 
-    paf, cs = _paf_and_cs(paf)
+    paf, cs, paf_band = _paf_and_cs(paf)
     orientations = [(bool(r), bool(c)) for r, c in orientations]
     if not 1 <= len(orientations) <= 4 or len(set(orientations)) != len(orientations):
         raise ValueError("multi.search_orientations: one to four distinct (reverse, complement) pairs")
     world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
-    _check_paf(paf, world, orientations, None, cs)
+    _check_paf(paf, world, orientations, None, cs, paf_band)
     reader = _choose_reader(reader, settings)
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     sts = [replace(settings, reverse=r, complement=c) for r, c in orientations]
-    run = _run(files, sts, dist, device_index, compute_score, with_sequences, reader, paf, cs=cs, paf_writer=paf_writer)
+    run = _run(files, sts, dist, device_index, compute_score, with_sequences, reader, paf, cs=cs, paf_writer=paf_writer,
+               paf_band=paf_band)
     if run is None:
         return None
     sizes = np.concatenate([np.diff(p.offs.astype(np.int64)) for p in run.parts])
@@ -598,6 +646,11 @@ def _parse(argv):
     ap.add_argument("--cs", nargs="?", const="short", choices=("short", "long"), default=None,
                     help="with --paf: give every row minimap2's difference string as a sixteenth column (cs:Z:), the bases "
                          "behind the CIGAR; short (what a bare --cs means) writes `:<n>` for matching bases, long writes them out")
+    ap.add_argument("--paf-band", default="full", metavar="auto|full|PERCENT",
+                    help="with --paf: how much of the edit matrix of two arms the alignment walks.  full (the default): all "
+                         "of it.  auto: a diagonal corridor, widened until every duplication is within it; the same file "
+                         "from cells and memory in proportion to the corridor.  PERCENT: a corridor for at most that share "
+                         "of the longer arm in edits; a duplication with more gets no row and a line on stderr")
     ap.add_argument("--prefix", default="")
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
@@ -631,7 +684,8 @@ def _parse(argv):
     if args.orientations and (args.slice_options.active() or args.format != "json"):
         ap.error("--orientations writes unsliced JSON files: slice them with python -m asgart_amd.slice")
     try:
-        _check_paf(args.paf, args.gpus, args.orientations or [(args.reverse, args.complement)], args.slice_options, args.cs)
+        _check_paf(args.paf, args.gpus, args.orientations or [(args.reverse, args.complement)], args.slice_options, args.cs,
+                   args.paf_band)
     except ValueError as e:
         ap.error(str(e))
     return args
@@ -708,7 +762,7 @@ def rank_main(argv) -> int:
                                         complement=args.complement, skip_masked=args.skip_masked)
         asked = dict(compute_score=args.compute_score, prefix=args.prefix, with_sequences=args.with_sequences,
                      reader="host" if args.host_reader else None, writer="host" if args.host_writer else None,
-                     paf=args.cs or args.paf)
+                     paf=Paf(args.cs, args.paf_band) if args.paf and args.paf_band != "full" else args.cs or args.paf)
         if args.orientations:
             out = search_orientations(args.files, args.orientations, settings, dist, device_index, **asked)
             texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])

@@ -417,7 +417,9 @@ int32_t asgart_compute_scores_flags_multi(asgart_index *const *indices, int32_t 
  *                 100 (1 - distance / max(left_length, right_length)) as float, bit-equal to asgart_compute_scores_flags
  *                 when inclusive = 1; status[q] = 1 aligned, 0 refused.  Any array of _copy may be NULL.
  * Errors, those of the score: an arm past the text, two empty arms, a flag bit other than 0 and 1 (ASGART_E_ARG), arms of
- * 2^32 bases (ASGART_E_CAP).  One wave walks each pair (a megabase pair too); there are no _shard / _multi variants. */
+ * 2^32 bases (ASGART_E_CAP).  One wave walks each pair, and this call walks the whole n x m matrix of it;
+ * asgart_align_duplications_banded below walks a diagonal corridor of it, which is what a megabase pair needs.  Neither
+ * has _shard / _multi variants. */
 typedef struct asgart_alignment asgart_alignment;
 int32_t asgart_align_duplications(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
                                   int32_t inclusive, uint64_t budget_bytes, asgart_alignment **out);
@@ -435,6 +437,65 @@ void asgart_align_geometry(uint64_t *band_rows, uint64_t *lane_rows, uint64_t *t
  * 4 (n_bands - 1)(m + 1) + 4 floor((m - 1) / W) n_bands band_rows, with n_bands = max(1, ceil(n / band_rows)) and no column
  * checkpoint for m = 0. */
 int32_t asgart_align_bytes(const asgart_proto_sd *sds, int64_t n_sd, int32_t inclusive, uint64_t *bytes);
+
+/* ---- the same alignment inside a diagonal corridor ---------------------------------------------------------
+ * asgart_align_duplications spends n m cells and n m / 51 checkpoint bytes on a duplication; two arms at edit distance d
+ * have every optimal path within about |m - n| + d diagonals.  This call spends cells and bytes in proportion to
+ * n (band_rows + corridor width), and gives the same runs.
+ * THE RULE.  For arms of n and m bases and a bound T = max_distance[q], let e = floor((T - |m - n|) / 2).
+ *   T < |m - n|   more than T edits, without any work: a path needs |m - n| insertions or deletions.
+ *   otherwise     every path of cost <= T stays on the diagonals k = j - i in [min(0, m - n) - e, max(0, m - n) + e].
+ *                 (A path that reaches diagonal k > max(0, m - n) has k deletions to get there from diagonal 0 and k - (m - n)
+ *                 insertions to get back to diagonal m - n: 2 k - (m - n) <= T gives k <= max(0, m - n) + e; below
+ *                 min(0, m - n) likewise.)
+ *   the region    for band b, the rows b band_rows + 1 .. min((b + 1) band_rows, n), the columns
+ *                 lo_b = max(1, b band_rows + 1 + kmin) .. hi_b = min(m, min((b + 1) band_rows, n) + kmax): the smallest
+ *                 rectangle that holds those diagonals of the band's rows, clipped to [1, m].  Row 0 is D[0][j] = j, column 0
+ *                 is D[i][0] = i where lo_b = 1, and every other cell outside the rectangles counts as 2^30.  n + m and T stay
+ *                 below 2^30 (see the errors), so a value that descends from such a cell is at least 2^30, more than any
+ *                 bound, and at most 2^30 + n + m: `+ 1` never wraps.
+ * Two facts follow; the tests rest on them.
+ *   THE BOUND IS DECISIVE.  Every computed value is 2^30 or more, or the cost of a path from (0, 0) that stays inside the
+ *                 region: the recurrence takes minima over such paths and over cells that count as 2^30.  So a computed
+ *                 D[n][m] <= T is the cost of a real path, hence >= the distance; and a path of the distance's cost, which is
+ *                 <= T then, stays on the diagonals above, inside the region, so the computed value is <= the distance: it IS
+ *                 the distance.  If the distance is <= T the same path makes the computed value <= T; so a computed value
+ *                 > T means a distance > T.
+ *   THE PATH IS THE SAME PATH.  Let the computed D[n][m] be <= T.  A cell on an optimal path (one of the distance's cost) has
+ *                 its true value: the path up to it is optimal for it and lies inside the region.  The trace stands on such
+ *                 a cell and tests its predecessors in the rule's order: diagonal, up, left.  A predecessor that satisfies
+ *                 its equality with true values lies on an optimal path too, so its computed value is its true value and the
+ *                 equality holds with computed values; one that does not satisfy it has a computed value that is no smaller
+ *                 than its true one (or counts as 2^30), so the equality fails with computed values as well.  Every test
+ *                 comes out as in the full matrix, step after step: runs, distance and identity are bit-equal to
+ *                 asgart_align_duplications'.
+ *   max_distance  one bound per duplication, each < 2^30.  status[q] = 2: q has more edits than its bound; no runs, distance
+ *                 0xFFFFFFFF, identity NaN, like a refusal.  status 0 (alone over the budget) and 1 as above; a status-1
+ *                 entry equals asgart_align_duplications' entry bit for bit.
+ *                 NULL: AUTOMATIC.  Every duplication starts at the bound |m - n| + max(64, max(n, m) / 64), at most n + m;
+ *                 those that come out with status 2 are aligned again with 4 times the bound, at most n + m, round after
+ *                 round; at n + m the corridor is the whole matrix, so no status 2 remains after the call.  The first bound
+ *                 and the factor are design constants.  THEY WERE REASONED, NOT SWEPT (csrc/align_dev.hpp gives the
+ *                 reasoning: a first corridor for young copies of 98.4 % identity and more; failed rounds that cost a third
+ *                 of the one that succeeds).
+ *   budget_bytes  as above, with asgart_align_bytes_banded's bytes: batching is by corridor bytes, and in automatic mode a
+ *                 duplication is refused when the corridor of the round it has reached exceeds the budget alone.  NO
+ *                 RESULT DEPENDS ON THE BUDGET OR ON THE BATCHING.
+ *   out           as above.  asgart_alignment_timings sums over batches and rounds.  asgart_alignment_rounds: the passes over
+ *                 the list (1 with given bounds, and for asgart_align_duplications) and the cells of the forward passes of
+ *                 all rounds, the rectangles' (n m each for asgart_align_duplications); either may be NULL.
+ * Errors: those above; a bound of 2^30 or more (ASGART_E_ARG); arms of 2^30 bases together, n + m (ASGART_E_CAP). */
+int32_t asgart_align_duplications_banded(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags, int64_t n_sd,
+                                         int32_t inclusive, const uint32_t *max_distance, uint64_t budget_bytes,
+                                         asgart_alignment **out);
+int32_t asgart_alignment_rounds(const asgart_alignment *a, uint32_t *rounds, uint64_t *cells);
+/* Host code, needs no device: bytes[q] = the checkpoint bytes of duplication q within max_distance[q] (not NULL here).  With
+ * span = |m - n| + 2 e, the corridor's diagonals less one, and wmax = min(m, band_rows + span), the widest rectangle:
+ *   4 n_bands band_rows ceil((wmax - 1) / W) + 4 (n_bands - 1)(wmax + 1)
+ * every band has column checkpoints at the multiples of W among its columns but the last and, but for the last band, a
+ * bottom row, each laid out for wmax columns.  0 for T < |m - n| and for an empty arm.  Errors as above. */
+int32_t asgart_align_bytes_banded(const asgart_proto_sd *sds, int64_t n_sd, int32_t inclusive, const uint32_t *max_distance,
+                                  uint64_t *bytes);
 
 /* ---- the steps behind the search step ------------------------------------------
  * Replaces FilterNs, ReOrder, ReduceOverlap and Sort of the reference's step chain (src/bin/asgart.rs:33-96 with
