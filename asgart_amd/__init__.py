@@ -49,6 +49,7 @@ ABI_SYMBOLS = (
     "asgart_fasta_source", "asgart_fasta_free", "asgart_fasta_timings", "asgart_fasta_geometry",
     "asgart_index_set_tail_up", "asgart_tier_segments", "asgart_tier_profile",
     "asgart_fill_counts", "asgart_fill_tally", "asgart_ranked_fill_takes", "asgart_hit_rule",
+    "asgart_join_cuts", "asgart_split_warm_next",
     "asgart_slice_families", "asgart_slice_counts", "asgart_slice_copy", "asgart_slice_timings", "asgart_slice_free",
     "asgart_plot_filter", "asgart_plot_counts", "asgart_plot_copy", "asgart_plot_timings", "asgart_plot_free",
     "asgart_plot_geometry",
@@ -248,6 +249,11 @@ def load_library() -> C.CDLL:
         L.asgart_tier_segments.restype = C.c_int32
         L.asgart_tier_profile.argtypes = [vp, vp]
         L.asgart_tier_profile.restype = C.c_int32
+    if hasattr(L, "asgart_join_cuts"):
+        L.asgart_join_cuts.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
+        L.asgart_join_cuts.restype = C.c_int32
+        L.asgart_split_warm_next.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
+        L.asgart_split_warm_next.restype = C.c_uint32
     if hasattr(L, "asgart_fill_counts"):
         L.asgart_fill_counts.argtypes = [vp, vp]
         L.asgart_fill_counts.restype = C.c_int32
@@ -967,6 +973,42 @@ def tier_profile() -> Tuple[np.ndarray, np.ndarray]:
     hits = np.zeros(8, dtype=np.uint64)
     _check(load_library().asgart_tier_profile(_ptr(ms), _ptr(hits)))
     return ms, hits
+
+
+FIX_HELD = 0xFFFFFFFE     # join_cuts: a range's records wait for the segment's tail run
+FIX_DROPPED = 0xFFFFFFFF  # ... are dropped
+JOINED, TAIL_RUN, WHOLE_AGAIN = 0, 1, 2  # join_cuts: what happens to the segment
+
+
+def join_cuts(cut_held, flushes, last_gave_up: bool = False, tail_gave_up: bool = False) -> dict:
+    """asgart_join_cuts (host code, no device needed): what a search call decides for ONE segment cut into
+    len(flushes) ranges -- cut_held[j] bit 0: cut j held; flushes[j]: the families range j flushed; last_gave_up: the run
+    over the last range gave up; tail_gave_up: so did the one more run over the rest, if there is one.
+    -> f: the first cut that did not hold (len(cut_held): none); action: JOINED, TAIL_RUN (ranges 0..f stand, one more
+    run from range f covers the rest) or WHOLE_AGAIN; tail_base: the family-ordinal base of that run; fix uint32[R]: what
+    is added to the family ordinals of each range's records before the tail run has come back (FIX_HELD: they wait,
+    FIX_DROPPED: they are dropped); settled uint32[R + 1]: the same after it has, [R] the tail run's own entry;
+    settled_action: the action after it has (a tail run that gave up: WHOLE_AGAIN)."""
+    flush = np.ascontiguousarray(flushes, dtype=np.uint32).reshape(-1)
+    held = np.ascontiguousarray(cut_held, dtype=np.uint32).reshape(-1)
+    R = len(flush)
+    if len(held) != max(R - 1, 0):
+        raise ValueError(f"{len(held)} cut verdicts for {R} ranges")
+    held = np.concatenate([held, np.zeros(1, dtype=np.uint32)])  # (never read; R = 1 has no cut)
+    fix = np.zeros(max(R, 1), dtype=np.uint32)
+    settled = np.zeros(R + 1, dtype=np.uint32)
+    out = np.zeros(4, dtype=np.uint32)
+    _check(load_library().asgart_join_cuts(R, _ptr(held), _ptr(flush), int(bool(last_gave_up)), int(bool(tail_gave_up)),
+                                           _ptr(fix), _ptr(settled), _ptr(out)))
+    return {"f": int(out[0]), "action": int(out[1]), "tail_base": int(out[2]), "fix": fix[:R], "settled": settled,
+            "settled_action": int(out[3])}
+
+
+def split_warm_next(warm_used: int, need: int, range_len: int, split_warm_max: int) -> int:
+    """asgart_split_warm_next (host code): the warm-up (probes) the index remembers for a segment a cut of which did not
+    hold with warm_used probes of warm-up, whose oldest arm in front of the cut was born `need` probes in front of it, in
+    a call with ranges of range_len probes and option split_warm_max; 0: none, only the cuts that held are planned again."""
+    return int(load_library().asgart_split_warm_next(int(warm_used), int(need), int(range_len), int(split_warm_max)))
 
 
 def compute_scores_multi(indices: Sequence[Index], sds: np.ndarray, reversed_: bool = False,

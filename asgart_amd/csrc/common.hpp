@@ -178,6 +178,11 @@ inline void background_call(F fn) {
     w->cv.notify_all();
 }
 
+// workgroups of `block` threads that cover n elements
+inline unsigned grid_for(uint64_t n, unsigned block = 256) {
+    return (unsigned)((n + block - 1) / block);
+}
+
 #define RC_TRY(expr)            \
     do {                        \
         int32_t rc_ = (expr);   \

@@ -9,7 +9,7 @@
 
 namespace asgart {
 
-constexpr int kTiers = 7;  // extension tiers (see the placement in pipeline.hip)
+constexpr int kTiers = 7;  // extension tiers (see the placement in call_place.hpp)
 constexpr int kRunsStat = kTiers + 1;  // statistics slot (ExtParams::tier) of the runs over ranges: after the tiers'
 
 // device counters (u64 each)

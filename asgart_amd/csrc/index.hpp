@@ -12,6 +12,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "range_join.hpp"
 
 #include <functional>
 #include <memory>
@@ -128,6 +129,19 @@ struct RunParams {
 };
 // the mode of the pass these settings ask for, as RunParams::modes and mode_of_pass hold it
 inline uint32_t mode_of_settings(const asgart_settings &st) { return (st.reverse ? 2u : 0u) | (st.complement ? 1u : 0u); }
+// probes of a chunk of L bases
+inline uint32_t probes_in_chunk(uint64_t L, uint64_t k, uint64_t step, uint64_t M) {
+    // loop of src/automaton.rs:92-97: `while i < L - k - step { i += step; ... }`
+    if (L < M || L < k + step || L - k - step == 0) return 0;
+    return (uint32_t)((L - k - step + step - 1) / step);
+}
+// The progress array of a call whose probes are all searched (reference src/automaton.rs:98 stores every probe's offset
+// for a polled progress bar): per chunk, the offset of its last probe.  len[c * stride]: chunk c's length.
+inline void fill_progress(volatile uint64_t *progress, const uint64_t *len, int64_t stride, int64_t n_chunks, const asgart_settings &st) {
+    const uint64_t k = st.probe_size, step = k / 2;
+    for (int64_t c = 0; c < n_chunks; ++c)
+        progress[c] = (uint64_t)probes_in_chunk(len[c * stride], k, step, st.min_duplication_length) * step;
+}
 
 // One emitted duplication arm, keyed for the reference's output order (chunk order, discovery order
 // inside the chunk, arm order inside the family).
@@ -224,7 +238,7 @@ struct SearchCtx {
     // times slower than the kernels that produce it); grow-only, freed with the index
     void *h_pinned = nullptr;
     size_t h_pinned_cap = 0;
-    // host-side parts of the family assembly (run_search_t), kept for their capacity
+    // host-side parts of the family assembly (records, call_records.hpp), kept for their capacity
     struct FamPart {
         std::vector<asgart_proto_sd> sds[4];
         std::vector<uint64_t> ends[4], keys[4];  // per family: records up to and including it (within the part), key
@@ -381,7 +395,7 @@ struct Options {
     int64_t watchdog_s = 120;       // a search call whose device work makes no progress for this many seconds returns ASGART_E_HIP with the
                                     // last heartbeats of its kernels instead of waiting forever; 0: wait forever
 };
-// The tail rule of the placement (place_tier, place_dev.hpp; the thresholds are TierTable's, pipeline.hip), set with
+// The tail rule of the placement (place_tier, place_dev.hpp; the thresholds are TierTable's, tiers.hpp), set with
 // asgart_index_set_tail_up.  (Not an entry of the option table above.)
 struct TailUp {
     int32_t mode = 1;  // 0: off; 1: on in calls with fewer tier streams than arm-resident tiers that can hold work; 2: always on (tests)
@@ -391,11 +405,6 @@ int32_t create_ctx_streams(SearchCtx &cx);
 // The normal-priority hardware queues this process may open: GPU_MAX_HW_QUEUES if it is set, otherwise HIP's default
 // of 4, clamped to 1..32 (the library reads the variable and never sets it).
 int hw_queue_budget();
-// The extension tiers' streams of one call (host code, asgart_tier_plan): stream_of[t - 1] = 0 for the main stream, s for
-// tier stream s (1 .. min(6, budget)), -1 for a tier without work; launch[] = the tiers with work in launch order (which
-// is also the order within each stream: longest estimate first), 0 behind them.
-int32_t tier_plan(int budget, const uint64_t *n_work, int64_t tier_order, const double *est_ms, double main_ms,
-                  int32_t *stream_of, int32_t *launch);
 template <class SlotT>
 int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_t n, SlotT *d_sap, SlotT *d_sar, uint32_t min_run,
                               int k, hipStream_t s);  // (sa_build.hip: only the runs of more than min_run equal keys; any slot width)  // the streams and events of one call context (current device)
@@ -505,15 +514,58 @@ struct asgart_index {
         int32_t n_fused = 0, n_piped = 0;      // calls timed each way
         int32_t unsettled = 0;                 // calls in a row that refused a cut (not samples, unless three in a row)
         double ms_fused = 1e30, ms_piped = 1e30;
+        // is this the verdict of the calls with these settings (st[0]), orientations and shard?
+        bool matches(const asgart_settings *st, int32_t np, uint64_t modes_sig, int32_t sh, int32_t n_sh) const {
+            return n_passes == np && k == st[0].probe_size && G == st[0].max_gap_size && M == st[0].min_duplication_length &&
+                   C == st[0].max_cardinality && modes == modes_sig && shard == sh && n_shards == n_sh;
+        }
+        void reset_for(const asgart_settings *st, int32_t np, uint64_t modes_sig, int32_t sh, int32_t n_sh) {
+            *this = FuseVerdict{};
+            n_passes = np;
+            k = st[0].probe_size;
+            G = st[0].max_gap_size;
+            M = st[0].min_duplication_length;
+            C = st[0].max_cardinality;
+            modes = modes_sig;
+            shard = sh;
+            n_shards = n_sh;
+        }
+        // the next call runs pipelined: measured both ways and pipelined was faster (stands from here on), or ONE segment
+        // is the extension and the pipelined way has fewer samples than the other
+        bool wants_pipelined() const {
+            if (n_fused >= 2 && n_piped >= 2) return !(ms_fused <= ms_piped);
+            return pole && n_piped < 2 && n_piped < n_fused;
+        }
+        // A call that refused a cut is not a sample -- the index is still learning which ranges join up, the next call will be
+        // shorter -- unless three in a row did.
+        bool is_sample(bool refused) {
+            if (refused && ++unsettled < 3) return false;
+            unsettled = 0;
+            return true;
+        }
+        // a call that ran as one job took ms; pole_: ONE segment was its extension.  (The first call with these settings
+        // is not timed: it may be the index's first.)
+        void note_fused(double ms, bool refused, bool pole_) {
+            if (seen && is_sample(refused)) {
+                ++n_fused;
+                ms_fused = std::min(ms_fused, ms);
+            }
+            seen = true;
+            pole = pole_;
+        }
+        // ... a call that ran pipelined because this verdict asked for it; false: not a sample
+        bool note_piped(double ms, bool refused) {
+            if (!is_sample(refused)) return false;
+            ++n_piped;
+            ms_piped = std::min(ms_piped, ms);
+            return true;
+        }
     } fuse_verdict;
     // segments a cut of which did not hold (option split): orientation << 32 | first probe counted from the start of its pass,
     // under which settings and chunk list (sig), how many of their cuts, from the start, held (only those are planned again)
     // and at which range length.  Cleared with the keys; the oldest entries age out.
-    struct SplitVerdict {
-        uint64_t key, sig;
-        uint32_t allowed, range_len;  // (the count belongs to the range length it was found at: one entry per segment and length)
-        uint32_t warm;                // the warm-up this segment's ranges get from now on (0: the call's own)
-    };
+    // (range_join.hpp: remember_split writes it, blocked_in_call reads it)
+    using SplitVerdict = asgart::SplitVerdict;
     std::vector<SplitVerdict> split_blocked;
     asgart::DevBuf ws_arena;  // the block the call contexts' per-probe buffers were carved from (carve_probe_workspace), or empty
     std::mutex pass_mu;  // one asgart_search_duplications_passes call at a time per index
@@ -591,6 +643,15 @@ struct asgart_families {
                                         // ascending == reference order; what a gatherer merges sharded results by
     std::vector<asgart_proto_sd> sds;
 };
+namespace asgart {
+// A fresh result object; null, with the error set: out of host memory.  An entry point releases it into *out when it
+// has succeeded, every other way out deletes it.
+inline std::unique_ptr<asgart_families> new_families() {
+    std::unique_ptr<asgart_families> f(new (std::nothrow) asgart_families());
+    if (!f) set_error("out of host memory");
+    return f;
+}
+}  // namespace asgart
 
 namespace asgart {
 // An index whose watchdog gave up (or whose teardown did) may still have work running on its streams and buffers: every
@@ -607,7 +668,7 @@ namespace asgart {
 // mutex its own thread owns: undefined for std::mutex)
 extern thread_local bool tl_owns_pass_mu;
 int32_t index_prepare(asgart_index *idx, uint64_t k);
-// per-probe workspace of one call context for a window of W probes (pipeline.hip; also what run_search_t reserves)
+// per-probe workspace of one call context for a window of W probes (call_front.hpp; also what a call's front reserves)
 int32_t reserve_probe_workspace(asgart_index *idx, SearchCtx &cx, uint64_t W);
 // asgart_index_prepare: the per-probe workspace of ALL call contexts (context c for Wc[c] probes) carved out of ONE block that
 // the suffix sorter has just released, if the block cache holds one of the right size (false: nothing done)

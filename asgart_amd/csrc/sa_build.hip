@@ -26,10 +26,6 @@ namespace asgart {
 
 namespace {
 
-inline unsigned grid_for(uint64_t n, unsigned block = 256) {
-    return (unsigned)((n + block - 1) / block);
-}
-
 template <bool DNA>
 __device__ inline uint64_t initial_key(const uint8_t *__restrict__ text, uint64_t n, uint64_t i) {
     uint64_t q = 0;

@@ -991,6 +991,28 @@ int32_t asgart_ranked_fill_takes(uint64_t interval, uint64_t kept, int32_t mode)
  * reversed pass or a direct one, as the kernels state it (host code, needs no device): occurrence x is kept when
  * x >= out[0] && x != out[1]  (src/automaton.rs:105-114). */
 void asgart_hit_rule(uint64_t i, uint64_t s, uint64_t L, int32_t reverse, uint64_t *out);
+/* asgart_join_cuts: host code, needs no device (for tests of the rule).  What a search call decides for ONE long segment
+ * that ran as n_ranges ranges side by side (option split): cut_held[j] bit 0 = cut j, between ranges j and j + 1, held
+ * (n_ranges - 1 verdicts); flushes[j] = the families range j flushed; last_gave_up != 0: the run over the last range gave
+ * up.  Every cut held: the family ordinals of range j count on from the flushes of ranges 0 .. j - 1 (fix[j] = their sum)
+ * and the segment is joined.  Otherwise f is the first cut that did not hold: ranges 0 .. f stand (fix = 0xFFFFFFFE: held
+ * until the tail run has come back), the records of the ranges behind it are dropped (fix = 0xFFFFFFFF), and ONE more run
+ * covers the rest, from where range f started, its family ordinals counting on from the flushes of ranges 0 .. f.  f = 0,
+ * or every cut held but the last run gave up (f = 0 then): every range is dropped and the whole segment runs again.
+ * Writes fix[n_ranges]; settled[n_ranges + 1]: fix when the tail run has come back -- ranges 0 .. f get their bases,
+ * settled[n_ranges] is the tail run's base (0xFFFFFFFF: no tail run) -- and with tail_gave_up != 0 every entry is dropped
+ * and the whole segment runs again; out[0] = f (n_ranges - 1: every cut held), out[1] = the action (0 = joined, 1 = one more
+ * run from range f, 2 = the whole segment again), out[2] = the tail run's base, out[3] = the action when the tail run has
+ * come back.  Errors: n_ranges outside 1..4096, a null pointer (ASGART_E_ARG). */
+int32_t asgart_join_cuts(int32_t n_ranges, const uint32_t *cut_held, const uint32_t *flushes, int32_t last_gave_up,
+                         int32_t tail_gave_up, uint32_t *fix, uint32_t *settled, uint32_t *out);
+/* asgart_split_warm_next: host code, needs no device (for tests of the rule).  The warm-up, in probes, the index remembers
+ * for a segment a cut of which did not hold: warm_used = the warm-up its ranges had (0: the warm-up is not the matter),
+ * need = how far in front of the failed cut the oldest arm of the range before it was born, range_len = probes per range,
+ * split_warm_max as the option.  limit = min(split_warm_max, 2 * range_len).  need > warm_used: need + 64 rounded up to a
+ * multiple of 256; else the limit itself while warm_used is below it.  0 when warm_used = 0 or the result would exceed the
+ * limit: the segment keeps the call's own warm-up and only the cuts that held are planned again. */
+uint32_t asgart_split_warm_next(uint32_t warm_used, uint32_t need, uint32_t range_len, uint64_t split_warm_max);
 /* The tier table's figures a call starts from (host code, needs no device): profile_ms[0] = the runs over ranges,
  * profile_ms[t] = tier t's estimated duration on the GRCh38-shaped profile (what asgart_tier_plan is fed before a call
  * has measurements of its own), for a thresholded tier what is left of it where the tail rule is in force; tail_hits[t] =

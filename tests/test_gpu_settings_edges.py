@@ -10,7 +10,7 @@ orientation; the others see them shifted by at most a probe), quiet runs inside 
 chunks shorter than k + k/2.
 
 The library deliberately refuses one setting: max_cardinality * (t* + 1) live arms of 2^24 and more (ASGART_E_CAP,
-pipeline.hip `heavy_cap64`); test_tier7_capacity_refusal_edge asserts that error and that nothing leaks with it.
+call_place.hpp `heavy_cap64`); test_tier7_capacity_refusal_edge asserts that error and that nothing leaks with it.
 
 Run with `pytest -m gpu` on an MI355X."""
 import random
@@ -31,7 +31,7 @@ _COMP = bytes.maketrans(b"ACGTN", b"TGCAN")
 
 # ---- the settings ----------------------------------------------------------------------------------------------------
 def tstar(k, gap):
-    """Quiet probes after which every arm is dead and a segment ends: ceil((gap + k) / (k / 2)) (pipeline.hip: rp.tstar)."""
+    """Quiet probes after which every arm is dead and a segment ends: ceil((gap + k) / (k / 2)) (call_setup.hpp: rp.tstar)."""
     return max(1, -(-(gap + k) // (k // 2)))
 
 
@@ -48,7 +48,7 @@ def corners(k):
 
 
 def heavy_cap64(C, t):
-    """pipeline.hip (place): live-arm capacity of a tier-7 workgroup, max_cardinality * (t* + 1) + 64, at least 4096,
+    """call_place.hpp (place): live-arm capacity of a tier-7 workgroup, max_cardinality * (t* + 1) + 64, at least 4096,
     rounded up to a multiple of 4 (max_cardinality clamped at 0xFFFFFF00 as rp.C is)."""
     C = min(C, 0xFFFFFF00)
     return (max(C * (t + 1) + 64, 4096) + 3) & ~3

@@ -156,7 +156,7 @@ def test_ranges_joined_equal_the_whole_run_and_the_oracle(period, copies, sub, n
     (171, 60, 0.0, 4, 200),
 ])
 def test_a_failed_cut_tells_the_warm_up_its_segment_needs(period, copies, sub, n_ranges, warm):
-    """What the library does with a cut that did not hold (pipeline.hip: remember(); validate_cuts_kernel reports where the
+    """What the library does with a cut that did not hold (range_join.hpp: split_warm_next(), which tests/test_range_join_host.py runs; validate_cuts_kernel reports where the
     oldest arm in front of the cut was born).  A run that is to hold that arm at the cut must START in front of the probe
     that created it -- creation keys are (probe, hit) in every run -- so a warm-up shorter than that distance cannot hold:
     the next call gives the segment's ranges that much.  That is necessary, not sufficient (what an arm looks like also
