@@ -27,6 +27,7 @@ __all__ = [
     "export_records", "export_geometry", "f32_shortest", "f32_pow10_table", "EXPORT_FORMATS",
     "ResultScan", "result_geometry", "E_REFUSED", "Alignments", "align_geometry", "align_bytes", "align_bytes_banded",
     "paf_records", "paf_geometry", "paf_records_cs", "paf_cs_geometry", "CS_MODES",
+    "AlignCounts", "alignment_stats_geometry", "sdtable_records", "sdtable_geometry",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,6 +65,7 @@ ABI_SYMBOLS = (
     "asgart_align_duplications_banded", "asgart_alignment_rounds", "asgart_align_bytes_banded",
     "asgart_paf_records", "asgart_paf_geometry", "asgart_paf_records_cs", "asgart_paf_cs_geometry",
     "asgart_index_read_text",
+    "asgart_alignment_stats", "asgart_alignment_stats_geometry", "asgart_sdtable_records", "asgart_sdtable_geometry",
 )
 
 
@@ -371,6 +373,16 @@ def load_library() -> C.CDLL:
         L.asgart_paf_cs_geometry.restype = None
         L.asgart_index_read_text.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
         L.asgart_index_read_text.restype = C.c_int32
+    if hasattr(L, "asgart_alignment_stats"):
+        L.asgart_alignment_stats.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, C.POINTER(C.c_double)]
+        L.asgart_alignment_stats.restype = C.c_int32
+        L.asgart_alignment_stats_geometry.argtypes = [u64p, u64p]
+        L.asgart_alignment_stats_geometry.restype = None
+        L.asgart_sdtable_records.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp,
+                                             vp, vp, vp, vp, C.c_uint64, C.POINTER(vp)]
+        L.asgart_sdtable_records.restype = C.c_int32
+        L.asgart_sdtable_geometry.argtypes = [u64p, u64p, u64p]
+        L.asgart_sdtable_geometry.restype = None
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []
@@ -677,6 +689,39 @@ class Index:
         finally:
             L.asgart_alignment_free(h)
 
+    def alignment_stats(self, sds: np.ndarray, flags: Optional[np.ndarray], aln: "Alignments",
+                        timings: Optional[list] = None) -> "AlignCounts":
+        """The counts of every alignment (asgart_alignment_stats; include/asgart_hip.h states them, align.stats_host is the
+        readable form): sds and flags as align took them, aln the Alignments of align(sds, flags, inclusive=False).  A
+        duplication whose status is not 1 gets ten zeros.  timings: a list that receives the milliseconds of upload,
+        kernels and copy back."""
+        L = load_library()
+        if not hasattr(L, "asgart_alignment_stats"):
+            raise AsgartError(-3, f"{library_path()} has no asgart_alignment_stats: rebuild it; there is no host fallback "
+                                  "behind this call (align.stats_host is the host statement)")
+        sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+        flags = _score_flags(flags, len(sds))
+        if flags is None:
+            flags = np.zeros(len(sds), dtype=np.uint8)
+        status = np.ascontiguousarray(aln.status, dtype=np.uint8).reshape(-1)
+        run_offsets = np.ascontiguousarray(aln.run_offsets, dtype=np.uint64).reshape(-1)
+        run_len = np.ascontiguousarray(aln.run_len, dtype=np.uint32).reshape(-1)
+        run_op = np.ascontiguousarray(aln.run_op, dtype=np.uint8).reshape(-1)
+        n = len(sds)
+        if len(status) != n or len(run_offsets) != n + 1 or len(run_len) != len(run_op):
+            raise ValueError("alignment_stats: the arrays differ in length")
+        if len(run_len) < int(run_offsets[-1]) < 1 << 32:   # (2^32 runs and more are the library's to refuse, unread)
+            raise ValueError(f"alignment_stats: run_offsets end at {int(run_offsets[-1])}, there are {len(run_len)} runs")
+        if len(run_len) == 0:
+            run_len, run_op = np.zeros(1, np.uint32), np.zeros(1, np.uint8)
+        out = np.zeros((n, len(AlignCounts.FIELDS)), dtype=np.uint64)
+        ms = (C.c_double * 3)()
+        _check(L.asgart_alignment_stats(self._h, _ptr(sds), _ptr(flags), _ptr(status), n, _ptr(run_offsets), _ptr(run_len),
+                                        _ptr(run_op), _ptr(out), ms))
+        if timings is not None:
+            timings[:] = list(ms)
+        return AlignCounts(out)
+
     def compute_scores_flags_shard(self, sds: np.ndarray, flags: Optional[np.ndarray], shard: int = 0,
                                    n_shards: int = 1) -> np.ndarray:
         """compute_scores_shard with one flag byte per duplication (asgart_compute_scores_flags_shard): the same owners,
@@ -796,6 +841,39 @@ class Alignments:
     def cigar(self, q: int) -> str:
         """`812=1X40=3I...`; empty for a refused duplication and for one beyond its max_distance."""
         return "".join(f"{n}{op}" for n, op in self.ops(q))
+
+
+class AlignCounts:
+    """The counts of asgart_alignment_stats: `table` is uint64[n, 10], one asgart_align_counts per duplication; every field
+    is also an attribute (counts.match is table[:, 0])."""
+
+    FIELDS = ("match", "mismatch", "transition", "transversion", "ins_runs", "ins_bases", "del_runs", "del_bases",
+              "longest_match", "longest_gap")
+
+    def __init__(self, table):
+        self.table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, len(self.FIELDS))
+
+    def __len__(self) -> int:
+        return len(self.table)
+
+    def __getattr__(self, name):
+        if name in AlignCounts.FIELDS:
+            return self.table[:, AlignCounts.FIELDS.index(name)]
+        raise AttributeError(name)
+
+    def __eq__(self, other):
+        return isinstance(other, AlignCounts) and np.array_equal(self.table, other.table)
+
+    def part(self, lo: int, hi: int) -> "AlignCounts":
+        """The duplications lo .. hi - 1 as counts of their own."""
+        return AlignCounts(self.table[lo:hi])
+
+
+def alignment_stats_geometry() -> Tuple[int, int]:
+    """asgart_alignment_stats_geometry: threads per workgroup, mismatch bases per workgroup of the bases kernel."""
+    a, b = C.c_uint64(), C.c_uint64()
+    load_library().asgart_alignment_stats_geometry(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
 
 
 def align_geometry() -> Tuple[int, int, int]:
@@ -1184,6 +1262,52 @@ def paf_cs_geometry() -> Tuple[int, int, int, int]:
     a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
     load_library().asgart_paf_cs_geometry(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
     return int(a.value), int(b.value), int(c.value), int(d.value)
+
+
+def sdtable_records(offs, sds, flags, status, chr_, chr_pos, names: Sequence[bytes], counts: "AlignCounts", figures,
+                    prefix: bytes, device: int = 0, timings: Optional[list] = None) -> np.ndarray:
+    """asgart_sdtable_records: the whole duplication table as uint8[size], written on the GPU (csrc/sdtable.hip).  offs, sds,
+    flags, chr_, chr_pos, names as export_records takes them; status: a row for every duplication where it is not 0; counts:
+    the AlignCounts of the duplications; figures: the four float32 arrays of align.divergence; prefix: the header line.
+    timings: a list that receives the call's three millisecond figures (asgart_export_timings: upload, kernels, copy back)."""
+    L = load_library()
+    if not hasattr(L, "asgart_sdtable_records"):
+        raise AsgartError(-3, f"{library_path()} has no asgart_sdtable_records: rebuild it; there is no host fallback behind "
+                              "this call (align.sd_table_text is the host writer)")
+    offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    status = np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
+    chr_ = np.ascontiguousarray(chr_, dtype=np.int32).reshape(-1, 2)
+    chr_pos = np.ascontiguousarray(chr_pos, dtype=np.uint64).reshape(-1, 2)
+    table = np.ascontiguousarray(counts.table, dtype=np.uint64)
+    figures = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in figures]
+    n = len(sds)
+    if len(offs) < 1 or not (len(flags) == len(status) == len(chr_) == len(chr_pos) == len(table) == n) or \
+            len(figures) != 4 or any(len(v) != n for v in figures):
+        raise ValueError("sdtable_records: the arrays differ in length")
+    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum([len(b) for b in names], out=name_off[1:])
+    name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+    pre = np.frombuffer(prefix or b"\0", dtype=np.uint8)
+    h = C.c_void_p()
+    _check(L.asgart_sdtable_records(int(device), _ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags), _ptr(status), _ptr(chr_),
+                                    _ptr(chr_pos), n, _ptr(name_bytes), _ptr(name_off), len(names), _ptr(table),
+                                    *[_ptr(v) for v in figures], _ptr(pre), len(prefix), C.byref(h)))
+    try:
+        out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
+        _check(L.asgart_export_copy(h, _ptr(out), len(out)))
+        _read_timings(L.asgart_export_timings, h, timings)
+    finally:
+        L.asgart_export_free(h)
+    return out
+
+
+def sdtable_geometry() -> Tuple[int, int, int]:
+    """asgart_sdtable_geometry: threads per workgroup, rows per workgroup, bytes of the LDS image of the write stage."""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    load_library().asgart_sdtable_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
 
 
 E_REFUSED = -5   # ASGART_E_REFUSED: the device reader of result files leaves the input to the host reader

@@ -12,6 +12,11 @@ This module states the same rule on the host, for the tests to compare byte for 
     paf_text_gpu the same bytes, written on the GPU (asgart_paf_records, csrc/paf.hip)
     cs_text      minimap2's difference string (cs:Z:) of one row: the bases behind its CIGAR; both writers add it as a
                  sixteenth column when asked (cs="short" or "long"; asgart_paf_records_cs on the GPU)
+    stats_host   the counts of an alignment, base by base: matches, mismatches, transitions and transversions, indels
+                 (Index.alignment_stats takes them on the GPU: asgart_alignment_stats, csrc/alnstats.hip)
+    divergence   fracMatch, fracMatchIndel and the Jukes-Cantor and Kimura distances from those counts
+    sd_table_text        the duplication table, BEDPE and UCSC's genomicSuperDups columns: one row per aligned duplication
+    sd_table_text_gpu    the same bytes, written on the GPU (asgart_sdtable_records, csrc/sdtable.hip)
 
 The arms: A = text[left ..] is the left arm; B is the right arm as ProtoSD::levenshtein walks it (reference
 src/structs.rs:439-452): reversed if flag bit 0 is set, complemented if bit 1 is set (ACGT and acgt swap, anything else is
@@ -410,3 +415,215 @@ def paf_text_gpu(offs, sds, flags, strand, aln, device: int = 0, stderr=None, ti
     if cs is None:
         return _paf_text_device(offs, sds, flags, strand, aln, device, stderr, timings).tobytes()
     return _paf_text_device(offs, sds, flags, strand, aln, device, stderr, timings, cs=cs, index=index).tobytes()
+
+
+# ---- the counts of an alignment and the duplication table -------------------------------------------------------------
+
+def _base_class(b: np.ndarray) -> np.ndarray:
+    """1 for a purine (a, g), 2 for a pyrimidine (c, t), 0 for every other byte; the bytes are already lower case"""
+    return np.where((b == ord("a")) | (b == ord("g")), 1, np.where((b == ord("c")) | (b == ord("t")), 2, 0))
+
+
+def stats_host(text, sds, flags, aln):
+    """The counts of every alignment, base by base: what Index.alignment_stats (asgart_alignment_stats) must return, as
+    asgart_amd.AlignCounts.  text: the text the duplications lie in; sds (n, 4) and flags as Index.align took them (all four
+    flag values are legal); aln its Alignments for inclusive=False.  The frame is the alignment's: A and B are arms(text,
+    sd, flag, False), B reversed and complemented as the flag says.  Run t starts at the arm offsets i (the bases of the
+    earlier runs with `=`, `X` or `I`) and j (`=`, `X` or `D`); base v of it pairs a = A[i + v] with b = B[j + v].
+        match, mismatch         the sums of the `=` and of the `X` run lengths
+        ins_runs, ins_bases     the number and the sum of the `I` runs; del_runs, del_bases the same for `D`
+        longest_match           the largest `=` run; longest_gap the largest `I` or `D` run
+        transition              the bases of `X` runs, A-Z folded to a-z, with a != b and both in {a, g} or both in {c, t}
+        transversion            those with one in {a, g} and the other in {c, t}
+    An `X` base with an N or any other byte, or over equal bytes, is neither; no `=` base is looked at.  A duplication whose
+    status is not 1 gets ten zeros, and nothing of it is read.  ValueError: an unknown operation, a run of no base, runs that
+    do not consume exactly both arms, arms that reach past the text."""
+    from . import AlignCounts
+
+    text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.zeros(len(sds), dtype=np.uint8) if flags is None else np.asarray(flags, dtype=np.uint8).reshape(-1)
+    out = np.zeros((len(sds), len(AlignCounts.FIELDS)), dtype=np.uint64)
+    col = {name: k for k, name in enumerate(AlignCounts.FIELDS)}
+    for q, sd in enumerate(sds.tolist()):
+        if aln.status[q] != 1:
+            continue
+        a, b = arms(text, sd, int(flags[q]), False)
+        c = dict.fromkeys(AlignCounts.FIELDS, 0)
+        i = j = 0
+        for n, op in aln.ops(q):
+            n = int(n)
+            if op not in ("=", "X", "I", "D"):
+                raise ValueError(f"duplication {q}: unknown operation `{op}`")
+            if n <= 0:
+                raise ValueError(f"duplication {q}: a run of {n} `{op}`")
+            if i + (n if op != "D" else 0) > len(a) or j + (n if op != "I" else 0) > len(b):
+                raise ValueError(f"duplication {q}: `{n}{op}` at ({i}, {j}) runs past an arm: the runs do not consume arms "
+                                 f"of {len(a)} and {len(b)}")
+            if op == "=":
+                c["match"] += n
+                c["longest_match"] = max(c["longest_match"], n)
+            elif op == "X":
+                c["mismatch"] += n
+                pa = np.frombuffer(_lower(a[i:i + n]), dtype=np.uint8)
+                pb = np.frombuffer(_lower(b[j:j + n]), dtype=np.uint8)
+                ka, kb = _base_class(pa), _base_class(pb)
+                differ = (pa != pb) & (ka != 0) & (kb != 0)
+                c["transition"] += int((differ & (ka == kb)).sum())
+                c["transversion"] += int((differ & (ka != kb)).sum())
+            else:
+                kind = "ins" if op == "I" else "del"
+                c[kind + "_runs"] += 1
+                c[kind + "_bases"] += n
+                c["longest_gap"] = max(c["longest_gap"], n)
+            if op != "D":
+                i += n
+            if op != "I":
+                j += n
+        if i != len(a) or j != len(b):
+            raise ValueError(f"duplication {q}: the runs consume {i} and {j} bases of arms of {len(a)} and {len(b)}")
+        for name, v in c.items():
+            out[q, col[name]] = v
+    return AlignCounts(out)
+
+
+def divergence(counts):
+    """The four derived figures of a duplication table, from the counts alone -> (fracMatch, fracMatchIndel, jcK, k2K),
+    float32 arrays of one value per duplication.  With alignB = match + mismatch and indelN = ins_runs + del_runs,
+        fracMatch       match / alignB
+        fracMatchIndel  match / (alignB + indelN)
+        jcK             -3/4 ln(1 - 4p/3), p = mismatch / alignB                  (Jukes-Cantor)
+        k2K             -1/2 ln((1 - 2P - Q) sqrt(1 - 2Q)), P = transition / alignB, Q = transversion / alignB  (Kimura)
+    computed in float64 and rounded once to float32.  A value is NaN where alignB is 0 or where the argument of its
+    logarithm is not above 0 (p >= 3/4; 1 - 2P - Q <= 0 or 1 - 2Q <= 0), never an infinity; a zero is +0 (0.0 is added
+    before the rounding), so that p = 0 prints `0`.  A mismatch that involves an N counts in p and in neither P nor Q.
+    Both writers of the table print THESE arrays: the file does not depend on whose logarithm ran."""
+    t = counts.table.astype(np.float64)
+    match, mismatch, ts, tv, ins_runs, del_runs = t[:, 0], t[:, 1], t[:, 2], t[:, 3], t[:, 4], t[:, 6]
+    align_b = match + mismatch
+    some = align_b > 0
+    nan = np.full(len(t), np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        frac = np.where(some, match / align_b, nan)
+        frac_indel = np.where(some, match / (align_b + ins_runs + del_runs), nan)
+        jc_arg = 1.0 - 4.0 * (mismatch / align_b) / 3.0
+        jc = np.where(some & (jc_arg > 0), -0.75 * np.log(np.where(jc_arg > 0, jc_arg, 1.0)), nan)
+        a1, a2 = 1.0 - 2.0 * (ts / align_b) - tv / align_b, 1.0 - 2.0 * (tv / align_b)
+        ok = some & (a1 > 0) & (a2 > 0)
+        k2_arg = np.where(ok, a1, 1.0) * np.sqrt(np.where(ok, a2, 1.0))
+        k2 = np.where(ok, -0.5 * np.log(k2_arg), nan)
+    return tuple((v + 0.0).astype(np.float32) for v in (frac, frac_indel, jc, k2))
+
+
+SD_TABLE_COLUMNS = ("chrom1", "start1", "end1", "chrom2", "start2", "end2", "name", "score", "strand1", "strand2", "family",
+                    "alignL", "alignB", "matchB", "mismatchB", "transitionsB", "transversionsB", "indelN", "indelS",
+                    "longestMatch", "longestGap", "fracMatch", "fracMatchIndel", "jcK", "k2K")
+SD_TABLE_HEADER = "#" + "\t".join(SD_TABLE_COLUMNS) + "\n"
+
+
+def sd_table_text(offs, sds, flags, strand, aln, counts, stderr=None) -> str:
+    """The duplication table of a result: a header line, `#` and the names of the 25 columns, then one tab-separated row
+    per aligned duplication (status 1), in order.  offs / sds / flags / strand / aln as paf_text takes them; counts the
+    AlignCounts of the same alignments (stats_host or Index.alignment_stats).  The first ten columns are BEDPE, the rest
+    carry the names of UCSC's genomicSuperDups:
+        chrom1 start1 end1      the left arm: names, lengths and positions resolved as paf_text resolves them, `unknown`
+        chrom2 start2 end2      with the global position included; the right arm
+        name                    `sd<q>`, q the duplication's ordinal in the result
+        score                   `0`;   strand1 `+`;   strand2 `+` for flag 0, `-` for flag 3
+        family                  the duplication's family
+        alignL                  alignB + indelS;   alignB   match + mismatch
+        matchB mismatchB transitionsB transversionsB     the counts
+        indelN                  ins_runs + del_runs;   indelS   ins_bases + del_bases
+        longestMatch longestGap the counts
+        fracMatch fracMatchIndel jcK k2K    divergence(counts), printed as slice.f32_display prints an identity
+    A reversed-only or complemented-only duplication has no strand: paf_text's ValueError.  A refused duplication (status
+    0 or 2) gets no row and is named on stderr."""
+    from .slice import f32_display
+
+    offs = np.asarray(offs, dtype=np.int64)
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds) or len(counts) != len(sds):
+        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, {len(counts)} "
+                         f"counts, families that end at {int(offs[-1])}")
+    for q, f in enumerate(flags.tolist()):
+        if f not in (0, 3):
+            raise ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
+                             "direct (+) and reverse-complemented (-) alignments and none for this one")
+    total = sum(c.length for c in strand.map)
+
+    def locate(pos: int):
+        for c in strand.map:   # first match, as RunResult's find_chr_by_pos
+            if c.position <= pos < c.position + c.length:
+                return c.name, pos - c.position
+        return "unknown", pos
+
+    family = np.repeat(np.arange(len(offs) - 1), np.diff(offs))
+    figures = divergence(counts)
+    rows = [SD_TABLE_HEADER]
+    for q, (left, right, ll, rl) in enumerate(sds.tolist()):
+        if aln.status[q] != 1:
+            print(f"sd-table: duplication {q} (family {int(family[q])}) was refused by the alignment's "
+                  f"{_REFUSAL[int(aln.status[q])]}: no row", file=stderr if stderr is not None else sys.stderr)
+            continue
+        match, mismatch, ts, tv, ins_runs, ins_bases, del_runs, del_bases, longest_match, longest_gap = \
+            (int(v) for v in counts.table[q])
+        name1, pos1 = locate(left)
+        name2, pos2 = locate(right)
+        rows.append("\t".join(str(v) for v in (
+            name1, pos1, pos1 + ll, name2, pos2, pos2 + rl, f"sd{q}", 0, "+", "-" if flags[q] == 3 else "+",
+            int(family[q]), match + mismatch + ins_bases + del_bases, match + mismatch, match, mismatch, ts, tv,
+            ins_runs + del_runs, ins_bases + del_bases, longest_match, longest_gap,
+            *(f32_display(v[q]) for v in figures))) + "\n")
+    return "".join(rows)
+
+
+def _sd_table_device(offs, sds, flags, strand, aln, counts, device: int = 0, stderr=None,
+                     timings: Optional[dict] = None) -> np.ndarray:
+    """sd_table_text_gpu as the uint8 array the library filled (the drivers decode it without another copy)."""
+    import time
+
+    from . import sdtable_records
+    from .postprocess import locate_arms
+
+    offs = np.asarray(offs, dtype=np.int64)
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds) or len(counts) != len(sds):
+        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, {len(counts)} "
+                         f"counts, families that end at {int(offs[-1])}")
+    odd = np.flatnonzero((flags != 0) & (flags != 3))
+    if len(odd):
+        q, f = int(odd[0]), int(flags[odd[0]])
+        raise ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
+                         "direct (+) and reverse-complemented (-) alignments and none for this one")
+    t0 = time.perf_counter()
+    names = [c.name.encode("utf-8") for c in strand.map] + [b"unknown"]
+    chr_, chr_pos = locate_arms(sds, strand)
+    why = np.asarray(aln.status, dtype=np.uint8).reshape(-1)
+    status = (why == 1).astype(np.uint8)
+    refused = np.flatnonzero(status == 0)
+    if len(refused):
+        family = np.searchsorted(offs, refused, side="right") - 1
+        for q, f in zip(refused.tolist(), family.tolist()):
+            print(f"sd-table: duplication {q} (family {f}) was refused by the alignment's {_REFUSAL[int(why[q])]}: no row",
+                  file=stderr if stderr is not None else sys.stderr)
+    figures = divergence(counts)
+    t1 = time.perf_counter()
+    ms: list = []
+    out = sdtable_records(offs, sds, flags, status, chr_, chr_pos, names, counts, figures, SD_TABLE_HEADER.encode("ascii"),
+                          device, ms)
+    if timings is not None:
+        timings.update(names=(t1 - t0) * 1e3, upload=ms[0], kernels=ms[1], copy=ms[2])
+    return out
+
+
+def sd_table_text_gpu(offs, sds, flags, strand, aln, counts, device: int = 0, stderr=None,
+                      timings: Optional[dict] = None) -> bytes:
+    """sd_table_text(offs, sds, flags, strand, aln, counts, stderr).encode("utf-8"), written on the GPU
+    (asgart_sdtable_records, csrc/sdtable.hip): the arms are located here by postprocess.locate_arms, the name table -- every
+    map entry's name, then `unknown` -- and the four figures of divergence(counts) are prepared here once, and the rows are
+    laid out and written by the library.  The same ValueError texts as sd_table_text and the same stderr line per refused
+    duplication, in the same order.  timings: a dict that receives the call's stages in milliseconds: names (locate, name
+    table and figures), upload, kernels, copy."""
+    return _sd_table_device(offs, sds, flags, strand, aln, counts, device, stderr, timings).tobytes()

@@ -77,11 +77,11 @@ __global__ __launch_bounds__(256) void paf_cs_runs_kernel(PafIn in, uint64_t n_r
     }
     const uint32_t len = in.run_len[t];
     const uint8_t op = in.run_op[t];
-    const bool known = op == '=' || op == 'X' || op == 'I' || op == 'D';
+    const bool known = run_op_known(op);
     if (known && len != 0) {
         cs[t] = cs_text_bytes(op, len, in.cs_mode);
-        on_left[t] = op != 'D' ? len : 0;
-        on_right[t] = op != 'I' ? len : 0;
+        on_left[t] = run_on_left(op, len);
+        on_right[t] = run_on_right(op, len);
         return;
     }
     cs[t] = on_left[t] = on_right[t] = 0;
@@ -189,34 +189,9 @@ int32_t check_arguments(const char *who, const uint64_t *fam_offsets, int64_t n_
         set_error("%s: bad argument (%llu runs and no run_len or run_op)", who, (unsigned long long)n_runs);
         return ASGART_E_ARG;
     }
-    if (name_offsets[0] != 0 || (name_offsets[n_names] && !name_bytes) || name_offsets[n_names] >= ((uint64_t)1 << 30)) {
-        set_error("%s: name_offsets must start at 0 and end below 2^30 bytes of names", who);
-        return ASGART_E_ARG;
-    }
-    for (int64_t k = 0; k < n_names; ++k)
-        if (name_offsets[k] > name_offsets[k + 1]) {
-            set_error("%s: name_offsets decrease at name %lld", who, (long long)k);
-            return ASGART_E_ARG;
-        }
+    RC_TRY(check_name_table(who, name_bytes, name_offsets, n_names));
     RC_TRY(check_name_ids(who, chr, n_sd, n_names));
-    for (int64_t q = 0; q < n_sd; ++q) {
-        if (!status[q]) continue;
-        if (flags[q] != 0 && flags[q] != 3) {
-            set_error("%s: duplication %lld has flag byte %u: a PAF row has a strand for 0 (direct, +) and 3 (reversed and "
-                      "complemented, -) only", who, (long long)q, (unsigned)flags[q]);
-            return ASGART_E_ARG;
-        }
-        for (int arm = 0; arm < 2; ++arm) {
-            const uint64_t pos = chr_pos[2 * q + arm], len = arm ? sds[q].right_length : sds[q].left_length;
-            if (pos + len < pos) {
-                set_error("%s: duplication %lld: position %llu + length %llu wraps past 2^64", who, (long long)q,
-                          (unsigned long long)pos, (unsigned long long)len);
-                return ASGART_E_ARG;
-            }
-        }
-        kept.push_back((uint32_t)q);
-    }
-    return 0;
+    return check_strand_rows(who, sds, flags, status, chr_pos, n_sd, kept);
 }
 
 template <bool kCs>

@@ -264,6 +264,12 @@ __host__ __device__ inline void paf_compose(const PafIn &in, uint64_t g0, uint64
 
 __host__ __device__ inline uint8_t lower_base(uint8_t c) { return c >= 'A' && c <= 'Z' ? (uint8_t)(c + ('a' - 'A')) : c; }
 
+// A run as the arms see it (the cs writer's scans I and J, and alnstats.hip's): is its operation one of `=XID`, and the
+// bases it consumes of the left and of the right arm.
+__host__ __device__ inline bool run_op_known(uint8_t op) { return op == '=' || op == 'X' || op == 'I' || op == 'D'; }
+__host__ __device__ inline uint64_t run_on_left(uint8_t op, uint32_t len) { return op != 'D' ? len : 0; }
+__host__ __device__ inline uint64_t run_on_right(uint8_t op, uint32_t len) { return op != 'I' ? len : 0; }
+
 // bytes of the cs text of a run of n bases (0 for an operation that is none: the row is refused before anything is written)
 __host__ __device__ inline uint64_t cs_text_bytes(uint8_t op, uint32_t n, uint32_t cs_mode) {
     switch (op) {

@@ -1,4 +1,4 @@
-// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, export.hip, paf.hip) are built on: the device check of an
+// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, export.hip, paf.hip, alnstats.hip, sdtable.hip) are built on: the device check of an
 // entry point, the device work of one call (ToolWork: stream, events, every device buffer, the rocPRIM two-call wrappers),
 // the host checks of offset arrays and name ids, the bisection of an offset array on the device, and the tail of an entry
 // point.  extract.hip, fasta.hip and prep.hip take use_device from here.
@@ -115,6 +115,44 @@ inline int32_t check_name_ids(const char *who, const int32_t *chr, int64_t n_sd,
                       chr[q], (long long)n_names);
             return ASGART_E_ARG;
         }
+    return 0;
+}
+
+// the name table of the PAF and table writers: offsets from 0, never decreasing, below 2^30 bytes of names
+inline int32_t check_name_table(const char *who, const uint8_t *name_bytes, const uint64_t *name_offsets, int64_t n_names) {
+    if (name_offsets[0] != 0 || (name_offsets[n_names] && !name_bytes) || name_offsets[n_names] >= ((uint64_t)1 << 30)) {
+        set_error("%s: name_offsets must start at 0 and end below 2^30 bytes of names", who);
+        return ASGART_E_ARG;
+    }
+    for (int64_t k = 0; k < n_names; ++k)
+        if (name_offsets[k] > name_offsets[k + 1]) {
+            set_error("%s: name_offsets decrease at name %lld", who, (long long)k);
+            return ASGART_E_ARG;
+        }
+    return 0;
+}
+
+// The duplications with a row (status != 0) of the PAF and table writers -> kept: each has a strand (flag 0 or 3), and
+// neither of its positions + lengths wraps.
+inline int32_t check_strand_rows(const char *who, const asgart_proto_sd *sds, const uint8_t *flags, const uint8_t *status,
+                                 const uint64_t *chr_pos, int64_t n_sd, std::vector<uint32_t> &kept) {
+    for (int64_t q = 0; q < n_sd; ++q) {
+        if (!status[q]) continue;
+        if (flags[q] != 0 && flags[q] != 3) {
+            set_error("%s: duplication %lld has flag byte %u: a PAF row has a strand for 0 (direct, +) and 3 (reversed and "
+                      "complemented, -) only", who, (long long)q, (unsigned)flags[q]);
+            return ASGART_E_ARG;
+        }
+        for (int arm = 0; arm < 2; ++arm) {
+            const uint64_t pos = chr_pos[2 * q + arm], len = arm ? sds[q].right_length : sds[q].left_length;
+            if (pos + len < pos) {
+                set_error("%s: duplication %lld: position %llu + length %llu wraps past 2^64", who, (long long)q,
+                          (unsigned long long)pos, (unsigned long long)len);
+                return ASGART_E_ARG;
+            }
+        }
+        kept.push_back((uint32_t)q);
+    }
     return 0;
 }
 

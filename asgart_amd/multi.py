@@ -321,33 +321,85 @@ def _align_for_paf(index, sds, flags, paf_band):
 
 
 def _check_paf(paf: bool, world: int, orientations, slice_options=None, cs: Optional[str] = None,
-               paf_band: Optional[str] = None) -> None:
-    """--paf, --cs and --paf-band, vetted before the run starts (on every rank): each refusal with its reason."""
+               paf_band: Optional[str] = None, table: bool = False) -> None:
+    """--paf, --cs, --paf-band and --sd-table (table), vetted before the run starts (on every rank): each refusal with its
+    reason.  The table is vetted like the PAF file: its rows come from the same alignment and have the same strands."""
     if cs not in (None, "short", "long"):
         raise ValueError("--cs: short or long")
     if cs is not None and not paf:
         raise ValueError("--cs: the cs:Z: tag is a column of the PAF file; it needs --paf")
     band = _paf_band(paf_band)
-    if band != "full" and not paf:
+    if band != "full" and not paf and not table:
         raise ValueError("--paf-band: the corridor is that of the alignment behind the PAF file; it needs --paf")
-    if not paf:
+    if not paf and not table:
         return
+    what, rows = ("--paf", "a PAF row") if paf else ("--sd-table", "a row of the duplication table")
     if world > 1:
-        raise ValueError("--paf: the alignment has no sharded variant, it runs on one GPU (use --gpus 1)")
+        raise ValueError(f"{what}: the alignment has no sharded variant, it runs on one GPU (use --gpus 1)")
     for r, c in orientations:
         if bool(r) != bool(c):
-            raise ValueError("--paf: a PAF row has a strand for direct (+) and reverse-complemented (-) duplications; a "
+            raise ValueError(f"{what}: {rows} has a strand for direct (+) and reverse-complemented (-) duplications; a "
                              f"{'reversed' if r else 'complemented'}-only run has none")
     o = slice_options
     if o is not None and (o.collapse or o.keep_fragments is not None or o.restrict_fragments is not None
                           or o.exclude_fragments is not None):
+        if not paf:
+            raise ValueError("--sd-table: --collapse and the fragment filters lay the fragments out again; the rows of the "
+                             "table name positions in the fragments of the run (slice the result without them, or write no "
+                             "table)")
         raise ValueError("--paf: --collapse and the fragment filters lay the fragments out again; the rows of a PAF file "
                          "name positions in the fragments of the run (slice the result without them, or write no PAF)")
 
 
 # `paf` of the entry points when the alignment is to stay inside a corridor: the cs:Z: form (None: no such column) and
-# --paf-band's value (_paf_band)
-Paf = namedtuple("Paf", "cs band", defaults=(None, "full"))
+# --paf-band's value (_paf_band); table: the duplication table (--sd-table) is written from the same alignment, one more
+# entry of the return value, an SdTable; rows = False: the table only, no PAF text
+Paf = namedtuple("Paf", "cs band table rows", defaults=(None, "full", False, True))
+
+
+class SdTable(str):
+    """The text of a duplication table (<result stem>.sd.tsv) among the entries an entry point returns."""
+
+
+def _paf_table(paf):
+    """The `paf` argument of the entry points -> (table, rows): is the duplication table asked for, and the PAF text."""
+    if isinstance(paf, Paf):
+        return bool(paf.table), bool(paf.rows)
+    return False, True
+
+
+# writer=None for a duplication table: the device (Index.alignment_stats and align.sd_table_text_gpu) from this many rows
+# on, the host (align.stats_host and align.sd_table_text) below; None: the host everywhere.  The standing rule: the device
+# from the smallest measured size at which its median is below the host's by more than both spreads.  The host walks every
+# run in Python and costs 3 ms per thousand runs; the two device calls cost 7 to 33 ms (spread 1 to 4 ms) from 512 rows
+# to 140 113.  profiles/sdtable_synth.json (tools/sdtable_bench.py): at 512 rows with 80 536 runs, the smallest size
+# measured, at 8 192 and at 140 113 rows the device's median is below the host's by more than both spreads.  Nothing smaller
+# was measured, so that size is the threshold.
+SDTABLE_DEVICE_MIN_ROWS = 512
+
+
+def _choose_sdtable_writer(writer: Optional[str], n_rows: int) -> str:
+    """The writer of a duplication table of n_rows duplications: "device" or "host" as asked (what --host-writer asks for);
+    writer=None: by size, see SDTABLE_DEVICE_MIN_ROWS."""
+    if writer is None:
+        return "device" if SDTABLE_DEVICE_MIN_ROWS is not None and n_rows >= SDTABLE_DEVICE_MIN_ROWS else "host"
+    if writer not in ("device", "host"):
+        raise ValueError("writer: 'device' or 'host'")
+    return writer
+
+
+def _sd_table_text(fam_offs, sds, flags, strand, aln, writer: Optional[str], device_index: int, index) -> "SdTable":
+    """The duplication table of aligned duplications, counts and text by the writer the run asked for
+    (_choose_sdtable_writer), while the index is open: "device" Index.alignment_stats and asgart_sdtable_records, "host"
+    align.stats_host -- over strand.data or, where the device reader left no copy on the host, Index.read_text -- and
+    align.sd_table_text; the text is the same either way."""
+    from .align import _sd_table_device, sd_table_text, stats_host
+
+    if _choose_sdtable_writer(writer, len(sds)) == "device":
+        return SdTable(_decode(_sd_table_device(fam_offs, sds, flags, strand, aln, index.alignment_stats(sds, flags, aln),
+                                                device_index)))
+    text = strand.data if strand.data is not None else index.read_text(0, index.n)
+    return SdTable(sd_table_text(fam_offs, sds, flags, strand, aln, stats_host(text, sds, flags, aln)))
 
 
 def _paf_and_cs(paf):
@@ -398,14 +450,15 @@ def _slice_run(post, strand, settings, slice_options, device_index: int):
 # file (behind post_process, or those of `cut`), the sliced slice.ResultArrays (None: not sliced) and the range of its
 # duplications, survivors[lo:hi].  survivors (n, 4) uint64 and flags uint8[n] hold the parts' duplications one behind the
 # other; ident float32[n], seqs (left, right) and aln (Alignments) are None unless the run was asked for them.  paf: the text of
-# the part's PAF file where it had to be written while the index was open (--cs: the bases are the index's), None otherwise.
-_Part = namedtuple("_Part", "settings offs cut lo hi paf", defaults=(None,))
+# the part's PAF file where it had to be written while the index was open (--cs: the bases are the index's), None otherwise;
+# table: the part's duplication table (an SdTable, written while the index was open: the counts need its text), None without.
+_Part = namedtuple("_Part", "settings offs cut lo hi paf table", defaults=(None, None))
 _Run = namedtuple("_Run", "files device_index strand parts survivors flags ident seqs aln")
 
 
 def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool, with_sequences: bool, reader: str,
          paf: bool, sliced: bool = False, slice_options=None, cs: Optional[str] = None,
-         paf_writer: Optional[str] = None, paf_band: Optional[str] = None) -> Optional[_Run]:
+         paf_writer: Optional[str] = None, paf_band: Optional[str] = None, table: bool = False) -> Optional[_Run]:
     """The run protocol, once: a whole `asgart` run (reference src/bin/asgart.rs:731-822) for each of the one to four
     RunSettings `sts`, which differ in orientation only, on the ranks of `dist` (None: one process, no collective), rank r
     on GPU device_index.  The entry points have vetted the arguments.  Built ONCE: rank 0 reads the input and builds the
@@ -417,7 +470,8 @@ def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool
     its original coordinates -- is one list with a flag byte each: with compute_score it is broadcast once and every rank
     scores its share; with_sequences is one extraction from the Source of the read (device reader) or the raw records
     (host reader); paf one alignment with exact ranges, inside the corridor paf_band asks for (_align_for_paf); with cs (the cs:Z: column) every part's PAF text is written right
-    there, by the writer paf_writer asks for, because the index is closed when this returns.  A slice that is refused
+    there, by the writer paf_writer asks for, because the index is closed when this returns; with table the same alignment
+    is counted and every part's duplication table written right there as well (_sd_table_text).  A slice that is refused
     (ValueError) is raised behind the collectives, which then run without survivors: the other ranks must not wait in them.
     -> the _Run on rank 0, None elsewhere; the Source and the index are closed either way."""
     from . import merge_shards, orientation_flags
@@ -477,7 +531,10 @@ def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool
             return None
         seqs = _sequences(source, records, device_index, survivors, (flags & 1).astype(bool),
                           (flags >> 1 & 1).astype(bool)) if with_sequences else None
-        aln = _align_for_paf(index, survivors, flags, paf_band) if paf else None
+        aln = _align_for_paf(index, survivors, flags, paf_band) if paf or table else None
+        if table:
+            parts = [p._replace(table=_sd_table_text(p.offs, survivors[p.lo:p.hi], flags[p.lo:p.hi], strand,
+                                                     aln.part(p.lo, p.hi), paf_writer, device_index, index)) for p in parts]
         if paf and cs is not None:
             parts = [p._replace(paf=_paf_text(p.offs, survivors[p.lo:p.hi], flags[p.lo:p.hi], strand, aln.part(p.lo, p.hi),
                                               paf_writer, device_index, cs, index)) for p in parts]
@@ -502,13 +559,16 @@ def _json_text(run: _Run, offs, lo: int, hi: int, settings, writer: str, flags=N
     return to_json_arrays(offs, sds, run.strand, settings, ident, seqs, flags)
 
 
-def _texts(run: _Run, part: _Part, prefix: str, writer: str, paf_writer: Optional[str], fmt: str = "json") -> tuple:
+def _texts(run: _Run, part: _Part, prefix: str, writer: str, paf_writer: Optional[str], fmt: str = "json",
+           paf_rows: bool = True) -> tuple:
     """One orientation's entry of what the entry points return: (the text of its result file, the file's name[, the text of
-    its PAF file]).  writer: what _choose_writer gave; paf_writer: the `writer` argument as it was asked for, None decides
-    by the run count of this orientation's own alignments.  fmt: of a sliced part, whose file is named after it."""
+    its PAF file][, its duplication table, an SdTable]).  writer: what _choose_writer gave; paf_writer: the `writer`
+    argument as it was asked for, None decides by the run count of this orientation's own alignments.  fmt: of a sliced
+    part, whose file is named after it.  paf_rows = False: the alignment was made for the table alone, no PAF text."""
     from .postprocess import out_filename
 
-    st, offs, cut, lo, hi, paf_text = part
+    st, offs, cut, lo, hi, paf_text, table = part
+    tables = () if table is None else (table,)
     name = out_filename(run.files, st, prefix)
     if cut is None:
         text = _json_text(run, offs, lo, hi, st, writer)
@@ -521,12 +581,12 @@ def _texts(run: _Run, part: _Part, prefix: str, writer: str, paf_writer: Optiona
             cut.seqs = (run.seqs[0][lo:hi], run.seqs[1][lo:hi])
         name = os.path.splitext(name)[0] + "." + fmt
         text = _decode(_export_arrays_device(cut, fmt, run.device_index)) if writer == "device" else export_arrays(cut, fmt)
-    if run.aln is None:
-        return text, name
+    if run.aln is None or not paf_rows:
+        return (text, name) + tables
     if paf_text is not None:
-        return text, name, paf_text
-    return text, name, _paf_text(offs, run.survivors[lo:hi], run.flags[lo:hi], run.strand, run.aln.part(lo, hi), paf_writer,
-                                 run.device_index)
+        return (text, name, paf_text) + tables
+    return (text, name, _paf_text(offs, run.survivors[lo:hi], run.flags[lo:hi], run.strand, run.aln.part(lo, hi), paf_writer,
+                                  run.device_index)) + tables
 
 
 def search_duplications(files: Sequence[str], settings, dist, device_index: int, compute_score: bool = False,
@@ -555,7 +615,11 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     paf=Paf(cs, band) (what --paf-band passes) is paf=True, with the column if cs is "short" or "long", aligned as band
     says: "full" over the whole edit matrix; "auto" inside a diagonal corridor that the library widens until every
     duplication is within it: the same text; a percentage P (a number or its text) bounds the edits of a duplication by
-    floor(P max(n, m) / 100): one with more gets no row and a line on stderr (_paf_band)."""
+    floor(P max(n, m) / 100): one with more gets no row and a line on stderr (_paf_band).  Paf(..., table=True) (what
+    --sd-table passes) also counts the same alignments while the index is open and adds the duplication table as one more
+    entry, an SdTable (align.sd_table_text; the writer as `writer` asks, None: by SDTABLE_DEVICE_MIN_ROWS); with rows=False
+    the alignment serves the table alone and there is no PAF text."""
+    table, paf_rows = _paf_table(paf)
     paf, cs, paf_band = _paf_and_cs(paf)
     world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
@@ -564,10 +628,10 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     sliced = _check_slice(slice_options, fmt)
-    _check_paf(paf, world, [(settings.reverse, settings.complement)], slice_options, cs, paf_band)
-    run = _run(files, [settings], dist, device_index, compute_score, with_sequences, reader, paf, sliced, slice_options, cs,
-               paf_writer, paf_band)
-    return None if run is None else _texts(run, run.parts[0], prefix, writer, paf_writer, fmt)
+    _check_paf(paf and paf_rows, world, [(settings.reverse, settings.complement)], slice_options, cs, paf_band, table)
+    run = _run(files, [settings], dist, device_index, compute_score, with_sequences, reader, paf and paf_rows, sliced,
+               slice_options, cs, paf_writer, paf_band, table)
+    return None if run is None else _texts(run, run.parts[0], prefix, writer, paf_writer, fmt, paf_rows)
 
 
 def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool, bool]], settings, dist,
@@ -581,10 +645,12 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     text) and None elsewhere; the merged text is what postprocess.merge_results gives over those files in that order
     (RunResult::from_files, reference src/structs.rs:114-141: strand and settings of the first, every duplication with the
     flags of its own run) and is written like the others.  `--trim`, reader, writer, with_sequences, paf (the merged
-    result gets no PAF text; direct and RC only, see _check_paf; "short" / "long": with the cs:Z: column; a Paf: inside a corridor): as
+    result gets no PAF text and no table; direct and RC only, see _check_paf; "short" / "long": with the cs:Z: column; a Paf:
+    inside a corridor, with the duplication table): as
     search_duplications.  Slicing is out of scope here: `python -m asgart_amd.slice` does it on the files this writes."""
     from dataclasses import replace
 
+    table, paf_rows = _paf_table(paf)
     paf, cs, paf_band = _paf_and_cs(paf)
     orientations = [(bool(r), bool(c)) for r, c in orientations]
     if not 1 <= len(orientations) <= 4 or len(set(orientations)) != len(orientations):
@@ -592,18 +658,18 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
-    _check_paf(paf, world, orientations, None, cs, paf_band)
+    _check_paf(paf and paf_rows, world, orientations, None, cs, paf_band, table)
     reader = _choose_reader(reader, settings)
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     sts = [replace(settings, reverse=r, complement=c) for r, c in orientations]
-    run = _run(files, sts, dist, device_index, compute_score, with_sequences, reader, paf, cs=cs, paf_writer=paf_writer,
-               paf_band=paf_band)
+    run = _run(files, sts, dist, device_index, compute_score, with_sequences, reader, paf and paf_rows, cs=cs,
+               paf_writer=paf_writer, paf_band=paf_band, table=table)
     if run is None:
         return None
     sizes = np.concatenate([np.diff(p.offs.astype(np.int64)) for p in run.parts])
     all_offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
-    return ([_texts(run, p, prefix, writer, paf_writer) for p in run.parts],
+    return ([_texts(run, p, prefix, writer, paf_writer, paf_rows=paf_rows) for p in run.parts],
             _json_text(run, all_offs, 0, len(run.survivors), sts[0], writer, run.flags))
 
 
@@ -651,6 +717,12 @@ def _parse(argv):
                          "of it.  auto: a diagonal corridor, widened until every duplication is within it; the same file "
                          "from cells and memory in proportion to the corridor.  PERCENT: a corridor for at most that share "
                          "of the longer arm in edits; a duplication with more gets no row and a line on stderr")
+    ap.add_argument("--sd-table", action="store_true",
+                    help="write <result stem>.sd.tsv beside every result file: one row per surviving duplication with its "
+                         "BEDPE columns and, under UCSC's genomicSuperDups names, the counts of its alignment (matches, "
+                         "mismatches, transitions, transversions, indels), fracMatch, fracMatchIndel and the Jukes-Cantor and "
+                         "Kimura distances.  With or without --paf (one alignment serves both); honours --paf-band; vetted "
+                         "like --paf")
     ap.add_argument("--prefix", default="")
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
@@ -685,7 +757,7 @@ def _parse(argv):
         ap.error("--orientations writes unsliced JSON files: slice them with python -m asgart_amd.slice")
     try:
         _check_paf(args.paf, args.gpus, args.orientations or [(args.reverse, args.complement)], args.slice_options, args.cs,
-                   args.paf_band)
+                   args.paf_band, args.sd_table)
     except ValueError as e:
         ap.error(str(e))
     return args
@@ -762,7 +834,8 @@ def rank_main(argv) -> int:
                                         complement=args.complement, skip_masked=args.skip_masked)
         asked = dict(compute_score=args.compute_score, prefix=args.prefix, with_sequences=args.with_sequences,
                      reader="host" if args.host_reader else None, writer="host" if args.host_writer else None,
-                     paf=Paf(args.cs, args.paf_band) if args.paf and args.paf_band != "full" else args.cs or args.paf)
+                     paf=Paf(args.cs, args.paf_band, True, args.paf) if args.sd_table else
+                     Paf(args.cs, args.paf_band) if args.paf and args.paf_band != "full" else args.cs or args.paf)
         if args.orientations:
             out = search_orientations(args.files, args.orientations, settings, dist, device_index, **asked)
             texts = None if out is None else out[0] + ([(out[1], args.merged)] if args.merged else [])
@@ -772,7 +845,8 @@ def rank_main(argv) -> int:
             texts = None if out is None else [out]
         for text, name, *paf in texts or []:
             for body, path in [(text, os.path.join(args.out_dir, name))] + \
-                    [(p_, os.path.join(args.out_dir, os.path.splitext(name)[0] + ".paf")) for p_ in paf]:
+                    [(p_, os.path.join(args.out_dir, os.path.splitext(name)[0] + (".sd.tsv" if isinstance(p_, SdTable) else
+                                                                                 ".paf"))) for p_ in paf]:
                 with open(path, "w", encoding="utf-8") as fh:
                     fh.write(body)
                 print(f"rank 0 of {world} ({backend}): wrote {path}", flush=True)

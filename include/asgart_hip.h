@@ -798,6 +798,87 @@ int32_t asgart_paf_records_cs(asgart_index *idx, int32_t cs_mode, const uint64_t
 /* asgart_paf_geometry's three sizes, which hold for asgart_paf_records_cs too, and solo_bytes: the most bytes of one run's
  * cs text inside a workgroup's range that one thread composes alone; a run with more is composed by the whole workgroup. */
 void asgart_paf_cs_geometry(uint64_t *block_threads, uint64_t *runs_per_block, uint64_t *stage_bytes, uint64_t *solo_bytes);
+
+/* ---- the counts of an alignment ---------------------------------------------------------------------------------
+ * What every catalogue of segmental duplications states per duplication (WGAC's genomicSuperDups, SEDEF, BISER), counted on
+ * the GPU from the runs of asgart_align_duplications (inclusive = 0, as asgart_alignment_copy gives them) and the text of
+ * the index.  No counterpart in the reference.  The frame is the alignment's, not the PAF row's: A is the left arm as
+ * stored; B(j), j in [0, rl), is the right arm as asgart_align_duplications walks it, text[right + (flags[q] & 1 ?
+ * rl - 1 - j : j)], complemented (ACGT and acgt swap, every other byte is kept) when bit 1 is set.  All four flag values
+ * are legal.  Run t of duplication q starts at the arm offsets i_t and j_t of the cs:Z: section above (the sums of the
+ * row's earlier `=XI` and `=XD` run lengths, in the order given); base v of it pairs a = text[left + i_t + v] with
+ * b = B(j_t + v).  Per duplication with status[q] == 1:
+ *    match, mismatch          the sums of the `=` and of the `X` run lengths
+ *    ins_runs, ins_bases      the number and the sum of the `I` runs (left-arm bases without a partner)
+ *    del_runs, del_bases      the same for `D`
+ *    longest_match            the largest `=` run;   longest_gap   the largest `I` or `D` run
+ *    transition, transversion over every base of every `X` run, A-Z folded to a-z: a transition where a != b and both are
+ *                             in {a, g} or both in {c, t}; a transversion where one is in {a, g} and the other in {c, t};
+ *                             neither otherwise (an N, any other byte, an `X` laid over equal bytes)
+ * The first eight look at no base, and no `=` base is inspected: like the writers, the call believes the runs.  A
+ * duplication with status[q] != 1 gets ten zeros; its runs, its arms and its flag are neither read nor checked.
+ * Example: the text `ACGTTAGC` `GG` `ACCTAGCA`, the duplication (0, 10, 8, 8), flag 0, runs `2=1I1X4=1D`: the `X` pairs
+ * a = text[3] = T with b = text[12] = C, a transition; the counts are 6, 1, 1, 0, 1, 1, 1, 1, 4, 1.
+ * Checked, for the duplications with status 1 only and with the codes of asgart_paf_records_cs (ASGART_E_ARG, the message
+ * names the first such duplication): idx NULL (before anything else); NULL arrays with a positive count, run_offsets not
+ * from 0, decreasing; a flag byte above 3; an arm that reaches past the text; and, on the device, before a base is read,
+ * a run_op outside `=XID`, a run_len of 0, runs that do not consume exactly left_length and right_length bases.  2^31
+ * duplications, 2^32 runs, arms of 2^32 bases and more: ASGART_E_CAP.  counts[n_sd] is written only by a call that returns 0;
+ * a refused call leaves nothing on the device.  ms3 (nullable): the milliseconds of upload, kernels and copy back. */
+typedef struct asgart_align_counts {
+    uint64_t match, mismatch;
+    uint64_t transition, transversion;
+    uint64_t ins_runs, ins_bases;
+    uint64_t del_runs, del_bases;
+    uint64_t longest_match, longest_gap;
+} asgart_align_counts;
+int32_t asgart_alignment_stats(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags, const uint8_t *status,
+                               int64_t n_sd, const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
+                               asgart_align_counts *counts, double *ms3);
+/* Sizes the kernels of asgart_alignment_stats work in, for tests that place their counts on the seams: threads per
+ * workgroup, and the mismatch bases one workgroup of the bases kernel takes (a wave takes a quarter of them, 64 at a time). */
+void asgart_alignment_stats_geometry(uint64_t *block_threads, uint64_t *bases_per_block);
+
+/* ---- the duplication table written on the GPU ---------------------------------------------------------------------
+ * The counts above as the table the field reads duplications by: one call gives the whole file in one device buffer, an
+ * asgart_export (asgart_export_size, _copy, _timings and _free work on it).  The file is `prefix` (the caller's header
+ * line: `#` and the 25 column names, tab-separated, `\n`) and, for every duplication q with status[q] != 0, in order, one
+ * line of 25 columns separated by tabs and ended by `\n`.  The first ten are BEDPE, the rest carry the names of UCSC's
+ * genomicSuperDups:
+ *    1 chrom1   the name chr[2q]         2 start1   chr_pos[2q]        3 end1   column 2 + left_length
+ *    4 chrom2   the name chr[2q + 1]     5 start2   chr_pos[2q + 1]    6 end2   column 5 + right_length
+ *    7 name     `sd<q>`     8 score  `0`     9 strand1  `+`     10 strand2  `+` for flags[q] == 0, `-` for flags[q] == 3
+ *   11 family   f, fam_offsets[f] <= q < fam_offsets[f + 1]
+ *   12 alignL   alignB + indelS          13 alignB  match + mismatch   14 matchB   15 mismatchB
+ *   16 transitionsB   17 transversionsB  18 indelN  ins_runs + del_runs    19 indelS  ins_bases + del_bases
+ *   20 longestMatch   21 longestGap
+ *   22 fracMatch      match / alignB                  23 fracMatchIndel   match / (alignB + indelN)
+ *   24 jcK            -3/4 ln(1 - 4p/3), p = mismatch / alignB                               (Jukes-Cantor)
+ *   25 k2K            -1/2 ln((1 - 2P - Q) sqrt(1 - 2Q)), P, Q = transition, transversion over alignB    (Kimura)
+ * Columns 22 to 25 are NOT computed here: they are the caller's four f32 arrays, printed as ASGART_F32_DISPLAY prints an
+ * f32 (`NaN` for NaN), so that the file does not depend on whose logarithm ran.  The convention of the Python host
+ * (align.divergence): float64 arithmetic rounded once to f32; NaN where alignB is 0 or the argument of the logarithm is
+ * not above 0, never an infinity; a zero is +0.  A mismatch that involves an N counts in p and in neither P nor Q.
+ * A row worked by hand, the example of the counts above: the text `ACGTTAGC` `GG` `ACCTAGCA` as the fragment `chr1` from
+ * 0, the duplication (0, 10, 8, 8), flag 0, family 0, runs `2=1I1X4=1D`, so the counts 6, 1, 1, 0, 1, 1, 1, 1, 4, 1:
+ * alignB 7, indelN 2, indelS 2, alignL 9; fracMatch 6/7, fracMatchIndel 6/9; p = 1/7, jcK = -3/4 ln(17/21); P = 1/7,
+ * Q = 0, k2K = -1/2 ln(5/7):
+ *    chr1 0 8 chr1 10 18 sd0 0 + + 0 9 7 6 1 1 0 2 2 4 1 0.85714287 0.6666667 0.15848182 0.16823612
+ * Checked on the host before anything is launched, as asgart_paf_records checks: NULL arrays with a positive count,
+ * fam_offsets / name_offsets not starting at 0, decreasing or (fam_offsets) not ending at n_sd, a name id outside the table,
+ * a flag other than 0 or 3 on a duplication with a row (the message names the first), a position + length that wraps past
+ * 2^64 on one: ASGART_E_ARG; 2^31 duplications and more: ASGART_E_CAP; no usable device: ASGART_E_HIP.  n_sd == 0, or every
+ * status 0, succeeds with the header alone.  The handle owns the file until asgart_export_free; nothing else stays on the
+ * device. */
+int32_t asgart_sdtable_records(int32_t device, const uint64_t *fam_offsets, int64_t n_families, const asgart_proto_sd *sds,
+                               const uint8_t *flags, const uint8_t *status, const int32_t *chr, const uint64_t *chr_pos,
+                               int64_t n_sd, const uint8_t *name_bytes, const uint64_t *name_offsets, int64_t n_names,
+                               const asgart_align_counts *counts, const float *frac_match, const float *frac_match_indel,
+                               const float *jc_k, const float *k2_k, const uint8_t *prefix, uint64_t prefix_len,
+                               asgart_export **out);
+/* Sizes the write stage of asgart_sdtable_records works in, as asgart_export_geometry gives them for its own: threads per
+ * workgroup, rows per workgroup, bytes of the LDS image (a workgroup whose rows do not fit it stores them directly). */
+void asgart_sdtable_geometry(uint64_t *block_threads, uint64_t *records_per_block, uint64_t *stage_bytes);
 /* An array of f32 rendered on the device as the exporters print an identity: the shortest decimal digits that read back
  * as the same f32, in one of two forms.
  *   ASGART_F32_JSON      serde_json's (ryu's pretty printer; `identity` in exporters.rs:12-25): `97.3`, `100.0`, `0.0`,
