@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "asgart_index_set_tail_up", "asgart_tier_segments", "asgart_tier_profile",
     "asgart_fill_counts", "asgart_fill_tally", "asgart_ranked_fill_takes", "asgart_hit_rule",
     "asgart_join_cuts", "asgart_split_warm_next",
+    "asgart_run_dir_info", "asgart_lookup_account", "asgart_run_dir_rule",
     "asgart_slice_families", "asgart_slice_counts", "asgart_slice_copy", "asgart_slice_timings", "asgart_slice_free",
     "asgart_plot_filter", "asgart_plot_counts", "asgart_plot_copy", "asgart_plot_timings", "asgart_plot_free",
     "asgart_plot_geometry",
@@ -266,6 +267,13 @@ def load_library() -> C.CDLL:
     if hasattr(L, "asgart_hit_rule"):
         L.asgart_hit_rule.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]
         L.asgart_hit_rule.restype = None
+    if hasattr(L, "asgart_run_dir_info"):
+        L.asgart_run_dir_info.argtypes = [vp, vp]
+        L.asgart_run_dir_info.restype = C.c_int32
+        L.asgart_lookup_account.argtypes = [vp, vp]
+        L.asgart_lookup_account.restype = C.c_int32
+        L.asgart_run_dir_rule.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.asgart_run_dir_rule.restype = None
     if hasattr(L, "asgart_slice_families"):
         L.asgart_slice_families.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp, C.POINTER(vp)]
         L.asgart_slice_families.restype = C.c_int32
@@ -594,6 +602,26 @@ class Index:
         out = np.zeros(12, dtype=np.uint64)
         _check(load_library().asgart_fill_tally(self._h, _ptr(out)))
         return out.reshape(4, 3)
+
+    RUN_DIR_FIELDS = ("bytes", "buckets", "T", "inserted", "bucket_full", "hits", "misses", "switch")
+
+    def run_dir_info(self) -> dict:
+        """The run directory of the prepared index (asgart_run_dir_info): bytes (0: none), buckets, T, runs it holds, runs
+        that found their bucket full, the lookups that hit and missed it in the last accounting pass (stats(1)), and
+        ASGART_RUN_DIR as the index read it."""
+        out = np.zeros(8, dtype=np.uint64)
+        _check(load_library().asgart_run_dir_info(self._h, _ptr(out)))
+        return {n: int(v) for n, v in zip(self.RUN_DIR_FIELDS, out)}
+
+    LOOKUP_ACCOUNT_FIELDS = ("ptab_loads", "ptab_bytes", "keys_loads", "keys_bytes", "sa_loads", "sa_bytes", "dir_hits",
+                             "dir_misses", "raw_1", "raw_2_8", "raw_9_32", "raw_33_256", "raw_above_256", "raw_0")
+
+    def lookup_account(self) -> dict:
+        """The loads of the looked-up probes by array, as the accounting pass of the last stats(1) counted them
+        (asgart_lookup_account)."""
+        out = np.zeros(16, dtype=np.uint64)
+        _check(load_library().asgart_lookup_account(self._h, _ptr(out)))
+        return {n: int(v) for n, v in zip(self.LOOKUP_ACCOUNT_FIELDS, out)}
 
     def check_sa(self) -> int:
         """GPU verifier of the resident suffix array: number of violating slots (0 = valid)."""

@@ -75,6 +75,36 @@ int32_t asgart_fill_tally(asgart_index *idx, uint64_t *out) {
     return 0;
 }
 
+int32_t asgart_lookup_account(asgart_index *idx, uint64_t *out) {
+    if (!idx || !out) {
+        set_error("bad argument");
+        return ASGART_E_ARG;
+    }
+    idx->acquire_all();
+    for (int j = 0; j < (int)LA_COUNT; ++j) out[j] = idx->lookup_acct[j];
+    idx->release_all();
+    return 0;
+}
+
+int32_t asgart_run_dir_info(asgart_index *idx, uint64_t *out) {
+    if (!idx || !out) {
+        set_error("bad argument");
+        return ASGART_E_ARG;
+    }
+    idx->acquire_all();
+    const bool have = idx->d_rdir != nullptr;
+    out[0] = have ? idx->rdir_buckets * kRunDirBucketBytes : 0;
+    out[1] = have ? idx->rdir_buckets : 0;
+    out[2] = have ? idx->rdir_T : 0;
+    out[3] = have ? idx->rdir_inserted : 0;
+    out[4] = idx->rdir_full;  // (also of a directory the index went without: every run it would have held)
+    out[5] = idx->rdir_hits;
+    out[6] = idx->rdir_misses;
+    out[7] = (uint64_t)idx->run_dir_env.on;
+    idx->release_all();
+    return 0;
+}
+
 int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out) {
     if (!idx || !out) {
         set_error("bad argument");
@@ -130,6 +160,7 @@ int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out) {
             // call left in the workspace
             HIP_TRY(hipMemsetAsync(d_ctr + CT_ALG_BYTES, 0, 16, s));
             HIP_TRY(hipMemsetAsync(d_ctr + CT_ALG_BYTES16, 0, 8, s));
+            HIP_TRY(hipMemsetAsync(d_ctr + CT_LOOKUP_ACCT, 0, (size_t)LA_COUNT * 8, s));
             const unsigned gp = rp.n_tiles((uint32_t)kProbeBlock);
             by_slot(idx, [&](auto slot_tag) {
                 using SlotT = decltype(slot_tag);
@@ -149,6 +180,11 @@ int32_t asgart_get_stats(asgart_index *idx, uint32_t flags, asgart_stats *out) {
             HIP_TRY(read_back(&v, d_ctr + CT_BISECT, 8, s));  // (polled drain first: common.hpp)
             HIP_TRY(read_back(ab, d_ctr + CT_ALG_BYTES, 16, s));
             HIP_TRY(read_back(&a16, d_ctr + CT_ALG_BYTES16, 8, s));
+            unsigned long long la[LA_COUNT];
+            HIP_TRY(read_back(la, d_ctr + CT_LOOKUP_ACCT, sizeof(la), s));
+            for (int j = 0; j < (int)LA_COUNT; ++j) idx->lookup_acct[j] = la[j];
+            idx->rdir_hits = la[LA_DIR_HIT];
+            idx->rdir_misses = la[LA_DIR_MISS];
             cx.stats.bisect_steps = v;
             cx.stats.search_bytes = ab[0];
             cx.stats.probes_filter_rejected = ab[1];

@@ -58,7 +58,8 @@ enum Counter {
     CT_CLUSTER_CUR = 169,     // its work cursors (two launches)
     CT_TAIL_UP = 171,         // placement: segments the tail rule moved to the next tier that holds more (place_tier)
     CT_FILL_ACCT = 176,       // fill_account_kernel (asgart_fill_counts, asgart_fill_tally): its 18 sums
-    CT_COUNT = 196
+    CT_LOOKUP_ACCT = 196,     // accounting pass: the looked-up probes' loads by array (LookupAcct, search_dev.hpp: 16 sums)
+    CT_COUNT = 212
 };
 
 __device__ inline int chunk_of(const ChunkTable &ch, uint32_t g) {

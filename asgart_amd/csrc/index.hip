@@ -161,6 +161,21 @@ int ranked_fill_from_env() {
     return end && *end == 0 && v >= 0 && v <= 2 ? (int)v : 1;
 }
 
+RunDirEnv run_dir_from_env() {
+    RunDirEnv r;
+    auto num = [](const char *name, long long lo, long long hi, long long dflt) {
+        const char *e = getenv(name);
+        if (!e || !*e) return dflt;
+        char *end = nullptr;
+        const long long v = strtoll(e, &end, 10);
+        return end && *end == 0 && v >= lo && v <= hi ? v : dflt;
+    };
+    r.on = (int)num("ASGART_RUN_DIR", 0, 1, 1);
+    r.T = (uint64_t)num("ASGART_RUN_DIR_T", 2, 1ll << 20, (long long)kRunDirT);
+    r.buckets = (uint64_t)num("ASGART_RUN_DIR_BUCKETS", 0, (long long)kRunDirMaxBuckets, 0);
+    return r;
+}
+
 void options_from_env(Options &o) {
     auto one = [&](const char *name) {
         char env[64] = "ASGART_";
@@ -383,6 +398,59 @@ __global__ __launch_bounds__(256) void add_offset_kernel(SlotT *__restrict__ sa,
         sa[r] = (SlotT)((uint64_t)sa[r] + add);
 }
 
+// ---- the run directory (run_dir.hpp) ------------------------------------------------------------------------------------
+// Slot i heads a run of at least T equal key words: keys is sorted, so two loads say it -- no run-length pass, no list of heads.
+__device__ inline bool heads_run(const uint64_t *__restrict__ keys, uint64_t n, uint64_t i, uint64_t T) {
+    if (i + T > n) return false;
+    const uint64_t q = keys[i];
+    return (i == 0 || keys[i - 1] != q) && keys[i + T - 1] == q;
+}
+
+__global__ __launch_bounds__(256) void run_dir_count_kernel(const uint64_t *__restrict__ keys, uint64_t n, uint64_t T,
+                                                            unsigned long long *__restrict__ out) {
+    unsigned long long cnt = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        cnt += heads_run(keys, n, i, T) ? 1u : 0u;
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+    if (cnt && (threadIdx.x & 63) == 0) atomicAdd(out, cnt);
+}
+
+// One entry per run: its end by doubling steps and one bisection, its place by a compare-and-swap on the key word of a free
+// entry of its bucket (the length word follows as a plain store: the table is read by later launches only).  A run that
+// finds its bucket full is counted and left out.  tab: n_buckets x 4 x {key word, lo | length << 40}, all ones.
+__global__ __launch_bounds__(256) void run_dir_insert_kernel(const uint64_t *__restrict__ keys, uint64_t n, uint64_t T,
+                                                             unsigned long long *__restrict__ tab, uint32_t n_buckets,
+                                                             unsigned long long *__restrict__ out) {
+    unsigned long long n_in = 0, n_full = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (!heads_run(keys, n, i, T)) continue;
+        const uint64_t q = keys[i];
+        uint64_t a = i + T - 1, step = T;  // keys[a] == q
+        while (a + step < n && keys[a + step] == q) {
+            a += step;
+            step <<= 1;
+        }
+        const uint64_t hi = upper_bound_keys(keys, a + 1, a + step < n ? a + step : n, q);
+        unsigned long long *e = tab + (uint64_t)run_dir_bucket(q, n_buckets) * (uint64_t)(2 * kRunDirWays);
+        bool placed = false;
+        for (int j = 0; j < kRunDirWays && !placed; ++j)
+            if (atomicCAS(e + 2 * j, (unsigned long long)kRunDirEmpty, (unsigned long long)q) == (unsigned long long)kRunDirEmpty) {
+                e[2 * j + 1] = run_dir_pack(i, hi - i);
+                placed = true;
+            }
+        n_in += placed ? 1u : 0u;
+        n_full += placed ? 0u : 1u;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        n_in += __shfl_down(n_in, off);
+        n_full += __shfl_down(n_full, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (n_in) atomicAdd(out, n_in);
+        if (n_full) atomicAdd(out + 1, n_full);
+    }
+}
+
 template <class SlotT>
 __global__ __launch_bounds__(256) void cache_get_kernel(IndexView<SlotT> ix,
                                                         const uint8_t *__restrict__ pats,
@@ -490,6 +558,9 @@ static void free_k_specific(asgart_index *idx) {
     idx->d_sap = nullptr;
     if (idx->d_sar) dev_free(idx->d_sar);
     idx->d_sar = nullptr;
+    if (idx->d_rdir) dev_free(idx->d_rdir);
+    idx->d_rdir = nullptr;
+    idx->rdir_buckets = idx->rdir_T = idx->rdir_inserted = idx->rdir_full = idx->rdir_hits = idx->rdir_misses = 0;
     for (auto &f : idx->d_pbits) {
         if (f) dev_free(f);
         f = nullptr;
@@ -606,6 +677,65 @@ static int32_t build_sap_locked(asgart_index *idx, uint64_t k) {
     return 0;
 }
 
+// The run directory of the keys just built (run_dir.hpp); the caller holds every call context.  A counting pass sizes the
+// table for a load of at most one half; while it would take more than an eighth of the bytes of keys, the shortest run that
+// gets an entry is doubled.  An accelerator only: k > kMaxKey, a --trim index, ASGART_RUN_DIR=0, or no memory for the
+// table -- the index does without.
+static int32_t build_run_dir_locked(asgart_index *idx, uint64_t k) {
+    const uint64_t n_sa = (uint64_t)idx->n_sa;
+    const RunDirEnv &env = idx->run_dir_env;
+    idx->ms_run_dir = 0.0;
+    if (!env.on || idx->trimmed || k > (uint64_t)kMaxKey || n_sa < 2 || n_sa > kRunDirLoMax || idx->d_rdir) return 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t s = idx->ctx[0].stream;
+    DevBuf &cb = idx->ctx[0].ws.counters;
+    RC_TRY(cb.reserve(256 * 8));
+    unsigned long long *d_cnt = cb.as<unsigned long long>();
+    const unsigned grid = std::min(grid_capped(n_sa), 1u << 16);
+    const uint64_t budget = n_sa * sizeof(uint64_t) / 8;  // bytes
+    uint64_t T = env.T, buckets = 0;
+    unsigned long long runs = 0;
+    for (;;) {
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, s));
+        run_dir_count_kernel<<<grid, 256, 0, s>>>(idx->d_keys, n_sa, T, d_cnt);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(read_back(&runs, d_cnt, 8, s));
+        HIP_TRY(stream_sync(s));
+        buckets = env.buckets ? env.buckets : std::max<uint64_t>(1, ((uint64_t)runs + 1) / 2);  // four entries each, half of them taken
+        if (env.buckets || buckets * kRunDirBucketBytes <= budget || T >= (1ull << 20)) break;
+        T *= 2;
+    }
+    if (!env.buckets && buckets * kRunDirBucketBytes > budget) return 0;
+    buckets = std::min(buckets, kRunDirMaxBuckets);
+    idx->rdir_T = T;
+    idx->rdir_full = runs;  // (until they are in)
+    if (dev_malloc(&idx->d_rdir, (size_t)(buckets * kRunDirBucketBytes)) != hipSuccess) {
+        (void)hipGetLastError();
+        idx->d_rdir = nullptr;
+        return 0;
+    }
+    unsigned long long h[2] = {0, 0};
+    const int32_t rc = [&]() -> int32_t {
+        HIP_TRY(hipMemsetAsync(idx->d_rdir, 0xFF, (size_t)(buckets * kRunDirBucketBytes), s));
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, 16, s));
+        run_dir_insert_kernel<<<grid, 256, 0, s>>>(idx->d_keys, n_sa, T, (unsigned long long *)idx->d_rdir, (uint32_t)buckets, d_cnt);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(read_back(h, d_cnt, 16, s));
+        HIP_TRY(stream_sync(s));
+        return 0;
+    }();
+    if (rc != 0) {
+        dev_free(idx->d_rdir);
+        idx->d_rdir = nullptr;
+        return rc;
+    }
+    idx->rdir_buckets = buckets;
+    idx->rdir_inserted = h[0];
+    idx->rdir_full = h[1];
+    idx->ms_run_dir = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
 // ... for the search path: builds them when the index has none yet and has not tried (keys prepared first)
 int32_t index_prepare_sap(asgart_index *idx, uint64_t k) {
     RC_TRY(index_prepare(idx, k));
@@ -705,6 +835,8 @@ int32_t index_prepare(asgart_index *idx, uint64_t k) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(stream_sync(s));
     lap("keys + tables");
+    RC_TRY(build_run_dir_locked(idx, k));
+    lap("run directory");
     // position-sorted occurrence lists: at once (option lazy_aux = 0), or by the first search call that has a predecessor
     idx->sap_tried = false;
     if (!idx->opt.lazy_aux) {
@@ -1107,6 +1239,7 @@ static int32_t index_create_impl(const uint8_t *T, int64_t n, const int64_t *SA,
     idx->trim_end = trim_end;
     options_from_env(idx->opt);  // the only place the environment is read (with the line below)
     idx->ranked_fill = ranked_fill_from_env();
+    idx->run_dir_env = run_dir_from_env();
     // force_wide (tests): 64-bit slots and positions also for a small text, so that the
     // instantiations a > 4 Gb input selects can be checked against the oracle
     idx->wide = (uint64_t)n >= 0xFFFFFF00ull || idx->opt.force_wide != 0;
@@ -1238,6 +1371,7 @@ int32_t asgart_index_clone(asgart_index *src, int32_t device, asgart_index **out
     idx->wide = src->wide;
     idx->opt = src->opt;
     idx->ranked_fill = src->ranked_fill;
+    idx->run_dir_env = src->run_dir_env;  // (the directory itself is rebuilt with the keys, by the clone's own prepare)
     idx->tail_up = src->tail_up;
     idx->h_tail = src->h_tail;
     for (auto &cx : idx->ctx) memset(&cx.stats, 0, sizeof(cx.stats));
@@ -1315,6 +1449,7 @@ int32_t asgart_index_create_device(const void *d_text, int64_t n, const void *d_
     idx->n_sa = n;
     idx->opt = opt;
     idx->ranked_fill = ranked_fill_from_env();
+    idx->run_dir_env = run_dir_from_env();
     idx->wide = wide;
     for (auto &cx : idx->ctx) memset(&cx.stats, 0, sizeof(cx.stats));
     int32_t rc = [&]() -> int32_t {

@@ -9,10 +9,12 @@
 //                           search over ONE array with no text gathers
 //   ptab   slot[4^d + 1]    first slot whose key >= the ACGT d-mer prefix
 //   c8lo/c8hi slot[5^8]     the reference's 8-mer cache (Searcher::new)
+//   rdir   16 B x 4 x buckets  the run directory (run_dir.hpp): the interval of every k-mer with at least T occurrences
 #pragma once
 
 #include "common.hpp"
 #include "range_join.hpp"
+#include "run_dir.hpp"
 
 #include <functional>
 #include <memory>
@@ -47,6 +49,9 @@ struct IndexView {
     // ... and, parallel to it, the suffix-array slot every entry came from (meaningful inside the sorted runs only: intervals
     // of more than kRankMin entries); null: none, hit rows are filled from the suffix array alone
     const SlotT *sar;
+    // the run directory (run_dir.hpp): buckets of four 16-byte entries; null: none, every lookup goes through ptab
+    const uint4 *rdir;
+    uint32_t rdir_buckets;
     // number of suffix-array slots: n, or end - start + 1 for a --trim index (reference
     // src/bin/asgart.rs:142-148), whose array holds the suffixes of data[start..end] + '$' only
     uint64_t n_sa;
@@ -410,6 +415,15 @@ int32_t build_rank_lists_runs(const uint64_t *d_keys, const SlotT *d_sa, uint64_
                               int k, hipStream_t s);  // (sa_build.hip: only the runs of more than min_run equal keys; any slot width)  // the streams and events of one call context (current device)
 int32_t option_set(Options &o, const char *name, int64_t value);  // ASGART_E_ARG: unknown name / bad value
 void options_from_env(Options &o);
+// ASGART_RUN_DIR (0 = no run directory, 1 = one, also when unset or unreadable), ASGART_RUN_DIR_T (the shortest run that
+// gets an entry, 2 .. 2^20; unset: kRunDirT; the build raises it until the table fits its budget) and
+// ASGART_RUN_DIR_BUCKETS (tests: the number of buckets, whatever the runs need; unset or 0: sized for a load of one half)
+constexpr uint64_t kRunDirT = 2;
+struct RunDirEnv {
+    int on = 1;
+    uint64_t T = kRunDirT, buckets = 0;
+};
+RunDirEnv run_dir_from_env();
 int ranked_fill_from_env();  // ASGART_RANKED_FILL: 0, 1 (also when unset or unreadable) or 2 -- asgart_index::ranked_fill
 }  // namespace asgart
 
@@ -482,6 +496,12 @@ struct asgart_index {
     void *d_c8hi = nullptr;
     void *d_sap = nullptr;   // position-sorted occurrence lists (IndexView::sap), or null
     void *d_sar = nullptr;   // ... the suffix-array slot of each of their entries (IndexView::sar), or null: 32-bit slots only
+    void *d_rdir = nullptr;  // the run directory (IndexView::rdir), or null: k > kMaxKey, a --trim index, ASGART_RUN_DIR=0, no memory
+    asgart::RunDirEnv run_dir_env;  // ASGART_RUN_DIR, ASGART_RUN_DIR_T and ASGART_RUN_DIR_BUCKETS when the index was created
+    uint64_t rdir_buckets = 0, rdir_T = 0, rdir_inserted = 0, rdir_full = 0;  // of the directory built last (asgart_run_dir_info)
+    uint64_t rdir_hits = 0, rdir_misses = 0;  // lookups of the last accounting pass (asgart_get_stats with the yardstick flag)
+    uint64_t lookup_acct[16] = {};            // ... and its loads by array (asgart_lookup_account)
+    double ms_run_dir = 0.0;
     int ranked_fill = 1;     // ASGART_RANKED_FILL when the index was created: 0 = no d_sar, 1 = ranked_fill_takes decides,
                              // 2 = every row fill_ranked_kernel can take (tests)
     uint64_t *d_pbits[4] = {nullptr, nullptr, nullptr, nullptr};  // per orientation (reverse * 2 + complement): position bits
@@ -629,6 +649,8 @@ struct asgart_index {
         v.tail_bloom = tail_bloom;
         v.sap = reinterpret_cast<const SlotT *>(d_sap);
         v.sar = reinterpret_cast<const SlotT *>(d_sar);
+        v.rdir = reinterpret_cast<const uint4 *>(d_rdir);
+        v.rdir_buckets = (uint32_t)rdir_buckets;
         v.n_sa = (uint64_t)n_sa;
         v.trim = trimmed ? 1 : 0;
         v.n_bad = n_bad;

@@ -83,6 +83,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
         pr.comp = complement;
         const bool all_occurrences = kmer_range(ix, q_, q2_, pr, lo, hi, cb);
         const uint64_t raw = hi - lo;
+        cb.looked_up(raw);
         if (!COUNT) {
             p_lo[g_] = (SlotT)lo;
             p_raw[g_] = (uint32_t)raw;
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
             bool any = false;  // an occurrence that could be kept, whatever chunk the probe came in (a reversed needle's
                                // `m.start != i` compares a text position with a chunk offset: left out)
             for (uint64_t r = lo; r < hi && !only_self; ++r) {
-                cb.rd(sizeof(SlotT));
+                cb.rd_sa(sizeof(SlotT));
                 const uint64_t x = ix.sa[r];
                 cnt += hr.keeps(x) ? 1u : 0u;
                 if (reverse) any |= x >= hr.thr;
@@ -264,6 +265,11 @@ __global__ __launch_bounds__(kProbeThreads) void probe_count_kernel(IndexView<Sl
             atomicAdd(&ctr[CT_ALG_BYTES], b);
             if (r) atomicAdd(&ctr[CT_FLT_REJECTED], r);
             if (b16) atomicAdd(&ctr[CT_ALG_BYTES16], b16);
+        }
+        for (int j = 0; j < (int)LA_COUNT; ++j) {  // the looked-up probes' loads by array (asgart_lookup_account)
+            unsigned long long a = cb.la[j];
+            for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off);
+            if (lane == 0 && a) atomicAdd(&ctr[CT_LOOKUP_ACCT + j], a);
         }
     }
 }

@@ -151,6 +151,15 @@ void asgart_hit_rule(uint64_t i, uint64_t s, uint64_t L, int32_t reverse, uint64
     out[1] = hr.self;
 }
 
+void asgart_run_dir_rule(uint64_t key, uint64_t lo, uint64_t len, uint64_t n_buckets, uint64_t *out) {
+    const uint64_t w = run_dir_pack(lo, len);
+    out[0] = w;
+    out[1] = run_dir_lo(w);
+    out[2] = run_dir_len(w);
+    out[3] = run_dir_bucket(key, (uint32_t)std::min<uint64_t>(n_buckets, kRunDirMaxBuckets));
+    out[4] = kRunDirEmpty;
+}
+
 int32_t asgart_join_cuts(int32_t n_ranges, const uint32_t *cut_held, const uint32_t *flushes, int32_t last_gave_up,
                          int32_t tail_gave_up, uint32_t *fix, uint32_t *settled, uint32_t *out) {
     if (n_ranges < 1 || n_ranges > 4096 || (n_ranges > 1 && !cut_held) || !flushes || !fix || !settled || !out) {

@@ -20,14 +20,46 @@ struct NoBytes {
     __device__ inline void rd(uint32_t) {}
     __device__ inline void wr(uint32_t) {}
     __device__ inline void rd16() {}
+    __device__ inline void rd_ptab(uint32_t) {}
+    __device__ inline void rd_keys(uint32_t) {}
+    __device__ inline void rd_sa(uint32_t) {}
+    __device__ inline void rd_dir(bool) {}
+    __device__ inline void looked_up(uint64_t) {}
+};
+// ... and, for the probes that are looked up, the loads by array (asgart_lookup_account): what a lookup costs and where
+enum LookupAcct {
+    LA_PTAB_N = 0, LA_PTAB_B,  // loads from the prefix table and their bytes
+    LA_KEYS_N, LA_KEYS_B,      // ... from keys: the bisections and the walk
+    LA_SA_N, LA_SA_B,          // ... from the suffix array
+    LA_DIR_HIT, LA_DIR_MISS,   // lookups the run directory answered / passed on to the prefix table (64 bytes each)
+    LA_RAW_1, LA_RAW_8, LA_RAW_32, LA_RAW_256, LA_RAW_MORE,  // lookups by interval size: 1, 2-8, 9-32, 33-256, above
+    LA_RAW_0,                  // ... and those that found nothing
+    LA_COUNT = 16
 };
 struct CountBytes {
     unsigned long long n = 0, n16 = 0;
+    unsigned long long la[LA_COUNT] = {};
     __device__ inline void rd(uint32_t b) { n += b; }
     __device__ inline void wr(uint32_t b) { n += b; }
     // ... the wide coalesced loads (16 bytes per lane, a whole wave at once): counted apart, because FETCH_SIZE
     // tallies exactly half their bytes on gfx950 (MI355X_MICROARCH.md, HBM)
     __device__ inline void rd16() { n += 16; n16 += 16; }
+    __device__ inline void tally(int what, uint32_t b) {
+        n += b;
+        la[what] += 1;
+        la[what + 1] += b;
+    }
+    __device__ inline void rd_ptab(uint32_t b) { tally(LA_PTAB_N, b); }
+    __device__ inline void rd_keys(uint32_t b) { tally(LA_KEYS_N, b); }
+    __device__ inline void rd_sa(uint32_t b) { tally(LA_SA_N, b); }
+    // one bucket of the run directory: the 64 bytes it moves
+    __device__ inline void rd_dir(bool hit) {
+        n += (uint32_t)kRunDirBucketBytes;
+        la[hit ? LA_DIR_HIT : LA_DIR_MISS] += 1;
+    }
+    __device__ inline void looked_up(uint64_t raw) {
+        la[raw == 0 ? LA_RAW_0 : raw == 1 ? LA_RAW_1 : raw <= 8 ? LA_RAW_8 : raw <= 32 ? LA_RAW_32 : raw <= 256 ? LA_RAW_256 : LA_RAW_MORE] += 1;
+    }
 };
 
 // index into the ACGT-only d-mer table from a k-mer key; false if one of the
@@ -50,7 +82,7 @@ __device__ inline uint64_t lower_bound_keys(const uint64_t *__restrict__ keys, u
                                             uint64_t hi, uint64_t q, Cnt &&cb = Cnt()) {
     while (lo < hi) {
         uint64_t mid = lo + ((hi - lo) >> 1);
-        cb.rd(8);
+        cb.rd_keys(8);
         if (keys[mid] < q) lo = mid + 1; else hi = mid;
     }
     return lo;
@@ -61,7 +93,7 @@ __device__ inline uint64_t upper_bound_keys(const uint64_t *__restrict__ keys, u
                                             uint64_t hi, uint64_t q, Cnt &&cb = Cnt()) {
     while (lo < hi) {
         uint64_t mid = lo + ((hi - lo) >> 1);
-        cb.rd(8);
+        cb.rd_keys(8);
         if (keys[mid] <= q) lo = mid + 1; else hi = mid;
     }
     return lo;
@@ -232,6 +264,30 @@ __device__ inline void kmer_range_trim(const IndexView<SlotT> &ix, uint64_t q, u
     refine_tail(ix, q2, pr, lo, hi, cb);
 }
 
+// The run directory (run_dir.hpp): the interval of a k-mer with at least T occurrences from ONE 64-byte bucket.  The four
+// entries are requested together; false: the key is not there (it occurs less often, or its run found the bucket full).
+template <class SlotT, class Cnt = NoBytes>
+__device__ inline bool run_dir_find(const IndexView<SlotT> &ix, uint64_t q, uint64_t &lo, uint64_t &hi, Cnt &&cb = Cnt()) {
+    const uint4 *__restrict__ b = ix.rdir + (uint64_t)run_dir_bucket(q, ix.rdir_buckets) * (uint64_t)kRunDirWays;
+    const uint4 e0 = b[0], e1 = b[1], e2 = b[2], e3 = b[3];
+    const uint32_t ql = (uint32_t)q, qh = (uint32_t)(q >> 32);
+    uint2 v;
+    bool hit = true;
+    if (e0.x == ql && e0.y == qh) v = make_uint2(e0.z, e0.w);
+    else if (e1.x == ql && e1.y == qh) v = make_uint2(e1.z, e1.w);
+    else if (e2.x == ql && e2.y == qh) v = make_uint2(e2.z, e2.w);
+    else if (e3.x == ql && e3.y == qh) v = make_uint2(e3.z, e3.w);
+    else hit = false;
+    cb.rd_dir(hit);
+    if (!hit) return false;
+    const uint64_t w = ((uint64_t)v.y << 32) | (uint64_t)v.x;
+    const uint64_t len = run_dir_len(w);
+    lo = run_dir_lo(w);
+    // (a run of 2^24 - 1 slots or more: its end is bisected from the slots the entry vouches for)
+    hi = len < kRunDirLenSat ? lo + len : upper_bound_keys(ix.keys, lo + kRunDirLenSat - 1u, ix.n_sa, q, cb);
+    return true;
+}
+
 template <class SlotT, class Cnt = NoBytes>
 __device__ inline bool kmer_range(const IndexView<SlotT> &ix, uint64_t q, uint64_t q2, const ProbeRef &pr, uint64_t &lo,
                                   uint64_t &hi, Cnt &&cb = Cnt()) {
@@ -243,12 +299,13 @@ __device__ inline bool kmer_range(const IndexView<SlotT> &ix, uint64_t q, uint64
         kmer_range_tail(ix, q, q2, pr, lo, hi, cb);
         return false;
     }
+    if (ix.rdir && run_dir_find(ix, q, lo, hi, cb)) return true;  // (single-word keys only: no tail to refine)
     uint64_t lo0 = 0, hi0 = ix.n_sa;
     uint32_t p;
     if (prefix_index(q, ix.kk, ix.d, p)) {
         lo0 = ix.ptab[p];
         hi0 = ix.ptab[p + 1];
-        cb.rd(2 * sizeof(SlotT));
+        cb.rd_ptab(2 * sizeof(SlotT));
     }
     uint64_t l = lower_bound_keys(ix.keys, lo0, hi0, q, cb);
     // most k-mers are unique or absent: walk a few equal keys (same cache
@@ -256,13 +313,13 @@ __device__ inline bool kmer_range(const IndexView<SlotT> &ix, uint64_t q, uint64
     uint64_t h = l;
     int walk = 0;
     while (h < hi0 && walk < 8) {
-        cb.rd(8);
+        cb.rd_keys(8);
         if (ix.keys[h] != q) break;
         ++h;
         ++walk;
     }
     if (walk == 8 && h < hi0) {
-        cb.rd(8);
+        cb.rd_keys(8);
         if (ix.keys[h] == q) h = upper_bound_keys(ix.keys, h, hi0, q, cb);
     }
     lo = l;

@@ -1072,6 +1072,29 @@ int32_t asgart_ranked_fill_takes(uint64_t interval, uint64_t kept, int32_t mode)
  * reversed pass or a direct one, as the kernels state it (host code, needs no device): occurrence x is kept when
  * x >= out[0] && x != out[1]  (src/automaton.rs:105-114). */
 void asgart_hit_rule(uint64_t i, uint64_t s, uint64_t L, int32_t reverse, uint64_t *out);
+/* The run directory of the index as asgart_index_prepare built it last: a hash table of 64-byte buckets of four entries
+ * that holds, for every k-mer with at least T occurrences, its suffix-array interval, so that the lookup of a repeated
+ * k-mer reads one bucket instead of bisecting the keys.  An accelerator only: a k-mer that is not in it (it occurs less
+ * often, or its bucket was full when it came) is looked up through the prefix table, and no result depends on it.
+ * out[0] = bytes of the table (0: the index has none -- probe sizes above 21, a --trim index, ASGART_RUN_DIR=0, no memory),
+ * out[1] = buckets, out[2] = T, out[3] = runs it holds, out[4] = runs that found their bucket full, out[5], out[6] =
+ * lookups that found their k-mer in it and lookups that did not, as the accounting pass of the last asgart_get_stats call
+ * with ASGART_STATS_YARDSTICK counted them (0 before), out[7] = ASGART_RUN_DIR as the index read it.
+ * Environment, read when an index is created: ASGART_RUN_DIR (0 = off; 1 or unset = on), ASGART_RUN_DIR_T (the shortest run
+ * that gets an entry, 2 when unset; doubled while the table would take more than an eighth of the bytes of the keys),
+ * ASGART_RUN_DIR_BUCKETS (tests: the number of buckets, whatever the runs need). */
+int32_t asgart_run_dir_info(asgart_index *idx, uint64_t *out);
+/* Diagnostic: the loads of the probes that the accounting pass of the last asgart_get_stats call with
+ * ASGART_STATS_YARDSTICK looked up, by array: out[0], out[1] = loads from the prefix table and their bytes; out[2], out[3] =
+ * from the keys (bisections and walk); out[4], out[5] = from the suffix array; out[6], out[7] = run-directory buckets read
+ * that held the k-mer / did not (64 bytes each); out[8..12] = lookups whose interval has 1, 2-8, 9-32, 33-256, more slots;
+ * out[13] = lookups that found nothing; out[14], out[15] = 0. */
+int32_t asgart_lookup_account(asgart_index *idx, uint64_t *out);
+/* Diagnostic (for tests of the rule; host code, needs no device): an entry of the run directory and the bucket function.
+ * out[0] = the entry's second word for a run of `len` slots that starts at slot `lo` (lo in the low 40 bits, the length in
+ * the high 24, saturated at 2^24 - 1: "bisect the end from lo"), out[1], out[2] = lo and length read back from it, out[3] =
+ * the bucket of `key` in a table of n_buckets buckets, out[4] = the key word that marks an empty entry. */
+void asgart_run_dir_rule(uint64_t key, uint64_t lo, uint64_t len, uint64_t n_buckets, uint64_t *out);
 /* asgart_join_cuts: host code, needs no device (for tests of the rule).  What a search call decides for ONE long segment
  * that ran as n_ranges ranges side by side (option split): cut_held[j] bit 0 = cut j, between ranges j and j + 1, held
  * (n_ranges - 1 verdicts); flushes[j] = the families range j flushed; last_gave_up != 0: the run over the last range gave
