@@ -57,6 +57,8 @@ ABI_SYMBOLS = (
     "asgart_plot_geometry",
     "asgart_rosary_clusters", "asgart_rosary_counts", "asgart_rosary_copy", "asgart_rosary_timings", "asgart_rosary_free",
     "asgart_rosary_geometry",
+    "asgart_duplication_groups", "asgart_groups_counts", "asgart_groups_copy", "asgart_groups_timings", "asgart_groups_free",
+    "asgart_groups_geometry",
     "asgart_export_records", "asgart_export_size", "asgart_export_copy", "asgart_export_timings", "asgart_export_free",
     "asgart_export_geometry", "asgart_f32_shortest", "asgart_f32_pow10_table",
     "asgart_result_scan", "asgart_result_parse", "asgart_result_counts", "asgart_result_copy", "asgart_result_timings",
@@ -312,6 +314,19 @@ def load_library() -> C.CDLL:
         L.asgart_rosary_free.restype = None
         L.asgart_rosary_geometry.argtypes = [u64p]
         L.asgart_rosary_geometry.restype = None
+    if hasattr(L, "asgart_duplication_groups"):
+        L.asgart_duplication_groups.argtypes = [C.c_int32, vp, vp, vp, C.c_int64, C.c_int64, C.c_uint64, C.POINTER(vp)]
+        L.asgart_duplication_groups.restype = C.c_int32
+        L.asgart_groups_counts.argtypes = [vp, u64p, u64p, u64p]
+        L.asgart_groups_counts.restype = None
+        L.asgart_groups_copy.argtypes = [vp] * 14
+        L.asgart_groups_copy.restype = None
+        L.asgart_groups_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_groups_timings.restype = C.c_int32
+        L.asgart_groups_free.argtypes = [vp]
+        L.asgart_groups_free.restype = None
+        L.asgart_groups_geometry.argtypes = [u64p]
+        L.asgart_groups_geometry.restype = None
     if hasattr(L, "asgart_export_records"):
         L.asgart_export_records.argtypes = [C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, vp, vp,
                                             C.c_int64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp)]

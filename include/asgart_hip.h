@@ -683,6 +683,47 @@ void asgart_rosary_free(asgart_rosary *r);
  * arm counts on the seams. */
 void asgart_rosary_geometry(uint64_t *block_threads);
 
+/* ---- paralogy groups: loci, copies ----------------------------------------------------------------------------
+ * From pairs to the genome: the arms merged into disjoint LOCI, the loci linked by the duplications into GROUPS (the
+ * connected components), copy numbers and non-redundant bases.  Nothing of the reference does this: its families are the
+ * runs of the seed automaton, and the rosary clusters above end where their LAST member ends and never link two arms.
+ * in: the arms in flatten order, arm 2q + side of duplication q (left 0, right 1): arm_name (ids into a table of n_names
+ * names; names never reach the device), arm_start (the position within the fragment), arm_length; one parameter, margin.
+ * Loci.  end = start + length.  Two arms of one name id are neighbours iff start_a < sat(end_b + margin) and
+ * start_b < sat(end_a + margin), sat(x + margin) = min(x + margin, 2^64 - 1).  The loci are the connected components of
+ * that relation, which is the fold over the arms sorted by (name id, start): an arm opens a locus iff it is the first of
+ * its name or start >= sat(M + margin), M the LARGEST end of all earlier arms of that name -- the running maximum, not the
+ * neighbour's end as in asgart_rosary_clusters.  Lengths are positive, so the partition does not depend on how ties of
+ * (name, start) are ordered.  A locus has its name, start = the smallest start of its members, length = the largest end
+ * - start, members = its number of arms.  Loci are numbered in (name id, start) order; name_offsets[n_names + 1] are their
+ * CSR rows per name id (a name without arms has an empty row).
+ * Groups.  Duplication q is an edge between the locus of arm 2q and the locus of arm 2q + 1; self-edges (both arms in one
+ * locus) and parallel edges are legal.  The groups are the connected components of the loci under these edges, numbered
+ * densely in the order of their SMALLEST locus index, so every output is a function of the input alone.  Per group: loci
+ * (the copies), duplications, bases = the sum of its loci's lengths (mod 2^64; loci are disjoint: non-redundant).
+ * Per locus also locus_group.  Per duplication: group[q] = the group of its left locus; order[n_sds] = the input ordinals
+ * of the duplications, stable by group, with group_offsets[n_groups + 1]: the offsets and gather keys of a result whose
+ * families are the groups.  Per arm: arm_locus[2 n_sds].
+ * Checked on the host before anything is launched (ASGART_E_ARG, the message names the first offending arm): NULL arrays
+ * with n_sds > 0, a negative count, a name id outside [0, n_names), an arm of length 0, start + length wrapping past
+ * 2^64.  2 * n_sds >= 2^32: ASGART_E_CAP; no usable device: ASGART_E_HIP.  n_sds == 0 succeeds with n_names + 1 zero
+ * offsets and no groups.  No device memory is held once the call has returned.  Every copy target is nullable. */
+typedef struct asgart_groups asgart_groups;
+int32_t asgart_duplication_groups(int32_t device, const int32_t *arm_name, const uint64_t *arm_start,
+                                  const uint64_t *arm_length, int64_t n_sds, int64_t n_names, uint64_t margin,
+                                  asgart_groups **out);
+void asgart_groups_counts(const asgart_groups *r, uint64_t *n_names, uint64_t *n_loci, uint64_t *n_groups);
+void asgart_groups_copy(const asgart_groups *r, uint64_t *name_offsets, int32_t *locus_name, uint64_t *locus_start,
+                        uint64_t *locus_length, uint32_t *locus_members, uint32_t *locus_group, uint32_t *group_loci,
+                        uint32_t *group_duplications, uint64_t *group_bases, uint32_t *group, uint32_t *order,
+                        uint64_t *group_offsets, uint32_t *arm_locus);
+/* Milliseconds of the call behind r: [0] the upload, [1] the kernels from the first to the last, [2] the copy back; HIP
+ * events for the first two.  ASGART_E_ARG for a NULL argument. */
+int32_t asgart_groups_timings(const asgart_groups *r, double *ms3);
+void asgart_groups_free(asgart_groups *r);
+/* Threads per workgroup of the kernels behind asgart_duplication_groups, for tests that place their counts on the seams. */
+void asgart_groups_geometry(uint64_t *block_threads);
+
 /* ---- result files written on the GPU ------------------------------------------------------------------------
  * Replace the per-duplication work of the three exporters of reference src/exporters.rs for a result held as arrays: one
  * call gives the whole file, byte for byte what the exporter writes, in one device buffer.
