@@ -1178,6 +1178,35 @@ EXPORT_FORMATS = {"json": 0, "gff2": 1, "gff3": 2}   # ASGART_EXPORT_JSON / _GFF
 F32_TEXT_MAX = 64                                     # ASGART_F32_TEXT_MAX
 
 
+def _result_arrays(who: str, offs, sds, flags, chr_, chr_pos, names: Sequence[bytes]):
+    """What the file writers share on the way in: offs, sds, flags, chr_, chr_pos as the library takes them, and the name
+    table as bytes and offsets -> (offs, sds, flags, chr_, chr_pos, name_bytes, name_off)."""
+    offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    chr_ = np.ascontiguousarray(chr_, dtype=np.int32).reshape(-1, 2)
+    chr_pos = np.ascontiguousarray(chr_pos, dtype=np.uint64).reshape(-1, 2)
+    if len(offs) < 1 or not (len(flags) == len(chr_) == len(chr_pos) == len(sds)):
+        raise ValueError(f"{who}: the arrays differ in length")
+    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
+    np.cumsum([len(b) for b in names], out=name_off[1:])
+    name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+    return offs, sds, flags, chr_, chr_pos, name_bytes, name_off
+
+
+def _written_file(h, timings: Optional[list]) -> np.ndarray:
+    """What the file writers share on the way out: the file behind the handle h as uint8[size], the call's three
+    millisecond figures into timings, the handle freed."""
+    L = load_library()
+    try:
+        out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
+        _check(L.asgart_export_copy(h, _ptr(out), len(out)))
+        _read_timings(L.asgart_export_timings, h, timings)
+    finally:
+        L.asgart_export_free(h)
+    return out
+
+
 def export_records(fmt: str, offs, sds, flags, identity, chr_, chr_pos, names: Sequence[bytes], prefix: bytes,
                    suffix: bytes, device: int = 0, timings: Optional[list] = None) -> np.ndarray:
     """asgart_export_records: the whole result file as uint8[size], written on the GPU.  fmt: "json", "gff2" or "gff3";
@@ -1188,31 +1217,18 @@ def export_records(fmt: str, offs, sds, flags, identity, chr_, chr_pos, names: S
     if fmt not in EXPORT_FORMATS:
         raise ValueError(f"unknown format `{fmt}` (one of {', '.join(EXPORT_FORMATS)})")
     L = load_library()
-    offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
-    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
-    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
-    chr_ = np.ascontiguousarray(chr_, dtype=np.int32).reshape(-1, 2)
-    chr_pos = np.ascontiguousarray(chr_pos, dtype=np.uint64).reshape(-1, 2)
+    offs, sds, flags, chr_, chr_pos, name_bytes, name_off = _result_arrays("export_records", offs, sds, flags, chr_, chr_pos, names)
+    n = len(sds)
     if identity is not None:
         identity = np.ascontiguousarray(identity, dtype=np.float32).reshape(-1)
-    n = len(sds)
-    if len(offs) < 1 or not (len(flags) == len(chr_) == len(chr_pos) == n) or (identity is not None and len(identity) != n):
-        raise ValueError("export_records: the arrays differ in length")
-    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in names], out=name_off[1:])
-    name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+        if len(identity) != n:
+            raise ValueError("export_records: the arrays differ in length")
     pre, suf = (np.frombuffer(b or b"\0", dtype=np.uint8) for b in (prefix, suffix))
     h = C.c_void_p()
     _check(L.asgart_export_records(int(device), EXPORT_FORMATS[fmt], _ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags),
                                    _ptr(identity), _ptr(chr_), _ptr(chr_pos), n, _ptr(name_bytes), _ptr(name_off),
                                    len(names), _ptr(pre), len(prefix), _ptr(suf), len(suffix), C.byref(h)))
-    try:
-        out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
-        _check(L.asgart_export_copy(h, _ptr(out), len(out)))
-        _read_timings(L.asgart_export_timings, h, timings)
-    finally:
-        L.asgart_export_free(h)
-    return out
+    return _written_file(h, timings)
 
 
 def export_geometry() -> Tuple[int, int, int]:
@@ -1230,39 +1246,26 @@ def _paf_records(call, who: str, offs, sds, flags, status, distance, chr_, chr_p
     if not hasattr(L, "asgart_" + who):
         raise AsgartError(-3, f"{library_path()} has no asgart_{who}: rebuild it; there is no host fallback behind "
                               "this call (align.paf_text is the host writer)")
-    offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
-    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
-    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    offs, sds, flags, chr_, chr_pos, name_bytes, name_off = _result_arrays(who, offs, sds, flags, chr_, chr_pos, names)
     status = np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
     distance = np.ascontiguousarray(distance, dtype=np.uint32).reshape(-1)
-    chr_ = np.ascontiguousarray(chr_, dtype=np.int32).reshape(-1, 2)
-    chr_pos = np.ascontiguousarray(chr_pos, dtype=np.uint64).reshape(-1, 2)
     run_offsets = np.ascontiguousarray(run_offsets, dtype=np.uint64).reshape(-1)
     run_len = np.ascontiguousarray(run_len, dtype=np.uint32).reshape(-1)
     run_op = np.ascontiguousarray(run_op, dtype=np.uint8).reshape(-1)
     name_length = np.ascontiguousarray(name_length, dtype=np.uint64).reshape(-1)
     n = len(sds)
-    if len(offs) < 1 or not (len(flags) == len(status) == len(distance) == len(chr_) == len(chr_pos) == n) or \
-            len(run_offsets) != n + 1 or len(run_len) != len(run_op) or len(name_length) != len(names):
+    if not (len(status) == len(distance) == n) or len(run_offsets) != n + 1 or len(run_len) != len(run_op) or \
+            len(name_length) != len(names):
         raise ValueError(f"{who}: the arrays differ in length")
     if len(run_len) < int(run_offsets[-1]) < 1 << 32:   # (2^32 runs and more are the library's to refuse, unread)
         raise ValueError(f"{who}: run_offsets end at {int(run_offsets[-1])}, there are {len(run_len)} runs")
-    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in names], out=name_off[1:])
-    name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
     if len(run_len) == 0:
         run_len, run_op = np.zeros(1, np.uint32), np.zeros(1, np.uint8)
     h = C.c_void_p()
     _check(call(_ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags), _ptr(status), _ptr(distance), _ptr(chr_), _ptr(chr_pos), n,
                 _ptr(run_offsets), _ptr(run_len), _ptr(run_op), _ptr(name_bytes), _ptr(name_off), _ptr(name_length),
                 len(names), C.byref(h)))
-    try:
-        out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
-        _check(L.asgart_export_copy(h, _ptr(out), len(out)))
-        _read_timings(L.asgart_export_timings, h, timings)
-    finally:
-        L.asgart_export_free(h)
-    return out
+    return _written_file(h, timings)
 
 
 def paf_records(offs, sds, flags, status, distance, chr_, chr_pos, run_offsets, run_len, run_op, names: Sequence[bytes],
@@ -1317,33 +1320,19 @@ def sdtable_records(offs, sds, flags, status, chr_, chr_pos, names: Sequence[byt
     if not hasattr(L, "asgart_sdtable_records"):
         raise AsgartError(-3, f"{library_path()} has no asgart_sdtable_records: rebuild it; there is no host fallback behind "
                               "this call (align.sd_table_text is the host writer)")
-    offs = np.ascontiguousarray(offs, dtype=np.uint64).reshape(-1)
-    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
-    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    offs, sds, flags, chr_, chr_pos, name_bytes, name_off = _result_arrays("sdtable_records", offs, sds, flags, chr_, chr_pos, names)
     status = np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
-    chr_ = np.ascontiguousarray(chr_, dtype=np.int32).reshape(-1, 2)
-    chr_pos = np.ascontiguousarray(chr_pos, dtype=np.uint64).reshape(-1, 2)
     table = np.ascontiguousarray(counts.table, dtype=np.uint64)
     figures = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in figures]
     n = len(sds)
-    if len(offs) < 1 or not (len(flags) == len(status) == len(chr_) == len(chr_pos) == len(table) == n) or \
-            len(figures) != 4 or any(len(v) != n for v in figures):
+    if not (len(status) == len(table) == n) or len(figures) != 4 or any(len(v) != n for v in figures):
         raise ValueError("sdtable_records: the arrays differ in length")
-    name_off = np.zeros(len(names) + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in names], out=name_off[1:])
-    name_bytes = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
     pre = np.frombuffer(prefix or b"\0", dtype=np.uint8)
     h = C.c_void_p()
     _check(L.asgart_sdtable_records(int(device), _ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags), _ptr(status), _ptr(chr_),
                                     _ptr(chr_pos), n, _ptr(name_bytes), _ptr(name_off), len(names), _ptr(table),
                                     *[_ptr(v) for v in figures], _ptr(pre), len(prefix), C.byref(h)))
-    try:
-        out = np.empty(int(L.asgart_export_size(h)), dtype=np.uint8)
-        _check(L.asgart_export_copy(h, _ptr(out), len(out)))
-        _read_timings(L.asgart_export_timings, h, timings)
-    finally:
-        L.asgart_export_free(h)
-    return out
+    return _written_file(h, timings)
 
 
 def sdtable_geometry() -> Tuple[int, int, int]:

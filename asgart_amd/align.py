@@ -298,6 +298,70 @@ def _check_cs(cs: Optional[str]) -> None:
 _REFUSAL = {0: "memory budget", 2: "bound on the edits"}
 
 
+def _row_arrays(offs, sds, flags, aln, counts=None):
+    """What the PAF and table writers check first, host and device -> offs, sds, flags as arrays: one flag byte, one
+    alignment and (the table) one row of counts per duplication, and families that end where the duplications do."""
+    offs = np.asarray(offs, dtype=np.int64)
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds) or \
+            (counts is not None and len(counts) != len(sds)):
+        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, "
+                         + (f"{len(counts)} counts, " if counts is not None else "") + f"families that end at {int(offs[-1])}")
+    return offs, sds, flags
+
+
+def _no_strand(q: int, f: int) -> ValueError:
+    return ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
+                      "direct (+) and reverse-complemented (-) alignments and none for this one")
+
+
+def _check_strands(flags) -> None:
+    """the host writers' refusal of a flag byte without a strand"""
+    for q, f in enumerate(flags.tolist()):
+        if f not in (0, 3):
+            raise _no_strand(q, f)
+
+
+def _locate(strand):
+    """-> locate(pos): the fragment of a global position as (name, fragment length, position in it), for the host writers"""
+    total = sum(c.length for c in strand.map)
+
+    def locate(pos: int):
+        for c in strand.map:   # first match, as RunResult's find_chr_by_pos
+            if c.position <= pos < c.position + c.length:
+                return c.name, c.length, pos - c.position
+        return "unknown", total, pos
+
+    return locate
+
+
+def _device_rows(label: str, offs, sds, flags, strand, aln, counts=None, stderr=None):
+    """What the device writers share ahead of the library call: the checks, the name table (every map entry's name, then
+    `unknown`), the arms located, a status byte per duplication (1: a row) and the stderr line of every refused one under
+    the caller's label -> (offs, sds, flags, names, chr_, chr_pos, status, t0), t0 the start of the `names` timing."""
+    import time
+
+    from .postprocess import locate_arms
+
+    offs, sds, flags = _row_arrays(offs, sds, flags, aln, counts)
+    odd = np.flatnonzero((flags != 0) & (flags != 3))
+    if len(odd):
+        raise _no_strand(int(odd[0]), int(flags[odd[0]]))
+    t0 = time.perf_counter()
+    names = [c.name.encode("utf-8") for c in strand.map] + [b"unknown"]
+    chr_, chr_pos = locate_arms(sds, strand)
+    why = np.asarray(aln.status, dtype=np.uint8).reshape(-1)
+    status = (why == 1).astype(np.uint8)   # (the library writes no row for status 0: beyond its bound is no row either)
+    refused = np.flatnonzero(status == 0)
+    if len(refused):
+        family = np.searchsorted(offs, refused, side="right") - 1
+        for q, f in zip(refused.tolist(), family.tolist()):
+            print(f"{label}: duplication {q} (family {f}) was refused by the alignment's {_REFUSAL[int(why[q])]}: no row",
+                  file=stderr if stderr is not None else sys.stderr)
+    return offs, sds, flags, names, chr_, chr_pos, status, t0
+
+
 def paf_text(offs, sds, flags, strand, aln, stderr=None, cs: Optional[str] = None, text=None) -> str:
     """One PAF row per aligned duplication of a result: offs / sds the family arrays, flags one byte per duplication, strand
     the run's Strand (its map names the fragments), aln the Alignments of Index.align(sds, flags, inclusive=False).
@@ -316,24 +380,9 @@ def paf_text(offs, sds, flags, strand, aln, stderr=None, cs: Optional[str] = Non
         if text is None:
             raise ValueError("paf_text: cs needs the text the duplications lie in (text=)")
         text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else text
-    offs = np.asarray(offs, dtype=np.int64)
-    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
-    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
-    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds):
-        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, "
-                         f"families that end at {int(offs[-1])}")
-    for q, f in enumerate(flags.tolist()):
-        if f not in (0, 3):
-            raise ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
-                             "direct (+) and reverse-complemented (-) alignments and none for this one")
-    total = sum(c.length for c in strand.map)
-
-    def locate(pos: int):
-        for c in strand.map:   # first match, as RunResult's find_chr_by_pos
-            if c.position <= pos < c.position + c.length:
-                return c.name, c.length, pos - c.position
-        return "unknown", total, pos
-
+    offs, sds, flags = _row_arrays(offs, sds, flags, aln)
+    _check_strands(flags)
+    locate = _locate(strand)
     family = np.repeat(np.arange(len(offs) - 1), np.diff(offs))
     rows = []
     for q, (left, right, ll, rl) in enumerate(sds.tolist()):
@@ -363,32 +412,9 @@ def _paf_text_device(offs, sds, flags, strand, aln, device: int = 0, stderr=None
     _check_cs(cs)
     if cs is not None and index is None:
         raise ValueError("paf_text_gpu: cs needs the index whose text the duplications lie in (index=)")
-    from .postprocess import locate_arms
-
-    offs = np.asarray(offs, dtype=np.int64)
-    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
-    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
-    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds):
-        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, "
-                         f"families that end at {int(offs[-1])}")
-    odd = np.flatnonzero((flags != 0) & (flags != 3))
-    if len(odd):
-        q, f = int(odd[0]), int(flags[odd[0]])
-        raise ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
-                         "direct (+) and reverse-complemented (-) alignments and none for this one")
-    t0 = time.perf_counter()
-    total = sum(c.length for c in strand.map)
-    names = [c.name.encode("utf-8") for c in strand.map] + [b"unknown"]
-    name_length = np.array([c.length for c in strand.map] + [total], dtype=np.uint64)
-    chr_, chr_pos = locate_arms(sds, strand)
-    why = np.asarray(aln.status, dtype=np.uint8).reshape(-1)
-    status = (why == 1).astype(np.uint8)   # (the library writes no row for status 0: beyond its bound is no row either)
-    refused = np.flatnonzero(status == 0)
-    if len(refused):
-        family = np.searchsorted(offs, refused, side="right") - 1
-        for q, f in zip(refused.tolist(), family.tolist()):
-            print(f"paf: duplication {q} (family {f}) was refused by the alignment's {_REFUSAL[int(why[q])]}: no row",
-                  file=stderr if stderr is not None else sys.stderr)
+    offs, sds, flags, names, chr_, chr_pos, status, t0 = _device_rows("paf", offs, sds, flags, strand, aln, stderr=stderr)
+    lengths = [c.length for c in strand.map]
+    name_length = np.array(lengths + [sum(lengths)], dtype=np.uint64)   # (`unknown` has the strand's length)
     t1 = time.perf_counter()
     ms: list = []
     if cs is None:
@@ -540,24 +566,9 @@ def sd_table_text(offs, sds, flags, strand, aln, counts, stderr=None) -> str:
     0 or 2) gets no row and is named on stderr."""
     from .slice import f32_display
 
-    offs = np.asarray(offs, dtype=np.int64)
-    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
-    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
-    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds) or len(counts) != len(sds):
-        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, {len(counts)} "
-                         f"counts, families that end at {int(offs[-1])}")
-    for q, f in enumerate(flags.tolist()):
-        if f not in (0, 3):
-            raise ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
-                             "direct (+) and reverse-complemented (-) alignments and none for this one")
-    total = sum(c.length for c in strand.map)
-
-    def locate(pos: int):
-        for c in strand.map:   # first match, as RunResult's find_chr_by_pos
-            if c.position <= pos < c.position + c.length:
-                return c.name, pos - c.position
-        return "unknown", pos
-
+    offs, sds, flags = _row_arrays(offs, sds, flags, aln, counts)
+    _check_strands(flags)
+    locate = _locate(strand)
     family = np.repeat(np.arange(len(offs) - 1), np.diff(offs))
     figures = divergence(counts)
     rows = [SD_TABLE_HEADER]
@@ -568,8 +579,8 @@ def sd_table_text(offs, sds, flags, strand, aln, counts, stderr=None) -> str:
             continue
         match, mismatch, ts, tv, ins_runs, ins_bases, del_runs, del_bases, longest_match, longest_gap = \
             (int(v) for v in counts.table[q])
-        name1, pos1 = locate(left)
-        name2, pos2 = locate(right)
+        name1, _, pos1 = locate(left)
+        name2, _, pos2 = locate(right)
         rows.append("\t".join(str(v) for v in (
             name1, pos1, pos1 + ll, name2, pos2, pos2 + rl, f"sd{q}", 0, "+", "-" if flags[q] == 3 else "+",
             int(family[q]), match + mismatch + ins_bases + del_bases, match + mismatch, match, mismatch, ts, tv,
@@ -584,30 +595,8 @@ def _sd_table_device(offs, sds, flags, strand, aln, counts, device: int = 0, std
     import time
 
     from . import sdtable_records
-    from .postprocess import locate_arms
 
-    offs = np.asarray(offs, dtype=np.int64)
-    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
-    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
-    if len(flags) != len(sds) or len(aln.distance) != len(sds) or int(offs[-1]) != len(sds) or len(counts) != len(sds):
-        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, {len(aln.distance)} alignments, {len(counts)} "
-                         f"counts, families that end at {int(offs[-1])}")
-    odd = np.flatnonzero((flags != 0) & (flags != 3))
-    if len(odd):
-        q, f = int(odd[0]), int(flags[odd[0]])
-        raise ValueError(f"duplication {q} is {'reversed' if f == 1 else 'complemented'} only: PAF has a strand for "
-                         "direct (+) and reverse-complemented (-) alignments and none for this one")
-    t0 = time.perf_counter()
-    names = [c.name.encode("utf-8") for c in strand.map] + [b"unknown"]
-    chr_, chr_pos = locate_arms(sds, strand)
-    why = np.asarray(aln.status, dtype=np.uint8).reshape(-1)
-    status = (why == 1).astype(np.uint8)
-    refused = np.flatnonzero(status == 0)
-    if len(refused):
-        family = np.searchsorted(offs, refused, side="right") - 1
-        for q, f in zip(refused.tolist(), family.tolist()):
-            print(f"sd-table: duplication {q} (family {f}) was refused by the alignment's {_REFUSAL[int(why[q])]}: no row",
-                  file=stderr if stderr is not None else sys.stderr)
+    offs, sds, flags, names, chr_, chr_pos, status, t0 = _device_rows("sd-table", offs, sds, flags, strand, aln, counts, stderr)
     figures = divergence(counts)
     t1 = time.perf_counter()
     ms: list = []

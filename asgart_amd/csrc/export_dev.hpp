@@ -14,22 +14,16 @@
 // behind the first line (GFF); a family unit is all first half.
 #pragma once
 #include "f32_digits.hpp"
+#include "file_writer.hpp"
 
 namespace asgart {
 
 enum : int32_t { kFormatJson = 0, kFormatGff2 = 1, kFormatGff3 = 2 };
 
-struct ExportIn {
-    const uint64_t *offs;      // [n_fam + 1]
-    const uint64_t *sds;       // [n][4]: global left, global right, left_length, right_length
-    const uint8_t *flags;      // [n]: bit 0 reversed, bit 1 complemented
+struct ExportIn : ResultView {   // (flags: bit 0 reversed, bit 1 complemented)
     const float *identity;     // [n], or nullptr: every identity 0
-    const int32_t *chr;        // [n][2] name ids
-    const uint64_t *chr_pos;   // [n][2]
-    const uint8_t *names;      // the name table: the bytes of all names, as the format prints them
-    const uint64_t *name_off;  // [n_names + 1]
     const Pow10Entry *pow10;
-    uint32_t n_fam, n;
+    uint32_t n;
     int32_t format;
 };
 

@@ -34,7 +34,7 @@
 // texts are disjoint and longer than kSolo, so kStage / (kSolo + 1) = 252 entries of 32 bytes (8 KiB of LDS beside the
 // 16 KiB image: six workgroups a CU) hold them.  A design constant, reasoned and not measured: no sweep was run.
 #include "index.hpp"
-#include "tool_base.hpp"
+#include "file_writer.hpp"
 #include "paf_dev.hpp"
 
 namespace asgart {
@@ -137,6 +137,8 @@ __global__ __launch_bounds__(kThreads) void paf_write_kernel(PafIn in, uint64_t 
         paf_cs_deal<kLongMax>(in, g0, g1, threadIdx.x, kThreads, stage, long_runs, &n_long);
     }
     __syncthreads();
+    // file_writer.hpp's copy_out_image where the image starts with the range (a0 == g0), kept as its own loop: through
+    // the general one the cs kernel spills two more scalar registers (profiles/writers_resources.txt)
     const uint32_t bytes = (uint32_t)(g1 - g0), lines = (bytes + kLine - 1) / kLine;
     for (uint32_t l = threadIdx.x; l < lines; l += kThreads) {
         if ((l + 1) * kLine <= bytes) {
@@ -147,9 +149,8 @@ __global__ __launch_bounds__(kThreads) void paf_write_kernel(PafIn in, uint64_t 
     }
 }
 
-struct PafWork : ToolWork {
-    DevBuf &offs = buf(), &sds = buf(), &flags = buf(), &distance = buf(), &chr = buf(), &chr_pos = buf(), &run_off = buf(),
-           &run_len = buf(), &run_op = buf(), &names = buf(), &name_off = buf(), &name_len = buf(), &kept = buf(),
+struct PafWork : FileWork {
+    DevBuf &distance = buf(), &run_off = buf(), &run_len = buf(), &run_op = buf(), &name_len = buf(), &kept = buf(),
            &text = buf(), &match = buf(), &bases = buf(), &P = buf(), &M = buf(), &B = buf(), &head_len = buf(), &fam = buf(),
            &lens = buf(), &row_start = buf(), &cs = buf(), &on_left = buf(), &on_right = buf(), &C = buf(), &I = buf(),
            &J = buf();
@@ -164,21 +165,19 @@ struct CsText {
 const char kWho[] = "asgart_paf_records", kWhoCs[] = "asgart_paf_records_cs";
 
 // Every argument check of the call, before the device is looked at; kept: the duplications with a row.
-int32_t check_arguments(const char *who, const uint64_t *fam_offsets, int64_t n_families, const asgart_proto_sd *sds,
-                        const uint8_t *flags, const uint8_t *status, const uint32_t *distance, const int32_t *chr, const uint64_t *chr_pos,
-                        int64_t n_sd, const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
-                        const uint8_t *name_bytes, const uint64_t *name_offsets, const uint64_t *name_length, int64_t n_names,
+int32_t check_arguments(const char *who, const ResultArg &a, const uint8_t *status, const uint32_t *distance,
+                        const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op, const uint64_t *name_length,
                         asgart_export **out, std::vector<uint32_t> &kept) {
-    if (!out || !fam_offsets || n_families < 0 || n_sd < 0 || n_names < 0 || !name_offsets || (n_names && !name_length) ||
-        (n_sd && (!sds || !flags || !status || !distance || !chr || !chr_pos || !run_offsets))) {
+    const int64_t n_sd = a.n_sd;
+    if (!out || a.missing() || (a.n_names && !name_length) || (n_sd && (!status || !distance || !run_offsets))) {
         set_error("%s: bad argument", who);
         return ASGART_E_ARG;
     }
-    if (n_sd >= (int64_t)1 << 31 || n_families >= (int64_t)1 << 31) {
+    if (n_sd >= (int64_t)1 << 31 || a.n_families >= (int64_t)1 << 31) {
         set_error("%s: 2^31 rows (or families) and more are not supported", who);
         return ASGART_E_CAP;
     }
-    RC_TRY(check_csr(who, "fam_offsets", fam_offsets, n_families, n_sd, "n_sd"));
+    RC_TRY(check_result_arg(who, a));
     const uint64_t n_runs = n_sd ? run_offsets[n_sd] : 0;
     if (n_runs >= (uint64_t)1 << 32) {
         set_error("%s: run_offsets end at %llu; 2^32 runs and more are not supported", who, (unsigned long long)n_runs);
@@ -189,37 +188,26 @@ int32_t check_arguments(const char *who, const uint64_t *fam_offsets, int64_t n_
         set_error("%s: bad argument (%llu runs and no run_len or run_op)", who, (unsigned long long)n_runs);
         return ASGART_E_ARG;
     }
-    RC_TRY(check_name_table(who, name_bytes, name_offsets, n_names));
-    RC_TRY(check_name_ids(who, chr, n_sd, n_names));
-    return check_strand_rows(who, sds, flags, status, chr_pos, n_sd, kept);
+    return check_strand_rows(who, a.sds, a.flags, status, a.chr_pos, n_sd, kept);
 }
 
 template <bool kCs>
-int32_t run_paf(PafWork &w, asgart_export *res, CsText cs, const uint64_t *fam_offsets, uint32_t nf, const asgart_proto_sd *sds,
-                const uint8_t *flags, const uint32_t *distance, const int32_t *chr, const uint64_t *chr_pos, uint32_t n,
-                const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op, const uint8_t *name_bytes,
-                const uint64_t *name_offsets, const uint64_t *name_length, size_t n_names,
+int32_t run_paf(PafWork &w, asgart_export *res, CsText cs, const ResultArg &a, const uint32_t *distance,
+                const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op, const uint64_t *name_length,
                 const std::vector<uint32_t> &kept) {
-    const uint32_t n_rows = (uint32_t)kept.size();
+    const uint32_t n = (uint32_t)a.n_sd, n_rows = (uint32_t)kept.size();
     if (n_rows == 0) return 0;   // an empty file: nothing to launch
     const uint64_t n_runs = run_offsets[n];
-    RC_TRY(w.open(5));
+    RC_TRY(w.open_call());
     hipStream_t s = w.s;
-    HIP_TRY(hipEventRecord(w.ev[0], s));
-    RC_TRY(w.upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8));
-    RC_TRY(w.upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd)));
-    RC_TRY(w.upload(w.flags, flags, n));
+    RC_TRY(w.upload(a));
     RC_TRY(w.upload(w.distance, distance, (size_t)n * 4));
-    RC_TRY(w.upload(w.chr, chr, (size_t)n * 8));
-    RC_TRY(w.upload(w.chr_pos, chr_pos, (size_t)n * 16));
     RC_TRY(w.upload(w.run_off, run_offsets, ((size_t)n + 1) * 8));
     RC_TRY(w.upload(w.run_len, run_len, (size_t)n_runs * 4));
     RC_TRY(w.upload(w.run_op, run_op, (size_t)n_runs));
-    RC_TRY(w.upload(w.names, name_bytes, (size_t)name_offsets[n_names]));
-    RC_TRY(w.upload(w.name_off, name_offsets, (n_names + 1) * 8));
-    RC_TRY(w.upload(w.name_len, name_length, n_names * 8));
+    RC_TRY(w.upload(w.name_len, name_length, (size_t)a.n_names * 8));
     RC_TRY(w.upload(w.kept, kept.data(), (size_t)n_rows * 4));
-    HIP_TRY(hipEventRecord(w.ev[1], s));
+    RC_TRY(w.stamp(w.kUploaded));
     for (DevBuf *b : {&w.text, &w.match, &w.bases, &w.P, &w.M, &w.B}) RC_TRY(b->reserve(((size_t)n_runs + 1) * 8));
     RC_TRY(w.head_len.reserve((size_t)n_rows * 4));
     RC_TRY(w.fam.reserve((size_t)n_rows * 4));
@@ -233,17 +221,11 @@ int32_t run_paf(PafWork &w, asgart_export *res, CsText cs, const uint64_t *fam_o
     RC_TRY(w.exclusive_scan(w.match.as<uint64_t>(), w.M.as<uint64_t>(), (size_t)n_runs + 1));
     RC_TRY(w.exclusive_scan(w.bases.as<uint64_t>(), w.B.as<uint64_t>(), (size_t)n_runs + 1));
     PafIn in{};
-    in.offs = w.offs.as<uint64_t>();
-    in.sds = w.sds.as<uint64_t>();
-    in.flags = w.flags.as<uint8_t>();
+    static_cast<ResultView &>(in) = w.view();
     in.distance = w.distance.as<uint32_t>();
-    in.chr = w.chr.as<int32_t>();
-    in.chr_pos = w.chr_pos.as<uint64_t>();
     in.run_off = w.run_off.as<uint64_t>();
     in.run_len = w.run_len.as<uint32_t>();
     in.run_op = w.run_op.as<uint8_t>();
-    in.names = w.names.as<uint8_t>();
-    in.name_off = w.name_off.as<uint64_t>();
     in.name_len = w.name_len.as<uint64_t>();
     in.kept = w.kept.as<uint32_t>();
     in.P = w.P.as<uint64_t>();
@@ -252,7 +234,6 @@ int32_t run_paf(PafWork &w, asgart_export *res, CsText cs, const uint64_t *fam_o
     in.head_len = w.head_len.as<uint32_t>();
     in.fam = w.fam.as<uint32_t>();
     in.row_start = w.row_start.as<uint64_t>();
-    in.n_fam = nf;
     in.n_rows = n_rows;
     if constexpr (kCs) {
         for (DevBuf *b : {&w.cs, &w.on_left, &w.on_right, &w.C, &w.I, &w.J}) RC_TRY(b->reserve(((size_t)n_runs + 1) * 8));
@@ -274,7 +255,7 @@ int32_t run_paf(PafWork &w, asgart_export *res, CsText cs, const uint64_t *fam_o
                                                                      w.lens.as<uint64_t>());
     HIP_TRY(hipGetLastError());
     RC_TRY(w.exclusive_scan(w.lens.as<uint64_t>(), w.row_start.as<uint64_t>(), (size_t)n_rows + 1));
-    HIP_TRY(hipEventRecord(w.ev[2], s));
+    RC_TRY(w.stamp(w.kPlaced));
     if constexpr (kCs) {
         uint64_t tail[2] = {0, 0};   // the size of the file and the lowest refused row, in one copy
         HIP_TRY(read_back(tail, in.row_start + n_rows, 16, s));
@@ -288,8 +269,8 @@ int32_t run_paf(PafWork &w, asgart_export *res, CsText cs, const uint64_t *fam_o
                     if (run_op[t] != 'I') j += run_len[t];
                 }
                 set_error("%s: the runs of duplication %lld consume %llu and %llu bases of arms of %llu and %llu", kWhoCs, q,
-                          (unsigned long long)i, (unsigned long long)j, (unsigned long long)sds[q].left_length,
-                          (unsigned long long)sds[q].right_length);
+                          (unsigned long long)i, (unsigned long long)j, (unsigned long long)a.sds[q].left_length,
+                          (unsigned long long)a.sds[q].right_length);
             } else if ((tail[1] & 3) == kPafBadLen) {
                 set_error("%s: duplication %lld has a run_len of 0 (a run of no base)", kWhoCs, q);
             } else {
@@ -305,18 +286,11 @@ int32_t run_paf(PafWork &w, asgart_export *res, CsText cs, const uint64_t *fam_o
         HIP_TRY(read_back(&res->size, in.row_start + n_rows, 8, s));
     }
     RC_TRY(res->file.reserve(std::max<size_t>(res->size, 16)));
-    HIP_TRY(hipEventRecord(w.ev[3], s));
+    RC_TRY(w.stamp(w.kSized));
     paf_write_kernel<kCs><<<blocks_for(res->size, kStage), kThreads, 0, s>>>(in, res->size, res->file.as<uint8_t>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(w.ev[4], s));
-    HIP_TRY(stream_sync(s));
-    float up = 0, a = 0, b = 0;
-    HIP_TRY(hipEventElapsedTime(&up, w.ev[0], w.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&a, w.ev[1], w.ev[2]));
-    HIP_TRY(hipEventElapsedTime(&b, w.ev[3], w.ev[4]));
-    res->ms[0] = up;
-    res->ms[1] = (double)a + (double)b;
-    return 0;
+    RC_TRY(w.stamp(w.kWritten));
+    return w.finish(res);
 }
 
 }  // namespace
@@ -331,14 +305,13 @@ extern "C" int32_t asgart_paf_records(int32_t device, const uint64_t *fam_offset
                                       const uint8_t *name_bytes, const uint64_t *name_offsets, const uint64_t *name_length,
                                       int64_t n_names, asgart_export **out) {
     if (out) *out = nullptr;
+    const ResultArg a{fam_offsets, n_families, sds, flags, chr, chr_pos, n_sd, name_bytes, name_offsets, n_names};
     std::vector<uint32_t> kept;
-    RC_TRY(check_arguments(kWho, fam_offsets, n_families, sds, flags, status, distance, chr, chr_pos, n_sd, run_offsets, run_len,
-                           run_op, name_bytes, name_offsets, name_length, n_names, out, kept));
+    RC_TRY(check_arguments(kWho, a, status, distance, run_offsets, run_len, run_op, name_length, out, kept));
     RC_TRY(use_device(kWho, device));
     return run_tool<PafWork>(out, [&](PafWork &w, asgart_export *res) {
         res->device = device;
-        return run_paf<false>(w, res, CsText{nullptr, 0}, fam_offsets, (uint32_t)n_families, sds, flags, distance, chr, chr_pos, (uint32_t)n_sd,
-                       run_offsets, run_len, run_op, name_bytes, name_offsets, name_length, (size_t)n_names, kept);
+        return run_paf<false>(w, res, CsText{nullptr, 0}, a, distance, run_offsets, run_len, run_op, name_length, kept);
     });
 }
 
@@ -357,9 +330,9 @@ extern "C" int32_t asgart_paf_records_cs(asgart_index *idx, int32_t cs_mode, con
         set_error("%s: bad argument (no index: the bases are its text's)", kWhoCs);
         return ASGART_E_ARG;
     }
+    const ResultArg a{fam_offsets, n_families, sds, flags, chr, chr_pos, n_sd, name_bytes, name_offsets, n_names};
     std::vector<uint32_t> kept;
-    RC_TRY(check_arguments(kWhoCs, fam_offsets, n_families, sds, flags, status, distance, chr, chr_pos, n_sd, run_offsets,
-                           run_len, run_op, name_bytes, name_offsets, name_length, n_names, out, kept));
+    RC_TRY(check_arguments(kWhoCs, a, status, distance, run_offsets, run_len, run_op, name_length, out, kept));
     const uint64_t n_text = (uint64_t)idx->n;
     for (uint32_t q : kept) {   // lev_dev.hpp's check_arms, for the duplications with a row (two empty arms are a row here)
         const asgart_proto_sd &sd = sds[q];
@@ -373,9 +346,8 @@ extern "C" int32_t asgart_paf_records_cs(asgart_index *idx, int32_t cs_mode, con
     const int32_t device = idx->device;
     return run_tool<PafWork>(out, [&](PafWork &w, asgart_export *res) {
         res->device = device;
-        return run_paf<true>(w, res, CsText{idx->d_text, (uint32_t)cs_mode}, fam_offsets, (uint32_t)n_families, sds, flags,
-                             distance, chr, chr_pos, (uint32_t)n_sd, run_offsets, run_len, run_op, name_bytes, name_offsets,
-                             name_length, (size_t)n_names, kept);
+        return run_paf<true>(w, res, CsText{idx->d_text, (uint32_t)cs_mode}, a, distance, run_offsets, run_len, run_op,
+                             name_length, kept);
     });
 }
 

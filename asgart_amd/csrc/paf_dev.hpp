@@ -34,25 +34,18 @@
 
 namespace asgart {
 
-struct PafIn {
-    const uint64_t *offs;       // [n_fam + 1]
-    const uint64_t *sds;        // [n][4]: global left, global right, left_length, right_length
-    const uint8_t *flags;       // [n]: 0 `+`, 3 `-`
+struct PafIn : ResultView {     // (flags: 0 `+`, 3 `-`)
     const uint32_t *distance;   // [n]
-    const int32_t *chr;         // [n][2] name ids
-    const uint64_t *chr_pos;    // [n][2]
     const uint64_t *run_off;    // [n + 1]
     const uint32_t *run_len;    // [n_runs]
     const uint8_t *run_op;      // [n_runs]
-    const uint8_t *names;       // the bytes of all names
-    const uint64_t *name_off;   // [n_names + 1]
     const uint64_t *name_len;   // [n_names]: the length of the fragment, column 2 and 7
     const uint32_t *kept;       // [n_rows]: the duplications with a row, ascending
     const uint64_t *P, *M, *B;  // [n_runs + 1]: exclusive sums over the runs of text bytes, `=` bases, all bases
     const uint32_t *head_len;   // [n_rows]
     const uint32_t *fam;        // [n_rows]
     const uint64_t *row_start;  // [n_rows + 1]; the last entry is the size of the file
-    uint32_t n_fam, n_rows;
+    uint32_t n_rows;
     // the cs:Z: column only (asgart_paf_records_cs):
     const uint8_t *text;        // the index's normalised text
     const uint64_t *C, *I, *J;  // [n_runs + 1]: exclusive sums over the runs of cs text bytes, `=XI` bases, `=XD` bases

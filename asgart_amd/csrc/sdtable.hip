@@ -2,18 +2,16 @@
 // for a caller of the C ABI.
 //
 // What a row consists of is stated once, in sdtable_dev.hpp.  Apart from its names a row's size is bounded, so this is the
-// shape of export.hip, built beside its kernels (they are specialised to the three result formats and stay as they are):
+// shape of export.hip, with row and length kernels of its own (export.hip's are specialised to the three result formats):
 //   lengths   one thread per row: its family by bisection of the offsets, its length by running both halves of the row
 //             through a sink that counts;
 //   scan      a 64-bit exclusive scan of the lengths (rocPRIM): every row's place in the file;
-//   write     a workgroup owns kRows consecutive rows, so one contiguous byte range.  Two threads share a row (its two
-//             halves) and store its bytes into an LDS image of the range, laid out so that a 16-byte line of the file is a
-//             16-byte line of the image; then all threads move the image out with one aligned 16-byte store per lane.
-//             Only the lines the range shares with its neighbours go out byte by byte.  A range that does not fit the
-//             image (a name of any length is legal) is stored from the threads directly: slower, never refused.
+//   write     a workgroup owns kRows consecutive rows, so one contiguous byte range, and two threads share a row (its two
+//             halves): file_writer.hpp's write_owned_range, through an LDS image of the range unless it does not fit (a
+//             name of any length is legal).
 // The four figures arrive as f32 arrays (align.divergence): the file does not depend on whose logarithm ran; their digits
 // are f32_digits.hpp's, in display form.
-#include "tool_base.hpp"
+#include "file_writer.hpp"
 #include "sdtable_dev.hpp"
 
 namespace asgart {
@@ -24,6 +22,7 @@ constexpr uint32_t kRows = 64;       // rows per workgroup
 constexpr uint32_t kStage = 24576;   // bytes of the LDS image: 384 per row (a row with short names has about 150); six
                                      // workgroups fit the 160 KiB of a CU
 constexpr uint32_t kLine = 16;       // bytes per store of the copy out
+static_assert(kThreads == 2 * kRows, "two threads per row");
 
 __global__ __launch_bounds__(256) void sdtable_lengths_kernel(SdTableIn in, uint32_t *__restrict__ fam, uint32_t *__restrict__ half_at,
                                                               uint64_t *__restrict__ lens) {
@@ -49,47 +48,26 @@ __global__ __launch_bounds__(kThreads) void sdtable_write_kernel(SdTableIn in, c
                                                                  const uint64_t *__restrict__ offsets, uint64_t body_at,
                                                                  uint8_t *__restrict__ out) {
     __shared__ __align__(16) uint8_t stage[kStage];
-    const uint32_t first = blockIdx.x * kRows;
-    const uint32_t last = min(first + kRows, in.n_rows);
-    const uint64_t g0 = body_at + offsets[first], g1 = body_at + offsets[last];   // the workgroup's bytes of the file
-    const uint64_t a0 = g0 & ~(uint64_t)(kLine - 1);                              // the image starts on a line of the file
-    const bool staged = g1 - a0 <= kStage;
-    const uint32_t k = first + (threadIdx.x >> 1), half = threadIdx.x & 1;
-    if (k < last) {
-        const uint64_t at = body_at + offsets[k] + (half ? half_at[k] : 0u);
-        ByteSink s{staged ? stage + (at - a0) : out + at};
+    const auto row = [&](uint8_t *dst, uint32_t k, uint32_t half) __attribute__((always_inline)) {
+        ByteSink s{dst + (half ? half_at[k] : 0u)};
         emit_sd_row(s, in, in.kept[k], fam[k], half);
-    }
-    if (!staged) return;   // (the same in every thread of the workgroup)
-    __syncthreads();
-    const uint32_t lines = (uint32_t)((g1 - a0 + kLine - 1) / kLine);
-    for (uint32_t l = threadIdx.x; l < lines; l += kThreads) {
-        const uint64_t a = a0 + (uint64_t)l * kLine;
-        if (a >= g0 && a + kLine <= g1) {
-            *reinterpret_cast<uint4 *>(out + a) = *reinterpret_cast<const uint4 *>(stage + l * kLine);
-        } else {   // a line shared with the neighbouring range or with the header: this range's bytes only
-            const uint64_t lo = max(a, g0), hi = min(a + kLine, g1);
-            for (uint64_t b = lo; b < hi; ++b) out[b] = stage[b - a0];
-        }
-    }
+    };
+    write_owned_range<kRows, kStage, kLine, false>(stage, offsets, body_at, in.n_rows, out, row);
 }
 
-struct SdTableWork : ToolWork {
-    DevBuf &offs = buf(), &sds = buf(), &flags = buf(), &chr = buf(), &chr_pos = buf(), &names = buf(), &name_off = buf(),
-           &kept = buf(), &counts = buf(), &figures = buf(), &pow10 = buf(), &fam = buf(), &half_at = buf(), &lens = buf(),
+struct SdTableWork : FileWork {
+    DevBuf &kept = buf(), &counts = buf(), &figures = buf(), &pow10 = buf(), &fam = buf(), &half_at = buf(), &lens = buf(),
            &offsets = buf();
 };
 
 const char kWho[] = "asgart_sdtable_records";
 
-int32_t run_sdtable(SdTableWork &w, asgart_export *res, const uint64_t *fam_offsets, uint32_t nf, const asgart_proto_sd *sds,
-                    const uint8_t *flags, const int32_t *chr, const uint64_t *chr_pos, uint32_t n, const uint8_t *name_bytes,
-                    const uint64_t *name_offsets, size_t n_names, const asgart_align_counts *counts, const float *const figures[4],
-                    const uint8_t *prefix, uint64_t prefix_len, const std::vector<uint32_t> &kept) {
-    const uint32_t n_rows = (uint32_t)kept.size();
-    RC_TRY(w.open(5));
+int32_t run_sdtable(SdTableWork &w, asgart_export *res, const ResultArg &a, const asgart_align_counts *counts,
+                    const float *const figures[4], const uint8_t *prefix, uint64_t prefix_len,
+                    const std::vector<uint32_t> &kept) {
+    const uint32_t n = (uint32_t)a.n_sd, n_rows = (uint32_t)kept.size();
+    RC_TRY(w.open_call());
     hipStream_t s = w.s;
-    HIP_TRY(hipEventRecord(w.ev[0], s));
     if (n_rows == 0) {   // the header only
         res->size = prefix_len;
         RC_TRY(res->file.reserve(std::max<size_t>(res->size, 16)));
@@ -97,63 +75,37 @@ int32_t run_sdtable(SdTableWork &w, asgart_export *res, const uint64_t *fam_offs
         HIP_TRY(stream_sync(s));
         return 0;
     }
-    RC_TRY(w.upload(w.offs, fam_offsets, ((size_t)nf + 1) * 8));
-    RC_TRY(w.upload(w.sds, sds, (size_t)n * sizeof(asgart_proto_sd)));
-    RC_TRY(w.upload(w.flags, flags, n));
-    RC_TRY(w.upload(w.chr, chr, (size_t)n * 8));
-    RC_TRY(w.upload(w.chr_pos, chr_pos, (size_t)n * 16));
-    RC_TRY(w.upload(w.names, name_bytes, (size_t)name_offsets[n_names]));
-    RC_TRY(w.upload(w.name_off, name_offsets, (n_names + 1) * 8));
+    RC_TRY(w.upload(a));
     RC_TRY(w.upload(w.kept, kept.data(), (size_t)n_rows * 4));
     RC_TRY(w.upload(w.counts, counts, (size_t)n * sizeof(asgart_align_counts)));
     RC_TRY(w.figures.reserve(std::max<size_t>((size_t)n * 16, 16)));
     for (int i = 0; i < 4; ++i)
         HIP_TRY(hipMemcpyAsync(w.figures.as<float>() + (size_t)i * n, figures[i], (size_t)n * 4, hipMemcpyHostToDevice, s));
     RC_TRY(w.upload(w.pow10, pow10_table(), sizeof(Pow10Entry) * kPow10Entries));
-    HIP_TRY(hipEventRecord(w.ev[1], s));
+    RC_TRY(w.stamp(w.kUploaded));
     RC_TRY(w.fam.reserve((size_t)n_rows * 4));
     RC_TRY(w.half_at.reserve((size_t)n_rows * 4));
     RC_TRY(w.lens.reserve(((size_t)n_rows + 1) * 8));
     RC_TRY(w.offsets.reserve(((size_t)n_rows + 1) * 8));
     SdTableIn in{};
-    in.offs = w.offs.as<uint64_t>();
-    in.sds = w.sds.as<uint64_t>();
-    in.flags = w.flags.as<uint8_t>();
-    in.chr = w.chr.as<int32_t>();
-    in.chr_pos = w.chr_pos.as<uint64_t>();
-    in.names = w.names.as<uint8_t>();
-    in.name_off = w.name_off.as<uint64_t>();
+    static_cast<ResultView &>(in) = w.view();
     in.kept = w.kept.as<uint32_t>();
     in.counts = w.counts.as<uint64_t>();
     for (int i = 0; i < 4; ++i) in.figures[i] = w.figures.as<float>() + (size_t)i * n;
     in.pow10 = w.pow10.as<Pow10Entry>();
-    in.n_fam = nf;
     in.n_rows = n_rows;
     uint64_t *lens = w.lens.as<uint64_t>(), *offsets = w.offsets.as<uint64_t>();
     sdtable_lengths_kernel<<<blocks_for((uint64_t)n_rows + 1), 256, 0, s>>>(in, w.fam.as<uint32_t>(), w.half_at.as<uint32_t>(),
                                                                           lens);
     HIP_TRY(hipGetLastError());
     RC_TRY(w.exclusive_scan(lens, offsets, (size_t)n_rows + 1));
-    HIP_TRY(hipEventRecord(w.ev[2], s));
-    uint64_t body = 0;
-    HIP_TRY(read_back(&body, offsets + n_rows, 8, s));
-    res->size = prefix_len + body;
-    RC_TRY(res->file.reserve(std::max<size_t>(res->size, 16)));
-    uint8_t *file = res->file.as<uint8_t>();
-    HIP_TRY(hipEventRecord(w.ev[3], s));
-    if (prefix_len) HIP_TRY(hipMemcpyAsync(file, prefix, prefix_len, hipMemcpyHostToDevice, s));
+    RC_TRY(w.stamp(w.kPlaced));
+    RC_TRY(w.frame_file(res, offsets + n_rows, prefix, prefix_len, nullptr, 0));
     sdtable_write_kernel<<<blocks_for(n_rows, kRows), kThreads, 0, s>>>(in, w.fam.as<uint32_t>(), w.half_at.as<uint32_t>(),
-                                                                       offsets, prefix_len, file);
+                                                                       offsets, prefix_len, res->file.as<uint8_t>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(w.ev[4], s));
-    HIP_TRY(stream_sync(s));
-    float up = 0, a = 0, b = 0;
-    HIP_TRY(hipEventElapsedTime(&up, w.ev[0], w.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&a, w.ev[1], w.ev[2]));
-    HIP_TRY(hipEventElapsedTime(&b, w.ev[3], w.ev[4]));
-    res->ms[0] = up;
-    res->ms[1] = (double)a + (double)b;
-    return 0;
+    RC_TRY(w.stamp(w.kWritten));
+    return w.finish(res);
 }
 
 }  // namespace
@@ -168,8 +120,9 @@ extern "C" int32_t asgart_sdtable_records(int32_t device, const uint64_t *fam_of
                                           const float *frac_match, const float *frac_match_indel, const float *jc_k,
                                           const float *k2_k, const uint8_t *prefix, uint64_t prefix_len, asgart_export **out) {
     if (out) *out = nullptr;
-    if (!out || !fam_offsets || n_families < 0 || n_sd < 0 || n_names < 0 || !name_offsets || (prefix_len && !prefix) ||
-        (n_sd && (!sds || !flags || !status || !chr || !chr_pos || !counts || !frac_match || !frac_match_indel || !jc_k || !k2_k))) {
+    const ResultArg a{fam_offsets, n_families, sds, flags, chr, chr_pos, n_sd, name_bytes, name_offsets, n_names};
+    if (!out || a.missing() || (prefix_len && !prefix) ||
+        (n_sd && (!status || !counts || !frac_match || !frac_match_indel || !jc_k || !k2_k))) {
         set_error("%s: bad argument", kWho);
         return ASGART_E_ARG;
     }
@@ -177,17 +130,14 @@ extern "C" int32_t asgart_sdtable_records(int32_t device, const uint64_t *fam_of
         set_error("%s: 2^31 rows (or families) and more are not supported", kWho);
         return ASGART_E_CAP;
     }
-    RC_TRY(check_csr(kWho, "fam_offsets", fam_offsets, n_families, n_sd, "n_sd"));
-    RC_TRY(check_name_table(kWho, name_bytes, name_offsets, n_names));
-    RC_TRY(check_name_ids(kWho, chr, n_sd, n_names));
+    RC_TRY(check_result_arg(kWho, a));
     std::vector<uint32_t> kept;
     RC_TRY(check_strand_rows(kWho, sds, flags, status, chr_pos, n_sd, kept));
     RC_TRY(use_device(kWho, device));
     const float *const figures[4] = {frac_match, frac_match_indel, jc_k, k2_k};
     return run_tool<SdTableWork>(out, [&](SdTableWork &w, asgart_export *res) {
         res->device = device;
-        return run_sdtable(w, res, fam_offsets, (uint32_t)n_families, sds, flags, chr, chr_pos, (uint32_t)n_sd, name_bytes,
-                           name_offsets, (size_t)n_names, counts, figures, prefix, prefix_len, kept);
+        return run_sdtable(w, res, a, counts, figures, prefix, prefix_len, kept);
     });
 }
 

@@ -11,19 +11,12 @@
 
 namespace asgart {
 
-struct SdTableIn {
-    const uint64_t *offs;      // [n_fam + 1]
-    const uint64_t *sds;       // [n][4]: global left, global right, left_length, right_length
-    const uint8_t *flags;      // [n]: 0 `+`, 3 `-`
-    const int32_t *chr;        // [n][2] name ids
-    const uint64_t *chr_pos;   // [n][2]
-    const uint8_t *names;      // the bytes of all names
-    const uint64_t *name_off;  // [n_names + 1]
+struct SdTableIn : ResultView {   // (flags: 0 `+`, 3 `-`)
     const uint32_t *kept;      // [n_rows]: the duplications with a row, ascending
     const uint64_t *counts;    // [n][10]: asgart_align_counts
     const float *figures[4];   // [n] each: fracMatch, fracMatchIndel, jcK, k2K
     const Pow10Entry *pow10;
-    uint32_t n_fam, n_rows;
+    uint32_t n_rows;
 };
 
 // half 0 or 1 of the row of duplication q, of family fam

@@ -1,6 +1,6 @@
-// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, export.hip, paf.hip, alnstats.hip, sdtable.hip) are built on: the device check of an
-// entry point, the device work of one call (ToolWork: stream, events, every device buffer, the rocPRIM two-call wrappers),
-// the host checks of offset arrays and name ids, the bisection of an offset array on the device, and the tail of an entry
+// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, groups.hip, alnstats.hip and, through
+// file_writer.hpp, the file writers export.hip, paf.hip and sdtable.hip) are built on: the device check of an entry point,
+// the device work of one call (ToolWork: stream, events, every device buffer, the rocPRIM two-call wrappers), the host checks of offset arrays and name ids, the bisection of an offset array on the device, and the tail of an entry
 // point.  extract.hip, fasta.hip and prep.hip take use_device from here.
 #pragma once
 
@@ -118,7 +118,7 @@ inline int32_t check_name_ids(const char *who, const int32_t *chr, int64_t n_sd,
     return 0;
 }
 
-// the name table of the PAF and table writers: offsets from 0, never decreasing, below 2^30 bytes of names
+// the name table of the file writers: offsets from 0, never decreasing, below 2^30 bytes of names
 inline int32_t check_name_table(const char *who, const uint8_t *name_bytes, const uint64_t *name_offsets, int64_t n_names) {
     if (name_offsets[0] != 0 || (name_offsets[n_names] && !name_bytes) || name_offsets[n_names] >= ((uint64_t)1 << 30)) {
         set_error("%s: name_offsets must start at 0 and end below 2^30 bytes of names", who);
@@ -211,15 +211,3 @@ __global__ __launch_bounds__(kThreads) void family_offsets_kernel(const uint64_t
 }  // namespace
 
 }  // namespace asgart
-
-// The handle of a file written on the device (export.hip: asgart_export_records; paf.hip: asgart_paf_records);
-// asgart_export_size, _copy, _timings and _free (export.hip) work on it whichever call made it.
-struct asgart_export {
-    int32_t device = 0;
-    asgart::DevBuf file;  // the whole file, on the device
-    uint64_t size = 0;
-    double ms[3] = {0, 0, 0};
-    ~asgart_export() {
-        if (file.p && hipSetDevice(device) == hipSuccess) file.release();
-    }
-};

@@ -121,6 +121,35 @@ def test_a_name_longer_than_the_image(hiplib):
     assert len(text.splitlines()[RECORDS + 6]) > STAGE
 
 
+def residue_case():
+    """2 * RECORDS + 3 rows (three workgroups, the last one partial) with short names and, in the middle workgroup, one name
+    longer than the image -> the arguments of asgart_amd.sdtable_records up to the prefix, and the rows the host writes."""
+    from asgart_amd.postprocess import locate_arms
+
+    rng = np.random.default_rng(89)
+    n = 2 * RECORDS + 3
+    offs, sds, flags, counts = random_case(rng, n)
+    sds[:, :2] %= 100_000
+    sds[RECORDS + 5, 1] = 120_000
+    strand = asgart_amd.Strand("f", None, [Start("chr1", 0, 100_000), Start("L" * (STAGE + 100), 100_000, 50_000)])
+    rows = align.sd_table_text(offs, sds, flags, strand, statuses(np.ones(n, np.uint8)), counts)[len(align.SD_TABLE_HEADER):]
+    names = [c.name.encode("utf-8") for c in strand.map] + [b"unknown"]
+    chr_, chr_pos = locate_arms(sds, strand)
+    return (offs, sds, flags, np.ones(n, np.uint8), chr_, chr_pos, names, counts, align.divergence(counts)), rows.encode("utf-8")
+
+
+def test_every_residue_of_the_first_store(hiplib):
+    """A prefix of 0 to 16 bytes in place of the header: the body starts at every offset within a 16-byte line, so the first
+    shared line of every workgroup's range (file_writer.hpp: copy_out_image) falls on every residue, next to a range that
+    is stored directly."""
+    arguments, rows = residue_case()
+    assert rows.count(b"\n") == 2 * RECORDS + 3 and len(rows.splitlines()[RECORDS + 5]) > STAGE
+    for k in range(17):
+        prefix = b"#123456789abcdef\n"[:k]
+        got = asgart_amd.sdtable_records(*arguments, prefix).tobytes()
+        assert got == prefix + rows, (k, len(got), len(prefix) + len(rows))
+
+
 def test_an_empty_table_is_the_header(hiplib):
     none = asgart_amd.AlignCounts(np.zeros((0, 10), np.uint64))
     assert same([0], np.zeros((0, 4), np.uint64), np.zeros(0, np.uint8), none) == align.SD_TABLE_HEADER.encode()
