@@ -69,6 +69,8 @@ ABI_SYMBOLS = (
     "asgart_paf_records", "asgart_paf_geometry", "asgart_paf_records_cs", "asgart_paf_cs_geometry",
     "asgart_index_read_text",
     "asgart_alignment_stats", "asgart_alignment_stats_geometry", "asgart_sdtable_records", "asgart_sdtable_geometry",
+    "asgart_mask_intervals", "asgart_mask_counts", "asgart_mask_copy", "asgart_mask_timings", "asgart_mask_free",
+    "asgart_mask_geometry", "asgart_fasta_write", "asgart_fasta_write_geometry",
 )
 
 
@@ -406,6 +408,24 @@ def load_library() -> C.CDLL:
         L.asgart_sdtable_records.restype = C.c_int32
         L.asgart_sdtable_geometry.argtypes = [u64p, u64p, u64p]
         L.asgart_sdtable_geometry.restype = None
+    if hasattr(L, "asgart_mask_intervals"):
+        L.asgart_mask_intervals.argtypes = [C.c_int32, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_uint64, C.c_uint32,
+                                            C.POINTER(vp)]
+        L.asgart_mask_intervals.restype = C.c_int32
+        L.asgart_mask_counts.argtypes = [vp, u64p, u64p, u64p]
+        L.asgart_mask_counts.restype = None
+        L.asgart_mask_copy.argtypes = [vp, vp]
+        L.asgart_mask_copy.restype = None
+        L.asgart_mask_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_mask_timings.restype = C.c_int32
+        L.asgart_mask_free.argtypes = [vp]
+        L.asgart_mask_free.restype = None
+        L.asgart_mask_geometry.argtypes = [u64p]
+        L.asgart_mask_geometry.restype = None
+        L.asgart_fasta_write.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        L.asgart_fasta_write.restype = C.c_int32
+        L.asgart_fasta_write_geometry.argtypes = [u64p, u64p, u64p]
+        L.asgart_fasta_write_geometry.restype = None
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []

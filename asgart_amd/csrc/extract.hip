@@ -229,6 +229,13 @@ int32_t source_adopt(DevBuf &text, uint64_t n, int32_t device, asgart_source **o
     return 0;
 }
 
+// What a reader of the raw strand needs of a source (fasta_write.hip): its device, its bytes and where they are.
+void source_view(const asgart_source *src, int32_t *device, uint64_t *n, const uint8_t **text) {
+    *device = src->device;
+    *n = src->n;
+    *text = src->text.as<uint8_t>();
+}
+
 }  // namespace asgart
 
 namespace {

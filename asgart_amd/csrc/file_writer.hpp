@@ -8,7 +8,7 @@
 #include "tool_base.hpp"
 
 // The handle of a file written on the device (asgart_export_records, asgart_paf_records, asgart_paf_records_cs,
-// asgart_sdtable_records); asgart_export_size, _copy, _timings and _free (export.hip) work on it whichever call made it.
+// asgart_sdtable_records, asgart_fasta_write); asgart_export_size, _copy, _timings and _free (export.hip) work on it whichever call made it.
 struct asgart_export {
     int32_t device = 0;
     asgart::DevBuf file;  // the whole file, on the device

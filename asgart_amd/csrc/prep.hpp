@@ -33,5 +33,7 @@ int32_t index_over_text(const uint8_t *d_text, uint64_t n, int32_t device, asgar
 
 // extract.hip: a source (asgart_source) over n bytes that are on the device already; takes `text` over on success
 int32_t source_adopt(DevBuf &text, uint64_t n, int32_t device, asgart_source **out);
+// extract.hip: the device of a source, its n bytes and where they lie (read, not taken over)
+void source_view(const asgart_source *src, int32_t *device, uint64_t *n, const uint8_t **text);
 
 }  // namespace asgart

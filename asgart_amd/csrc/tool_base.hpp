@@ -1,5 +1,5 @@
-// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, groups.hip, alnstats.hip and, through
-// file_writer.hpp, the file writers export.hip, paf.hip and sdtable.hip) are built on: the device check of an entry point,
+// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, groups.hip, mask.hip, alnstats.hip and, through
+// file_writer.hpp, the file writers export.hip, paf.hip, sdtable.hip and fasta_write.hip) are built on: the device check of an entry point,
 // the device work of one call (ToolWork: stream, events, every device buffer, the rocPRIM two-call wrappers), the host checks of offset arrays and name ids, the bisection of an offset array on the device, and the tail of an entry
 // point.  extract.hip, fasta.hip and prep.hip take use_device from here.
 #pragma once

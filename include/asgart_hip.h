@@ -1049,6 +1049,66 @@ int32_t asgart_fasta_timings(const asgart_fasta *f, double *ms4);
  * staging piece, bytes per output store. */
 void asgart_fasta_geometry(uint64_t *tile_bytes, uint64_t *piece_bytes, uint64_t *vector_bytes);
 
+/* ---- masking: which bases the arms cover ----------------------------------------------------------------------
+ * From a result back to the genome: the bases of the strand that at least min_depth arms hold.  Nothing of the reference
+ * does this.  asgart_duplication_groups above folds the arms per NAME and counts no depth; here the arms lie on the strand.
+ * in: the arms in flatten order (arm 2q + side of duplication q): arm_record (ids into the record table), arm_start (the
+ * position WITHIN the record), arm_length; the record table record_start[n_records], record_len[n_records] in strand
+ * coordinates (asgart_fasta_copy's start and len); margin; min_depth >= 1.
+ * The rule.  With rs the start of its record, an arm covers the strand bases
+ *     [rs + (start > margin ? start - margin : 0),  rs + min(record_len, sat(start + length + margin))),
+ * sat saturating at 2^64 - 1: the margin never leaves the arm's own record.  depth(x) is the number of arms whose clipped
+ * range holds base x.  The result is the MAXIMAL RUNS of strand bases with depth >= min_depth: (start, end) pairs, sorted,
+ * disjoint and non-touching ([0,10) and [10,20) at depth 1 are one run, and nothing at depth 2).  A run may cross a record
+ * start when both sides are covered; a caller that needs records splits the runs there.  Also: the number of intervals,
+ * masked_bases = the sum of end - start, and max_depth = the largest depth anywhere.
+ * Checked on the host before anything is launched (ASGART_E_ARG, the message names the first offender): NULL arrays with a
+ * positive count, a negative count, min_depth == 0, records that are not ascending and non-overlapping (or wrap), a record
+ * id outside the table, an arm of length 0, arm_start + arm_length > record_len (the arm leaves its record: the result does
+ * not belong to these records).  n_arms >= 2^31: ASGART_E_CAP; no usable device: ASGART_E_HIP.  n_arms == 0 succeeds with
+ * no intervals.  No device memory is held once the call has returned.  Every copy target is nullable. */
+typedef struct asgart_mask asgart_mask;
+int32_t asgart_mask_intervals(int32_t device, const int32_t *arm_record, const uint64_t *arm_start,
+                              const uint64_t *arm_length, int64_t n_arms, const uint64_t *record_start,
+                              const uint64_t *record_len, int64_t n_records, uint64_t margin, uint32_t min_depth,
+                              asgart_mask **out);
+void asgart_mask_counts(const asgart_mask *r, uint64_t *n_intervals, uint64_t *masked_bases, uint64_t *max_depth);
+/* intervals[2 * n_intervals]: start, end of every run. */
+void asgart_mask_copy(const asgart_mask *r, uint64_t *intervals);
+/* Milliseconds of the call behind r: [0] the upload, [1] the kernels from the first to the last, [2] the copy back; HIP
+ * events for the first two.  ASGART_E_ARG for a NULL argument. */
+int32_t asgart_mask_timings(const asgart_mask *r, double *ms3);
+void asgart_mask_free(asgart_mask *r);
+/* Threads per workgroup of the kernels behind asgart_mask_intervals, for tests that place their counts on the seams. */
+void asgart_mask_geometry(uint64_t *block_threads);
+
+/* ---- FASTA files written on the GPU ---------------------------------------------------------------------------
+ * The strand back as a file, with the bases inside the intervals masked.  src is read, not taken over: the raw strand on
+ * its device (asgart_fasta_source or asgart_source_create).  record_start / record_len as for asgart_mask_intervals;
+ * header_bytes and header_offsets[n_records + 1] are the header lines (header r is printed verbatim and followed by '\n':
+ * the '>' is the caller's, a trailing '\r' should be left out); intervals[2 * n_intervals] are (start, end) pairs of strand
+ * bases, ascending and disjoint (what asgart_mask_intervals gives, or any others); width = bases per line, 0 = the whole
+ * record on one line; fill = 0 masks softly (a byte 'A'..'Z' inside an interval becomes byte | 0x20, every other byte
+ * stays), any other value replaces every byte inside an interval.  Bytes outside the intervals are the source's, so
+ * soft-masking that was there survives.
+ * The file, record by record: the header, '\n', then the record's bytes in lines of `width` bases, each followed by '\n';
+ * the last line may be shorter, an empty record has no sequence line, and there is no blank line when len is a multiple of
+ * width.  The body of a record of len bases is len + ceil(len / width) bytes (width 0: len + 1, or 0 when len is 0); base b
+ * sits at body offset b + b / width; body offset o is a '\n' iff o mod (width + 1) == width or o is the body's last byte,
+ * and otherwise base o - o / (width + 1).  Sizes and offsets are 64-bit throughout.
+ * out: an asgart_export; asgart_export_size, _copy, _timings ([0] upload, [1] the write kernel, [2] the last copy) and
+ * _free work on it as on the other writers' handles.
+ * Checked on the host before anything is launched (ASGART_E_ARG, naming the first offender): NULL or negative arguments, a
+ * header that holds '\n', header_offsets not starting at 0 or decreasing, records not ascending, overlapping or past the
+ * source's bytes, intervals that are empty, not ascending, overlapping or past the source's bytes, fill above 255 or equal
+ * to '\n', '\r' or '>'.  More than 2^24 records or 2^32 intervals: ASGART_E_CAP; no usable device: ASGART_E_HIP. */
+int32_t asgart_fasta_write(asgart_source *src, const uint64_t *record_start, const uint64_t *record_len, int64_t n_records,
+                           const uint8_t *header_bytes, const uint64_t *header_offsets, const uint64_t *intervals,
+                           int64_t n_intervals, uint32_t width, uint32_t fill, asgart_export **out);
+/* Sizes the write stage of asgart_fasta_write works in, for tests that place their bytes on the seams: threads per
+ * workgroup, bytes of the file per workgroup (a window, and the LDS image of it), bytes per store of the copy out. */
+void asgart_fasta_write_geometry(uint64_t *block_threads, uint64_t *window_bytes, uint64_t *store_bytes);
+
 /* ---- finer-grained entry points mirroring the reference's inner API;
  *      used by the parity tests ------------------------------------------ */
 
