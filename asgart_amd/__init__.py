@@ -28,6 +28,8 @@ __all__ = [
     "ResultScan", "result_geometry", "E_REFUSED", "Alignments", "align_geometry", "align_bytes", "align_bytes_banded",
     "paf_records", "paf_geometry", "paf_records_cs", "paf_cs_geometry", "CS_MODES",
     "AlignCounts", "alignment_stats_geometry", "sdtable_records", "sdtable_geometry",
+    "Variants", "Sites", "SiteArrays", "VARIANT_DTYPE", "SITE_CLASSES", "variants_geometry", "sites_geometry",
+    "variants_records_geometry", "sites_records_geometry",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -71,6 +73,11 @@ ABI_SYMBOLS = (
     "asgart_alignment_stats", "asgart_alignment_stats_geometry", "asgart_sdtable_records", "asgart_sdtable_geometry",
     "asgart_mask_intervals", "asgart_mask_counts", "asgart_mask_copy", "asgart_mask_timings", "asgart_mask_free",
     "asgart_mask_geometry", "asgart_fasta_write", "asgart_fasta_write_geometry",
+    "asgart_alignment_variants", "asgart_variants_counts", "asgart_variants_copy", "asgart_variants_timings",
+    "asgart_variants_free", "asgart_variants_geometry",
+    "asgart_variant_sites", "asgart_sites_counts", "asgart_sites_copy", "asgart_sites_timings", "asgart_sites_free",
+    "asgart_sites_geometry",
+    "asgart_variants_records", "asgart_sites_records", "asgart_variants_records_geometry", "asgart_sites_records_geometry",
 )
 
 
@@ -426,6 +433,34 @@ def load_library() -> C.CDLL:
         L.asgart_fasta_write.restype = C.c_int32
         L.asgart_fasta_write_geometry.argtypes = [u64p, u64p, u64p]
         L.asgart_fasta_write_geometry.restype = None
+    if hasattr(L, "asgart_alignment_variants"):
+        L.asgart_alignment_variants.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp, C.POINTER(vp)]
+        L.asgart_alignment_variants.restype = C.c_int32
+        L.asgart_variants_counts.argtypes = [vp, u64p, u64p, u64p]
+        L.asgart_variants_counts.restype = None
+        L.asgart_variants_copy.argtypes = [vp, vp, vp]
+        L.asgart_variants_copy.restype = C.c_int32
+        L.asgart_variant_sites.argtypes = [vp, C.POINTER(vp)]
+        L.asgart_variant_sites.restype = C.c_int32
+        L.asgart_sites_counts.argtypes = [vp, u64p, u64p]
+        L.asgart_sites_counts.restype = None
+        L.asgart_sites_copy.argtypes = [vp] * 7
+        L.asgart_sites_copy.restype = C.c_int32
+        for name in ("variants", "sites"):
+            timings, free = getattr(L, f"asgart_{name}_timings"), getattr(L, f"asgart_{name}_free")
+            timings.argtypes = [vp, C.POINTER(C.c_double)]
+            timings.restype = C.c_int32
+            free.argtypes = [vp]
+            free.restype = None
+            records, geometry = getattr(L, f"asgart_{name}_records"), getattr(L, f"asgart_{name}_records_geometry")
+            records.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_uint64, C.POINTER(vp)]
+            records.restype = C.c_int32
+            geometry.argtypes = [u64p, u64p, u64p]
+            geometry.restype = None
+        L.asgart_variants_geometry.argtypes = [u64p, u64p]
+        L.asgart_variants_geometry.restype = None
+        L.asgart_sites_geometry.argtypes = [u64p]
+        L.asgart_sites_geometry.restype = None
     L.asgart_last_error.argtypes = []
     L.asgart_last_error.restype = C.c_char_p
     L.asgart_version.argtypes = []
@@ -762,21 +797,8 @@ class Index:
         if not hasattr(L, "asgart_alignment_stats"):
             raise AsgartError(-3, f"{library_path()} has no asgart_alignment_stats: rebuild it; there is no host fallback "
                                   "behind this call (align.stats_host is the host statement)")
-        sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
-        flags = _score_flags(flags, len(sds))
-        if flags is None:
-            flags = np.zeros(len(sds), dtype=np.uint8)
-        status = np.ascontiguousarray(aln.status, dtype=np.uint8).reshape(-1)
-        run_offsets = np.ascontiguousarray(aln.run_offsets, dtype=np.uint64).reshape(-1)
-        run_len = np.ascontiguousarray(aln.run_len, dtype=np.uint32).reshape(-1)
-        run_op = np.ascontiguousarray(aln.run_op, dtype=np.uint8).reshape(-1)
+        sds, flags, status, run_offsets, run_len, run_op = _alignment_arrays("alignment_stats", sds, flags, aln)
         n = len(sds)
-        if len(status) != n or len(run_offsets) != n + 1 or len(run_len) != len(run_op):
-            raise ValueError("alignment_stats: the arrays differ in length")
-        if len(run_len) < int(run_offsets[-1]) < 1 << 32:   # (2^32 runs and more are the library's to refuse, unread)
-            raise ValueError(f"alignment_stats: run_offsets end at {int(run_offsets[-1])}, there are {len(run_len)} runs")
-        if len(run_len) == 0:
-            run_len, run_op = np.zeros(1, np.uint32), np.zeros(1, np.uint8)
         out = np.zeros((n, len(AlignCounts.FIELDS)), dtype=np.uint64)
         ms = (C.c_double * 3)()
         _check(L.asgart_alignment_stats(self._h, _ptr(sds), _ptr(flags), _ptr(status), n, _ptr(run_offsets), _ptr(run_len),
@@ -784,6 +806,25 @@ class Index:
         if timings is not None:
             timings[:] = list(ms)
         return AlignCounts(out)
+
+    def variants(self, sds: np.ndarray, flags: Optional[np.ndarray], aln: "Alignments",
+                 timings: Optional[list] = None) -> "Variants":
+        """The variants between the arms of every aligned duplication (asgart_alignment_variants; include/asgart_hip.h states
+        the rule, align.variants_host is the readable form): one record per base of an `X` run and per `I` or `D` run, global
+        forward-strand coordinates.  sds, flags and aln as alignment_stats takes them.  The records stay on the device of the
+        index behind the Variants handle (sites() and the device writers of align read them there); records() copies them.
+        timings: a list that receives the milliseconds of upload, kernels and copy back."""
+        L = load_library()
+        if not hasattr(L, "asgart_alignment_variants"):
+            raise AsgartError(-3, f"{library_path()} has no asgart_alignment_variants: rebuild it; there is no host fallback "
+                                  "behind this call (align.variants_host is the host statement)")
+        sds, flags, status, run_offsets, run_len, run_op = _alignment_arrays("variants", sds, flags, aln)
+        h = C.c_void_p()
+        _check(L.asgart_alignment_variants(self._h, _ptr(sds), _ptr(flags), _ptr(status), len(sds), _ptr(run_offsets),
+                                           _ptr(run_len), _ptr(run_op), C.byref(h)))
+        out = Variants(h)
+        _read_timings(L.asgart_variants_timings, h, timings)
+        return out
 
     def compute_scores_flags_shard(self, sds: np.ndarray, flags: Optional[np.ndarray], shard: int = 0,
                                    n_shards: int = 1) -> np.ndarray:
@@ -937,6 +978,194 @@ def alignment_stats_geometry() -> Tuple[int, int]:
     a, b = C.c_uint64(), C.c_uint64()
     load_library().asgart_alignment_stats_geometry(C.byref(a), C.byref(b))
     return int(a.value), int(b.value)
+
+
+def _alignment_arrays(who: str, sds, flags, aln: "Alignments"):
+    """What Index.alignment_stats and Index.variants share on the way in -> (sds, flags, status, run_offsets, run_len,
+    run_op) as the library takes them."""
+    sds = np.ascontiguousarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = _score_flags(flags, len(sds))
+    if flags is None:
+        flags = np.zeros(len(sds), dtype=np.uint8)
+    status = np.ascontiguousarray(aln.status, dtype=np.uint8).reshape(-1)
+    run_offsets = np.ascontiguousarray(aln.run_offsets, dtype=np.uint64).reshape(-1)
+    run_len = np.ascontiguousarray(aln.run_len, dtype=np.uint32).reshape(-1)
+    run_op = np.ascontiguousarray(aln.run_op, dtype=np.uint8).reshape(-1)
+    n = len(sds)
+    if len(status) != n or len(run_offsets) != n + 1 or len(run_len) != len(run_op):
+        raise ValueError(f"{who}: the arrays differ in length")
+    if len(run_len) < int(run_offsets[-1]) < 1 << 32:   # (2^32 runs and more are the library's to refuse, unread)
+        raise ValueError(f"{who}: run_offsets end at {int(run_offsets[-1])}, there are {len(run_len)} runs")
+    if len(run_len) == 0:
+        run_len, run_op = np.zeros(1, np.uint32), np.zeros(1, np.uint8)
+    return sds, flags, status, run_offsets, run_len, run_op
+
+
+# asgart_variant, as a numpy record: 32 bytes
+VARIANT_DTYPE = np.dtype([("left_pos", "<u8"), ("right_pos", "<u8"), ("left_len", "<u4"), ("right_len", "<u4"), ("sd", "<u4"),
+                          ("op", "u1"), ("left_base", "u1"), ("right_base", "u1"), ("flag", "u1")])
+SITE_CLASSES = "ACGTN"   # the classes of a site's ref and the bits of its alt_mask, in order
+
+
+@dataclass
+class SiteArrays:
+    """The arrays of asgart_sites_copy (and of align.sites_host), one entry per site in ascending position: pos uint64; ref
+    uint8, a class (an index into SITE_CLASSES); alt_mask uint8, bit c for class c; pairs uint32, the number of entries;
+    sd uint32 and side uint8 (0 left, 1 right) of the first entry."""
+
+    pos: np.ndarray
+    ref: np.ndarray
+    alt_mask: np.ndarray
+    pairs: np.ndarray
+    sd: np.ndarray
+    side: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.pos)
+
+    def __eq__(self, other):
+        return isinstance(other, SiteArrays) and all(
+            a.dtype == b.dtype and np.array_equal(a, b) for a, b in zip(self.columns(), other.columns()))
+
+    def columns(self):
+        return self.pos, self.ref, self.alt_mask, self.pairs, self.sd, self.side
+
+
+class _Handle:
+    """A result handle of the library that stays alive until close() (or the end of a `with`, or collection)."""
+
+    _free = ""
+
+    def __init__(self, h):
+        self._h = h
+
+    def close(self) -> None:
+        if self._h:
+            getattr(load_library(), self._free)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _rows_file(call, who: str, h, offs, sds, flags, chr_, chr_pos, names: Sequence[bytes], prefix: bytes,
+               timings: Optional[list]) -> np.ndarray:
+    """What the two device writers of the variants share: the result arrays as the library takes them, the call, the file."""
+    offs, sds, flags, chr_, chr_pos, name_bytes, name_off = _result_arrays(who, offs, sds, flags, chr_, chr_pos, names)
+    pre = np.frombuffer(prefix or b"\0", dtype=np.uint8)
+    out = C.c_void_p()
+    _check(call(h, _ptr(offs), len(offs) - 1, _ptr(sds), _ptr(flags), _ptr(chr_), _ptr(chr_pos), len(sds), _ptr(name_bytes),
+                _ptr(name_off), len(names), _ptr(pre), len(prefix), C.byref(out)))
+    return _written_file(out, timings)
+
+
+class Variants(_Handle):
+    """The records of Index.variants, on the device (asgart_variants): n_sd, n_variants, n_snv; records() and var_offsets()
+    copy them; sites() makes the sites of the `X` records; table() writes the pair table on the device."""
+
+    _free = "asgart_variants_free"
+
+    def __init__(self, h):
+        super().__init__(h)
+        v = [C.c_uint64() for _ in range(3)]
+        load_library().asgart_variants_counts(h, *[C.byref(x) for x in v])
+        self.n_sd, self.n_variants, self.n_snv = (int(x.value) for x in v)
+
+    def __len__(self) -> int:
+        return self.n_variants
+
+    def records(self) -> np.ndarray:
+        """The records as a VARIANT_DTYPE array."""
+        out = np.zeros(self.n_variants, dtype=VARIANT_DTYPE)
+        _check(load_library().asgart_variants_copy(self._h, _ptr(out) if len(out) else None, None))
+        return out
+
+    def var_offsets(self) -> np.ndarray:
+        out = np.zeros(self.n_sd + 1, dtype=np.uint64)
+        _check(load_library().asgart_variants_copy(self._h, None, _ptr(out)))
+        return out
+
+    def sites(self, timings: Optional[list] = None) -> "Sites":
+        """asgart_variant_sites: the distinct positions the `X` records touch, on the device."""
+        L = load_library()
+        h = C.c_void_p()
+        _check(L.asgart_variant_sites(self._h, C.byref(h)))
+        out = Sites(h)
+        _read_timings(L.asgart_sites_timings, h, timings)
+        return out
+
+    def table(self, offs, sds, flags, chr_, chr_pos, names: Sequence[bytes], prefix: bytes,
+              timings: Optional[list] = None) -> np.ndarray:
+        """asgart_variants_records: the pair table as uint8[size]; the arrays as sdtable_records takes them."""
+        return _rows_file(load_library().asgart_variants_records, "variants_records", self._h, offs, sds, flags, chr_,
+                          chr_pos, names, prefix, timings)
+
+
+class Sites(_Handle):
+    """The sites of Variants.sites, on the device (asgart_sites): n_sites, n_entries; arrays() copies them; vcf() writes
+    the VCF body rows on the device."""
+
+    _free = "asgart_sites_free"
+
+    def __init__(self, h):
+        super().__init__(h)
+        a, b = C.c_uint64(), C.c_uint64()
+        load_library().asgart_sites_counts(h, C.byref(a), C.byref(b))
+        self.n_sites, self.n_entries = int(a.value), int(b.value)
+
+    def __len__(self) -> int:
+        return self.n_sites
+
+    def arrays(self) -> SiteArrays:
+        n = self.n_sites
+        out = SiteArrays(np.zeros(n, np.uint64), np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint32),
+                         np.zeros(n, np.uint32), np.zeros(n, np.uint8))
+        if n:
+            _check(load_library().asgart_sites_copy(self._h, *[_ptr(c) for c in out.columns()]))
+        return out
+
+    def vcf(self, offs, sds, flags, chr_, chr_pos, names: Sequence[bytes], prefix: bytes,
+            timings: Optional[list] = None) -> np.ndarray:
+        """asgart_sites_records: the caller's header and one VCF row per site as uint8[size]."""
+        return _rows_file(load_library().asgart_sites_records, "sites_records", self._h, offs, sds, flags, chr_, chr_pos,
+                          names, prefix, timings)
+
+
+def variants_geometry() -> Tuple[int, int]:
+    """asgart_variants_geometry: threads per workgroup, records per workgroup of the records kernel."""
+    a, b = C.c_uint64(), C.c_uint64()
+    load_library().asgart_variants_geometry(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
+
+
+def sites_geometry() -> int:
+    """asgart_sites_geometry: threads per workgroup of the site kernels."""
+    a = C.c_uint64()
+    load_library().asgart_sites_geometry(C.byref(a))
+    return int(a.value)
+
+
+def variants_records_geometry() -> Tuple[int, int, int]:
+    """asgart_variants_records_geometry: threads per workgroup, rows per workgroup, bytes of the LDS image."""
+    v = [C.c_uint64() for _ in range(3)]
+    load_library().asgart_variants_records_geometry(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
+def sites_records_geometry() -> Tuple[int, int, int]:
+    """asgart_sites_records_geometry: threads per workgroup, rows per workgroup, bytes of the LDS image."""
+    v = [C.c_uint64() for _ in range(3)]
+    load_library().asgart_sites_records_geometry(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
 
 
 def align_geometry() -> Tuple[int, int, int]:

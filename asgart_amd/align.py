@@ -17,6 +17,14 @@ This module states the same rule on the host, for the tests to compare byte for 
     divergence   fracMatch, fracMatchIndel and the Jukes-Cantor and Kimura distances from those counts
     sd_table_text        the duplication table, BEDPE and UCSC's genomicSuperDups columns: one row per aligned duplication
     sd_table_text_gpu    the same bytes, written on the GPU (asgart_sdtable_records, csrc/sdtable.hip)
+    variants_host        the variants between the arms, base by base: one record per `X` base and per `I` or `D` run, in
+                         global forward-strand coordinates (Index.variants takes them on the GPU: asgart_alignment_variants,
+                         csrc/variants.hip)
+    sites_host           the distinct positions the `X` records touch, per object; sites_numpy the same by argsort and
+                         reduceat (Variants.sites makes them on the GPU: asgart_variant_sites)
+    psv_table_text       the pair table of the variants; psv_vcf_text the site VCF under vcf_header; their _gpu forms are the
+                         same bytes, written on the GPU (asgart_variants_records, asgart_sites_records,
+                         csrc/variants_write.hip)
 
 The arms: A = text[left ..] is the left arm; B is the right arm as ProtoSD::levenshtein walks it (reference
 src/structs.rs:439-452): reversed if flag bit 0 is set, complemented if bit 1 is set (ACGT and acgt swap, anything else is
@@ -616,3 +624,256 @@ def sd_table_text_gpu(offs, sds, flags, strand, aln, counts, device: int = 0, st
     duplication, in the same order.  timings: a dict that receives the call's stages in milliseconds: names (locate, name
     table and figures), upload, kernels, copy."""
     return _sd_table_device(offs, sds, flags, strand, aln, counts, device, stderr, timings).tobytes()
+
+
+# ---- the variants between the copies: records, sites, the pair table and the site VCF -----------------------------------
+
+def variants_host(text, sds, flags, aln) -> np.ndarray:
+    """The variants of every alignment, base by base: what Index.variants (asgart_alignment_variants) must hold, as an array
+    of asgart_amd.VARIANT_DTYPE.  text, sds, flags and aln as stats_host takes them, in its frame; all four flag values are
+    legal and a duplication whose status is not 1 has no records and is not read.  Run t of duplication (left, right, ll,
+    rl) starts at the arm offsets i and j; with rev = flag & 1, in global forward-strand half-open coordinates:
+        `X`, base v     left [left + i + v, +1)    right [p, p + 1), p = right + (rl - 1 - (j + v) if rev else j + v)
+        `I`, n bases    left [left + i, +n)        right empty at right + (rl - j if rev else j)
+        `D`, n bases    left empty at left + i     right [right + (rl - j - n if rev else j), +n)
+    left_base / right_base are the text's bytes as stored at the two positions of an `X` record, 0 for an indel.  One
+    record per base of an `X` run and one per `I` or `D` run, in the order of the duplications, the runs, the bases.
+    ValueError as stats_host raises it."""
+    from . import VARIANT_DTYPE
+
+    text = np.frombuffer(bytes(text), dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.zeros(len(sds), dtype=np.uint8) if flags is None else np.asarray(flags, dtype=np.uint8).reshape(-1)
+    rows = []
+    for q, (left, right, ll, rl) in enumerate(sds.tolist()):
+        if aln.status[q] != 1:
+            continue
+        if left + ll > len(text) or right + rl > len(text):
+            raise ValueError("the duplication reaches past the end of the text")
+        flag = int(flags[q])
+        rev = flag & 1
+        i = j = 0
+        for n, op in aln.ops(q):
+            n = int(n)
+            if op not in ("=", "X", "I", "D"):
+                raise ValueError(f"duplication {q}: unknown operation `{op}`")
+            if n <= 0:
+                raise ValueError(f"duplication {q}: a run of {n} `{op}`")
+            if i + (n if op != "D" else 0) > ll or j + (n if op != "I" else 0) > rl:
+                raise ValueError(f"duplication {q}: `{n}{op}` at ({i}, {j}) runs past an arm: the runs do not consume arms "
+                                 f"of {ll} and {rl}")
+            if op == "X":
+                for v in range(n):
+                    lp = left + i + v
+                    rp = right + (rl - 1 - (j + v) if rev else j + v)
+                    rows.append((lp, rp, 1, 1, q, ord("X"), int(text[lp]), int(text[rp]), flag))
+            elif op == "I":
+                rows.append((left + i, right + (rl - j if rev else j), n, 0, q, ord("I"), 0, 0, flag))
+            elif op == "D":
+                rows.append((left + i, right + (rl - j - n if rev else j), 0, n, q, ord("D"), 0, 0, flag))
+            if op != "D":
+                i += n
+            if op != "I":
+                j += n
+        if i != ll or j != rl:
+            raise ValueError(f"duplication {q}: the runs consume {i} and {j} bases of arms of {ll} and {rl}")
+    return np.array(rows, dtype=VARIANT_DTYPE)
+
+
+def variant_offsets(variants: np.ndarray, n_sd: int) -> np.ndarray:
+    """var_offsets[n_sd + 1] of records in the order of their duplications: those of q are [var_offsets[q], var_offsets[q + 1])."""
+    return np.searchsorted(variants["sd"], np.arange(n_sd + 1), side="left").astype(np.uint64)
+
+
+def _site_class(b: int) -> int:
+    """0 A, 1 C, 2 G, 3 T with the case folded, 4 (N) for every other byte"""
+    return "ACGT".find(chr(b).upper()) if chr(b).upper() in "ACGT" else 4
+
+
+def site_entries(variants: np.ndarray):
+    """The entries of the `X` records, in record order, left before right -> [(pos, ref class, alt class, sd, side)].  An
+    `X` record makes (left_pos, ref = left_base, alt = o(right_base)) and (right_pos, ref = right_base, alt = o(left_base)),
+    o complementing when bit 1 of the record's flag is set; an entry exists only where class(ref) != class(alt)."""
+    out = []
+    for r in variants.tolist():
+        lp, rp, _, _, sd, op, lb, rb, flag = r
+        if op != ord("X"):
+            continue
+        o = (lambda b: int(_COMPLEMENT[b])) if flag & 2 else (lambda b: b)
+        for side, (pos, ref, alt) in enumerate(((lp, lb, o(rb)), (rp, rb, o(lb)))):
+            if _site_class(ref) != _site_class(alt):
+                out.append((pos, _site_class(ref), _site_class(alt), sd, side))
+    return out
+
+
+def sites_host(variants: np.ndarray):
+    """The sites of the records, in plain Python: what Variants.sites (asgart_variant_sites) must hold, as
+    asgart_amd.SiteArrays.  A site is a distinct position of an entry (site_entries); per site, in ascending position: ref,
+    the class of the text's byte there; alt_mask, a bit per alt class seen; pairs, the number of entries -- a duplication
+    whose arms overlap can hold one position in both arms and then counts twice --; (sd, side) of the first entry in record
+    order, left before right.  Indels make no sites."""
+    from . import SiteArrays
+
+    sites = {}
+    for pos, ref, alt, sd, side in site_entries(variants):
+        if pos not in sites:
+            sites[pos] = [ref, 0, 0, sd, side]
+        sites[pos][1] |= 1 << alt
+        sites[pos][2] += 1
+    order = sorted(sites)
+    col = lambda k, dt: np.array([sites[p][k] for p in order], dtype=dt)
+    return SiteArrays(np.array(order, dtype=np.uint64), col(0, np.uint8), col(1, np.uint8), col(2, np.uint32),
+                      col(3, np.uint32), col(4, np.uint8))
+
+
+_CLASS_OF = np.full(256, 4, dtype=np.uint8)
+for _k, _pair in enumerate(("Aa", "Cc", "Gg", "Tt")):
+    for _c in _pair:
+        _CLASS_OF[ord(_c)] = _k
+
+
+def sites_numpy(variants: np.ndarray):
+    """sites_host in numpy: the entries by masks, one stable argsort by position, np.add / np.bitwise_or.reduceat over the
+    sites.  The form the drivers' host writer runs."""
+    from . import SiteArrays
+
+    x = variants[variants["op"] == ord("X")]
+    comp = (x["flag"] & 2) != 0
+    lb, rb = x["left_base"], x["right_base"]
+    alt_l = _CLASS_OF[np.where(comp, _COMPLEMENT[rb], rb)]
+    alt_r = _CLASS_OF[np.where(comp, _COMPLEMENT[lb], lb)]
+    # entry 2k + side of record k: interleave left and right, then keep those whose classes differ
+    pos = np.stack([x["left_pos"], x["right_pos"]], axis=1).reshape(-1)
+    ref = np.stack([_CLASS_OF[lb], _CLASS_OF[rb]], axis=1).reshape(-1)
+    alt = np.stack([alt_l, alt_r], axis=1).reshape(-1)
+    sd = np.repeat(x["sd"], 2)
+    side = np.tile(np.array([0, 1], dtype=np.uint8), len(x))
+    keep = ref != alt
+    pos, ref, alt, sd, side = pos[keep], ref[keep], alt[keep], sd[keep], side[keep]
+    if len(pos) == 0:
+        z = lambda dt: np.zeros(0, dtype=dt)
+        return SiteArrays(z(np.uint64), z(np.uint8), z(np.uint8), z(np.uint32), z(np.uint32), z(np.uint8))
+    order = np.argsort(pos, kind="stable")
+    pos, ref, alt, sd, side = pos[order], ref[order], alt[order], sd[order], side[order]
+    heads = np.flatnonzero(np.concatenate([[True], pos[1:] != pos[:-1]]))
+    pairs = np.diff(np.concatenate([heads, [len(pos)]])).astype(np.uint32)
+    mask = np.bitwise_or.reduceat((1 << alt.astype(np.uint32)), heads).astype(np.uint8)
+    return SiteArrays(pos[heads].astype(np.uint64), ref[heads].astype(np.uint8), mask, pairs, sd[heads].astype(np.uint32),
+                      side[heads].astype(np.uint8))
+
+
+PSV_TABLE_COLUMNS = ("chrom1", "start1", "end1", "chrom2", "start2", "end2", "name", "op", "strand2", "family", "base1",
+                     "base2")
+PSV_TABLE_HEADER = "#" + "\t".join(PSV_TABLE_COLUMNS) + "\n"
+
+
+def _check_record_strands(flags, has_records) -> None:
+    """a duplication with records needs a strand, as a row of the duplication table does"""
+    for q in np.flatnonzero(has_records).tolist():
+        if flags[q] not in (0, 3):
+            raise _no_strand(q, int(flags[q]))
+
+
+def _psv_arrays(offs, sds, flags):
+    offs = np.asarray(offs, dtype=np.int64)
+    sds = np.asarray(sds, dtype=np.uint64).reshape(-1, 4)
+    flags = np.asarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != len(sds) or int(offs[-1]) != len(sds):
+        raise ValueError(f"{len(sds)} duplications, {len(flags)} flag bytes, families that end at {int(offs[-1])}")
+    return offs, sds, flags
+
+
+def psv_table_text(offs, sds, flags, strand, variants: np.ndarray) -> str:
+    """The pair table of the variants: a header line, `#` and the names of the 12 columns, then one tab-separated row per
+    record (variants_host or Variants.records()), in order.  offs / sds / flags / strand as sd_table_text takes them.
+        chrom1 start1 end1      the left interval: name and position resolved as paf_text resolves those of the arm, so
+        chrom2 start2 end2      local = the arm's local start + (global - the arm's global start); the right interval
+        name                    `sd<q>`;   op   X, I or D;   strand2  `+` for flag 0, `-` for flag 3;   family
+        base1 base2             the two bytes as stored for `X`, `.` for an indel
+    A reversed-only or complemented-only duplication with a record has no strand: paf_text's ValueError."""
+    offs, sds, flags = _psv_arrays(offs, sds, flags)
+    _check_record_strands(flags, np.bincount(variants["sd"], minlength=len(sds)) > 0)
+    locate = _locate(strand)
+    family = np.repeat(np.arange(len(offs) - 1), np.diff(offs))
+    arm = {}
+    rows = [PSV_TABLE_HEADER]
+    for lp, rp, ln, rn, q, op, lb, rb, flag in variants.tolist():
+        if q not in arm:
+            left, right = int(sds[q][0]), int(sds[q][1])
+            n1, _, p1 = locate(left)
+            n2, _, p2 = locate(right)
+            arm[q] = (n1, p1 - left, n2, p2 - right)
+        n1, d1, n2, d2 = arm[q]
+        x = op == ord("X")
+        rows.append("\t".join(str(v) for v in (
+            n1, lp + d1, lp + d1 + ln, n2, rp + d2, rp + d2 + rn, f"sd{q}", chr(op), "-" if flag == 3 else "+",
+            int(family[q]), chr(lb) if x else ".", chr(rb) if x else ".")) + "\n")
+    return "".join(rows)
+
+
+def vcf_header(strand) -> str:
+    """The header of the site VCF: the file format, one contig line per fragment of the strand's map, the NP INFO line and
+    the column line."""
+    lines = ["##fileformat=VCFv4.2"]
+    lines += [f"##contig=<ID={c.name},length={c.length}>" for c in strand.map]
+    lines.append('##INFO=<ID=NP,Number=1,Type=Integer,Description="Arm positions of aligned duplications that differ '
+                 'here from their partner arm">')
+    lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO")
+    return "".join(line + "\n" for line in lines)
+
+
+def psv_vcf_text(offs, sds, flags, strand, sites, variants: Optional[np.ndarray] = None) -> str:
+    """The site VCF: vcf_header(strand) and one row per site (sites_host, sites_numpy or Sites.arrays()), in ascending
+    global position: `name  pos+1  .  REF  ALT  .  .  NP=<pairs>`, name and pos from the arm (sd, side) of the site's first
+    entry, REF the class letter, ALT the mask's letters in the order A, C, G, T, N joined by `,`.  variants: the records
+    the sites were made from, when the strands of every duplication with a record are to be checked as the device writer
+    checks them; without them the duplications the sites name are."""
+    from . import SITE_CLASSES
+
+    offs, sds, flags = _psv_arrays(offs, sds, flags)
+    named = sites.sd if variants is None else variants["sd"]
+    _check_record_strands(flags, np.bincount(named, minlength=len(sds)) > 0)
+    locate = _locate(strand)
+    rows = [vcf_header(strand)]
+    for pos, ref, mask, pairs, q, side in zip(*(c.tolist() for c in sites.columns())):
+        start = int(sds[q][side])
+        name, _, p = locate(start)
+        alt = ",".join(SITE_CLASSES[c] for c in range(5) if mask >> c & 1)
+        rows.append(f"{name}\t{p + (pos - start) + 1}\t.\t{SITE_CLASSES[ref]}\t{alt}\t.\t.\tNP={pairs}\n")
+    return "".join(rows)
+
+
+def _psv_device_rows(offs, sds, flags, strand, var_offsets):
+    """What the two device writers of the variants share ahead of the library call: the checks of the host writers, the
+    name table (every map entry's name, then `unknown`) and the arms located."""
+    from .postprocess import locate_arms
+
+    offs, sds, flags = _psv_arrays(offs, sds, flags)
+    if len(var_offsets) != len(sds) + 1:
+        raise ValueError(f"{len(sds)} duplications, and the variants were called from {len(var_offsets) - 1}")
+    _check_record_strands(flags, np.diff(var_offsets.astype(np.int64)) > 0)
+    names = [c.name.encode("utf-8") for c in strand.map] + [b"unknown"]
+    chr_, chr_pos = locate_arms(sds, strand)
+    return offs, sds, flags, names, chr_, chr_pos
+
+
+def psv_table_text_gpu(offs, sds, flags, strand, variants, timings: Optional[dict] = None) -> bytes:
+    """psv_table_text(offs, sds, flags, strand, variants.records()).encode("utf-8"), written on the GPU from the Variants
+    handle of Index.variants (asgart_variants_records, csrc/variants_write.hip); the records never leave the device."""
+    offs, sds, flags, names, chr_, chr_pos = _psv_device_rows(offs, sds, flags, strand, variants.var_offsets())
+    ms: list = []
+    out = variants.table(offs, sds, flags, chr_, chr_pos, names, PSV_TABLE_HEADER.encode("ascii"), ms)
+    if timings is not None:
+        timings.update(upload=ms[0], kernels=ms[1], copy=ms[2])
+    return out.tobytes()
+
+
+def psv_vcf_text_gpu(offs, sds, flags, strand, sites, variants, timings: Optional[dict] = None) -> bytes:
+    """psv_vcf_text(offs, sds, flags, strand, sites.arrays(), variants.records()).encode("utf-8"), written on the GPU from
+    the Sites handle of variants.sites() (asgart_sites_records)."""
+    offs, sds, flags, names, chr_, chr_pos = _psv_device_rows(offs, sds, flags, strand, variants.var_offsets())
+    ms: list = []
+    out = sites.vcf(offs, sds, flags, chr_, chr_pos, names, vcf_header(strand).encode("utf-8"), ms)
+    if timings is not None:
+        timings.update(upload=ms[0], kernels=ms[1], copy=ms[2])
+    return out.tobytes()

@@ -149,53 +149,6 @@ struct StatsWork : ToolWork {
 
 const char kWho[] = "asgart_alignment_stats";
 
-int32_t check_arguments(const asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags, const uint8_t *status,
-                        int64_t n_sd, const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
-                        const asgart_align_counts *counts) {
-    if (!idx) {
-        set_error("%s: bad argument (no index: the bases are its text's)", kWho);
-        return ASGART_E_ARG;
-    }
-    if (n_sd < 0 || (n_sd && (!sds || !flags || !status || !run_offsets || !counts))) {
-        set_error("%s: bad argument", kWho);
-        return ASGART_E_ARG;
-    }
-    if (n_sd >= (int64_t)1 << 31) {
-        set_error("%s: 2^31 duplications and more are not supported", kWho);
-        return ASGART_E_CAP;
-    }
-    if (n_sd == 0) return 0;
-    const uint64_t n_runs = run_offsets[n_sd];
-    if (n_runs >= (uint64_t)1 << 32) {
-        set_error("%s: run_offsets end at %llu; 2^32 runs and more are not supported", kWho, (unsigned long long)n_runs);
-        return ASGART_E_CAP;
-    }
-    RC_TRY(check_csr(kWho, "run_offsets", run_offsets, n_sd, (int64_t)n_runs, "the run count", "duplication"));
-    if (n_runs && (!run_len || !run_op)) {
-        set_error("%s: bad argument (%llu runs and no run_len or run_op)", kWho, (unsigned long long)n_runs);
-        return ASGART_E_ARG;
-    }
-    const uint64_t n_text = (uint64_t)idx->n;
-    for (int64_t q = 0; q < n_sd; ++q) {
-        if (status[q] != 1) continue;
-        if (flags[q] & ~3u) {
-            set_error("%s: duplication %lld has flag byte %u (bit 0 reversed, bit 1 complemented)", kWho, (long long)q,
-                      (unsigned)flags[q]);
-            return ASGART_E_ARG;
-        }
-        const asgart_proto_sd &sd = sds[q];
-        if (sd.left > n_text || sd.right > n_text || sd.left_length > n_text - sd.left || sd.right_length > n_text - sd.right) {
-            set_error("%s: duplication %lld reaches past the end of the text", kWho, (long long)q);
-            return ASGART_E_ARG;
-        }
-        if (arms_too_long(sd)) {   // (the right arm is walked with lev_dev.hpp's 32-bit offsets)
-            set_error("%s: arms of 2^32 bases are not supported", kWho);
-            return ASGART_E_CAP;
-        }
-    }
-    return 0;
-}
-
 int32_t run_stats(StatsWork &w, const uint8_t *text, const asgart_proto_sd *sds, const uint8_t *flags, const uint8_t *status,
                   uint32_t n, const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
                   asgart_align_counts *counts, double *ms3) {
@@ -244,28 +197,7 @@ int32_t run_stats(StatsWork &w, const uint8_t *text, const asgart_proto_sd *sds,
     HIP_TRY(hipMemcpyAsync(in.bad + 1, in.X + n_runs, 8, hipMemcpyDeviceToDevice, s));
     uint64_t tail[2] = {0, 0};
     HIP_TRY(read_back(tail, in.bad, 16, s));
-    if (tail[0] != ~(uint64_t)0) {
-        const long long q = (long long)(tail[0] >> 2);
-        const uint64_t b = run_offsets[q], e = run_offsets[q + 1];
-        if ((tail[0] & 3) == kPafBadSums) {
-            uint64_t i = 0, j = 0;
-            for (uint64_t t = b; t < e; ++t) {
-                i += run_on_left(run_op[t], run_len[t]);
-                j += run_on_right(run_op[t], run_len[t]);
-            }
-            set_error("%s: the runs of duplication %lld consume %llu and %llu bases of arms of %llu and %llu", kWho, q,
-                      (unsigned long long)i, (unsigned long long)j, (unsigned long long)sds[q].left_length,
-                      (unsigned long long)sds[q].right_length);
-        } else if ((tail[0] & 3) == kPafBadLen) {
-            set_error("%s: duplication %lld has a run_len of 0 (a run of no base)", kWho, q);
-        } else {
-            uint64_t t = b;
-            while (t + 1 < e && run_op_known(run_op[t])) ++t;
-            set_error("%s: duplication %lld has run_op %u: an operation is one of `=`, `X`, `I`, `D`", kWho, q,
-                      (unsigned)run_op[t]);
-        }
-        return ASGART_E_ARG;
-    }
+    if (tail[0] != ~(uint64_t)0) return refuse_runs(kWho, tail[0], sds, run_offsets, run_len, run_op);
     HIP_TRY(hipEventRecord(w.ev[2], s));
     if (tail[1]) {
         alnstats_bases_kernel<<<blocks_for(tail[1], kBases), kThreads, 0, s>>>(in, tail[1]);
@@ -298,7 +230,7 @@ extern "C" int32_t asgart_alignment_stats(asgart_index *idx, const asgart_proto_
                                           const uint8_t *status, int64_t n_sd, const uint64_t *run_offsets,
                                           const uint32_t *run_len, const uint8_t *run_op, asgart_align_counts *counts,
                                           double *ms3) {
-    RC_TRY(check_arguments(idx, sds, flags, status, n_sd, run_offsets, run_len, run_op, counts));
+    RC_TRY(check_alignment_arguments(kWho, idx, sds, flags, status, n_sd, run_offsets, run_len, run_op, counts));
     REFUSE_POISONED(idx);
     RC_TRY(use_device(kWho, idx->device));
     if (ms3) ms3[0] = ms3[1] = ms3[2] = 0;

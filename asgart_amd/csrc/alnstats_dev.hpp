@@ -1,12 +1,15 @@
 // alnstats_dev.hpp -- what the counts of an alignment consist of (asgart_alignment_stats; align.stats_host is the readable
 // statement): the kind of a mismatch, the pair of bytes a base of an `X` run stands for, and how the lanes of a wave that
-// hold consecutive items of consecutive rows find the part of the wave that is their row's.
+// hold consecutive items of consecutive rows find the part of the wave that is their row's; and, at the end, the host half
+// of the call's checks, which asgart_alignment_variants (variants.hip) makes in the same words.
 //
 // The frame is the alignment's: A is the left arm as stored, B the right arm as lev_dev.hpp's RightArm walks it (reversed
 // if flag bit 0 is set, then complemented if bit 1 is).  Run t of duplication (left, right, ll, rl) starts at the arm
 // offsets i_t and j_t of paf_dev.hpp -- the exclusive sums I and J of run_on_left and run_on_right, counted from the
 // row's first run -- and base v of it pairs a = text[left + i_t + v] with b = B(j_t + v).
 #pragma once
+#include "index.hpp"
+#include "tool_base.hpp"
 #include "lev_dev.hpp"
 #include "paf_dev.hpp"
 
@@ -87,5 +90,82 @@ __device__ inline uint32_t row_max(uint32_t v, uint32_t lane, uint32_t end) {
         if (lane + off < end && o > v) v = o;
     }
     return v;
+}
+
+// ---- the host side of the checks, for every call that takes asgart_alignment_stats' arguments (alnstats.hip,
+// variants.hip): the same refusals in the same words, under the caller's name ---------------------------------------------
+
+// what is checked before anything is launched; `result` is where the call's answer goes (counts, a handle)
+inline int32_t check_alignment_arguments(const char *who, const asgart_index *idx, const asgart_proto_sd *sds,
+                                         const uint8_t *flags, const uint8_t *status, int64_t n_sd,
+                                         const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
+                                         const void *result) {
+    if (!idx) {
+        set_error("%s: bad argument (no index: the bases are its text's)", who);
+        return ASGART_E_ARG;
+    }
+    if (n_sd < 0 || (n_sd && (!sds || !flags || !status || !run_offsets || !result))) {
+        set_error("%s: bad argument", who);
+        return ASGART_E_ARG;
+    }
+    if (n_sd >= (int64_t)1 << 31) {
+        set_error("%s: 2^31 duplications and more are not supported", who);
+        return ASGART_E_CAP;
+    }
+    if (n_sd == 0) return 0;
+    const uint64_t n_runs = run_offsets[n_sd];
+    if (n_runs >= (uint64_t)1 << 32) {
+        set_error("%s: run_offsets end at %llu; 2^32 runs and more are not supported", who, (unsigned long long)n_runs);
+        return ASGART_E_CAP;
+    }
+    RC_TRY(check_csr(who, "run_offsets", run_offsets, n_sd, (int64_t)n_runs, "the run count", "duplication"));
+    if (n_runs && (!run_len || !run_op)) {
+        set_error("%s: bad argument (%llu runs and no run_len or run_op)", who, (unsigned long long)n_runs);
+        return ASGART_E_ARG;
+    }
+    const uint64_t n_text = (uint64_t)idx->n;
+    for (int64_t q = 0; q < n_sd; ++q) {
+        if (status[q] != 1) continue;
+        if (flags[q] & ~3u) {
+            set_error("%s: duplication %lld has flag byte %u (bit 0 reversed, bit 1 complemented)", who, (long long)q,
+                      (unsigned)flags[q]);
+            return ASGART_E_ARG;
+        }
+        const asgart_proto_sd &sd = sds[q];
+        if (sd.left > n_text || sd.right > n_text || sd.left_length > n_text - sd.left || sd.right_length > n_text - sd.right) {
+            set_error("%s: duplication %lld reaches past the end of the text", who, (long long)q);
+            return ASGART_E_ARG;
+        }
+        if (arms_too_long(sd)) {   // (the right arm is walked with lev_dev.hpp's 32-bit offsets)
+            set_error("%s: arms of 2^32 bases are not supported", who);
+            return ASGART_E_CAP;
+        }
+    }
+    return 0;
+}
+
+// the message for the word the device checks left behind (bad = q << 2 | kPafBad.., not all ones) -> ASGART_E_ARG
+inline int32_t refuse_runs(const char *who, uint64_t bad, const asgart_proto_sd *sds, const uint64_t *run_offsets,
+                           const uint32_t *run_len, const uint8_t *run_op) {
+    const long long q = (long long)(bad >> 2);
+    const uint64_t b = run_offsets[q], e = run_offsets[q + 1];
+    if ((bad & 3) == kPafBadSums) {
+        uint64_t i = 0, j = 0;
+        for (uint64_t t = b; t < e; ++t) {
+            i += run_on_left(run_op[t], run_len[t]);
+            j += run_on_right(run_op[t], run_len[t]);
+        }
+        set_error("%s: the runs of duplication %lld consume %llu and %llu bases of arms of %llu and %llu", who, q,
+                  (unsigned long long)i, (unsigned long long)j, (unsigned long long)sds[q].left_length,
+                  (unsigned long long)sds[q].right_length);
+    } else if ((bad & 3) == kPafBadLen) {
+        set_error("%s: duplication %lld has a run_len of 0 (a run of no base)", who, q);
+    } else {
+        uint64_t t = b;
+        while (t + 1 < e && run_op_known(run_op[t])) ++t;
+        set_error("%s: duplication %lld has run_op %u: an operation is one of `=`, `X`, `I`, `D`", who, q,
+                  (unsigned)run_op[t]);
+    }
+    return ASGART_E_ARG;
 }
 }  // namespace asgart

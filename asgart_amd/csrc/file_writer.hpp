@@ -1,4 +1,4 @@
-// file_writer.hpp -- what the file writers (export.hip, paf.hip, sdtable.hip) are built on, on top of tool_base.hpp: the handle
+// file_writer.hpp -- what the file writers (export.hip, paf.hip, sdtable.hip, variants_write.hip) are built on, on top of tool_base.hpp: the handle
 // of a written file, the result arrays as they arrive at the C boundary and their checks, the device work of a writer call
 // (FileWork: the common buffers, their upload, their view for the kernels, the five events of a call and its two figures),
 // the way of an LDS image out to the file, the write stage of a writer whose workgroups own consecutive items, and the

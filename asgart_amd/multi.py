@@ -321,19 +321,21 @@ def _align_for_paf(index, sds, flags, paf_band):
 
 
 def _check_paf(paf: bool, world: int, orientations, slice_options=None, cs: Optional[str] = None,
-               paf_band: Optional[str] = None, table: bool = False) -> None:
-    """--paf, --cs, --paf-band and --sd-table (table), vetted before the run starts (on every rank): each refusal with its
-    reason.  The table is vetted like the PAF file: its rows come from the same alignment and have the same strands."""
+               paf_band: Optional[str] = None, table: bool = False, psv: bool = False) -> None:
+    """--paf, --cs, --paf-band, --sd-table (table) and --psv, vetted before the run starts (on every rank): each refusal with
+    its reason.  The table and the variant files are vetted like the PAF file: their rows come from the same alignment and
+    have the same strands."""
     if cs not in (None, "short", "long"):
         raise ValueError("--cs: short or long")
     if cs is not None and not paf:
         raise ValueError("--cs: the cs:Z: tag is a column of the PAF file; it needs --paf")
     band = _paf_band(paf_band)
-    if band != "full" and not paf and not table:
+    if band != "full" and not paf and not table and not psv:
         raise ValueError("--paf-band: the corridor is that of the alignment behind the PAF file; it needs --paf")
-    if not paf and not table:
+    if not paf and not table and not psv:
         return
-    what, rows = ("--paf", "a PAF row") if paf else ("--sd-table", "a row of the duplication table")
+    what, rows = ("--paf", "a PAF row") if paf else ("--sd-table", "a row of the duplication table") if table else \
+        ("--psv", "a row of the variant files")
     if world > 1:
         raise ValueError(f"{what}: the alignment has no sharded variant, it runs on one GPU (use --gpus 1)")
     for r, c in orientations:
@@ -343,6 +345,10 @@ def _check_paf(paf: bool, world: int, orientations, slice_options=None, cs: Opti
     o = slice_options
     if o is not None and (o.collapse or o.keep_fragments is not None or o.restrict_fragments is not None
                           or o.exclude_fragments is not None):
+        if not paf and not table:
+            raise ValueError("--psv: --collapse and the fragment filters lay the fragments out again; the rows of the variant "
+                             "files name positions in the fragments of the run (slice the result without them, or write no "
+                             "variant files)")
         if not paf:
             raise ValueError("--sd-table: --collapse and the fragment filters lay the fragments out again; the rows of the "
                              "table name positions in the fragments of the run (slice the result without them, or write no "
@@ -353,12 +359,26 @@ def _check_paf(paf: bool, world: int, orientations, slice_options=None, cs: Opti
 
 # `paf` of the entry points when the alignment is to stay inside a corridor: the cs:Z: form (None: no such column) and
 # --paf-band's value (_paf_band); table: the duplication table (--sd-table) is written from the same alignment, one more
-# entry of the return value, an SdTable; rows = False: the table only, no PAF text
-Paf = namedtuple("Paf", "cs band table rows", defaults=(None, "full", False, True))
+# entry of the return value, an SdTable; rows = False: the table only, no PAF text; psv: the variant files (--psv) are written
+# from the same alignment, two more entries, a PsvTable and a PsvVcf
+Paf = namedtuple("Paf", "cs band table rows psv", defaults=(None, "full", False, True, False))
 
 
 class SdTable(str):
     """The text of a duplication table (<result stem>.sd.tsv) among the entries an entry point returns."""
+
+
+class PsvTable(str):
+    """The text of the pair table of the variants (<result stem>.psv.tsv) among the entries an entry point returns."""
+
+
+class PsvVcf(str):
+    """The text of the site VCF of the variants (<result stem>.psv.vcf) among the entries an entry point returns."""
+
+
+def _paf_psv(paf) -> bool:
+    """The `paf` argument of the entry points -> are the variant files asked for"""
+    return isinstance(paf, Paf) and bool(paf.psv)
 
 
 def _paf_table(paf):
@@ -400,6 +420,43 @@ def _sd_table_text(fam_offs, sds, flags, strand, aln, writer: Optional[str], dev
                                                 device_index)))
     text = strand.data if strand.data is not None else index.read_text(0, index.n)
     return SdTable(sd_table_text(fam_offs, sds, flags, strand, aln, stats_host(text, sds, flags, aln)))
+
+
+# writer=None for the variant files: the device (Index.variants, Variants.sites and the two device writers of align) from
+# this many duplications on, the host (align.variants_host, sites_numpy and the two text statements) below; None: the host
+# everywhere.  The standing rule: the device from the smallest measured size at which its median is below the host's by more
+# than both spreads.  The host walks every mismatch base in Python and formats every row: 1.6 ms per thousand runs; the four
+# device calls cost 15 ms (spread 8 ms) at 512 rows and 43 ms at 8 192.  profiles/psv_synth.json (tools/psv_bench.py): at
+# 512 rows with 80 536 runs, the smallest size measured, at 8 192 and at 140 113 rows the device's median is below the
+# host's by more than both spreads.  Nothing smaller was measured, so that size is the threshold.
+PSV_DEVICE_MIN_ROWS = 512
+
+
+def _choose_psv_writer(writer: Optional[str], n_rows: int) -> str:
+    """The writer of the variant files of n_rows duplications: "device" or "host" as asked (what --host-writer asks for);
+    writer=None: by size, see PSV_DEVICE_MIN_ROWS."""
+    if writer is None:
+        return "device" if PSV_DEVICE_MIN_ROWS is not None and n_rows >= PSV_DEVICE_MIN_ROWS else "host"
+    if writer not in ("device", "host"):
+        raise ValueError("writer: 'device' or 'host'")
+    return writer
+
+
+def _psv_texts(fam_offs, sds, flags, strand, aln, writer: Optional[str], index):
+    """The two variant files of aligned duplications -> (PsvTable, PsvVcf), records, sites and text by the writer the run
+    asked for (_choose_psv_writer), while the index is open: "device" Index.variants, Variants.sites, asgart_variants_records
+    and asgart_sites_records; "host" align.variants_host -- over strand.data or, where the device reader left no copy on the
+    host, Index.read_text --, align.sites_numpy and the two text statements; the texts are the same either way."""
+    from .align import (psv_table_text, psv_table_text_gpu, psv_vcf_text, psv_vcf_text_gpu, sites_numpy, variants_host)
+
+    if _choose_psv_writer(writer, len(sds)) == "device":
+        with index.variants(sds, flags, aln) as v, v.sites() as sites:
+            return (PsvTable(psv_table_text_gpu(fam_offs, sds, flags, strand, v).decode("utf-8")),
+                    PsvVcf(psv_vcf_text_gpu(fam_offs, sds, flags, strand, sites, v).decode("utf-8")))
+    text = strand.data if strand.data is not None else index.read_text(0, index.n)
+    records = variants_host(text, sds, flags, aln)
+    return (PsvTable(psv_table_text(fam_offs, sds, flags, strand, records)),
+            PsvVcf(psv_vcf_text(fam_offs, sds, flags, strand, sites_numpy(records), records)))
 
 
 def _paf_and_cs(paf):
@@ -451,14 +508,16 @@ def _slice_run(post, strand, settings, slice_options, device_index: int):
 # duplications, survivors[lo:hi].  survivors (n, 4) uint64 and flags uint8[n] hold the parts' duplications one behind the
 # other; ident float32[n], seqs (left, right) and aln (Alignments) are None unless the run was asked for them.  paf: the text of
 # the part's PAF file where it had to be written while the index was open (--cs: the bases are the index's), None otherwise;
-# table: the part's duplication table (an SdTable, written while the index was open: the counts need its text), None without.
-_Part = namedtuple("_Part", "settings offs cut lo hi paf table", defaults=(None, None))
+# table: the part's duplication table (an SdTable, written while the index was open: the counts need its text), None without;
+# psv: the part's variant files (a PsvTable and a PsvVcf, written while the index was open as well), None without.
+_Part = namedtuple("_Part", "settings offs cut lo hi paf table psv", defaults=(None, None, None))
 _Run = namedtuple("_Run", "files device_index strand parts survivors flags ident seqs aln")
 
 
 def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool, with_sequences: bool, reader: str,
          paf: bool, sliced: bool = False, slice_options=None, cs: Optional[str] = None,
-         paf_writer: Optional[str] = None, paf_band: Optional[str] = None, table: bool = False) -> Optional[_Run]:
+         paf_writer: Optional[str] = None, paf_band: Optional[str] = None, table: bool = False,
+         psv: bool = False) -> Optional[_Run]:
     """The run protocol, once: a whole `asgart` run (reference src/bin/asgart.rs:731-822) for each of the one to four
     RunSettings `sts`, which differ in orientation only, on the ranks of `dist` (None: one process, no collective), rank r
     on GPU device_index.  The entry points have vetted the arguments.  Built ONCE: rank 0 reads the input and builds the
@@ -471,7 +530,8 @@ def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool
     scores its share; with_sequences is one extraction from the Source of the read (device reader) or the raw records
     (host reader); paf one alignment with exact ranges, inside the corridor paf_band asks for (_align_for_paf); with cs (the cs:Z: column) every part's PAF text is written right
     there, by the writer paf_writer asks for, because the index is closed when this returns; with table the same alignment
-    is counted and every part's duplication table written right there as well (_sd_table_text).  A slice that is refused
+    is counted and every part's duplication table written right there as well (_sd_table_text); with psv its differences are
+    listed and every part's two variant files written right there too (_psv_texts).  A slice that is refused
     (ValueError) is raised behind the collectives, which then run without survivors: the other ranks must not wait in them.
     -> the _Run on rank 0, None elsewhere; the Source and the index are closed either way."""
     from . import merge_shards, orientation_flags
@@ -531,10 +591,13 @@ def _run(files: Sequence[str], sts, dist, device_index: int, compute_score: bool
             return None
         seqs = _sequences(source, records, device_index, survivors, (flags & 1).astype(bool),
                           (flags >> 1 & 1).astype(bool)) if with_sequences else None
-        aln = _align_for_paf(index, survivors, flags, paf_band) if paf or table else None
+        aln = _align_for_paf(index, survivors, flags, paf_band) if paf or table or psv else None
         if table:
             parts = [p._replace(table=_sd_table_text(p.offs, survivors[p.lo:p.hi], flags[p.lo:p.hi], strand,
                                                      aln.part(p.lo, p.hi), paf_writer, device_index, index)) for p in parts]
+        if psv:
+            parts = [p._replace(psv=_psv_texts(p.offs, survivors[p.lo:p.hi], flags[p.lo:p.hi], strand, aln.part(p.lo, p.hi),
+                                               paf_writer, index)) for p in parts]
         if paf and cs is not None:
             parts = [p._replace(paf=_paf_text(p.offs, survivors[p.lo:p.hi], flags[p.lo:p.hi], strand, aln.part(p.lo, p.hi),
                                               paf_writer, device_index, cs, index)) for p in parts]
@@ -562,13 +625,13 @@ def _json_text(run: _Run, offs, lo: int, hi: int, settings, writer: str, flags=N
 def _texts(run: _Run, part: _Part, prefix: str, writer: str, paf_writer: Optional[str], fmt: str = "json",
            paf_rows: bool = True) -> tuple:
     """One orientation's entry of what the entry points return: (the text of its result file, the file's name[, the text of
-    its PAF file][, its duplication table, an SdTable]).  writer: what _choose_writer gave; paf_writer: the `writer`
+    its PAF file][, its duplication table, an SdTable][, its variant files, a PsvTable and a PsvVcf]).  writer: what _choose_writer gave; paf_writer: the `writer`
     argument as it was asked for, None decides by the run count of this orientation's own alignments.  fmt: of a sliced
     part, whose file is named after it.  paf_rows = False: the alignment was made for the table alone, no PAF text."""
     from .postprocess import out_filename
 
-    st, offs, cut, lo, hi, paf_text, table = part
-    tables = () if table is None else (table,)
+    st, offs, cut, lo, hi, paf_text, table, psv = part
+    tables = (() if table is None else (table,)) + (() if psv is None else tuple(psv))
     name = out_filename(run.files, st, prefix)
     if cut is None:
         text = _json_text(run, offs, lo, hi, st, writer)
@@ -618,8 +681,12 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     floor(P max(n, m) / 100): one with more gets no row and a line on stderr (_paf_band).  Paf(..., table=True) (what
     --sd-table passes) also counts the same alignments while the index is open and adds the duplication table as one more
     entry, an SdTable (align.sd_table_text; the writer as `writer` asks, None: by SDTABLE_DEVICE_MIN_ROWS); with rows=False
-    the alignment serves the table alone and there is no PAF text."""
+    the alignment serves the table alone and there is no PAF text.  Paf(..., psv=True) (what --psv passes) also lists the
+    differences of the same alignments while the index is open and adds the two variant files as two more entries, a
+    PsvTable and a PsvVcf (align.psv_table_text, align.psv_vcf_text; the writer as `writer` asks, None: by
+    PSV_DEVICE_MIN_ROWS)."""
     table, paf_rows = _paf_table(paf)
+    psv = _paf_psv(paf)
     paf, cs, paf_band = _paf_and_cs(paf)
     world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
@@ -628,9 +695,9 @@ def search_duplications(files: Sequence[str], settings, dist, device_index: int,
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     sliced = _check_slice(slice_options, fmt)
-    _check_paf(paf and paf_rows, world, [(settings.reverse, settings.complement)], slice_options, cs, paf_band, table)
+    _check_paf(paf and paf_rows, world, [(settings.reverse, settings.complement)], slice_options, cs, paf_band, table, psv)
     run = _run(files, [settings], dist, device_index, compute_score, with_sequences, reader, paf and paf_rows, sliced,
-               slice_options, cs, paf_writer, paf_band, table)
+               slice_options, cs, paf_writer, paf_band, table, psv)
     return None if run is None else _texts(run, run.parts[0], prefix, writer, paf_writer, fmt, paf_rows)
 
 
@@ -646,11 +713,12 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     (RunResult::from_files, reference src/structs.rs:114-141: strand and settings of the first, every duplication with the
     flags of its own run) and is written like the others.  `--trim`, reader, writer, with_sequences, paf (the merged
     result gets no PAF text and no table; direct and RC only, see _check_paf; "short" / "long": with the cs:Z: column; a Paf:
-    inside a corridor, with the duplication table): as
+    inside a corridor, with the duplication table, with the variant files): as
     search_duplications.  Slicing is out of scope here: `python -m asgart_amd.slice` does it on the files this writes."""
     from dataclasses import replace
 
     table, paf_rows = _paf_table(paf)
+    psv = _paf_psv(paf)
     paf, cs, paf_band = _paf_and_cs(paf)
     orientations = [(bool(r), bool(c)) for r, c in orientations]
     if not 1 <= len(orientations) <= 4 or len(set(orientations)) != len(orientations):
@@ -658,13 +726,13 @@ def search_orientations(files: Sequence[str], orientations: Sequence[Tuple[bool,
     world = dist.get_world_size() if dist is not None else 1
     if settings.trim is not None and world > 1:
         raise ValueError("multi.search_orientations: --trim runs on one rank only")
-    _check_paf(paf and paf_rows, world, orientations, None, cs, paf_band, table)
+    _check_paf(paf and paf_rows, world, orientations, None, cs, paf_band, table, psv)
     reader = _choose_reader(reader, settings)
     paf_writer = writer                          # (as asked for: with_sequences sends only the result file to the host)
     writer = _choose_writer(writer, with_sequences)
     sts = [replace(settings, reverse=r, complement=c) for r, c in orientations]
     run = _run(files, sts, dist, device_index, compute_score, with_sequences, reader, paf and paf_rows, cs=cs,
-               paf_writer=paf_writer, paf_band=paf_band, table=table)
+               paf_writer=paf_writer, paf_band=paf_band, table=table, psv=psv)
     if run is None:
         return None
     sizes = np.concatenate([np.diff(p.offs.astype(np.int64)) for p in run.parts])
@@ -723,6 +791,12 @@ def _parse(argv):
                          "mismatches, transitions, transversions, indels), fracMatch, fracMatchIndel and the Jukes-Cantor and "
                          "Kimura distances.  With or without --paf (one alignment serves both); honours --paf-band; vetted "
                          "like --paf")
+    ap.add_argument("--psv", action="store_true",
+                    help="write <result stem>.psv.tsv and <result stem>.psv.vcf beside every result file: the paralogous "
+                         "sequence variants, that is the differences between the two arms of every surviving duplication as "
+                         "positions in the genome -- one row per mismatch base and per indel in the table, one VCF row per "
+                         "distinct mismatch position.  With or without --paf / --sd-table (one alignment serves all three); "
+                         "honours --paf-band and --host-writer; vetted like --sd-table")
     ap.add_argument("--prefix", default="")
     ap.add_argument("--out-dir", default=".", help="where the JSON file goes (its name is the reference's)")
     ap.add_argument("--one-device", action="store_true",
@@ -757,7 +831,7 @@ def _parse(argv):
         ap.error("--orientations writes unsliced JSON files: slice them with python -m asgart_amd.slice")
     try:
         _check_paf(args.paf, args.gpus, args.orientations or [(args.reverse, args.complement)], args.slice_options, args.cs,
-                   args.paf_band, args.sd_table)
+                   args.paf_band, args.sd_table, args.psv)
     except ValueError as e:
         ap.error(str(e))
     return args
@@ -811,6 +885,12 @@ def launch(argv, timeout: Optional[float] = None) -> int:
     return rc
 
 
+def _side_suffix(text) -> str:
+    """the extension of a file written beside the result file, by the kind of its text"""
+    return ".sd.tsv" if isinstance(text, SdTable) else ".psv.tsv" if isinstance(text, PsvTable) else \
+        ".psv.vcf" if isinstance(text, PsvVcf) else ".paf"
+
+
 def rank_main(argv) -> int:
     """One rank: RCCL when every rank has a GPU of its own, otherwise every rank on device 0 over gloo."""
     import torch
@@ -834,7 +914,7 @@ def rank_main(argv) -> int:
                                         complement=args.complement, skip_masked=args.skip_masked)
         asked = dict(compute_score=args.compute_score, prefix=args.prefix, with_sequences=args.with_sequences,
                      reader="host" if args.host_reader else None, writer="host" if args.host_writer else None,
-                     paf=Paf(args.cs, args.paf_band, True, args.paf) if args.sd_table else
+                     paf=Paf(args.cs, args.paf_band, args.sd_table, args.paf, args.psv) if args.sd_table or args.psv else
                      Paf(args.cs, args.paf_band) if args.paf and args.paf_band != "full" else args.cs or args.paf)
         if args.orientations:
             out = search_orientations(args.files, args.orientations, settings, dist, device_index, **asked)
@@ -845,8 +925,7 @@ def rank_main(argv) -> int:
             texts = None if out is None else [out]
         for text, name, *paf in texts or []:
             for body, path in [(text, os.path.join(args.out_dir, name))] + \
-                    [(p_, os.path.join(args.out_dir, os.path.splitext(name)[0] + (".sd.tsv" if isinstance(p_, SdTable) else
-                                                                                 ".paf"))) for p_ in paf]:
+                    [(p_, os.path.join(args.out_dir, os.path.splitext(name)[0] + _side_suffix(p_))) for p_ in paf]:
                 with open(path, "w", encoding="utf-8") as fh:
                     fh.write(body)
                 print(f"rank 0 of {world} ({backend}): wrote {path}", flush=True)

@@ -1109,6 +1109,109 @@ int32_t asgart_fasta_write(asgart_source *src, const uint64_t *record_start, con
  * workgroup, bytes of the file per workgroup (a window, and the LDS image of it), bytes per store of the copy out. */
 void asgart_fasta_write_geometry(uint64_t *block_threads, uint64_t *window_bytes, uint64_t *store_bytes);
 
+/* ---- the variants between the copies: records, sites, and their two files -----------------------------------------
+ * The differences an alignment found, as positions in the genome: the paralogous sequence variants (PSVs) that tell one
+ * copy from another.  No counterpart in the reference.  asgart_alignment_variants takes the arguments of
+ * asgart_alignment_stats and uses its frame: all four flag values are legal, only duplications with status[q] == 1 are read
+ * or checked, run t of duplication q = (left, right, ll, rl) starts at the arm offsets i_t and j_t of the cs:Z: section, and
+ * rev = flags[q] & 1.  The rule: one record per base of every `X` run and one per `I` run and per `D` run, in the order of
+ * the duplications and, inside one, of the runs and bases.  All coordinates are global, on the forward strand, half-open:
+ *    op              left interval            right interval
+ *    `X`, base v     [left + i_t + v, +1)     [p, p + 1), p = right + (rev ? rl - 1 - (j_t + v) : j_t + v)
+ *    `I`, n bases    [left + i_t, +n)         empty at right + (rev ? rl - j_t : j_t)
+ *    `D`, n bases    empty at left + i_t      [right + (rev ? rl - j_t - n : j_t), +n)
+ * left_base and right_base are the text's bytes AS STORED at the two positions of an `X` record (not complemented, case
+ * kept) and 0 for an indel; flag is flags[q], sd is q.  Like the counts, the call believes the runs: an `X` laid over equal
+ * bytes is a record with two equal bases.  var_offsets[n_sd + 1]: the records of duplication q are var_offsets[q] ..
+ * var_offsets[q + 1].
+ * Example 1: the text `ACGTTAGC` `GG` `ACCTAGCA`, the duplication (0, 10, 8, 8), flag 0, runs `2=1I1X4=1D`: three records,
+ *    I  left [2, 3)  right empty at 12;     X  left [3, 4) `T`  right [12, 13) `C`;     D  left empty at 8  right [17, 18).
+ * Example 2: `TGCTAGGT` as the right arm and flag 3: the `X` is left 3 (`T`) against right 15 (`G`); the `I` boundary is 16;
+ * the `D` is [10, 11).
+ * Checks and refusals are those of asgart_alignment_stats, under this call's name: idx NULL (before anything else); NULL
+ * arrays with a positive count, run_offsets not from 0, decreasing; a flag byte above 3; an arm that reaches past the text;
+ * and, on the device, through one atomic minimum before a base is read, a run_op outside `=XID`, a run_len of 0, runs that
+ * do not consume exactly left_length and right_length bases (ASGART_E_ARG, the message names the first such duplication).
+ * 2^31 duplications, 2^32 runs, arms of 2^32 bases, 2^31 variants and more: ASGART_E_CAP.  A refused call leaves nothing on
+ * the device and no handle.  The handle keeps the records on the device of the index (asgart_variant_sites and
+ * asgart_variants_records read them there) until asgart_variants_free. */
+typedef struct asgart_variant {      /* 32 bytes */
+    uint64_t left_pos, right_pos;
+    uint32_t left_len, right_len;    /* 1/1, n/0, 0/n */
+    uint32_t sd;                     /* q */
+    uint8_t  op, left_base, right_base, flag;
+} asgart_variant;
+typedef struct asgart_variants asgart_variants;
+int32_t asgart_alignment_variants(asgart_index *idx, const asgart_proto_sd *sds, const uint8_t *flags, const uint8_t *status,
+                                  int64_t n_sd, const uint64_t *run_offsets, const uint32_t *run_len, const uint8_t *run_op,
+                                  asgart_variants **out);
+/* n_sd of the call, the number of records, the number of `X` records (SNVs).  Every target is nullable. */
+void asgart_variants_counts(const asgart_variants *r, uint64_t *n_sd, uint64_t *n_variants, uint64_t *n_snv);
+/* records[n_variants], var_offsets[n_sd + 1]; either may be NULL. */
+int32_t asgart_variants_copy(const asgart_variants *r, asgart_variant *records, uint64_t *var_offsets);
+/* Milliseconds of the call behind r: [0] the upload, [1] the kernels, [2] the copies back of the offsets and the counts. */
+int32_t asgart_variants_timings(const asgart_variants *r, double *ms3);
+void asgart_variants_free(asgart_variants *r);
+/* Threads per workgroup and records per workgroup of the records kernel, for tests that place their runs on the seams. */
+void asgart_variants_geometry(uint64_t *block_threads, uint64_t *records_per_block);
+
+/* The sites of the `X` records of v: this call needs no index.  Every `X` record makes up to two ENTRIES,
+ *    (left_pos,  ref = left_base,  alt = o(right_base))   and   (right_pos, ref = right_base, alt = o(left_base)),
+ * where o complements (ACGT and acgt swap, every other byte is kept) when bit 1 of the record's flag is set.  The classes
+ * are A, C, G, T with the case folded (0, 1, 2, 3) and N (4) for every other byte; an entry exists only where
+ * class(ref) != class(alt).  A site is a distinct position; for each, in ascending position: pos; ref, the class of the
+ * text's byte there; alt_mask, bit c set where an entry has the alt class c; pairs, the number of entries; (sd, side) of
+ * its first entry in record order, left (0) before right (1).  A duplication whose arms overlap can hold one position in
+ * both arms, and then counts twice in pairs.  Indels make no sites.
+ * Example 1 above: sites 3 (ref T, alt C, pairs 1, sd 0, side 0) and 12 (ref C, alt T, pairs 1, sd 0, side 1); example 2:
+ * 3 (T, alt C) and 15 (G, alt A).
+ * The result stays on the device of the records until asgart_sites_free; all of it is integer, so it does not depend on
+ * the order anything arrives in.  v NULL: ASGART_E_ARG; no usable device: ASGART_E_HIP. */
+typedef struct asgart_sites asgart_sites;
+int32_t asgart_variant_sites(const asgart_variants *v, asgart_sites **out);
+void asgart_sites_counts(const asgart_sites *r, uint64_t *n_sites, uint64_t *n_entries);
+/* pos, ref, alt_mask, pairs, sd, side: n_sites entries each; every target is nullable. */
+int32_t asgart_sites_copy(const asgart_sites *r, uint64_t *pos, uint8_t *ref, uint8_t *alt_mask, uint32_t *pairs,
+                          uint32_t *sd, uint8_t *side);
+/* Milliseconds of the call behind r: [1] everything from the first kernel to the last (nothing is uploaded). */
+int32_t asgart_sites_timings(const asgart_sites *r, double *ms3);
+void asgart_sites_free(asgart_sites *r);
+/* Threads per workgroup of the kernels behind asgart_variant_sites (a wave of 64 reduces its entries by site). */
+void asgart_sites_geometry(uint64_t *block_threads);
+
+/* The two files, each one call that gives the whole file in one device buffer, an asgart_export, on the device of the
+ * handle.  The result arrays are those of asgart_sdtable_records and belong to the call the records were made from (the
+ * same n_sd); a position becomes local as chr_pos[2q + s] + (global - start of arm s of duplication q).  `prefix` is the
+ * caller's header.
+ * asgart_variants_records: the pair table, one line per record, 12 columns separated by tabs and ended by `\n`:
+ *    1 chrom1   the name chr[2q]        2 start1, 3 end1   the left interval
+ *    4 chrom2   the name chr[2q + 1]    5 start2, 6 end2   the right interval
+ *    7 `sd<q>`     8 op     9 strand2, `+` for flag 0 and `-` for flag 3     10 family
+ *   11 base1, 12 base2   the two bytes as stored for `X`, `.` for an indel
+ * asgart_sites_records: VCF 4.2 body rows, one per site: the name and the local position + 1 of the site's (sd, side),
+ * `.`, REF (the class letter), ALT (the letters of alt_mask in the order A, C, G, T, N, joined by `,`), `.`, `.`,
+ * `NP=<pairs>`.
+ * Example 1 as the fragment `chr1` from 0, family 0:
+ *    chr1 2 3 chr1 12 12 sd0 I + 0 . .      chr1 3 4 chr1 12 13 sd0 X + 0 T C      chr1 8 8 chr1 17 18 sd0 D + 0 . .
+ *    chr1 4 . T C . . NP=1                  chr1 13 . C T . . NP=1
+ * Checked on the host before anything is launched, as asgart_sdtable_records checks, for the duplications with a record:
+ * NULL arrays with a positive count, n_sd other than the records' call had, fam_offsets / name_offsets not starting at 0,
+ * decreasing or (fam_offsets) not ending at n_sd, a name id outside the table, a flag other than 0 or 3 (the message names
+ * the first), a position + length that wraps past 2^64: ASGART_E_ARG; 2^31 families and more: ASGART_E_CAP.  No records or
+ * no sites: the prefix alone. */
+int32_t asgart_variants_records(const asgart_variants *v, const uint64_t *fam_offsets, int64_t n_families,
+                                const asgart_proto_sd *sds, const uint8_t *flags, const int32_t *chr, const uint64_t *chr_pos,
+                                int64_t n_sd, const uint8_t *name_bytes, const uint64_t *name_offsets, int64_t n_names,
+                                const uint8_t *prefix, uint64_t prefix_len, asgart_export **out);
+int32_t asgart_sites_records(const asgart_sites *r, const uint64_t *fam_offsets, int64_t n_families,
+                             const asgart_proto_sd *sds, const uint8_t *flags, const int32_t *chr, const uint64_t *chr_pos,
+                             int64_t n_sd, const uint8_t *name_bytes, const uint64_t *name_offsets, int64_t n_names,
+                             const uint8_t *prefix, uint64_t prefix_len, asgart_export **out);
+/* Sizes the write stages work in: threads per workgroup, rows per workgroup, bytes of the LDS image (a workgroup whose
+ * rows do not fit it stores them directly: a name of any length is legal). */
+void asgart_variants_records_geometry(uint64_t *block_threads, uint64_t *rows_per_block, uint64_t *stage_bytes);
+void asgart_sites_records_geometry(uint64_t *block_threads, uint64_t *rows_per_block, uint64_t *stage_bytes);
+
 /* ---- finer-grained entry points mirroring the reference's inner API;
  *      used by the parity tests ------------------------------------------ */
 
