@@ -61,6 +61,8 @@ ABI_SYMBOLS = (
     "asgart_rosary_geometry",
     "asgart_duplication_groups", "asgart_groups_counts", "asgart_groups_copy", "asgart_groups_timings", "asgart_groups_free",
     "asgart_groups_geometry",
+    "asgart_chain_duplications", "asgart_chains_counts", "asgart_chains_copy", "asgart_chains_timings", "asgart_chains_free",
+    "asgart_chain_geometry",
     "asgart_export_records", "asgart_export_size", "asgart_export_copy", "asgart_export_timings", "asgart_export_free",
     "asgart_export_geometry", "asgart_f32_shortest", "asgart_f32_pow10_table",
     "asgart_result_scan", "asgart_result_parse", "asgart_result_counts", "asgart_result_copy", "asgart_result_timings",
@@ -336,6 +338,20 @@ def load_library() -> C.CDLL:
         L.asgart_groups_free.restype = None
         L.asgart_groups_geometry.argtypes = [u64p]
         L.asgart_groups_geometry.restype = None
+    if hasattr(L, "asgart_chain_duplications"):
+        L.asgart_chain_duplications.argtypes = [C.c_int32, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_uint64, C.c_int32,
+                                                C.POINTER(vp)]
+        L.asgart_chain_duplications.restype = C.c_int32
+        L.asgart_chains_counts.argtypes = [vp, u64p, u64p, u64p, u64p]
+        L.asgart_chains_counts.restype = None
+        L.asgart_chains_copy.argtypes = [vp] * 8
+        L.asgart_chains_copy.restype = None
+        L.asgart_chains_timings.argtypes = [vp, C.POINTER(C.c_double)]
+        L.asgart_chains_timings.restype = C.c_int32
+        L.asgart_chains_free.argtypes = [vp]
+        L.asgart_chains_free.restype = None
+        L.asgart_chain_geometry.argtypes = [u64p, u64p, u64p]
+        L.asgart_chain_geometry.restype = None
     if hasattr(L, "asgart_export_records"):
         L.asgart_export_records.argtypes = [C.c_int32, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, vp, vp,
                                             C.c_int64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp)]

@@ -44,25 +44,8 @@ constexpr uint32_t kBlock = 256;  // threads per workgroup, every kernel; a mult
 constexpr uint32_t kGaveUpWalk = 1u, kGaveUpCas = 2u;
 constexpr uint32_t kStrides[] = {64, 8, 1};  // the union launches: one duplication in 64, then in 8, then the rest
 
-struct NameEnd {
-    uint64_t end;
-    uint32_t name;
-    uint32_t pad;
-};
-
-// the running maximum of the ends within a name; associative where the names never decrease from left to right
-struct SegmentedMax {
-    __host__ __device__ NameEnd operator()(const NameEnd &a, const NameEnd &b) const {
-        NameEnd r = b;
-        if (a.name == b.name && a.end > b.end) r.end = a.end;
-        return r;
-    }
-};
-
-__device__ inline uint64_t sat_add(uint64_t a, uint64_t b) {
-    const uint64_t s = a + b;
-    return s < a ? ~(uint64_t)0 : s;
-}
+// (name, end) of a sorted arm: the record of tool_base.hpp's segmented max-scan, which chain.hip shares
+using NameEnd = KeyEnd<uint32_t>;
 
 __global__ __launch_bounds__(kBlock) void groups_emit_kernel(uint32_t *__restrict__ ord, uint32_t m) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -87,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void groups_ends_kernel(const uint32_t *__r
     const uint32_t o = ord[i];
     const uint64_t st = start[o];
     s_start[i] = st;
-    pair[i] = NameEnd{st + length[o], sorted_name[i], 0u};  // (the host has refused a sum that wraps)
+    pair[i] = NameEnd{st + length[o], sorted_name[i]};  // (the host has refused a sum that wraps)
 }
 
 // run[i - 1] is the largest end of all earlier arms of record i's name, where there is one
@@ -99,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void groups_heads_kernel(const NameEnd *__r
     uint32_t h = 1u;
     if (i > 0) {
         const NameEnd before = run[i - 1];
-        h = (before.name != run[i].name || s_start[i] >= sat_add(before.end, margin)) ? 1u : 0u;
+        h = (before.key != run[i].key || s_start[i] >= sat_add(before.end, margin)) ? 1u : 0u;
     }
     head[i] = h;
 }
@@ -117,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void groups_open_kernel(const uint32_t *__r
     const uint32_t h = head[i], c = rank[i] + h - 1u;  // (rank is exclusive, and record 0 is a head)
     arm_locus[ord[i]] = c;
     if (!h) return;
-    l_name[c] = (int32_t)run[i].name;
+    l_name[c] = (int32_t)run[i].key;
     l_start[c] = s_start[i];
     l_first[c] = i;
     parent[c] = c;
@@ -314,14 +297,6 @@ struct GroupsWork : ToolWork {
     DevBuf &name_offsets = buf(), &parent = buf(), &give_up = buf(), &root = buf(), &is_root = buf(), &g_rank = buf();
     DevBuf &l_group = buf(), &g_loci = buf(), &g_bases = buf(), &group = buf(), &dord0 = buf(), &sorted_group = buf();
     DevBuf &order = buf(), &group_offsets = buf(), &g_dups = buf();
-
-    int32_t segmented_max_scan(const NameEnd *in, NameEnd *out, size_t items) {
-        size_t tmp = 0;
-        HIP_TRY(rocprim::inclusive_scan(nullptr, tmp, in, out, items, SegmentedMax(), s));
-        RC_TRY(scan_tmp.reserve(tmp + 16));
-        HIP_TRY(rocprim::inclusive_scan(scan_tmp.p, tmp, in, out, items, SegmentedMax(), s));
-        return 0;
-    }
 };
 
 const char *side_of(int64_t arm) { return (arm & 1) ? "right" : "left"; }

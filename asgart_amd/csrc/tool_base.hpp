@@ -26,6 +26,31 @@ inline int32_t use_device(const char *who, int32_t device) {
 
 inline unsigned blocks_for(uint64_t items, uint32_t block = 256) { return (unsigned)((items + block - 1) / block); }
 
+// ---- the segmented running maximum of groups.hip (loci: key = the name) and chain.hip (segments: key = the packed group) ----
+// Record i of a sequence sorted by (key, start): its key and its end.  ToolWork::segmented_max_scan turns the ends into the
+// largest end of record i and of every earlier record of its key; a record then opens a piece iff it is the first of its
+// key or its start lies beyond sat(that maximum in front of it + margin).
+template <class Key>
+struct KeyEnd {
+    uint64_t end;
+    Key key;
+};
+
+// the running maximum of the ends within a key; associative where the keys never decrease from left to right
+template <class Key>
+struct SegmentedMax {
+    __host__ __device__ KeyEnd<Key> operator()(const KeyEnd<Key> &a, const KeyEnd<Key> &b) const {
+        KeyEnd<Key> r = b;
+        if (a.key == b.key && a.end > b.end) r.end = a.end;
+        return r;
+    }
+};
+
+__host__ __device__ inline uint64_t sat_add(uint64_t a, uint64_t b) {
+    const uint64_t s = a + b;
+    return s < a ? ~(uint64_t)0 : s;
+}
+
 // The device work of one call: one non-blocking stream, its events and every device buffer the call uses.  A tool derives
 // from it and names each of its buffers once, as a reference that buf() hands out; the destructor is the only place where
 // they are released, so a call that returns early (a refusal after the launches, a failed allocation) leaves nothing.
@@ -71,6 +96,14 @@ struct ToolWork {
         HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, in, out, (T)0, items, rocprim::plus<T>(), s));
         RC_TRY(scan_tmp.reserve(tmp + 16));
         HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, tmp, in, out, (T)0, items, rocprim::plus<T>(), s));
+        return 0;
+    }
+    template <class Key>
+    int32_t segmented_max_scan(const KeyEnd<Key> *in, KeyEnd<Key> *out, size_t items) {
+        size_t tmp = 0;
+        HIP_TRY(rocprim::inclusive_scan(nullptr, tmp, in, out, items, SegmentedMax<Key>(), s));
+        RC_TRY(scan_tmp.reserve(tmp + 16));
+        HIP_TRY(rocprim::inclusive_scan(scan_tmp.p, tmp, in, out, items, SegmentedMax<Key>(), s));
         return 0;
     }
     template <class K>

@@ -724,6 +724,74 @@ void asgart_groups_free(asgart_groups *r);
 /* Threads per workgroup of the kernels behind asgart_duplication_groups, for tests that place their counts on the seams. */
 void asgart_groups_geometry(uint64_t *block_threads);
 
+/* ---- chaining: collinear duplications joined into pairs -----------------------------------------------------------
+ * The seed automaton closes an arm at the first stretch of max_gap_size bases without a hit, so one duplication with an
+ * insertion, a diverged stretch or an interspersed repeat comes out as several that lie one behind the other on both
+ * arms.  This call joins them.  Nothing of the reference does this; asgart_duplication_groups above joins arms into loci
+ * and never makes a PAIR longer.
+ * in: the anchors.  Duplication q has the name ids cl = chr[2q], cr = chr[2q + 1] (into a table of n_names names), the
+ * positions within them pl = chr_pos[2q], pr = chr_pos[2q + 1], the lengths ll = length[2q], rl = length[2q + 1], each at
+ * least 1, and a flag byte fl = flags[q] in 0 .. 3.  Both arms are stored on the forward strand, and bit 0 of the flag
+ * (reversed) decides the geometry: the frame of asgart_alignment_variants.  el = pl + ll, er = pr + rl.
+ * Two parameters: max_gap (u64, below 2^62; the tools default to 10 000, which is a choice, not a measurement) and
+ * lookback H in 1 .. 1024 (the tools default to 64).
+ * Groups and order.  Anchors of one (cl, cr, fl) form a group; inside it they are ordered by (pl, pr, q), and the rank is
+ * the position in that order.
+ * A link j -> i.  Both in one group, rank_i - H <= rank_j < rank_i.  It exists iff pl_i > pl_j and el_i > el_j (strict
+ * progress on the left); on the right, for fl & 1 == 0, pr_i > pr_j and er_i > er_j with dr = pr_i - er_j, and for
+ * fl & 1 == 1, pr_i < pr_j and er_i < er_j with dr = pr_j - er_i; and, with dl = pl_i - el_j (dl and dr signed, a
+ * negative value is an overlap), gl = max(dl, 0) <= max_gap and gr = max(dr, 0) <= max_gap.  Its value is
+ * t(j, i) = min(ll_i - max(-dl, 0), rl_i - max(-dr, 0)) - max(gl, gr): the new bases of i on its shorter side minus the
+ * longer gap.
+ * Scores (int64).  base(i) = min(ll_i, rl_i); f(i) = max(base(i), max_j f(j) + t(j, i)); pred(i) is the j of the maximum
+ * if that is STRICTLY above base(i), ties among j to the LARGEST rank (the nearest anchor); otherwise -1.
+ * Disjoint chains.  g(i) = max(f(i), max g(i') over pred(i') = i), the best score reachable through i; succ(j) is the
+ * child with the largest g, ties to the SMALLEST rank; the link of i is kept iff succ(pred(i)) = i, then
+ * link(i) = pred(i), otherwise -1.  The chains are the maximal paths of kept links, and a chain's score is base(head) plus
+ * t(link(i), i) of every other member.  (g and not f: the best path of a tree stays whole.)
+ * Numbering.  Chains are numbered densely in the order of their smallest member ordinal q.  order[n_sds] and
+ * chain_offsets[n_chains + 1] are the members chain by chain, in rank order: by the progress rule the head holds the
+ * smallest pl and the tail the largest el; on the right the head holds the smallest pr and the tail the largest er when
+ * direct, the other way round when reversed.  f, pred, link and chain are indexed by q, and pred and link hold ordinals.
+ * Example 1 (direct, max_gap 10 000, one group): A = (pl 100, pr 5 000, ll 400, rl 400), B = (800, 5 650, 300, 320),
+ * C = (1 050, 5 900, 200, 200).  A -> B: dl = 800 - 500 = 300, dr = 5 650 - 5 400 = 250, t = min(300, 320) - 300 = 0, so
+ * f(A) + t = 400 > base(B) = 300: f(B) = 400, pred(B) = A.  B -> C: dl = 1 050 - 1 100 = -50, dr = 5 900 - 5 970 = -70,
+ * t = min(200 - 50, 200 - 70) - 0 = 130, f(B) + t = 530; A -> C: dl = 550, dr = 500, t = 200 - 550 = -350, which gives 50.  f(C) = 530,
+ * pred(C) = B.  One chain A, B, C of score 400 + 0 + 130 = 530: left [100, 1 250), right [5 000, 6 100).
+ * Example 2 (a branch, direct, max_gap 10 000): J = (0, 0, 100, 100), I = (100, 100, 10, 10), I' = (100, 130, 50, 50),
+ * T = (200, 120, 1 000, 1 000), in rank order.  J -> I: dl = dr = 0, t = 10, f(I) = 110.  J -> I': dl = 0, dr = 30,
+ * t = 50 - 30 = 20, f(I') = 120; I -> I' is no link (pl does not grow).  I -> T: dl = 90, dr = 10, t = 1 000 - 90 = 910,
+ * f(T) = 1 020; J -> T gives 100 + 900, and I' -> T is no link (pr does not grow).  pred(I) = pred(I') = J, pred(T) = I.
+ * g(T) = g(I) = 1 020, g(I') = 120: succ(J) = I although f(I') > f(I), so the chains are J, I, T of score
+ * 100 + 10 + 910 = 1 020 = f(T), and I' alone, with link(I') = -1 and the score base(I') = 50.
+ * The library cuts the ranks of a group into segments: rank i opens one iff it is the first of its group or
+ * pl_i > sat(M + max_gap), M the largest el of the earlier ranks of its group (the running maximum of
+ * asgart_duplication_groups, STRICTLY beyond it, as gl <= max_gap admits a gap of exactly max_gap).  No link crosses such
+ * a boundary, so no output depends on the cut; n_segments counts the pieces.
+ * Checked on the host before anything is launched, the message naming the first offending duplication (ASGART_E_ARG
+ * unless said otherwise): NULL arrays with n_sds > 0, a negative count, lookback outside 1 .. 1024, max_gap >= 2^62,
+ * n_sds >= 2^31 (ASGART_E_CAP); then per duplication, left arm before right: a name id outside [0, n_names), a length of
+ * 0, position + length wrapping past 2^64, an arm of 2^32 bases or more (ASGART_E_CAP: f stays below 2^63), and a flag
+ * byte above 3.  No usable device: ASGART_E_HIP.  n_sds == 0 succeeds with no chains.  No device memory is held once the
+ * call has returned.  Every copy target is nullable. */
+typedef struct asgart_chains asgart_chains;
+int32_t asgart_chain_duplications(int32_t device, const int32_t *chr, const uint64_t *chr_pos, const uint64_t *length,
+                                  const uint8_t *flags, int64_t n_sds, int64_t n_names, uint64_t max_gap, int32_t lookback,
+                                  asgart_chains **out);
+/* n_links: the kept links, n_sds - n_chains. */
+void asgart_chains_counts(const asgart_chains *r, uint64_t *n_sds, uint64_t *n_chains, uint64_t *n_links,
+                          uint64_t *n_segments);
+void asgart_chains_copy(const asgart_chains *r, int64_t *f, int32_t *pred, int32_t *link, uint32_t *chain, uint32_t *order,
+                        uint64_t *chain_offsets, int64_t *chain_score);
+/* Milliseconds of the call behind r: [0] the upload, [1] the kernels from the first to the last, [2] the copy back; HIP
+ * events for the first two.  ASGART_E_ARG for a NULL argument. */
+int32_t asgart_chains_timings(const asgart_chains *r, double *ms3);
+void asgart_chains_free(asgart_chains *r);
+/* Threads per workgroup of the elementwise kernels behind asgart_chain_duplications, the lanes of one window round of its
+ * segment walk (a lookback above them takes a second round, and the ring in place of the registers), and the largest
+ * lookback, for tests that place their counts on the seams. */
+void asgart_chain_geometry(uint64_t *block_threads, uint64_t *window_lanes, uint64_t *max_lookback);
+
 /* ---- result files written on the GPU ------------------------------------------------------------------------
  * Replace the per-duplication work of the three exporters of reference src/exporters.rs for a result held as arrays: one
  * call gives the whole file, byte for byte what the exporter writes, in one device buffer.
