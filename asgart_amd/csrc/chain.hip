@@ -45,31 +45,12 @@ constexpr uint32_t kRingMask = kChainMaxLookback - 1;
 using GroupEnd = KeyEnd<uint64_t>;  // (packed group, el) of a rank
 
 // ---- order ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void chain_emit_kernel(const uint64_t *__restrict__ chr_pos, uint32_t n,
-                                                           uint32_t *__restrict__ ord, uint64_t *__restrict__ key) {
-    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
-    if (q >= n) return;
-    ord[q] = q;
-    key[q] = chr_pos[2 * (size_t)q + 1];
-}
-
-__global__ __launch_bounds__(kBlock) void chain_left_keys_kernel(const uint32_t *__restrict__ ord,
-                                                                const uint64_t *__restrict__ chr_pos, uint32_t n,
-                                                                uint64_t *__restrict__ key) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) key[i] = chr_pos[2 * (size_t)ord[i]];
-}
-
-// the third sort's key: cl, cr (name_bits each) and the two flag bits
-__global__ __launch_bounds__(kBlock) void chain_group_keys_kernel(const uint32_t *__restrict__ ord,
-                                                                 const int32_t *__restrict__ chr,
-                                                                 const uint8_t *__restrict__ flags, uint32_t n,
-                                                                 unsigned name_bits, uint64_t *__restrict__ key) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const size_t q = ord[i];
-    key[i] = ((uint64_t)(uint32_t)chr[2 * q] << (name_bits + 2)) | ((uint64_t)(uint32_t)chr[2 * q + 1] << 2) | flags[q];
-}
+// the keys of the first two passes: where the right (side 1), then the left (side 0) arm of duplication q starts
+struct ChainStart {
+    const uint64_t *__restrict__ chr_pos;
+    uint32_t side;
+    __device__ uint64_t operator()(uint32_t q) const { return chr_pos[2 * (size_t)q + side]; }
+};
 
 __global__ __launch_bounds__(kBlock) void chain_gather_kernel(const uint32_t *__restrict__ r_q,
                                                              const uint64_t *__restrict__ group_key,
@@ -110,14 +91,10 @@ __global__ __launch_bounds__(kBlock) void chain_open_kernel(const uint32_t *__re
 
 // the sort key of segment k: its length complemented, so that the longest come first; the slots behind the last segment
 // sort behind every segment (a length is at least 1)
-__global__ __launch_bounds__(kBlock) void chain_length_keys_kernel(const uint32_t *__restrict__ seg_start,
-                                                                  const uint32_t *__restrict__ n_seg, uint32_t n,
-                                                                  uint32_t *__restrict__ key, uint32_t *__restrict__ seg) {
-    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
-    if (k >= n) return;
-    key[k] = k < *n_seg ? ~(seg_start[k + 1] - seg_start[k]) : ~0u;
-    seg[k] = k;
-}
+struct ChainLengthKey {
+    const uint32_t *__restrict__ seg_start, *__restrict__ n_seg;
+    __device__ uint32_t operator()(uint32_t k) const { return k < *n_seg ? ~(seg_start[k + 1] - seg_start[k]) : ~0u; }
+};
 
 // ---- walk -----------------------------------------------------------------------------------------------------------
 struct ChainWalk {
@@ -373,15 +350,6 @@ __global__ __launch_bounds__(kBlock) void chain_members_kernel(const uint32_t *_
     term[x] = (uint64_t)r_term[i];
 }
 
-__device__ inline uint32_t first_at_least(const uint32_t *__restrict__ keys, uint32_t n, uint32_t c) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // chain_offsets[c], c in [0, n_chains]: the first sorted rank whose chain is >= c; the score is a difference of the scan
 __global__ __launch_bounds__(kBlock) void chain_offsets_kernel(const uint32_t *__restrict__ sorted_chain, uint32_t n,
                                                               const uint32_t *__restrict__ total,
@@ -423,12 +391,6 @@ struct ChainWork : ToolWork {
     DevBuf &r_chain = buf(), &r_self = buf(), &sorted_chain = buf(), &sorted_rank = buf(), &order = buf(), &term = buf();
     DevBuf &term_before = buf(), &offsets = buf(), &score = buf();
 };
-
-unsigned bits_for(uint64_t values) {  // ceil(log2(values)), at least one
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)1 << bits) < values) ++bits;
-    return bits;
-}
 
 const char *side_of(int arm) { return arm ? "right" : "left"; }
 
@@ -490,12 +452,6 @@ int32_t check_arguments(const int32_t *chr, const uint64_t *chr_pos, const uint6
     return 0;
 }
 
-template <class T>
-hipError_t fetch(std::vector<T> &to, const DevBuf &from, size_t items, hipStream_t s) {
-    to.resize(items);
-    return items ? hipMemcpyAsync(to.data(), from.p, items * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess;
-}
-
 int32_t run_chain(ChainWork &w, asgart_chains *res, const int32_t *chr, const uint64_t *chr_pos, const uint64_t *length,
                   const uint8_t *flags, uint32_t n, uint64_t n_names, uint64_t max_gap, uint32_t lookback) {
     RC_TRY(w.open(3));
@@ -522,16 +478,11 @@ int32_t run_chain(ChainWork &w, asgart_chains *res, const int32_t *chr, const ui
     uint32_t *head = w.head.as<uint32_t>(), *rank = w.rank.as<uint32_t>(), *number = w.number.as<uint32_t>();
     uint32_t *r_q = w.r_q.as<uint32_t>();
     const unsigned name_bits = bits_for(std::min<uint64_t>(n_names, (uint64_t)1 << 31));  // (ids are below 2^31)
-    chain_emit_kernel<<<grid, kBlock, 0, s>>>(w.chr_pos.as<uint64_t>(), n, w.ord0.as<uint32_t>(), w.key_a.as<uint64_t>());
-    HIP_TRY(hipGetLastError());
-    RC_TRY(w.sort_pairs(w.key_a.as<uint64_t>(), w.key_b.as<uint64_t>(), w.ord0.as<uint32_t>(), w.ord1.as<uint32_t>(), n, 64));
-    chain_left_keys_kernel<<<grid, kBlock, 0, s>>>(w.ord1.as<uint32_t>(), w.chr_pos.as<uint64_t>(), n, w.key_a.as<uint64_t>());
-    HIP_TRY(hipGetLastError());
-    RC_TRY(w.sort_pairs(w.key_a.as<uint64_t>(), w.key_b.as<uint64_t>(), w.ord1.as<uint32_t>(), w.ord2.as<uint32_t>(), n, 64));
-    chain_group_keys_kernel<<<grid, kBlock, 0, s>>>(w.ord2.as<uint32_t>(), w.chr.as<int32_t>(), w.flags.as<uint8_t>(), n,
-                                                    name_bits, w.key_a.as<uint64_t>());
-    HIP_TRY(hipGetLastError());
-    RC_TRY(w.sort_pairs(w.key_a.as<uint64_t>(), w.group_key.as<uint64_t>(), w.ord2.as<uint32_t>(), r_q, n, 2 * name_bits + 2));
+    // by pr, then by pl, then by the packed group (cl, cr, fl)
+    RC_TRY(w.order_pass<uint64_t>(ChainStart{w.chr_pos.as<uint64_t>(), 1}, w.key_a, w.key_b, w.ord0, kNoOrder, w.ord1, n, 64));
+    RC_TRY(w.order_pass<uint64_t>(ChainStart{w.chr_pos.as<uint64_t>(), 0}, w.key_a, w.key_b, w.ord1, kOrdered, w.ord2, n, 64));
+    RC_TRY(w.order_pass<uint64_t>(ChainGroupKey{w.chr.as<int32_t>(), w.flags.as<uint8_t>(), name_bits}, w.key_a, w.group_key,
+                                  w.ord2, kOrdered, w.r_q, n, 2 * name_bits + 2));
     chain_gather_kernel<<<grid, kBlock, 0, s>>>(r_q, w.group_key.as<uint64_t>(), w.chr_pos.as<uint64_t>(),
                                                 w.length.as<uint64_t>(), n, w.r_anchor.as<ChainAnchor>(),
                                                 w.pair.as<GroupEnd>());
@@ -543,11 +494,9 @@ int32_t run_chain(ChainWork &w, asgart_chains *res, const int32_t *chr, const ui
     RC_TRY(w.exclusive_scan(head, rank, (size_t)n + 1));
     chain_open_kernel<<<grid1, kBlock, 0, s>>>(head, rank, n, w.seg_start.as<uint32_t>());
     HIP_TRY(hipGetLastError());
-    chain_length_keys_kernel<<<grid, kBlock, 0, s>>>(w.seg_start.as<uint32_t>(), rank + n, n, w.len_key.as<uint32_t>(),
-                                                     w.seg0.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    RC_TRY(w.sort_pairs(w.len_key.as<uint32_t>(), w.len_sorted.as<uint32_t>(), w.seg0.as<uint32_t>(),
-                        w.seg_order.as<uint32_t>(), n, 32));
+    // the segments by length, the longest first: an ordering of its own, one pass
+    RC_TRY(w.order_pass<uint32_t>(ChainLengthKey{w.seg_start.as<uint32_t>(), rank + n}, w.len_key, w.len_sorted, w.seg0, kNoOrder,
+                                  w.seg_order, n, 32));
 
     const ChainWalk walk{w.r_anchor.as<ChainAnchor>(), w.flags.as<uint8_t>(), r_q, w.seg_start.as<uint32_t>(),
                          w.seg_order.as<uint32_t>(), rank + n, w.r_f.as<int64_t>(), w.r_term.as<int64_t>(),
@@ -589,29 +538,18 @@ int32_t run_chain(ChainWork &w, asgart_chains *res, const int32_t *chr, const ui
         set_error("%s: %u segments and %u chains of %u duplications", kWho, n_seg, n_chains, n);
         return ASGART_E_HIP;
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(fetch(res->f, w.f, n, s));
-    HIP_TRY(fetch(res->pred, w.pred, n, s));
-    HIP_TRY(fetch(res->link, w.link, n, s));
-    HIP_TRY(fetch(res->chain, w.chain, n, s));
-    HIP_TRY(fetch(res->order, w.order, n, s));
-    HIP_TRY(fetch(res->chain_offsets, w.offsets, (size_t)n_chains + 1, s));
-    HIP_TRY(fetch(res->chain_score, w.score, n_chains, s));
-    HIP_TRY(stream_sync(s));
-    res->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     res->n_sds = n;
     res->n_segments = n_seg;
-    float up = 0, kernels = 0;
-    HIP_TRY(hipEventElapsedTime(&up, w.ev[0], w.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&kernels, w.ev[1], w.ev[2]));
-    res->ms[0] = (double)up;
-    res->ms[1] = (double)kernels;
-    return 0;
-}
-
-template <class T>
-void give(T *to, const std::vector<T> &from) {
-    if (to && !from.empty()) memcpy(to, from.data(), from.size() * sizeof(T));
+    w.start_copy_back();
+    RC_TRY(w.fetch(res->f, w.f, n));
+    RC_TRY(w.fetch(res->pred, w.pred, n));
+    RC_TRY(w.fetch(res->link, w.link, n));
+    RC_TRY(w.fetch(res->chain, w.chain, n));
+    RC_TRY(w.fetch(res->order, w.order, n));
+    RC_TRY(w.fetch(res->chain_offsets, w.offsets, (size_t)n_chains + 1));
+    RC_TRY(w.fetch(res->chain_score, w.score, n_chains));
+    HIP_TRY(stream_sync(s));
+    return w.figures(res->ms);
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
-// chain_dev.hpp -- the link of the chaining rule (include/asgart_hip.h) and the wave primitives of the segment walk in
-// chain.hip.  chain_link is host and device code: the rule's inequalities and t(j, i) in unsigned 64-bit arithmetic that
+// chain_dev.hpp -- the link of the chaining rule (include/asgart_hip.h), the packed group key of the order and the wave
+// primitives of the segment walk in chain.hip.  chain_link and ChainGroupKey are host and device code, for the stand-alone
+// host checks of tools/.  chain_link: the rule's inequalities and t(j, i) in unsigned 64-bit arithmetic that
 // cannot wrap for what the host has let through (position + length does not wrap, lengths are 1 .. 2^32 - 1,
 // max_gap < 2^62).
 #pragma once
@@ -42,6 +43,18 @@ __host__ __device__ inline bool chain_link(uint64_t pl_j, uint64_t el_j, uint64_
     *t = (int64_t)(new_l < new_r ? new_l : new_r) - (int64_t)(gap_l > gap_r ? gap_l : gap_r);
     return true;
 }
+
+// The key of the third pass of the order, the group of duplication q: cl, cr (name_bits each, ids below 2^name_bits) and
+// the two flag bits, 2 * name_bits + 2 bits in all; equal (cl, cr, fl) give equal keys, and the keys order as the triples do.
+struct ChainGroupKey {
+    const int32_t *__restrict__ chr;
+    const uint8_t *__restrict__ flags;
+    unsigned name_bits;
+    __host__ __device__ uint64_t operator()(uint32_t q) const {
+        return ((uint64_t)(uint32_t)chr[2 * (size_t)q] << (name_bits + 2)) | ((uint64_t)(uint32_t)chr[2 * (size_t)q + 1] << 2) |
+               flags[q];
+    }
+};
 
 #if defined(__HIPCC__)
 __device__ inline int64_t wave_max(int64_t v) {

@@ -5,7 +5,7 @@
 // Nothing of the reference does this.  rosary.hip next door restates the reference's clusters, where an arm is compared with
 // the END OF THE ARM IN FRONT OF IT; here an arm is compared with the LARGEST end of all arms in front of it (an interval
 // union), which needs a scan where rosary needs a neighbour, and the two arms of a duplication are linked, which needs a
-// union-find.  The kernels of rosary.hip keep their code; what is shared is tool_base.hpp.
+// union-find.  What is shared is tool_base.hpp: the ordering, the name offsets and the host tail are the ones of rosary.hip.
 //
 // Stages, all on one stream; two counts and one give-up word are read back at the very end:
 //   emit, sort   the arm ordinals 0 .. 2n - 1 sorted by the 64-bit start, then stably by the name bits (rocPRIM radix sorts,
@@ -46,19 +46,6 @@ constexpr uint32_t kStrides[] = {64, 8, 1};  // the union launches: one duplicat
 
 // (name, end) of a sorted arm: the record of tool_base.hpp's segmented max-scan, which chain.hip shares
 using NameEnd = KeyEnd<uint32_t>;
-
-__global__ __launch_bounds__(kBlock) void groups_emit_kernel(uint32_t *__restrict__ ord, uint32_t m) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < m) ord[i] = i;
-}
-
-// the second sort's key: the name of the arm at every slot of the start-sorted order
-__global__ __launch_bounds__(kBlock) void groups_name_keys_kernel(const uint32_t *__restrict__ ord,
-                                                                 const int32_t *__restrict__ name, uint32_t m,
-                                                                 uint32_t *__restrict__ key) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < m) key[i] = (uint32_t)name[ord[i]];
-}
 
 __global__ __launch_bounds__(kBlock) void groups_ends_kernel(const uint32_t *__restrict__ ord,
                                                             const uint32_t *__restrict__ sorted_name,
@@ -119,20 +106,6 @@ __global__ __launch_bounds__(kBlock) void groups_close_kernel(const uint32_t *__
     const uint32_t c = rank[i] + head[i] - 1u;
     l_length[c] = run[i].end - l_start[c];
     l_members[c] = i + 1u - l_first[c];
-}
-
-// offsets[k], k in [0, n_names]: the first locus whose name is >= k; the count of loci is *total (the scan's last entry)
-__global__ __launch_bounds__(kBlock) void groups_name_offsets_kernel(const int32_t *__restrict__ l_name,
-                                                                    const uint32_t *__restrict__ total, uint64_t n_names,
-                                                                    uint64_t *__restrict__ offsets) {
-    const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k > n_names) return;
-    uint32_t lo = 0, hi = *total;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if ((uint64_t)l_name[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    offsets[k] = lo;
 }
 
 __device__ inline uint32_t parent_of(const uint32_t *parent, uint32_t x) {
@@ -241,24 +214,11 @@ __global__ __launch_bounds__(kBlock) void groups_label_kernel(const uint32_t *__
     }
 }
 
-// the sort key of duplication q: the group of its left locus (its right locus has the same); the ordinals go with it
-__global__ __launch_bounds__(kBlock) void groups_dup_keys_kernel(const uint32_t *__restrict__ arm_locus,
-                                                                const uint32_t *__restrict__ l_group, uint32_t n,
-                                                                uint32_t *__restrict__ group, uint32_t *__restrict__ ord) {
-    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
-    if (q >= n) return;
-    group[q] = l_group[arm_locus[2 * q]];
-    ord[q] = q;
-}
-
-__device__ inline uint32_t first_at_least(const uint32_t *__restrict__ keys, uint32_t n, uint32_t g) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < g) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// the sort key of duplication q: the group of its left locus (its right locus has the same)
+struct GroupOfDuplication {
+    const uint32_t *__restrict__ arm_locus, *__restrict__ l_group;
+    __device__ uint32_t operator()(uint32_t q) const { return l_group[arm_locus[2 * q]]; }
+};
 
 // group_offsets[g], g in [0, n_groups]: the first sorted duplication whose group is >= g; duplications per group between
 __global__ __launch_bounds__(kBlock) void groups_group_offsets_kernel(const uint32_t *__restrict__ sorted_group, uint32_t n,
@@ -339,18 +299,6 @@ int32_t check_arguments(const int32_t *arm_name, const uint64_t *arm_start, cons
     return 0;
 }
 
-unsigned bits_for(uint64_t values) {  // ceil(log2(values)), at least one
-    unsigned bits = 1;
-    while (bits < 32 && ((uint64_t)1 << bits) < values) ++bits;
-    return bits;
-}
-
-template <class T>
-hipError_t fetch(std::vector<T> &to, const DevBuf &from, size_t items, hipStream_t s) {
-    to.resize(items);
-    return items ? hipMemcpyAsync(to.data(), from.p, items * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess;
-}
-
 int32_t run_groups(GroupsWork &w, asgart_groups *res, const int32_t *arm_name, const uint64_t *arm_start,
                    const uint64_t *arm_length, uint32_t n, uint64_t n_names, uint64_t margin) {
     const uint32_t m = 2 * n;  // arms; no more loci than arms, no more groups than loci
@@ -378,14 +326,11 @@ int32_t run_groups(GroupsWork &w, asgart_groups *res, const int32_t *arm_name, c
     HIP_TRY(hipMemsetAsync(w.g_bases.p, 0, (size_t)m * 8, s));
     HIP_TRY(hipEventRecord(w.ev[1], s));
 
-    const unsigned grid = blocks_for(m, kBlock), grid1 = blocks_for((uint64_t)m + 1, kBlock), grid_n = blocks_for(n, kBlock);
-    groups_emit_kernel<<<grid, kBlock, 0, s>>>(w.ord0.as<uint32_t>(), m);
-    HIP_TRY(hipGetLastError());
-    RC_TRY(w.sort_pairs(w.start.as<uint64_t>(), w.key1.as<uint64_t>(), w.ord0.as<uint32_t>(), w.ord1.as<uint32_t>(), m, 64));
-    groups_name_keys_kernel<<<grid, kBlock, 0, s>>>(w.ord1.as<uint32_t>(), w.name.as<int32_t>(), m, w.key2.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    RC_TRY(w.sort_pairs(w.key2.as<uint32_t>(), w.sorted_name.as<uint32_t>(), w.ord1.as<uint32_t>(), w.ord2.as<uint32_t>(), m,
-                      bits_for(n_names)));
+    const unsigned grid = blocks_for(m, kBlock), grid1 = blocks_for((uint64_t)m + 1, kBlock);
+    // by start (the uploaded column is the key), then by name
+    RC_TRY(w.order_pass<uint64_t>(KeyGiven{}, w.start, w.key1, w.ord0, kNoOrder, w.ord1, m, 64));
+    RC_TRY(w.order_pass<uint32_t>(ArmName{w.name.as<int32_t>()}, w.key2, w.sorted_name, w.ord1, kOrdered, w.ord2, m,
+                                  bits_for(n_names)));
     groups_ends_kernel<<<grid, kBlock, 0, s>>>(w.ord2.as<uint32_t>(), w.sorted_name.as<uint32_t>(), w.start.as<uint64_t>(),
                                                w.length.as<uint64_t>(), m, w.s_start.as<uint64_t>(), w.pair.as<NameEnd>());
     HIP_TRY(hipGetLastError());
@@ -402,7 +347,8 @@ int32_t run_groups(GroupsWork &w, asgart_groups *res, const int32_t *arm_name, c
                                                 w.l_first.as<uint32_t>(), m, w.l_length.as<uint64_t>(),
                                                 w.l_members.as<uint32_t>());
     HIP_TRY(hipGetLastError());
-    groups_name_offsets_kernel<<<blocks_for(n_names + 1, kBlock), kBlock, 0, s>>>(w.l_name.as<int32_t>(), rank + m, n_names,
+    // row k of the name offsets: the first locus whose name is >= k; the count of loci is the scan's total
+    row_offsets_kernel<kBlock><<<blocks_for(n_names + 1, kBlock), kBlock, 0, s>>>(w.l_name.as<int32_t>(), rank + m, n_names,
                                                                                   w.name_offsets.as<uint64_t>());
     HIP_TRY(hipGetLastError());
     uint32_t taken = 0;
@@ -424,11 +370,9 @@ int32_t run_groups(GroupsWork &w, asgart_groups *res, const int32_t *arm_name, c
                                                 w.l_group.as<uint32_t>(), w.g_loci.as<uint32_t>(),
                                                 w.g_bases.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
-    groups_dup_keys_kernel<<<grid_n, kBlock, 0, s>>>(w.arm_locus.as<uint32_t>(), w.l_group.as<uint32_t>(), n,
-                                                     w.group.as<uint32_t>(), w.dord0.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    RC_TRY(w.sort_pairs(w.group.as<uint32_t>(), w.sorted_group.as<uint32_t>(), w.dord0.as<uint32_t>(), w.order.as<uint32_t>(),
-                      n, bits_for(m)));
+    // the duplications by group: an ordering of its own, one pass
+    RC_TRY(w.order_pass<uint32_t>(GroupOfDuplication{w.arm_locus.as<uint32_t>(), w.l_group.as<uint32_t>()}, w.group,
+                                  w.sorted_group, w.dord0, kNoOrder, w.order, n, bits_for(m)));
     groups_group_offsets_kernel<<<grid1, kBlock, 0, s>>>(w.sorted_group.as<uint32_t>(), n, g_rank + m,
                                                          w.group_offsets.as<uint64_t>(), w.g_dups.as<uint32_t>());
     HIP_TRY(hipGetLastError());
@@ -447,33 +391,22 @@ int32_t run_groups(GroupsWork &w, asgart_groups *res, const int32_t *arm_name, c
         set_error("%s: %u loci and %u groups of %u arms", kWho, n_loci, n_groups, m);
         return ASGART_E_HIP;
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(fetch(res->name_offsets, w.name_offsets, n_names + 1, s));
-    HIP_TRY(fetch(res->l_name, w.l_name, n_loci, s));
-    HIP_TRY(fetch(res->l_start, w.l_start, n_loci, s));
-    HIP_TRY(fetch(res->l_length, w.l_length, n_loci, s));
-    HIP_TRY(fetch(res->l_members, w.l_members, n_loci, s));
-    HIP_TRY(fetch(res->l_group, w.l_group, n_loci, s));
-    HIP_TRY(fetch(res->g_loci, w.g_loci, n_groups, s));
-    HIP_TRY(fetch(res->g_dups, w.g_dups, n_groups, s));
-    HIP_TRY(fetch(res->g_bases, w.g_bases, n_groups, s));
-    HIP_TRY(fetch(res->group, w.group, n, s));
-    HIP_TRY(fetch(res->order, w.order, n, s));
-    HIP_TRY(fetch(res->group_offsets, w.group_offsets, (size_t)n_groups + 1, s));
-    HIP_TRY(fetch(res->arm_locus, w.arm_locus, m, s));
+    w.start_copy_back();
+    RC_TRY(w.fetch(res->name_offsets, w.name_offsets, n_names + 1));
+    RC_TRY(w.fetch(res->l_name, w.l_name, n_loci));
+    RC_TRY(w.fetch(res->l_start, w.l_start, n_loci));
+    RC_TRY(w.fetch(res->l_length, w.l_length, n_loci));
+    RC_TRY(w.fetch(res->l_members, w.l_members, n_loci));
+    RC_TRY(w.fetch(res->l_group, w.l_group, n_loci));
+    RC_TRY(w.fetch(res->g_loci, w.g_loci, n_groups));
+    RC_TRY(w.fetch(res->g_dups, w.g_dups, n_groups));
+    RC_TRY(w.fetch(res->g_bases, w.g_bases, n_groups));
+    RC_TRY(w.fetch(res->group, w.group, n));
+    RC_TRY(w.fetch(res->order, w.order, n));
+    RC_TRY(w.fetch(res->group_offsets, w.group_offsets, (size_t)n_groups + 1));
+    RC_TRY(w.fetch(res->arm_locus, w.arm_locus, m));
     HIP_TRY(stream_sync(s));
-    res->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    float up = 0, kernels = 0;
-    HIP_TRY(hipEventElapsedTime(&up, w.ev[0], w.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&kernels, w.ev[1], w.ev[2]));
-    res->ms[0] = (double)up;
-    res->ms[1] = (double)kernels;
-    return 0;
-}
-
-template <class T>
-void give(T *to, const std::vector<T> &from) {
-    if (to && !from.empty()) memcpy(to, from.data(), from.size() * sizeof(T));
+    return w.figures(res->ms);
 }
 
 }  // namespace

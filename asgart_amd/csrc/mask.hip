@@ -252,17 +252,10 @@ int32_t run_mask(MaskWork &w, asgart_mask *res, const int32_t *arm_record, const
     }
     res->masked = words[0];
     res->max_depth = (uint32_t)words[1];
-    const auto t0 = std::chrono::steady_clock::now();
-    res->bounds.resize(n_edges);
-    if (n_edges) HIP_TRY(hipMemcpyAsync(res->bounds.data(), w.bounds.p, (size_t)n_edges * 8, hipMemcpyDeviceToHost, s));
+    w.start_copy_back();
+    RC_TRY(w.fetch(res->bounds, w.bounds, n_edges));
     HIP_TRY(stream_sync(s));
-    res->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    float up = 0, kernels = 0;
-    HIP_TRY(hipEventElapsedTime(&up, w.ev[0], w.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&kernels, w.ev[1], w.ev[2]));
-    res->ms[0] = (double)up;
-    res->ms[1] = (double)kernels;
-    return 0;
+    return w.figures(res->ms);
 }
 
 }  // namespace
@@ -291,7 +284,7 @@ extern "C" void asgart_mask_counts(const asgart_mask *r, uint64_t *n_intervals, 
 }
 
 extern "C" void asgart_mask_copy(const asgart_mask *r, uint64_t *intervals) {
-    if (r && intervals && !r->bounds.empty()) memcpy(intervals, r->bounds.data(), r->bounds.size() * 8);
+    if (r) give(intervals, r->bounds);
 }
 
 extern "C" int32_t asgart_mask_timings(const asgart_mask *r, double *ms3) {

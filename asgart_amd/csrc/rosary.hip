@@ -34,19 +34,6 @@ namespace {
 
 constexpr uint32_t kBlock = 256;  // threads per workgroup, every kernel; a multiple of the wave size
 
-__global__ __launch_bounds__(kBlock) void rosary_emit_kernel(uint32_t *__restrict__ ord, uint32_t m) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < m) ord[i] = i;
-}
-
-// the second sort's key: the name of the arm at every slot of the start-sorted order
-__global__ __launch_bounds__(kBlock) void rosary_name_keys_kernel(const uint32_t *__restrict__ ord,
-                                                                 const int32_t *__restrict__ name, uint32_t m,
-                                                                 uint32_t *__restrict__ key) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < m) key[i] = (uint32_t)name[ord[i]];
-}
-
 // sorted record i: start, end, flag bits; head[i] by the predicate on record i - 1.  Every lane runs the shuffles.
 __global__ __launch_bounds__(kBlock) void rosary_heads_kernel(const uint32_t *__restrict__ ord,
                                                              const uint32_t *__restrict__ sorted_name,
@@ -125,20 +112,6 @@ __global__ __launch_bounds__(kBlock) void rosary_join_kernel(const uint32_t *__r
     if (in_range && (i == m - 1 || head[i + 1])) c_length[c] = s_end[i] - c_start[c];
 }
 
-// offsets[k], k in [0, n_names]: the first cluster whose name is >= k; the count of clusters is rank[m] (the scan's total)
-__global__ __launch_bounds__(kBlock) void rosary_offsets_kernel(const uint32_t *__restrict__ c_name,
-                                                               const uint32_t *__restrict__ total, uint64_t n_names,
-                                                               uint64_t *__restrict__ offsets) {
-    const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k > n_names) return;
-    uint32_t lo = 0, hi = *total;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if ((uint64_t)c_name[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    offsets[k] = lo;
-}
-
 }  // namespace
 }  // namespace asgart
 
@@ -201,15 +174,10 @@ int32_t run_rosary(RosaryWork &w, asgart_rosary *res, const int32_t *arm_name, c
     HIP_TRY(hipEventRecord(w.ev[1], s));
 
     const unsigned grid = blocks_for(m);
-    rosary_emit_kernel<<<grid, kBlock, 0, s>>>(w.ord0.as<uint32_t>(), m);
-    HIP_TRY(hipGetLastError());
-    RC_TRY(w.sort_pairs(w.start.as<uint64_t>(), w.key1.as<uint64_t>(), w.ord0.as<uint32_t>(), w.ord1.as<uint32_t>(), m, 64));
-    rosary_name_keys_kernel<<<grid, kBlock, 0, s>>>(w.ord1.as<uint32_t>(), w.name.as<int32_t>(), m, w.key2.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    unsigned name_bits = 1;  // ceil(log2(n_names)), at least one
-    while (name_bits < 32 && ((uint64_t)1 << name_bits) < n_names) ++name_bits;
-    RC_TRY(w.sort_pairs(w.key2.as<uint32_t>(), w.sorted_name.as<uint32_t>(), w.ord1.as<uint32_t>(), w.ord2.as<uint32_t>(), m,
-                      name_bits));
+    // by start (the uploaded column is the key), then by name
+    RC_TRY(w.order_pass<uint64_t>(KeyGiven{}, w.start, w.key1, w.ord0, kNoOrder, w.ord1, m, 64));
+    RC_TRY(w.order_pass<uint32_t>(ArmName{w.name.as<int32_t>()}, w.key2, w.sorted_name, w.ord1, kOrdered, w.ord2, m,
+                                  bits_for(n_names)));
     rosary_heads_kernel<<<grid, kBlock, 0, s>>>(w.ord2.as<uint32_t>(), w.sorted_name.as<uint32_t>(), w.start.as<uint64_t>(),
                                                 w.length.as<uint64_t>(), flags ? w.flags.as<uint8_t>() : nullptr, m, margin,
                                                 w.s_start.as<uint64_t>(), w.s_end.as<uint64_t>(), w.s_bits.as<uint8_t>(), head);
@@ -223,8 +191,9 @@ int32_t run_rosary(RosaryWork &w, asgart_rosary *res, const int32_t *arm_name, c
                                                w.c_start.as<uint64_t>(), w.c_length.as<uint64_t>(), w.c_klass.as<uint32_t>(),
                                                w.c_members.as<uint32_t>());
     HIP_TRY(hipGetLastError());
-    rosary_offsets_kernel<<<blocks_for(n_names + 1), kBlock, 0, s>>>(w.c_name.as<uint32_t>(), rank + m, n_names,
-                                                                     w.offsets.as<uint64_t>());
+    // row k of the name offsets: the first cluster whose name is >= k; the count of clusters is the scan's total
+    row_offsets_kernel<kBlock><<<blocks_for(n_names + 1, kBlock), kBlock, 0, s>>>(w.c_name.as<uint32_t>(), rank + m, n_names,
+                                                                                  w.offsets.as<uint64_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(w.ev[2], s));
 
@@ -234,27 +203,16 @@ int32_t run_rosary(RosaryWork &w, asgart_rosary *res, const int32_t *arm_name, c
         set_error("asgart_rosary_clusters: %u clusters of %u arms", nc, m);
         return ASGART_E_HIP;
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint32_t> klass32(nc);
-    res->offsets.resize(n_names + 1);
-    res->start.resize(nc);
-    res->length.resize(nc);
-    res->members.resize(nc);
-    HIP_TRY(hipMemcpyAsync(res->offsets.data(), w.offsets.p, (n_names + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(res->start.data(), w.c_start.p, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(res->length.data(), w.c_length.p, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(res->members.data(), w.c_members.p, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(klass32.data(), w.c_klass.p, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+    w.start_copy_back();
+    std::vector<uint32_t> klass32;
+    RC_TRY(w.fetch(res->offsets, w.offsets, n_names + 1));
+    RC_TRY(w.fetch(res->start, w.c_start, nc));
+    RC_TRY(w.fetch(res->length, w.c_length, nc));
+    RC_TRY(w.fetch(res->members, w.c_members, nc));
+    RC_TRY(w.fetch(klass32, w.c_klass, nc));
     HIP_TRY(stream_sync(s));
-    res->klass.resize(nc);
-    for (uint32_t c = 0; c < nc; ++c) res->klass[c] = (uint8_t)klass32[c];
-    res->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    float up = 0, kernels = 0;
-    HIP_TRY(hipEventElapsedTime(&up, w.ev[0], w.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&kernels, w.ev[1], w.ev[2]));
-    res->ms[0] = (double)up;
-    res->ms[1] = (double)kernels;
-    return 0;
+    res->klass.assign(klass32.begin(), klass32.end());  // (words on the device, where atomicOr sets `both`; bytes in the handle)
+    return w.figures(res->ms);
 }
 
 }  // namespace
@@ -283,12 +241,11 @@ extern "C" void asgart_rosary_counts(const asgart_rosary *r, uint64_t *n_names, 
 extern "C" void asgart_rosary_copy(const asgart_rosary *r, uint64_t *name_offsets, uint64_t *start, uint64_t *length,
                                    uint8_t *klass, uint32_t *members) {
     if (!r) return;
-    const size_t nc = r->start.size();
-    if (name_offsets) memcpy(name_offsets, r->offsets.data(), r->offsets.size() * 8);
-    if (start && nc) memcpy(start, r->start.data(), nc * 8);
-    if (length && nc) memcpy(length, r->length.data(), nc * 8);
-    if (klass && nc) memcpy(klass, r->klass.data(), nc);
-    if (members && nc) memcpy(members, r->members.data(), nc * 4);
+    give(name_offsets, r->offsets);
+    give(start, r->start);
+    give(length, r->length);
+    give(klass, r->klass);
+    give(members, r->members);
 }
 
 extern "C" int32_t asgart_rosary_timings(const asgart_rosary *r, double *ms3) {

@@ -1,13 +1,20 @@
-// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, groups.hip, mask.hip, alnstats.hip and, through
+// tool_base.hpp -- what the result tools (slice.hip, plot.hip, rosary.hip, groups.hip, mask.hip, chain.hip, alnstats.hip and, through
 // file_writer.hpp, the file writers export.hip, paf.hip, sdtable.hip and fasta_write.hip) are built on: the device check of an entry point,
 // the device work of one call (ToolWork: stream, events, every device buffer, the rocPRIM two-call wrappers), the host checks of offset arrays and name ids, the bisection of an offset array on the device, and the tail of an entry
 // point.  extract.hip, fasta.hip and prep.hip take use_device from here.
+//
+// The arm tools (rosary.hip, groups.hip, chain.hip, mask.hip) share their frame as well.  An ordering is a chain of
+// ToolWork::order_pass calls, one stable radix sort of the ordinals per key, the least significant key first; the key of a
+// pass is a device functor of the tool's, gathered through the order so far by order_keys_kernel.  CSR rows come from
+// first_at_least, a bisection of a sorted key column, and where nothing else is computed per row from row_offsets_kernel.
+// The host tail is bits_for, ToolWork::fetch, give and the three figures of ToolWork::start_copy_back / figures.
 #pragma once
 
 #include "common.hpp"
 
 #include <algorithm>
 #include <deque>
+#include <type_traits>
 
 #include <rocprim/rocprim.hpp>
 
@@ -25,6 +32,13 @@ inline int32_t use_device(const char *who, int32_t device) {
 }
 
 inline unsigned blocks_for(uint64_t items, uint32_t block = 256) { return (unsigned)((items + block - 1) / block); }
+
+// the bits of a radix sort whose keys are below `values`: ceil(log2(values)), at least one, at most 32
+inline unsigned bits_for(uint64_t values) {
+    unsigned bits = 1;
+    while (bits < 32 && ((uint64_t)1 << bits) < values) ++bits;
+    return bits;
+}
 
 // ---- the segmented running maximum of groups.hip (loci: key = the name) and chain.hip (segments: key = the packed group) ----
 // Record i of a sequence sorted by (key, start): its key and its end.  ToolWork::segmented_max_scan turns the ends into the
@@ -49,6 +63,57 @@ struct SegmentedMax {
 __host__ __device__ inline uint64_t sat_add(uint64_t a, uint64_t b) {
     const uint64_t s = a + b;
     return s < a ? ~(uint64_t)0 : s;
+}
+
+// ---- the ordering and the rows of the arm tools ----
+// the first entry of keys[0 .. n), which never decrease, that is >= k; n where there is none
+template <class Key>
+__host__ __device__ inline uint32_t first_at_least(const Key *__restrict__ keys, uint32_t n, uint64_t k) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((uint64_t)keys[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct KeyGiven {};  // the key_of of a pass whose key column stands in memory already: only the ordinals are numbered
+enum OrderSoFar { kNoOrder, kOrdered };  // a tool's first pass numbers the ordinals, every later one reads them
+
+struct ArmName {  // the key "name of arm o" of rosary.hip and groups.hip (the host has checked: ids are not negative)
+    const int32_t *__restrict__ name;
+    __device__ uint32_t operator()(uint32_t o) const { return (uint32_t)name[o]; }
+};
+
+namespace {  // (internal, and templates: a file holds the instances it launches and links its own)
+
+// The keys of one sort pass: key[i] = key_of(the record at slot i of the order so far).  Without an order so far that
+// record is i, and ord[i] = i is written for the sort to carry.
+template <uint32_t kThreads, class Key, class KeyOf>
+__global__ __launch_bounds__(kThreads) void order_keys_kernel(KeyOf key_of, uint32_t *ord, OrderSoFar so_far, uint32_t n,
+                                                              Key *__restrict__ key) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    uint32_t o = i;
+    if (so_far == kOrdered) o = ord[i]; else ord[i] = i;
+    if constexpr (!std::is_same<KeyOf, KeyGiven>::value) key[i] = key_of(o);
+}
+
+// offsets[k], k in [0, n_rows]: the first of the *total entries of keys, which never decrease, that is >= k
+template <uint32_t kThreads, class Key>
+__global__ __launch_bounds__(kThreads) void row_offsets_kernel(const Key *__restrict__ keys,
+                                                               const uint32_t *__restrict__ total, uint64_t n_rows,
+                                                               uint64_t *__restrict__ offsets) {
+    const uint64_t k = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (k <= n_rows) offsets[k] = first_at_least(keys, *total, k);
+}
+
+}  // namespace
+
+// what a handle's vector gives the caller's array (NULL: the caller does not want it)
+template <class T>
+void give(T *to, const std::vector<T> &from) {
+    if (to && !from.empty()) memcpy(to, from.data(), from.size() * sizeof(T));
 }
 
 // The device work of one call: one non-blocking stream, its events and every device buffer the call uses.  A tool derives
@@ -120,6 +185,39 @@ struct ToolWork {
         HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, k_in, k_out, v_in, v_out, items, 0, end_bit, s));
         RC_TRY(sort_tmp.reserve(tmp + 16));
         HIP_TRY(rocprim::radix_sort_pairs(sort_tmp.p, tmp, k_in, k_out, v_in, v_out, items, 0, end_bit, s));
+        return 0;
+    }
+    // One pass of an ordering: the n ordinals of ord, in the order so far, sorted stably into ord_out by the low end_bit
+    // bits of key_of(record); the sorted keys land in sorted_key.  A later pass is the more significant key.
+    template <class Key, uint32_t kThreads = 256, class KeyOf>
+    int32_t order_pass(KeyOf key_of, DevBuf &key, DevBuf &sorted_key, DevBuf &ord, OrderSoFar so_far, DevBuf &ord_out,
+                       uint32_t n, unsigned end_bit) {
+        order_keys_kernel<kThreads><<<blocks_for(n, kThreads), kThreads, 0, s>>>(key_of, ord.as<uint32_t>(), so_far, n,
+                                                                                 key.as<Key>());
+        HIP_TRY(hipGetLastError());
+        return sort_pairs(key.as<Key>(), sorted_key.as<Key>(), ord.as<uint32_t>(), ord_out.as<uint32_t>(), n, end_bit);
+    }
+
+    // the first `items` entries of a device buffer into a vector of the handle (waited for by the caller's stream_sync)
+    template <class T>
+    int32_t fetch(std::vector<T> &to, const DevBuf &from, size_t items) {
+        to.resize(items);
+        if (items) HIP_TRY(hipMemcpyAsync(to.data(), from.p, items * sizeof(T), hipMemcpyDeviceToHost, s));
+        return 0;
+    }
+
+    // The three figures of an arm tool, which records ev[0] before its upload, ev[1] before its first kernel and ev[2]
+    // behind its last: ms[0] the upload, ms[1] the kernels, ms[2] the copy back by the host's clock, from start_copy_back
+    // to figures, which is called once the stream is drained.
+    std::chrono::steady_clock::time_point copy_back_from;
+    void start_copy_back() { copy_back_from = std::chrono::steady_clock::now(); }
+    int32_t figures(double *ms) {
+        ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - copy_back_from).count();
+        float up = 0, kernels = 0;
+        HIP_TRY(hipEventElapsedTime(&up, ev[0], ev[1]));
+        HIP_TRY(hipEventElapsedTime(&kernels, ev[1], ev[2]));
+        ms[0] = (double)up;
+        ms[1] = (double)kernels;
         return 0;
     }
 };
